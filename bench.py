@@ -2,15 +2,25 @@
 """Headline benchmark: images/sec of one full FastSCNN train step (zero_grad + forward + CrossEntropy(ignore 255)
 + backward + AdamW) on synthetic 8 x 3 x 1024 x 2048 batches per GPU, bf16 activations / f32 parameters.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--model fastscnn|contextnet14] [--dtype bf16|f32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--model fastscnn|contextnet14] [--dtype bf16|f32] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-One JSON line on rank 0 (contract in the task statement) with two extra objects:
+One JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step = wall time of the K timed steps / K,
+...).  A plain run sets up, warms up, times the K steps and prints that line; with --full it also measures, in
+separate passes after the timed steps:
   roofline     : the kernel with the largest share of step time, timed with HIP events on its launch stream
                  (libtss_hip's profiler) over a few un-captured steps; achieved = algorithmic bytes / time.
+  extra        : BASELINE configs 3 and 5 (contextnet14, OHEM loss, eval forwards; N=1, default workload only).
   cpu_baseline : the CPU oracle (oracle/, a torch restatement of the reference) timed on this node's host
                  cores on a bounded sample of the same workload, N=1 only.
+
+--dump-outputs DIR writes what the last timed step computed, right after the timed steps, as DIR/<name>.npy (rank 0):
+  train: loss.npy (float32, 1), params.npy (the flat float32 parameters after AdamW), grads.npy (the flat float32
+         gradients of that step), buffers.npy (the floating-point buffers, BatchNorm running statistics, concatenated)
+  eval : logits.npy (float32; a fixed seeded sample of OUTPUT_SAMPLE elements when the logits are larger)
+The inputs depend on the arguments only (seeded weights and batch), so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -31,6 +41,7 @@ S_REF = {'fastscnn': 1819e6, 'contextnet14': 2086e6, 'fastscnn_aspp': 2088e6}
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: 8 TB/s spec
 HBM_COPY_GBS = 6290.0        # ... and the measured float4 copy rate on MI355X (79 % of spec)
 MFMA_BF16_PEAK_TF = 2500.0
+OUTPUT_SAMPLE = 4 << 20      # --dump-outputs: at most this many elements per array (16 MB in float32)
 
 
 def parse():
@@ -59,6 +70,11 @@ def parse():
                     help='skip the extra.contextnet14 / extra.eval_c5 legs (BASELINE configs 3 and 5; N=1, default workload only)')
     ap.add_argument('--syncbn', action='store_true',
                     help='convert_syncbn_model before training (cross-replica BatchNorm, SURVEY.md section 8f N1)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the roofline pass, the extra configs and the CPU baseline (each can still be turned off '
+                         'with its --no-* option); a plain run only times the steps')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (see the module docstring)')
     args = ap.parse_args()
     dflt = (8, 1024, 2048) if args.mode == 'train' else (1, 2048, 4096)
     args.batch, args.height, args.width = (args.batch or dflt[0], args.height or dflt[1], args.width or dflt[2])
@@ -307,6 +323,21 @@ def roofline_block(alg_bytes, ms):
             'frac_of_measured_copy': round(gbs / HBM_COPY_GBS, 4)}
 
 
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy in float32 (float64 stays float64).  An array of more than OUTPUT_SAMPLE
+    elements is replaced by the same fixed, seeded sample of its flattened elements every run (sorted indices)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > OUTPUT_SAMPLE:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (OUTPUT_SAMPLE,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(out_dir, name + '.npy'), t.cpu().numpy())
+
+
 def main_eval(args):
     """SURVEY config C5 / TSS/utils/benchmark.py: eval-mode forward (running BatchNorm statistics, no dropout, no grad)
     through the x8 decoder head, HIP-graph replay, input resident in HBM."""
@@ -331,6 +362,8 @@ def main_eval(args):
             out = fwd(x)
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'logits': out})
     esz = 2 if dtype == torch.bfloat16 else 4
     ms = 1e3 * elapsed / args.steps
     S_ref = S_REF.get(args.model)
@@ -344,7 +377,7 @@ def main_eval(args):
     if S_ref:   # A = (sum over blocks of in + out elements + full-resolution logits) * b
         a = (S_ref * args.batch * args.height * args.width / (8.0 * 1024 * 2048) + args.batch * 19.0 * args.height * args.width) * esz
         res['step_roofline'] = roofline_block(a, ms)
-    if args.model == 'fastscnn_aspp' and dtype == torch.bfloat16:
+    if args.full and args.model == 'fastscnn_aspp' and dtype == torch.bfloat16:
         rf = mfma_roofline(model, x)
         if rf:
             res['roofline'] = rf
@@ -416,6 +449,10 @@ def main():
     final_loss = float(loss)
     if final_loss != final_loss or abs(final_loss) == float('inf'):
         raise SystemExit('bench.py: the training loss is not finite after %d steps -- the timed steps are not a valid workload' % args.steps)
+    if args.dump_outputs and rank == 0:     # before any pass below moves the weights on
+        dump_outputs(args.dump_outputs, {
+            'loss': loss.reshape(1), 'params': opt.flat_param, 'grads': opt.flat_grad,
+            'buffers': torch.cat([b.detach().reshape(-1).float() for b in model.buffers() if b.dtype.is_floating_point])})
 
     host_batch = None
     if args.host_batch:          # all ranks: the steps contain the gradient all-reduce
@@ -460,7 +497,7 @@ def main():
 
     roofline = None
     breakdown = None
-    if not args.no_roofline:     # every rank takes part (the un-captured steps all-reduce like the timed ones); rank 0 reports
+    if args.full and not args.no_roofline:     # every rank takes part (the un-captured steps all-reduce like the timed ones); rank 0 reports
         from torch_semantic_segmentation_amd import ops as _ops
         _ops.overlap_wgrad = False      # one kernel at a time, so that an event pair times exactly one kernel
         eager = make_trainer(False)
@@ -530,7 +567,7 @@ def main():
             out['roofline'] = roofline
             out['kernel_breakdown'] = breakdown
         default_workload = (args.model, args.batch, args.height, args.width, args.dtype) == ('fastscnn', 8, 1024, 2048, 'bf16')
-        if world == 1 and default_workload and not args.no_extras:
+        if args.full and world == 1 and default_workload and not args.no_extras:
             # BASELINE configs 3 and 5 in the same driver-run line (never the headline value)
             del trainer
             torch.cuda.empty_cache()
@@ -541,7 +578,7 @@ def main():
                             'eval_c5_aspp': extra_eval('fastscnn_aspp', 2048, 4096, device, n_extra, 5)}
         if args.stock:
             out['stock_pytorch_rocm_images_per_sec'] = round(stock_gpu(args.model, args.batch, args.height, args.width, device), 2)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args.model, args.cpu_seconds)
         print(json.dumps(out))
     if dist.is_initialized():

@@ -468,8 +468,26 @@ def gen_seeded():
     print('wrote', path, '%.1f KiB' % (os.path.getsize(path) / 1024))
 
 
+# ----------------------------------------------------------------------------- state_dict layout of the reference models
+
+def gen_keys():
+    """The reference's state_dict layout (key order, shapes, dtypes) of FastSCNN and ContextNet12, as strings: the oracle's
+    key / shape contract is checked against it without importing the reference."""
+    blob = {}
+    for name, m in (('fastscnn', ref_fast.fastscnn(3, 19)), ('contextnet12', ref_ctx.contextnet12(3, 19))):
+        sd = m.state_dict()
+        blob[name + '/keys'] = np.array(list(sd))
+        blob[name + '/shapes'] = np.array([','.join(str(d) for d in v.shape) for v in sd.values()])
+        blob[name + '/dtypes'] = np.array([str(v.dtype) for v in sd.values()])
+    path = os.path.join(HERE, 'state_dict_keys.npz')
+    np.savez_compressed(path, **blob)
+    print('wrote', path, '%.1f KiB' % (os.path.getsize(path) / 1024))
+
+
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['blocks', 'eval', 'train', 'frozen', 'seeded', 'pspnet', 'zoo', 'zoo_frozen']
+    which = sys.argv[1:] or ['blocks', 'eval', 'train', 'frozen', 'seeded', 'pspnet', 'zoo', 'zoo_frozen', 'keys']
+    if 'keys' in which:
+        gen_keys()
     if 'zoo' in which:
         gen_zoo()
     if 'zoo_frozen' in which:

@@ -330,7 +330,7 @@ def test_bench_two_rank_rehearsal_runs_to_completion():
         env.pop(k, None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', '29547', os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '2',
-           '--batch', '2', '--height', '128', '--width', '256', '--no-cpu-baseline']
+           '--batch', '2', '--height', '128', '--width', '256', '--full', '--no-cpu-baseline']
     res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith('{')]

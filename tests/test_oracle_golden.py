@@ -112,20 +112,14 @@ def test_state_dict_contract():
     assert f.state_dict()['classifier.3.bias'].shape == (19,)
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='reference only exists in the build container')
-def test_oracle_keys_equal_reference():
-    import importlib
-    import sys
-    sys.path.insert(0, '/root/reference')
-    try:
-        rf = importlib.import_module('torch_semantic_segmentation.models.fastscnn')
-        rc = importlib.import_module('torch_semantic_segmentation.models.contextnet')
-    finally:
-        sys.path.remove('/root/reference')
-    for ours, theirs in ((O.build('fastscnn'), rf.fastscnn(3, 19)), (O.build('contextnet12'), rc.contextnet12(3, 19))):
-        a, b = ours.state_dict(), theirs.state_dict()
-        assert list(a) == list(b)
-        assert all(a[k].shape == b[k].shape and a[k].dtype == b[k].dtype for k in a)
+def test_oracle_keys_equal_reference(golden_dir):
+    """Key order, shapes and dtypes of the oracle's state_dict == the reference's (make_golden.py gen_keys)."""
+    g = cases.load_npz(os.path.join(golden_dir, 'state_dict_keys.npz'))
+    for name in ('fastscnn', 'contextnet12'):
+        a = O.build(name).state_dict()
+        assert list(a) == list(g[name + '/keys'])
+        assert [','.join(str(d) for d in v.shape) for v in a.values()] == list(g[name + '/shapes'])
+        assert [str(v.dtype) for v in a.values()] == list(g[name + '/dtypes'])
 
 
 @pytest.mark.parametrize('name', ['fastscnn', 'contextnet14'])
