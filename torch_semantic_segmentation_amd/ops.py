@@ -2132,6 +2132,8 @@ def ssnbt_tail(left, right, x, drop_p, training):
     ok = (fuse_ssnbt_tail and dl.link is not None and dr.link is not None and not dl.relu and not dr.relu
           and dl.raw.shape == dr.raw.shape and dl.raw.dtype == dr.raw.dtype == x.dtype and dl.raw.shape[1] % 8 == 0
           and x.shape[1] == 2 * dl.raw.shape[1] and tuple(x.shape[2:]) == tuple(dl.raw.shape[2:]) and x.shape[0] == dl.raw.shape[0])
+    # the envelope of tss_ssnbt_tail_fwd / _bwd (csrc/ssnbt.hip): C <= 512, pitches % 8, 16-byte aligned tensors
+    ok = ok and x.shape[1] <= 512 and all(ld(t) % 8 == 0 and t.data_ptr() % 16 == 0 for t in (dl.raw, dr.raw, x))
     if not ok:
         y = concat_joined([dl, dr], relu=False)
         y = channel_dropout(y, drop_p, training)
@@ -2163,7 +2165,7 @@ class SSnbtTailFn(Function):
     def backward(ctx, dout):
         out, l, r, m = ctx.saved_tensors
         ll, lr = ctx.cfg.links
-        dout = to_nhwc(dout)
+        dout = to_nhwc(dout)       # is_nhwc: a view with a pitch % 8 or a pointer not 16-byte aligned is copied (the kernel's envelope)
         B, C, H, W = out.shape
         half = C // 2
         gs = new_nhwc(B, C, H, W, dout.dtype, dout.device)
