@@ -12,6 +12,7 @@ ordinary tensors with ordinary gradients.
 
 There is no torch/ATen fallback here: every operator calls the C ABI and raises if it is unavailable.
 """
+import collections
 import ctypes
 import os
 import threading
@@ -240,6 +241,30 @@ def _bn_bwd_finalize(link, C, acc, dgamma, dbeta, st, training=None):
          ptr(dgamma), ptr(dbeta), ptr(link.ga), ptr(link.gb), ptr(link.gce), C, st)
 
 
+def _bn_backward_prologue(link, has_affine, p_gamma, p_beta, C, y, dev, st):
+    """What the backward of a unit with a BatchNorm behind it does first: d(gamma) / d(beta) targets (the parameters' own .grad under
+    direct_grads, else one fresh pair), the finalize, and the coefficients its kernels apply on load.
+    Returns (d(gamma), d(beta) for autograd -- None when accumulated directly --, y, ga, gb, gce, mean); a frozen BatchNorm needs
+    neither y nor gb / gce / mean (None), a unit without BatchNorm (link None) none of them."""
+    if link is None:
+        return None, None, None, None, None, None, None
+    dgamma = dbeta = None
+    acc = 0
+    if has_affine:
+        dgamma, dbeta = _direct_target(p_gamma), _direct_target(p_beta)
+        if dgamma is not None and dbeta is not None:
+            acc = 1
+        else:
+            dgb = torch.empty((2, C), dtype=torch.float32, device=dev)
+            dgamma, dbeta = dgb[0], dgb[1]
+    _bn_bwd_finalize(link, C, acc, dgamma, dbeta, st)       # (local or cross-replica statistics: link.sync)
+    if acc:
+        dgamma = dbeta = None
+    if not link.training:
+        return dgamma, dbeta, None, link.ga, None, None, None
+    return dgamma, dbeta, y, link.ga, link.gb, link.gce, link.mean
+
+
 def _flush_dw_reductions(ps):
     with _lock:
         jobs = list(ps.dw)
@@ -278,6 +303,15 @@ def _defer_dw_reduction(ws, dw, ncols, nrows, param=None):
         _flush_dw_reductions(ps)
     with _lock:
         ps.dw.append((ws, dw, ncols, nrows))
+
+
+def _add_rows(ws, target, ncols, nrows, param, returned):
+    """target += the nrows rows of per-block partial sums in ws: queued for the one launch at the end of the pass when `target` is
+    the parameter's own gradient buffer (returned None), at once when it goes back to autograd (complete on return)."""
+    if returned is None and batch_dw_reductions:
+        _defer_dw_reduction(ws, target, ncols, nrows, param)
+    else:
+        _reduce_rows_now(ws, target, ncols, nrows)
 
 
 class _PerThread:
@@ -629,6 +663,16 @@ def _direct_target(param):
     if _DIRECT[0] and g is not None and g.dtype == torch.float32 and g.is_contiguous() and g.is_cuda:
         return g
     return None
+
+
+def _grad_target(param, like, shape=None):
+    """(buffer the kernels add a parameter's gradient into, the tensor to hand back to autograd): the parameter's own .grad and None
+    under direct_grads, else one fresh zero-filled tensor for both (zeros_like(like), or float32 `shape` on like's device)."""
+    g = _direct_target(param)
+    if g is not None:
+        return g, None
+    g = torch.zeros_like(like) if shape is None else torch.zeros(shape, dtype=torch.float32, device=like.device)
+    return g, g
 
 
 # ----------------------------------------------------------------------------- layout helpers
@@ -1019,11 +1063,7 @@ def conv_unit_multi(branches, conv, bn=None, relu=False):
     weight = conv.weight
     call('tss_pwconv_fwd_multi', srcs, lds, means, scales, biases, n, int(in_relu), ptr(weight), _shadow(weight, 0), ptr(_f32(conv.bias)),
          ptr(y), ld(y), P, Cout, N.dtype_code(torch.bfloat16), st)
-    link = None
-    if bn is not None:
-        gamma, beta = _f32(bn.weight), _f32(bn.bias)
-        link = BNLink(Cout, P, False, gamma, beta, dev, slabs=False)
-        _finalize_forward(link, bn, False, P, Cout, gamma, st)
+    link = _frozen_link(bn, Cout, P, dev, st)[0] if bn is not None else None
     return Deferred(y, link, relu)
 
 
@@ -1059,9 +1099,7 @@ def conv_unit_joined(x, block, residual=None, relu=True):
             return None
     d = as_deferred(x).take()
     dev, st = raw.device, stream()
-    gamma, beta = _f32(bn.weight), _f32(bn.bias)
-    link = BNLink(Cout, P, False, gamma, beta, dev, slabs=False)
-    _finalize_forward(link, bn, False, P, Cout, gamma, st)
+    link, beta = _frozen_link(bn, Cout, P, dev, st)
     y = new_nhwc(B, Cout, H, W, raw.dtype, dev)
     call('tss_pwconv_fwd_joined', ptr(d.raw), ld(d.raw), *_aff(d.link), int(d.relu), ptr(conv.weight), _shadow(conv.weight, 0),
          ptr(_f32(conv.bias)), ptr(link.mean), ptr(link.scale), ptr(beta), ptr(residual), ld(residual) if residual is not None else 0,
@@ -1110,12 +1148,7 @@ def bottleneck_eval(x, conv1, conv2, conv3):
         return None
     x = to_nhwc(x)
     dev, st = x.device, stream()
-    links = []
-    for bn, C in ((bn1, Cmid), (bn2, Cmid), (bn3, Cout)):
-        gamma, beta = _f32(bn.weight), _f32(bn.bias)
-        link = BNLink(C, 1, False, gamma, beta, dev, slabs=False)
-        _finalize_forward(link, bn, False, 1, C, gamma, st)
-        links.append((link, beta))
+    links = [_frozen_link(bn, C, 1, dev, st) for bn, C in ((bn1, Cmid), (bn2, Cmid), (bn3, Cout))]
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     y = new_nhwc(B, Cout, Ho, Wo, x.dtype, dev)
     aff = []
@@ -1209,6 +1242,484 @@ def _finalize_forward(link, bn, training, P, Cout, gamma, st):
                  float(bn.eps), ptr(link.mean), ptr(link.invstd), ptr(link.scale), Cout, st)
 
 
+def _frozen_link(bn, C, P, dev, st):
+    """(link, beta) of a BatchNorm with frozen statistics behind an eval-only fast path: mean / scale from the running statistics,
+    no slab rows (nothing is summed)."""
+    gamma, beta = _f32(bn.weight), _f32(bn.bias)
+    link = BNLink(C, P, False, gamma, beta, dev, slabs=False)
+    _finalize_forward(link, bn, False, P, C, gamma, st)
+    return link, beta
+
+
+# What one ConvUnitFn.forward hands the handler of its kind: aff = the pending BatchNorm of the input (applied on load),
+# stats = the slab rows of this layer's own BatchNorm (NULL when it keeps none).
+_FwdArgs = collections.namedtuple('_FwdArgs', 'cfg x weight bias y aff stats B Hin Win Cout P s d dt dev st')
+
+
+def _fwd_stem(f):
+    cfg, y = f.cfg, f.y
+    if f.bias is not None:
+        raise NotImplementedError('HIP path: stem convolution with bias')
+    call('tss_stem3x3_fwd', ptr(f.x), int(cfg.image_f32), ptr(f.weight), ptr(y), ld(y), f.stats,
+         f.B, cfg.cin, f.Hin, f.Win, f.Cout, f.s, f.dt, f.st)
+
+
+def _fwd_pw(f):
+    """Returns the dropout mask of a dropout-on-load layer (saved for the backward sweep), else None."""
+    cfg, x, weight, y, st = f.cfg, f.x, f.weight, f.y, f.st
+    if not cfg.drop_p:
+        call('tss_pwconv_fwd', ptr(x), ld(x), *f.aff, int(cfg.in_relu), ptr(weight), _shadow(weight, 0), ptr(f.bias),
+             ptr(y), ld(y), f.stats, f.P, cfg.cin, f.Cout, f.dt, st)
+        return None
+    # the mask is drawn by its own small launch (one byte per 8 channels), applied on load here and in the backward sweep
+    mask = torch.empty((f.P, 16), dtype=torch.uint8, device=f.dev)
+    counter = _dropout_counter(f.dev)
+    call('tss_dropout_mask', ptr(counter), ptr(mask), f.P, cfg.cin, cfg.drop_p, st)
+    if _drop_mask_probe is not None:         # tests read the mask back to hand the oracle the same one
+        _drop_mask_probe.append(mask)
+    call('tss_pwconv_fwd_drop', ptr(x), ld(x), *f.aff, int(cfg.in_relu), ptr(weight), _shadow(weight, 0), ptr(f.bias),
+         ptr(y), ld(y), ptr(mask), cfg.drop_p, ptr(counter), f.P, cfg.cin, f.Cout, f.dt, st)
+    return mask
+
+
+def _fwd_dw(f):
+    cfg, x, y = f.cfg, f.x, f.y
+    if f.bias is not None:
+        raise NotImplementedError('HIP path: depthwise convolution with bias')
+    call('tss_dwconv3x3_fwd', ptr(x), ld(x), *f.aff, int(cfg.in_relu), ptr(f.weight),
+         ptr(y), ld(y), f.stats, f.B, f.Hin, f.Win, f.Cout, f.s, f.d, f.dt, f.st)
+
+
+def _fwd_ckk(f):
+    cfg, x, y, Cout, st = f.cfg, f.x, f.y, f.Cout, f.st
+    nt = cfg.kh * cfg.kw
+    w_tnc = torch.empty((nt, Cout, cfg.cin), dtype=torch.float32, device=f.dev)
+    call('tss_permute_wtaps', ptr(f.weight), ptr(w_tnc), None, Cout, cfg.cin, nt, st)
+    call('tss_convkxk_fwd', ptr(x), ld(x), *f.aff, int(cfg.in_relu), ptr(w_tnc), ptr(f.bias), ptr(y), ld(y), f.stats,
+         f.B, f.Hin, f.Win, cfg.cin, Cout, cfg.kh, cfg.kw, f.s, f.d, f.dt, st)
+
+
+def _fwd_dense(f):
+    if f.bias is not None:          # the 3x3 kernels add no bias: the general tap-grid kernel
+        return _fwd_ckk(f)
+    cfg, x, weight, y, Cout, st = f.cfg, f.x, f.weight, f.y, f.Cout, f.st
+    w_tnc = w_tnc16 = None
+    if _conv3x3_stream(x.dtype, cfg.cin, Cout, f.s, cfg.in_link, cfg.in_relu) or _conv3x3_lean(x.dtype, cfg.cin, Cout, f.s, f.d):
+        # bf16 tap-major copy: the weight-stationary / register-streamed kernels (wstat.hip, atrous.hip), the LDS-halo kernel (conv3x3.hip)
+        w_tnc16 = _W3X3.get(weight.data_ptr()) if _W3X3 else None          # prepared ahead of the forward (Dense3x3Shadows)
+        if w_tnc16 is None:
+            w_tnc16 = torch.empty((9, Cout, cfg.cin), dtype=torch.bfloat16, device=f.dev)
+            call('tss_permute_w3x3_bf16', ptr(weight), ptr(w_tnc16), None, Cout, cfg.cin, st)
+    else:
+        w_tnc = torch.empty((9, Cout, cfg.cin), dtype=torch.float32, device=f.dev)
+        call('tss_permute_w3x3', ptr(weight), ptr(w_tnc), None, Cout, cfg.cin, st)
+    call('tss_conv3x3_fwd', ptr(x), ld(x), *f.aff, int(cfg.in_relu), ptr(w_tnc), ptr(w_tnc16),
+         ptr(y), ld(y), f.stats, f.B, f.Hin, f.Win, cfg.cin, Cout, f.s, f.d, f.dt, st)
+
+
+def _fwd_dense1d(f):
+    cfg, x, weight, y, Cout, st = f.cfg, f.x, f.weight, f.y, f.Cout, f.st
+    axis = 0 if cfg.kind == 'dense1d_w' else 1
+    if N.lib().tss_conv1d3_lean_supported(cfg.cin, Cout, f.dt):      # reads the layer's own weight tensor
+        call('tss_conv1d3_fwd_w', ptr(x), ld(x), *f.aff, int(cfg.in_relu), ptr(weight), ptr(f.bias), ptr(y), ld(y), f.stats,
+             f.B, f.Hin, f.Win, cfg.cin, Cout, axis, f.d, f.dt, st)
+    else:
+        w_tnc = torch.empty((3, Cout, cfg.cin), dtype=torch.float32, device=f.dev)
+        call('tss_permute_wtaps', ptr(weight), ptr(w_tnc), None, Cout, cfg.cin, 3, st)
+        call('tss_conv1d3_fwd', ptr(x), ld(x), *f.aff, int(cfg.in_relu), ptr(w_tnc), ptr(f.bias), ptr(y), ld(y), f.stats,
+             f.B, f.Hin, f.Win, cfg.cin, Cout, axis, f.d, f.dt, st)
+
+
+# keyed by what _classify returns
+_FWD = {'stem': _fwd_stem, 'pw': _fwd_pw, 'dw': _fwd_dw, 'ckk': _fwd_ckk, 'dense': _fwd_dense,
+        'dense1d_w': _fwd_dense1d, 'dense1d_h': _fwd_dense1d}
+
+
+class _Bwd:
+    """What one ConvUnitFn.backward hands the handler of its kind (built once per layer and pass; every field is bound for every kind).
+    y, ga are what _bn_backward_prologue left (y None: no BatchNorm behind the layer, or a frozen one).
+    gargs: the gradient operand -- e, y and the BatchNorm-backward coefficients applied on load.  xargs: the layer's input with its
+    pending BatchNorm / ReLU.  margs: the same where a backward-data kernel masks / sums for that pending BatchNorm (deferred_in),
+    else NULLs; bst: the slab rows those sums go to.  dw / dw_ret: _grad_target of the weight.  st: this stream, wst: the stream of
+    the weight-gradient launch (the side stream when there is one)."""
+    __slots__ = ('cfg', 'x', 'weight', 'y', 'e', 'drop_mask', 'ga', 'gargs', 'xargs', 'margs', 'bst', 'B', 'Hin', 'Win', 'Cin', 'Cout',
+                 'P', 's', 'd', 'dt', 'dev', 'st', 'wst', 'side', 'need_dx', 'has_bias', 'dw', 'dw_ret', 'p_weight', 'p_bias',
+                 'link', 'il', 'deferred_in', 'temps')
+
+    def tmp(self, shape, dtype=torch.float32):
+        """A workspace / weight permute for this layer's launches.  It stays alive until backward() returns: the launch that uses it
+        may be on the side stream, which joins only there."""
+        t = torch.empty(shape, dtype=dtype, device=self.dev)
+        self.temps.append(t)
+        return t
+
+
+# what a handler returns next to e_in: (rows of weight-gradient partial sums to add after the side stream has joined: (ws, nrows,
+# ncols) or None; the handler has produced the bias gradient; that gradient where it goes back to autograd)
+_NO_EXTRAS = (None, False, None)
+
+
+def _wgrad_side_stream(cfg, need_dx, drop_mask, P, dev):
+    """Backward-weight and backward-data of one layer are independent: the side stream the weight gradient goes to, or None."""
+    if (overlap_wgrad and need_dx and cfg.kind != 'stem' and drop_mask is None
+            and overlap_min_elems <= P * (cfg.cin + cfg.cout) <= overlap_max_elems):
+        return _side_stream(dev)
+    return None
+
+
+def _new_e_in(c):
+    """The input-gradient tensor, when this backward writes one (dropout on load: always -- the one sweep is the only backward)."""
+    if c.need_dx or c.drop_mask is not None:
+        return new_nhwc(c.B, c.Cin, c.Hin, c.Win, c.e.dtype, c.dev)
+    return None
+
+
+def _res_grad(cfg):
+    """(fork, the gradient the other consumer of this layer's input left for the epilogue of its backward-data kernel, or None)"""
+    fork = cfg.res_fork
+    return fork, (fork.g2 if fork is not None else None)
+
+
+def _bwd_stem(c):
+    ws = c.tmp((N.stat_slabs(), c.Cout * 28))
+    call('tss_stem3x3_bwd_weight', *c.gargs, ptr(c.x), int(c.cfg.image_f32), ptr(c.dw), ptr(ws),
+         c.B, c.Cin, c.Hin, c.Win, c.Cout, c.s, c.dt, c.st)
+    if c.need_dx:
+        raise NotImplementedError('HIP path: gradient with respect to the input image is not implemented')
+    return None, _NO_EXTRAS
+
+
+# ---- 1x1: one of three strategies, chosen once
+
+def _bwd_pw(c):
+    P, Cin, Cout, dt = c.P, c.Cin, c.Cout, c.dt
+    # few channels, many pixels: input gradient and weight gradient in ONE sweep (csrc/pwbwd.hip): e, y, x read once
+    fused = bool(fuse_pw_backward and c.need_dx and c.side is None and c.e.dtype == torch.bfloat16
+                 and not N.fast_paths_disabled() and N.lib().tss_pwconv_bwd_fused_preferred(P, Cin, Cout, dt))
+    if c.drop_mask is not None:        # dropout on load: the one sweep is the only backward that knows the mask
+        fused = True
+    if fused:
+        return _bwd_pw_fused(c)
+    # the large layers (128 -> 128, 64 -> 384, 384 -> 64 with enough pixels): one sweep with the whole weight-gradient tile in
+    # the registers of one 512-thread block per CU (csrc/pwsweep.hip)
+    radd_s = _res_grad(c.cfg)[1]
+    sweep = bool(sweep_pw_backward and c.need_dx and c.side is None and c.e.dtype == torch.bfloat16 and c.x.dtype == torch.bfloat16
+                 and not N.fast_paths_disabled()
+                 and N.lib().tss_pwconv_bwd_sweep_preferred(P, Cin, Cout, int(bool(c.deferred_in)), dt)
+                 and (radd_s is None or (not c.deferred_in and radd_s.dtype == c.e.dtype and tuple(radd_s.shape) == tuple(c.x.shape)
+                                         and is_nhwc(radd_s))))
+    if sweep:
+        return _bwd_pw_sweep(c)
+    return _bwd_pw_split(c)
+
+
+def _bwd_pw_fused(c):
+    """tss_pwconv_bwd_fused[_drop]: input, weight and bias gradient of the layer from one sweep."""
+    e_in = _new_e_in(c)
+    if e_in is None:
+        return None, _NO_EXTRAS
+    P, Cin, Cout, weight, drop_mask = c.P, c.Cin, c.Cout, c.weight, c.drop_mask
+    rows = (N.lib().tss_pwconv_bwd_fused_drop_rows(P) if drop_mask is not None
+            else N.lib().tss_pwconv_bwd_fused_rows(P, Cin, Cout))
+    ws = c.tmp((rows, Cout * Cin))
+    bws = dbias = dbias_ret = None
+    if c.has_bias:          # the bias gradient leaves the same sweep as per-block rows (no colsum launch, no atomics)
+        bws = c.tmp((rows, Cout))
+        dbias, dbias_ret = _grad_target(c.p_bias, weight, Cout)
+    if drop_mask is not None:
+        call('tss_pwconv_bwd_fused_drop', *c.gargs, ptr(weight), *c.xargs, int(bool(c.deferred_in)), ptr(drop_mask),
+             c.cfg.drop_p, ptr(e_in), ld(e_in), c.bst, ptr(ws), ptr(bws), P, Cin, Cout, c.dt, c.st)
+    else:
+        call('tss_pwconv_bwd_fused', *c.gargs, ptr(weight), _shadow(weight, 1), *c.xargs, int(bool(c.deferred_in)),
+             ptr(e_in), ld(e_in), c.bst, ptr(ws), ptr(bws), P, Cin, Cout, c.dt, c.st)
+    # weight and bias rows together: both queued for the end of the pass (summed with the depthwise rows), or both added now because
+    # one of the two gradients goes back to autograd
+    returned = c.dw_ret if c.dw_ret is not None else dbias_ret
+    _add_rows(ws, c.dw, Cout * Cin, rows, c.p_weight, returned)
+    if bws is not None:
+        _add_rows(bws, dbias, Cout, rows, c.p_bias, returned)
+    return e_in, (None, True, dbias_ret)
+
+
+def _bwd_pw_sweep(c):
+    """tss_pwconv_bwd_sweep: input and weight gradient from one sweep; adds the skip's gradient in its epilogue."""
+    e_in = _new_e_in(c)
+    if e_in is None:
+        return None, _NO_EXTRAS
+    P, Cin, Cout, weight = c.P, c.Cin, c.Cout, c.weight
+    fork, radd_s = _res_grad(c.cfg)
+    rows = N.lib().tss_pwconv_bwd_sweep_rows(P, Cin, Cout)
+    ws = c.tmp((rows, Cout * Cin))
+    wT = _shadow(weight, 1)
+    hold_wT = None
+    if wT is None:          # no current shadow (plain autograd outside a Trainer): a transpose of this call's own
+        hold_wT = weight.detach().reshape(Cout, Cin).t().contiguous().to(torch.bfloat16)
+        wT = ptr(hold_wT)
+    call('tss_pwconv_bwd_sweep', *c.gargs, wT, *c.xargs, int(bool(c.deferred_in)), ptr(radd_s),
+         ld(radd_s) if radd_s is not None else 0, ptr(e_in), ld(e_in), c.bst, ptr(ws), P, Cin, Cout, c.dt, c.st)
+    del hold_wT
+    if radd_s is not None:
+        fork.consumed = True
+    _add_rows(ws, c.dw, Cout * Cin, rows, c.p_weight, c.dw_ret)       # summed with the depthwise rows, at the end of the pass
+    return e_in, _NO_EXTRAS
+
+
+def _bwd_pw_split(c):
+    """Weight gradient and input gradient as two launches: the weight gradient at once, or postponed behind the input gradient until
+    the next BatchNorm-backward finalize of this pass is due, which it then carries (see _Pass.wg)."""
+    P, Cin, Cout, dt = c.P, c.Cin, c.Cout, c.dt
+    nws = N.lib().tss_pwconv_bwd_weight_ws(P, Cin, Cout, dt) if c.y is not None else 0
+    ws = c.tmp(nws) if nws else None
+    defer = 1 if (ws is not None and c.need_dx and c.side is None) else 0   # a backward-data launch carries the reduce
+    postponed = bool(defer and postpone_wgrad and c.dw_ret is None and not c.cfg.overlapped
+                     and _backward_task() != -1 and not _param_observed(c.p_weight))
+    if not postponed:
+        _flush_wg(c.st)
+        _flush_red(c.st)
+        call('tss_pwconv_bwd_weight', *c.gargs, *c.xargs, ptr(c.dw), ptr(ws), defer, P, Cin, Cout, dt, None, c.wst)
+    e_in = _new_e_in(c)
+    if e_in is None:
+        return None, _NO_EXTRAS
+    if postponed:      # this launch carries the slot reduction of an EARLIER layer's weight gradient, if one waits
+        red, hold = _take_red(c.dev)
+    else:
+        red, hold = ((ptr(ws), ptr(c.dw), 0, 0, 0) if defer else (None, None, 0, 0, 0)), None
+    _pw_data_grad(c, e_in, red)
+    del hold
+    if postponed:
+        _postpone_pw_wgrad(c, ws)
+    return e_in, _NO_EXTRAS
+
+
+def _pw_data_grad(c, e_in, red):
+    """The backward-data launch of a 1x1 layer; `red`: the weight-gradient slot reduction that rides in front of its grid."""
+    e, x, y, weight, P, Cin, Cout, dt, st = c.e, c.x, c.y, c.weight, c.P, c.Cin, c.Cout, c.dt, c.st
+    deferred_in = c.deferred_in
+    fork, radd = _res_grad(c.cfg)
+    radd_ok = (radd is not None and not deferred_in and y is not None and e.dtype == torch.bfloat16 and radd.dtype == e.dtype
+               and tuple(radd.shape) == tuple(e_in.shape) and N.lib().tss_pwconv_bwd_data_radd_supported(P, Cin, Cout, dt))
+    pj = c.cfg.prev_join
+    if (pj is not None and (radd is None or radd_ok) and not deferred_in and y is not None and e.dtype == torch.bfloat16
+            and P * Cin <= fuse_join_backward_max
+            and pj.j_a is not None and pj.j_ptr == x.data_ptr() and tuple(pj.j_a.shape) == tuple(x.shape)
+            and is_nhwc(pj.j_a) and N.lib().tss_pwconv_bwd_data_radd_supported(P, Cin, Cout, dt)):
+        # this layer's input is a block output: that join's backward (ReLU mask + BatchNorm-backward sums) in the epilogue
+        jl = pj.a_link
+        call('tss_pwconv_bwd_data_joined', *c.gargs, ptr(weight), _shadow(weight, 1), ptr(e_in), ld(e_in), *red,
+             ptr(radd), ld(radd) if radd is not None else 0, ptr(x), ld(x), ptr(pj.j_a), ld(pj.j_a), ptr(jl.mean),
+             ptr(jl.bstats), P, Cin, Cout, dt, st)
+        pj.fused_e = e_in
+        if radd is not None:
+            fork.consumed = True
+    elif radd_ok:
+        call('tss_pwconv_bwd_data_radd', *c.gargs, ptr(weight), _shadow(weight, 1), ptr(e_in), ld(e_in),
+             *red, ptr(radd), ld(radd), P, Cin, Cout, dt, st)
+        fork.consumed = True
+    else:
+        call('tss_pwconv_bwd_data', *c.gargs, ptr(weight), _shadow(weight, 1), *c.margs, ptr(e_in), ld(e_in), c.bst,
+             *red, P, Cin, Cout, dt, st)
+
+
+def _postpone_pw_wgrad(c, ws):
+    """Register this layer's weight-gradient launch with the running pass: the next BatchNorm-backward finalize on this stream rides
+    in front of its grid (_bn_bwd_finalize), or the end of the pass flushes it.  The closure's defaults keep every tensor the launch
+    reads alive until then; its slot reduction waits in _Pass.red for the next backward-data launch."""
+    st = c.st
+    _flush_wg(st)          # at most one weight gradient waits per stream
+    own = torch.cuda.current_stream(c.dev)
+    ps = _cur_pass()
+
+    def launch_wg(fin, _keep=(c.e, c.y, c.x, c.link, c.il, ws, c.dw), _args=(c.gargs, c.xargs, ptr(c.dw), ptr(ws), c.P, c.Cin, c.Cout, c.dt),
+                  _sid=st, _own=own, _ps=ps):
+        ga_, xa_, dwp, wsp, P_, K_, N_, dt_ = _args
+        call('tss_pwconv_bwd_weight', *ga_, *xa_, dwp, wsp, 1, P_, K_, N_, dt_,
+             ctypes.byref(fin) if fin is not None else None, _sid)
+        _flush_red(_sid, _ps)
+        with _lock:
+            _ps.red[_sid] = (_keep[5], _keep[6], P_, K_, N_, _keep[0].device, _own)
+    with _lock:
+        ps.wg[st] = (launch_wg, c.dev, own)
+
+
+# ---- the other kinds
+
+def _bwd_dw(c):
+    weight, B, Hin, Win, Cout, s, d, dt, st = c.weight, c.B, c.Hin, c.Win, c.Cout, c.s, c.d, c.dt, c.st
+    ws = c.tmp((N.stat_slabs(), Cout * 9))
+    defer = 1 if (c.need_dx and c.side is None) else 0      # backward-data carries the row reduction
+    # input gradient and weight gradient in ONE sweep when the shape allows (e, y, x read once)
+    fused = bool(defer and ((fuse_dw_backward and N.lib().tss_dwconv3x3_bwd_fused_supported(Cout, s, d, dt))
+                            or N.lib().tss_dwconv3x3_bwd_fused_preferred(Cout, s, d, dt)))
+    if not fused:
+        call('tss_dwconv3x3_bwd_weight', *c.gargs, *c.xargs, ptr(c.dw), ptr(ws), defer, B, Hin, Win, Cout, s, d, dt, c.wst)
+    e_in = _new_e_in(c)
+    if e_in is None:
+        return None, _NO_EXTRAS
+    if fused and c.dw_ret is None and batch_dw_reductions:
+        # the rows of per-block partial sums stay in ws; they are added to the (direct) gradient together with
+        # those of every other depthwise layer, in one launch at the end of this backward pass
+        rows = ctypes.c_int(0)
+        call('tss_dwconv3x3_bwd_fused_sweep', *c.gargs, ptr(weight), *c.xargs, int(bool(c.deferred_in)), ptr(e_in), ld(e_in),
+             c.bst, ptr(ws), B, Hin, Win, Cout, s, d, dt, st, ctypes.byref(rows))
+        _add_rows(ws, c.dw, Cout * 9, rows.value, c.p_weight, c.dw_ret)      # (queued: the test above is _add_rows' own)
+    elif fused:
+        call('tss_dwconv3x3_bwd_fused', *c.gargs, ptr(weight), *c.xargs, int(bool(c.deferred_in)), ptr(e_in), ld(e_in),
+             c.bst, ptr(ws), ptr(c.dw), B, Hin, Win, Cout, s, d, dt, st)
+    else:
+        call('tss_dwconv3x3_bwd_data', *c.gargs, ptr(weight), *c.margs, ptr(e_in), ld(e_in), c.bst,
+             ptr(ws) if defer else None, ptr(c.dw) if defer else None, B, Hin, Win, Cout, s, d, dt, st)
+    return e_in, _NO_EXTRAS
+
+
+def _tap_sweep_wgrad(c, entry, rows, taps, *geom):
+    """Weight gradient of a tap-row layer from one sweep over e, y and x (csrc/fc1d.hip, fcg.hip, sconv.hip).  The sweep may be on the
+    side stream: its rows of per-block partial sums are queued / added after the join, together with those of every other such layer
+    in one launch at the end of the backward pass.  Returns the handler's rows_after_join."""
+    ncols = c.Cout * c.Cin * taps
+    ws = c.tmp((rows, ncols))
+    call(entry, *c.gargs, *c.xargs, ptr(ws), c.B, c.Hin, c.Win, c.Cin, c.Cout, *geom, c.dt, c.wst)
+    return ws, rows, ncols
+
+
+def _pw_wgrad_of_columns(c, gargs, col, K):
+    """The pointwise weight-gradient kernel on an unfolded input (col: bf16 [P][K], no pending BatchNorm), complete on return."""
+    nws = N.lib().tss_pwconv_bwd_weight_ws(c.P, K, c.Cout, c.dt)
+    ws = c.tmp(nws) if nws else None
+    call('tss_pwconv_bwd_weight', *gargs, ptr(col), K, None, None, None, 0, ptr(c.dw), ptr(ws), 0,
+         c.P, K, c.Cout, c.dt, None, c.wst)
+
+
+def _dense1d_wgrad(c, axis):
+    """Weight gradient of a 1x3 / 3x1 layer; returns rows_after_join."""
+    e, y, P, Cin, Cout, d, dt = c.e, c.y, c.P, c.Cin, c.Cout, c.d, c.dt
+    rows = N.lib().tss_conv1d3_bwd_weight_rows(P, Cin, Cout, dt)
+    rows_w = 0 if rows else N.lib().tss_convtap_bwd_weight_rows(P, Cin, Cout, 3, dt)      # 128-channel layers (csrc/fcg.hip)
+    if rows_w:
+        return _tap_sweep_wgrad(c, 'tss_convtap_bwd_weight_sweep', rows_w, 3, 3, axis, d)
+    if rows:
+        return _tap_sweep_wgrad(c, 'tss_conv1d3_bwd_weight_sweep', rows, 3, axis, d)
+    if (e.dtype == torch.bfloat16 and Cin % 8 == 0 and Cout % 8 == 0 and unfold_1d_wgrad and not N.fast_paths_disabled()):
+        # unfold once (bf16 [P][Cin*3], column c*3 + tap), then the pipelined pointwise MFMA weight-gradient kernel with
+        # K = 3*Cin writes torch's [N][Cin][1][3] / [N][Cin][3][1] layout directly (as the dense 3x3)
+        col = c.tmp((P, Cin * 3), torch.bfloat16)
+        call('tss_im2col1d3', *c.xargs, ptr(col), c.B, c.Hin, c.Win, Cin, axis, d, dt, c.wst)
+        g_ = c.gargs
+        if y is None:        # no BatchNorm behind this layer (or a frozen one): g = ga * e, written as ga * e + 0 * e + 0
+            one, zero = _const_rows(c.dev, Cout)
+            g_ = (ptr(e), ld(e), ptr(e), ld(e), ptr(c.ga) if c.ga is not None else ptr(one), ptr(zero), ptr(zero), ptr(zero))
+        _pw_wgrad_of_columns(c, g_, col, Cin * 3)
+    else:
+        call('tss_conv1d3_bwd_weight', *c.gargs, *c.xargs, ptr(c.dw), c.B, c.Hin, c.Win, Cin, Cout, axis, d, dt, c.wst)
+    return None
+
+
+def _bwd_dense1d(c):
+    weight, B, Hin, Win, Cin, Cout, d, dt, st = c.weight, c.B, c.Hin, c.Win, c.Cin, c.Cout, c.d, c.dt, c.st
+    axis = 0 if c.cfg.kind == 'dense1d_w' else 1
+    extras = (_dense1d_wgrad(c, axis), False, None)
+    e_in = _new_e_in(c)
+    if e_in is None:
+        return None, extras
+    if N.lib().tss_conv1d3_lean_supported(Cin, Cout, dt):
+        call('tss_conv1d3_bwd_data_w', *c.gargs, ptr(weight), *c.margs, ptr(e_in), ld(e_in), c.bst,
+             B, Hin, Win, Cin, Cout, axis, d, dt, st)
+    else:
+        w_tcn = c.tmp((3, Cin, Cout))
+        call('tss_permute_wtaps', ptr(weight), None, ptr(w_tcn), Cout, Cin, 3, st)
+        call('tss_conv1d3_bwd_data', *c.gargs, ptr(w_tcn), *c.margs, ptr(e_in), ld(e_in), c.bst,
+             B, Hin, Win, Cin, Cout, axis, d, dt, st)
+    return e_in, extras
+
+
+def _kxk_data_grad(c, e_in):
+    """General tap grid / transposed gather of a strided layer (generic implicit-GEMM kernel)."""
+    cfg, Cin, Cout, st = c.cfg, c.Cin, c.Cout, c.st
+    nt = cfg.kh * cfg.kw
+    w_tcn = c.tmp((nt, Cin, Cout))
+    call('tss_permute_wtaps', ptr(c.weight), None, ptr(w_tcn), Cout, Cin, nt, st)
+    call('tss_convkxk_bwd_data', *c.gargs, ptr(w_tcn), *c.margs, ptr(e_in), ld(e_in), c.bst,
+         c.B, c.Hin, c.Win, Cin, Cout, cfg.kh, cfg.kw, c.s, c.d, c.dt, st)
+
+
+def _bwd_ckk(c):
+    cfg, P, Cin, Cout, s, d, dt = c.cfg, c.P, c.Cin, c.Cout, c.s, c.d, c.dt
+    rows_after_join = None
+    if (s == 1 and (cfg.kh, cfg.kw) in ((1, 5), (5, 1)) and N.lib().tss_convtap_bwd_weight_rows(P, Cin, Cout, 5, dt)):
+        # ESNet's 64-channel 1x5 / 5x1 layers: one sweep over e, y and x (csrc/fcg.hip), rows added at the end of the pass
+        rows = N.lib().tss_convtap_bwd_weight_rows(P, Cin, Cout, 5, dt)
+        rows_after_join = _tap_sweep_wgrad(c, 'tss_convtap_bwd_weight_sweep', rows, 5, 5, 0 if cfg.kh == 1 else 1, d)
+    else:
+        call('tss_convkxk_bwd_weight', *c.gargs, *c.xargs, ptr(c.dw), c.B, c.Hin, c.Win, Cin, Cout, cfg.kh, cfg.kw, s, d, dt, c.wst)
+    e_in = _new_e_in(c)
+    if e_in is not None:
+        _kxk_data_grad(c, e_in)
+    return e_in, (rows_after_join, False, None)
+
+
+def _dense_wgrad(c):
+    """Weight gradient of a dense 3x3 layer; returns rows_after_join."""
+    e, B, Hin, Win, P, Cin, Cout, s, d, dt = c.e, c.B, c.Hin, c.Win, c.P, c.Cin, c.Cout, c.s, c.d, c.dt
+    if (s == 2 and d == 1 and N.lib().tss_sconv_bwd_weight_rows(B, Hin, Win, Cin, Cout, dt)):
+        # stride-2 3x3 of the downsampling blocks: one sweep over e and x (csrc/sconv.hip), rows added at the end of the pass
+        rows = N.lib().tss_sconv_bwd_weight_rows(B, Hin, Win, Cin, Cout, dt)
+        return _tap_sweep_wgrad(c, 'tss_sconv_bwd_weight_sweep', rows, 9)
+    if (e.dtype == torch.bfloat16 and s == 1 and c.y is not None and (Cin * 9) % 8 == 0 and Cout % 8 == 0
+            and not N.fast_paths_disabled()):
+        # unfold once (bf16 [P][Cin*9], column c*9 + tap), then the pointwise MFMA weight-gradient kernel with
+        # K = 9*Cin writes torch's [N][Cin][3][3] layout directly
+        col = c.tmp((P, Cin * 9), torch.bfloat16)
+        call('tss_im2col3x3', *c.xargs, ptr(col), B, Hin, Win, Cin, d, dt, c.wst)
+        _pw_wgrad_of_columns(c, c.gargs, col, Cin * 9)
+    else:
+        call('tss_conv3x3_bwd_weight', *c.gargs, *c.xargs, ptr(c.dw), B, Hin, Win, Cin, Cout, s, d, dt, c.wst)
+    return None
+
+
+def _bwd_dense(c):
+    weight, Cin, Cout, d, st = c.weight, c.Cin, c.Cout, c.d, c.st
+    extras = (_dense_wgrad(c), False, None)
+    e_in = _new_e_in(c)
+    if e_in is None:
+        return None, extras
+    if c.s != 1:
+        _kxk_data_grad(c, e_in)
+        return e_in, extras
+    w_tcn = w_tcn16 = None
+    if _conv3x3_lean(c.e.dtype, Cout, Cin, 1, d):       # contraction over Cout, outputs = Cin
+        w_tcn16 = c.tmp((9, Cin, Cout), torch.bfloat16)
+        call('tss_permute_w3x3_bf16', ptr(weight), None, ptr(w_tcn16), Cout, Cin, st)
+    else:
+        w_tcn = c.tmp((9, Cin, Cout))
+        call('tss_permute_w3x3', ptr(weight), None, ptr(w_tcn), Cout, Cin, st)
+    call('tss_conv3x3_bwd_data', *c.gargs, ptr(w_tcn), ptr(w_tcn16), *c.margs, ptr(e_in), ld(e_in), c.bst,
+         c.B, c.Hin, c.Win, Cin, Cout, d, c.dt, st)
+    return e_in, extras
+
+
+# keyed by what _classify returns
+_BWD = {'stem': _bwd_stem, 'pw': _bwd_pw, 'dw': _bwd_dw, 'ckk': _bwd_ckk, 'dense': _bwd_dense,
+        'dense1d_w': _bwd_dense1d, 'dense1d_h': _bwd_dense1d}
+
+
+def _bias_backward(c):
+    """d(bias) of a layer whose backward sweep has not produced it.  Returns the tensor for autograd (None: accumulated directly)."""
+    e, P, Cout, link = c.e, c.P, c.Cout, c.link
+    if link is not None and link.training:
+        # BatchNorm with batch statistics removes any per-channel shift: d(loss)/d(bias) is exactly zero
+        return _grad_target(c.p_bias, c.weight, Cout)[1]
+    if link is not None:          # frozen statistics: d(bias) = scale * sum(e)
+        dbias = _direct_target(c.p_bias)
+        tmp = torch.zeros(Cout, dtype=torch.float32, device=c.dev)
+        _bias_grad_into(e, P, Cout, tmp, c.dt, c.st)
+        if dbias is None:
+            return tmp * link.ga
+        dbias.addcmul_(tmp, link.ga)
+        return None
+    dbias, dbias_ret = _grad_target(c.p_bias, c.weight, Cout)
+    _bias_grad_into(e, P, Cout, dbias, c.dt, c.st)
+    return dbias_ret
+
+
 class ConvUnitFn(Function):
     @staticmethod
     def forward(ctx, x, weight, gamma, beta, bias, cfg):
@@ -1228,60 +1739,8 @@ class ConvUnitFn(Function):
                                  % (tuple(y.shape),))
             link = BNLink(Cout, P, cfg.training, gamma, beta, dev)
         stats = ptr(link.stats) if (link is not None and cfg.training) else None
-        aff = _aff(cfg.in_link)
         st = stream()
-        mask = None
-        if cfg.kind == 'pw' and cfg.drop_p:
-            # the mask is drawn by its own small launch (one byte per 8 channels), applied on load here and in the backward sweep
-            mask = torch.empty((P, 16), dtype=torch.uint8, device=dev)
-            counter = _dropout_counter(dev)
-            call('tss_dropout_mask', ptr(counter), ptr(mask), P, cfg.cin, cfg.drop_p, st)
-            if _drop_mask_probe is not None:         # tests read the mask back to hand the oracle the same one
-                _drop_mask_probe.append(mask)
-            call('tss_pwconv_fwd_drop', ptr(x), ld(x), *aff, int(cfg.in_relu), ptr(weight), _shadow(weight, 0), ptr(bias),
-                 ptr(y), ld(y), ptr(mask), cfg.drop_p, ptr(counter), P, cfg.cin, Cout, dt, st)
-        elif cfg.kind == 'pw':
-            call('tss_pwconv_fwd', ptr(x), ld(x), *aff, int(cfg.in_relu), ptr(weight), _shadow(weight, 0), ptr(bias),
-                 ptr(y), ld(y), stats, P, cfg.cin, Cout, dt, st)
-        elif cfg.kind == 'dw':
-            if bias is not None:
-                raise NotImplementedError('HIP path: depthwise convolution with bias')
-            call('tss_dwconv3x3_fwd', ptr(x), ld(x), *aff, int(cfg.in_relu), ptr(weight),
-                 ptr(y), ld(y), stats, B, Hin, Win, Cout, s, d, dt, st)
-        elif cfg.kind == 'ckk' or (cfg.kind == 'dense' and bias is not None):
-            nt = cfg.kh * cfg.kw
-            w_tnc = torch.empty((nt, Cout, cfg.cin), dtype=torch.float32, device=dev)
-            call('tss_permute_wtaps', ptr(weight), ptr(w_tnc), None, Cout, cfg.cin, nt, st)
-            call('tss_convkxk_fwd', ptr(x), ld(x), *aff, int(cfg.in_relu), ptr(w_tnc), ptr(bias), ptr(y), ld(y), stats,
-                 B, Hin, Win, cfg.cin, Cout, cfg.kh, cfg.kw, s, d, dt, st)
-        elif cfg.kind == 'dense':
-            w_tnc = w_tnc16 = None
-            if _conv3x3_stream(x.dtype, cfg.cin, Cout, s, cfg.in_link, cfg.in_relu) or _conv3x3_lean(x.dtype, cfg.cin, Cout, s, d):
-                # bf16 tap-major copy: the weight-stationary / register-streamed kernels (wstat.hip, atrous.hip), the LDS-halo kernel (conv3x3.hip)
-                w_tnc16 = _W3X3.get(weight.data_ptr()) if _W3X3 else None          # prepared ahead of the forward (Dense3x3Shadows)
-                if w_tnc16 is None:
-                    w_tnc16 = torch.empty((9, Cout, cfg.cin), dtype=torch.bfloat16, device=dev)
-                    call('tss_permute_w3x3_bf16', ptr(weight), ptr(w_tnc16), None, Cout, cfg.cin, st)
-            else:
-                w_tnc = torch.empty((9, Cout, cfg.cin), dtype=torch.float32, device=dev)
-                call('tss_permute_w3x3', ptr(weight), ptr(w_tnc), None, Cout, cfg.cin, st)
-            call('tss_conv3x3_fwd', ptr(x), ld(x), *aff, int(cfg.in_relu), ptr(w_tnc), ptr(w_tnc16),
-                 ptr(y), ld(y), stats, B, Hin, Win, cfg.cin, Cout, s, d, dt, st)
-        elif cfg.kind in ('dense1d_w', 'dense1d_h'):
-            axis = 0 if cfg.kind == 'dense1d_w' else 1
-            if N.lib().tss_conv1d3_lean_supported(cfg.cin, Cout, dt):      # reads the layer's own weight tensor
-                call('tss_conv1d3_fwd_w', ptr(x), ld(x), *aff, int(cfg.in_relu), ptr(weight), ptr(bias), ptr(y), ld(y), stats,
-                     B, Hin, Win, cfg.cin, Cout, axis, d, dt, st)
-            else:
-                w_tnc = torch.empty((3, Cout, cfg.cin), dtype=torch.float32, device=dev)
-                call('tss_permute_wtaps', ptr(weight), ptr(w_tnc), None, Cout, cfg.cin, 3, st)
-                call('tss_conv1d3_fwd', ptr(x), ld(x), *aff, int(cfg.in_relu), ptr(w_tnc), ptr(bias), ptr(y), ld(y), stats,
-                     B, Hin, Win, cfg.cin, Cout, axis, d, dt, st)
-        else:  # stem
-            if bias is not None:
-                raise NotImplementedError('HIP path: stem convolution with bias')
-            call('tss_stem3x3_fwd', ptr(x), int(cfg.image_f32), ptr(weight), ptr(y), ld(y), stats,
-                 B, cfg.cin, Hin, Win, Cout, s, dt, st)
+        mask = _FWD[cfg.kind](_FwdArgs(cfg, x, weight, bias, y, _aff(cfg.in_link), stats, B, Hin, Win, Cout, P, s, d, dt, dev, st))
         if link is not None:
             _finalize_forward(link, cfg.bn, cfg.training, P, Cout, gamma, st)
         cfg.out_link = link
@@ -1294,322 +1753,53 @@ class ConvUnitFn(Function):
     @staticmethod
     def backward(ctx, e):
         cfg = ctx.cfg
+        c = _Bwd()
+        c.cfg, c.temps = cfg, []
         x, weight, y, drop_mask = ctx.saved_tensors
-        dev = x.device
-        e = to_nhwc(e)
-        dt = N.dtype_code(e.dtype)
-        st = stream()
-        link = cfg.out_link
-        B, Hin, Win = x.shape[0], x.shape[2], x.shape[3]
-        s, d = cfg.stride, cfg.dil
-        Cout, Cin = cfg.cout, cfg.cin
-        P = npix(e)
-        p_weight, p_gamma, p_beta, p_bias = cfg.params
-        dgamma = dbeta = None
-        if link is not None:
-            acc = 0
-            if ctx.has_affine:
-                dgamma, dbeta = _direct_target(p_gamma), _direct_target(p_beta)
-                if dgamma is not None and dbeta is not None:
-                    acc = 1
-                else:
-                    dgb = torch.empty((2, Cout), dtype=torch.float32, device=dev)
-                    dgamma, dbeta = dgb[0], dgb[1]
-            _bn_bwd_finalize(link, Cout, acc, dgamma, dbeta, st)       # (local or cross-replica statistics: link.sync)
-            if acc:
-                dgamma = dbeta = None
-            ga, gb, gce, gmu = link.ga, link.gb, link.gce, link.mean
-            if not link.training:
-                y, gb, gce, gmu = None, None, None, None
-        else:
-            ga = gb = gce = gmu = None
-            y = None
-        gargs = (ptr(e), ld(e), ptr(y), ld(y) if y is not None else 0, ptr(ga), ptr(gb), ptr(gce), ptr(gmu))
-        il = cfg.in_link
-
-        dw = _direct_target(p_weight)
-        dw_ret = None
-        if dw is None:
-            dw = dw_ret = torch.zeros_like(weight)
-        need_dx = ctx.needs_input_grad[0]
-        e_in = None
+        c.x, c.weight, c.drop_mask = x, weight, drop_mask
+        c.dev = dev = x.device
+        c.e = e = to_nhwc(e)
+        c.dt = N.dtype_code(e.dtype)
+        c.st = st = stream()
+        c.link = link = cfg.out_link
+        c.B, c.Hin, c.Win = x.shape[0], x.shape[2], x.shape[3]
+        c.s, c.d = cfg.stride, cfg.dil
+        c.Cout, c.Cin = cfg.cout, cfg.cin
+        Cout = c.Cout
+        c.P = P = npix(e)
+        c.p_weight, p_gamma, p_beta, c.p_bias = cfg.params
+        dgamma, dbeta, c.y, c.ga, gb, gce, gmu = _bn_backward_prologue(link, ctx.has_affine, p_gamma, p_beta, Cout, y, dev, st)
+        y = c.y
+        c.gargs = (ptr(e), ld(e), ptr(y), ld(y) if y is not None else 0, ptr(c.ga), ptr(gb), ptr(gce), ptr(gmu))
+        c.il = il = cfg.in_link
+        c.xargs = (ptr(x), ld(x), *_aff(il), int(cfg.in_relu))
+        c.deferred_in = il is not None or cfg.in_relu
+        c.margs = c.xargs if c.deferred_in else (None, 0, None, None, None, 0)
+        c.bst = ptr(il.bstats) if il is not None else None
+        c.dw, c.dw_ret = _grad_target(c.p_weight, weight)
+        c.need_dx = need_dx = ctx.needs_input_grad[0]
+        c.has_bias = ctx.has_bias
         # backward-weight and backward-data of one layer are independent: the weight gradient goes to a side stream
         # (fork after the finalize above, join before this function returns, so every tensor it reads is still alive
         # and a HIP-graph capture sees two parallel branches)
         main = torch.cuda.current_stream(dev)
-        side = _side_stream(dev) if (overlap_wgrad and need_dx and cfg.kind != 'stem' and drop_mask is None
-                                    and overlap_min_elems <= P * (Cin + Cout) <= overlap_max_elems) else None
-        wst = st
+        c.side = side = _wgrad_side_stream(cfg, need_dx, drop_mask, P, dev)
+        c.wst = st
         if side is not None:
             side.wait_stream(main)
-            wst = side.cuda_stream
-        fused_pw = False
-        fused_dbias = None
-        rows_after_join = None
-        if cfg.kind == 'stem':
-            ws = torch.empty((N.stat_slabs(), Cout * 28), dtype=torch.float32, device=dev)
-            call('tss_stem3x3_bwd_weight', *gargs, ptr(x), int(cfg.image_f32), ptr(dw), ptr(ws),
-                 B, Cin, Hin, Win, Cout, s, dt, st)
-            if need_dx:
-                raise NotImplementedError('HIP path: gradient with respect to the input image is not implemented')
-        else:
-            xargs = (ptr(x), ld(x), *_aff(il), int(cfg.in_relu))
-            deferred_in = il is not None or cfg.in_relu
-            if cfg.kind == 'pw':
-                # few channels, many pixels: input gradient and weight gradient in ONE sweep (csrc/pwbwd.hip): e, y, x read once
-                fused_pw = bool(fuse_pw_backward and need_dx and side is None and e.dtype == torch.bfloat16
-                                and not N.fast_paths_disabled() and N.lib().tss_pwconv_bwd_fused_preferred(P, Cin, Cout, dt))
-                if drop_mask is not None:        # dropout on load: the one sweep is the only backward that knows the mask
-                    fused_pw = True
-            postponed = False
-            sweep_pw = False
-            if cfg.kind == 'pw' and not fused_pw:
-                # the large layers (128 -> 128, 64 -> 384, 384 -> 64 with enough pixels): one sweep with the whole weight-gradient tile in
-                # the registers of one 512-thread block per CU (csrc/pwsweep.hip)
-                fork = getattr(cfg, 'res_fork', None)
-                radd_s = fork.g2 if fork is not None else None
-                sweep_pw = bool(sweep_pw_backward and need_dx and side is None and e.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
-                                and not N.fast_paths_disabled()
-                                and N.lib().tss_pwconv_bwd_sweep_preferred(P, Cin, Cout, int(bool(deferred_in)), dt)
-                                and (radd_s is None or (not deferred_in and radd_s.dtype == e.dtype and tuple(radd_s.shape) == tuple(x.shape)
-                                                        and is_nhwc(radd_s))))
-            if fused_pw or sweep_pw:
-                pass
-            elif cfg.kind == 'pw':
-                nws = N.lib().tss_pwconv_bwd_weight_ws(P, Cin, Cout, dt) if y is not None else 0
-                ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws else None
-                defer = 1 if (ws is not None and need_dx and side is None) else 0   # a backward-data launch carries the reduce
-                # the launch itself waits for the next BatchNorm-backward finalize of this pass and carries it (see _Pass.wg)
-                postponed = bool(defer and postpone_wgrad and dw_ret is None and not getattr(cfg, 'overlapped', False)
-                                 and _backward_task() != -1 and not _param_observed(p_weight))
-                if not postponed:
-                    _flush_wg(st)
-                    _flush_red(st)
-                    call('tss_pwconv_bwd_weight', *gargs, *xargs, ptr(dw), ptr(ws), defer, P, Cin, Cout, dt, None, wst)
-            elif cfg.kind == 'dw':
-                ws = torch.empty((N.stat_slabs(), Cout * 9), dtype=torch.float32, device=dev)
-                defer = 1 if (need_dx and side is None) else 0      # backward-data carries the row reduction
-                # input gradient and weight gradient in ONE sweep when the shape allows (e, y, x read once)
-                fused_dw = bool(defer and ((fuse_dw_backward and N.lib().tss_dwconv3x3_bwd_fused_supported(Cout, s, d, dt))
-                                          or N.lib().tss_dwconv3x3_bwd_fused_preferred(Cout, s, d, dt)))
-                if not fused_dw:
-                    call('tss_dwconv3x3_bwd_weight', *gargs, *xargs, ptr(dw), ptr(ws), defer, B, Hin, Win, Cout, s, d, dt, wst)
-            elif cfg.kind in ('dense1d_w', 'dense1d_h'):
-                axis = 0 if cfg.kind == 'dense1d_w' else 1
-                rows = N.lib().tss_conv1d3_bwd_weight_rows(P, Cin, Cout, dt)
-                rows_w = 0 if rows else N.lib().tss_convtap_bwd_weight_rows(P, Cin, Cout, 3, dt)      # 128-channel layers (csrc/fcg.hip)
-                if rows_w:
-                    ws = torch.empty((rows_w, Cout * Cin * 3), dtype=torch.float32, device=dev)
-                    call('tss_convtap_bwd_weight_sweep', *gargs, *xargs, ptr(ws), B, Hin, Win, Cin, Cout, 3, axis, d, dt, wst)
-                    rows_after_join = (ws, rows_w, Cout * Cin * 3)
-                elif rows:
-                    # one sweep over e, y and x (csrc/fc1d.hip); the rows of per-block partial sums are added to the gradient together with
-                    # those of every other such layer, in one launch at the end of this backward pass
-                    ws = torch.empty((rows, Cout * Cin * 3), dtype=torch.float32, device=dev)
-                    call('tss_conv1d3_bwd_weight_sweep', *gargs, *xargs, ptr(ws), B, Hin, Win, Cin, Cout, axis, d, dt, wst)
-                    rows_after_join = (ws, rows, Cout * Cin * 3)      # the sweep may be on the side stream: its rows are queued / added after the join below
-                elif (e.dtype == torch.bfloat16 and Cin % 8 == 0 and Cout % 8 == 0 and unfold_1d_wgrad and not N.fast_paths_disabled()):
-                    # unfold once (bf16 [P][Cin*3], column c*3 + tap), then the pipelined pointwise MFMA weight-gradient kernel with
-                    # K = 3*Cin writes torch's [N][Cin][1][3] / [N][Cin][3][1] layout directly (as the dense 3x3 below)
-                    col = torch.empty((P, Cin * 3), dtype=torch.bfloat16, device=dev)
-                    call('tss_im2col1d3', *xargs, ptr(col), B, Hin, Win, Cin, axis, d, dt, wst)
-                    g_ = gargs
-                    if y is None:        # no BatchNorm behind this layer (or a frozen one): g = ga * e, written as ga * e + 0 * e + 0
-                        one, zero = _const_rows(dev, Cout)
-                        g_ = (ptr(e), ld(e), ptr(e), ld(e), ptr(ga) if ga is not None else ptr(one), ptr(zero), ptr(zero), ptr(zero))
-                    nws = N.lib().tss_pwconv_bwd_weight_ws(P, Cin * 3, Cout, dt)
-                    ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws else None
-                    call('tss_pwconv_bwd_weight', *g_, ptr(col), Cin * 3, None, None, None, 0, ptr(dw), ptr(ws), 0,
-                         P, Cin * 3, Cout, dt, None, wst)
-                else:
-                    call('tss_conv1d3_bwd_weight', *gargs, *xargs, ptr(dw), B, Hin, Win, Cin, Cout, axis, d, dt, wst)
-            elif (cfg.kind == 'ckk' and s == 1 and (cfg.kh, cfg.kw) in ((1, 5), (5, 1))
-                  and N.lib().tss_convtap_bwd_weight_rows(P, Cin, Cout, 5, dt)):
-                # ESNet's 64-channel 1x5 / 5x1 layers: one sweep over e, y and x (csrc/fcg.hip), rows added at the end of the pass
-                rows = N.lib().tss_convtap_bwd_weight_rows(P, Cin, Cout, 5, dt)
-                ws = torch.empty((rows, Cout * Cin * 5), dtype=torch.float32, device=dev)
-                call('tss_convtap_bwd_weight_sweep', *gargs, *xargs, ptr(ws), B, Hin, Win, Cin, Cout, 5, 0 if cfg.kh == 1 else 1, d, dt, wst)
-                rows_after_join = (ws, rows, Cout * Cin * 5)
-            elif cfg.kind == 'ckk':
-                call('tss_convkxk_bwd_weight', *gargs, *xargs, ptr(dw), B, Hin, Win, Cin, Cout, cfg.kh, cfg.kw, s, d, dt, wst)
-            elif (cfg.kind == 'dense' and s == 2 and d == 1 and N.lib().tss_sconv_bwd_weight_rows(B, Hin, Win, Cin, Cout, dt)):
-                # stride-2 3x3 of the downsampling blocks: one sweep over e and x (csrc/sconv.hip), rows added at the end of the pass
-                rows = N.lib().tss_sconv_bwd_weight_rows(B, Hin, Win, Cin, Cout, dt)
-                ws = torch.empty((rows, Cout * Cin * 9), dtype=torch.float32, device=dev)
-                call('tss_sconv_bwd_weight_sweep', *gargs, *xargs, ptr(ws), B, Hin, Win, Cin, Cout, dt, wst)
-                rows_after_join = (ws, rows, Cout * Cin * 9)
-            elif (e.dtype == torch.bfloat16 and s == 1 and y is not None and (Cin * 9) % 8 == 0 and Cout % 8 == 0
-                  and not N.fast_paths_disabled()):
-                # unfold once (bf16 [P][Cin*9], column c*9 + tap), then the pointwise MFMA weight-gradient kernel with
-                # K = 9*Cin writes torch's [N][Cin][3][3] layout directly
-                col = torch.empty((P, Cin * 9), dtype=torch.bfloat16, device=dev)
-                call('tss_im2col3x3', *xargs, ptr(col), B, Hin, Win, Cin, d, dt, wst)
-                nws = N.lib().tss_pwconv_bwd_weight_ws(P, Cin * 9, Cout, dt)
-                ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws else None
-                call('tss_pwconv_bwd_weight', *gargs, ptr(col), Cin * 9, None, None, None, 0, ptr(dw), ptr(ws), 0,
-                     P, Cin * 9, Cout, dt, None, wst)
-            else:
-                call('tss_conv3x3_bwd_weight', *gargs, *xargs, ptr(dw), B, Hin, Win, Cin, Cout, s, d, dt, wst)
-            if need_dx or drop_mask is not None:
-                e_in = new_nhwc(B, Cin, Hin, Win, e.dtype, dev)
-                margs = xargs if deferred_in else (None, 0, None, None, None, 0)
-                bst = ptr(il.bstats) if il is not None else None
-                if fused_pw:
-                    rows = (N.lib().tss_pwconv_bwd_fused_drop_rows(P) if drop_mask is not None
-                            else N.lib().tss_pwconv_bwd_fused_rows(P, Cin, Cout))
-                    ws = torch.empty((rows, Cout * Cin), dtype=torch.float32, device=dev)
-                    bws = dbias = None
-                    if ctx.has_bias:          # the bias gradient leaves the same sweep as per-block rows (no colsum launch, no atomics)
-                        bws = torch.empty((rows, Cout), dtype=torch.float32, device=dev)
-                        dbias = _direct_target(p_bias)
-                        if dbias is None:
-                            dbias = fused_dbias = torch.zeros(Cout, dtype=torch.float32, device=dev)
-                    if drop_mask is not None:
-                        call('tss_pwconv_bwd_fused_drop', *gargs, ptr(weight), *xargs, int(bool(deferred_in)), ptr(drop_mask),
-                             cfg.drop_p, ptr(e_in), ld(e_in), bst, ptr(ws), ptr(bws), P, Cin, Cout, dt, st)
-                    else:
-                        call('tss_pwconv_bwd_fused', *gargs, ptr(weight), _shadow(weight, 1), *xargs, int(bool(deferred_in)),
-                             ptr(e_in), ld(e_in), bst, ptr(ws), ptr(bws), P, Cin, Cout, dt, st)
-                    if dw_ret is None and fused_dbias is None and batch_dw_reductions:
-                        _defer_dw_reduction(ws, dw, Cout * Cin, rows, p_weight)       # summed with the depthwise rows, at the end of the pass
-                        if bws is not None:
-                            _defer_dw_reduction(bws, dbias, Cout, rows, p_bias)
-                    else:
-                        _reduce_rows_now(ws, dw, Cout * Cin, rows)
-                        if bws is not None:
-                            _reduce_rows_now(bws, dbias, Cout, rows)
-                elif sweep_pw:
-                    rows = N.lib().tss_pwconv_bwd_sweep_rows(P, Cin, Cout)
-                    ws = torch.empty((rows, Cout * Cin), dtype=torch.float32, device=dev)
-                    wT = _shadow(weight, 1)
-                    hold_wT = None
-                    if wT is None:          # no current shadow (plain autograd outside a Trainer): a transpose of this call's own
-                        hold_wT = weight.detach().reshape(Cout, Cin).t().contiguous().to(torch.bfloat16)
-                        wT = ptr(hold_wT)
-                    call('tss_pwconv_bwd_sweep', *gargs, wT, *xargs, int(bool(deferred_in)), ptr(radd_s),
-                         ld(radd_s) if radd_s is not None else 0, ptr(e_in), ld(e_in), bst, ptr(ws), P, Cin, Cout, dt, st)
-                    del hold_wT
-                    if radd_s is not None:
-                        fork.consumed = True
-                    if dw_ret is None and batch_dw_reductions:
-                        _defer_dw_reduction(ws, dw, Cout * Cin, rows, p_weight)       # summed with the depthwise rows, at the end of the pass
-                    else:
-                        _reduce_rows_now(ws, dw, Cout * Cin, rows)
-                elif cfg.kind == 'pw':
-                    fork = getattr(cfg, 'res_fork', None)
-                    radd = fork.g2 if fork is not None else None
-                    if postponed:      # this launch carries the slot reduction of an EARLIER layer's weight gradient, if one waits
-                        red, hold = _take_red(dev)
-                    else:
-                        red, hold = ((ptr(ws), ptr(dw), 0, 0, 0) if defer else (None, None, 0, 0, 0)), None
-                    radd_ok = (radd is not None and not deferred_in and y is not None and e.dtype == torch.bfloat16 and radd.dtype == e.dtype
-                               and tuple(radd.shape) == tuple(e_in.shape) and N.lib().tss_pwconv_bwd_data_radd_supported(P, Cin, Cout, dt))
-                    pj = getattr(cfg, 'prev_join', None)
-                    if (pj is not None and (radd is None or radd_ok) and not deferred_in and y is not None and e.dtype == torch.bfloat16
-                            and P * Cin <= fuse_join_backward_max
-                            and pj.j_a is not None and pj.j_ptr == x.data_ptr() and tuple(pj.j_a.shape) == tuple(x.shape)
-                            and is_nhwc(pj.j_a) and N.lib().tss_pwconv_bwd_data_radd_supported(P, Cin, Cout, dt)):
-                        # this layer's input is a block output: that join's backward (ReLU mask + BatchNorm-backward sums) in the epilogue
-                        jl = pj.a_link
-                        call('tss_pwconv_bwd_data_joined', *gargs, ptr(weight), _shadow(weight, 1), ptr(e_in), ld(e_in), *red,
-                             ptr(radd), ld(radd) if radd is not None else 0, ptr(x), ld(x), ptr(pj.j_a), ld(pj.j_a), ptr(jl.mean),
-                             ptr(jl.bstats), P, Cin, Cout, dt, st)
-                        pj.fused_e = e_in
-                        if radd is not None:
-                            fork.consumed = True
-                    elif radd_ok:
-                        call('tss_pwconv_bwd_data_radd', *gargs, ptr(weight), _shadow(weight, 1), ptr(e_in), ld(e_in),
-                             *red, ptr(radd), ld(radd), P, Cin, Cout, dt, st)
-                        fork.consumed = True
-                    else:
-                        call('tss_pwconv_bwd_data', *gargs, ptr(weight), _shadow(weight, 1), *margs, ptr(e_in), ld(e_in), bst,
-                             *red, P, Cin, Cout, dt, st)
-                    del hold
-                    if postponed:
-                        _flush_wg(st)          # at most one weight gradient waits per stream
-                        own = torch.cuda.current_stream(dev)
-
-                        ps = _cur_pass()
-
-                        def launch_wg(fin, _keep=(e, y, x, link, il, ws, dw), _args=(gargs, xargs, ptr(dw), ptr(ws), P, Cin, Cout, dt),
-                                      _sid=st, _own=own, _ps=ps):
-                            ga_, xa_, dwp, wsp, P_, K_, N_, dt_ = _args
-                            call('tss_pwconv_bwd_weight', *ga_, *xa_, dwp, wsp, 1, P_, K_, N_, dt_,
-                                 ctypes.byref(fin) if fin is not None else None, _sid)
-                            _flush_red(_sid, _ps)
-                            with _lock:
-                                _ps.red[_sid] = (_keep[5], _keep[6], P_, K_, N_, _keep[0].device, _own)
-                        with _lock:
-                            ps.wg[st] = (launch_wg, dev, own)
-                elif cfg.kind == 'dw' and fused_dw and dw_ret is None and batch_dw_reductions:
-                    # the rows of per-block partial sums stay in ws; they are added to the (direct) gradient together with
-                    # those of every other depthwise layer, in one launch at the end of this backward pass
-                    rows = ctypes.c_int(0)
-                    call('tss_dwconv3x3_bwd_fused_sweep', *gargs, ptr(weight), *xargs, int(bool(deferred_in)), ptr(e_in), ld(e_in),
-                         bst, ptr(ws), B, Hin, Win, Cout, s, d, dt, st, ctypes.byref(rows))
-                    _defer_dw_reduction(ws, dw, Cout * 9, rows.value, p_weight)
-                elif cfg.kind == 'dw' and fused_dw:
-                    call('tss_dwconv3x3_bwd_fused', *gargs, ptr(weight), *xargs, int(bool(deferred_in)), ptr(e_in), ld(e_in),
-                         bst, ptr(ws), ptr(dw), B, Hin, Win, Cout, s, d, dt, st)
-                elif cfg.kind == 'dw':
-                    call('tss_dwconv3x3_bwd_data', *gargs, ptr(weight), *margs, ptr(e_in), ld(e_in), bst,
-                         ptr(ws) if defer else None, ptr(dw) if defer else None, B, Hin, Win, Cout, s, d, dt, st)
-                elif cfg.kind in ('dense1d_w', 'dense1d_h'):
-                    if N.lib().tss_conv1d3_lean_supported(Cin, Cout, dt):
-                        call('tss_conv1d3_bwd_data_w', *gargs, ptr(weight), *margs, ptr(e_in), ld(e_in), bst,
-                             B, Hin, Win, Cin, Cout, 0 if cfg.kind == 'dense1d_w' else 1, d, dt, st)
-                    else:
-                        w_tcn = torch.empty((3, Cin, Cout), dtype=torch.float32, device=dev)
-                        call('tss_permute_wtaps', ptr(weight), None, ptr(w_tcn), Cout, Cin, 3, st)
-                        call('tss_conv1d3_bwd_data', *gargs, ptr(w_tcn), *margs, ptr(e_in), ld(e_in), bst,
-                             B, Hin, Win, Cin, Cout, 0 if cfg.kind == 'dense1d_w' else 1, d, dt, st)
-                elif cfg.kind == 'ckk' or s != 1:
-                    # general tap grid / transposed gather of a strided layer (generic implicit-GEMM kernel)
-                    nt = cfg.kh * cfg.kw
-                    w_tcn = torch.empty((nt, Cin, Cout), dtype=torch.float32, device=dev)
-                    call('tss_permute_wtaps', ptr(weight), None, ptr(w_tcn), Cout, Cin, nt, st)
-                    call('tss_convkxk_bwd_data', *gargs, ptr(w_tcn), *margs, ptr(e_in), ld(e_in), bst,
-                         B, Hin, Win, Cin, Cout, cfg.kh, cfg.kw, s, d, dt, st)
-                else:
-                    w_tcn = w_tcn16 = None
-                    if _conv3x3_lean(e.dtype, Cout, Cin, 1, d):       # contraction over Cout, outputs = Cin
-                        w_tcn16 = torch.empty((9, Cin, Cout), dtype=torch.bfloat16, device=dev)
-                        call('tss_permute_w3x3_bf16', ptr(weight), None, ptr(w_tcn16), Cout, Cin, st)
-                    else:
-                        w_tcn = torch.empty((9, Cin, Cout), dtype=torch.float32, device=dev)
-                        call('tss_permute_w3x3', ptr(weight), None, ptr(w_tcn), Cout, Cin, st)
-                    call('tss_conv3x3_bwd_data', *gargs, ptr(w_tcn), ptr(w_tcn16), *margs, ptr(e_in), ld(e_in), bst,
-                         B, Hin, Win, Cin, Cout, d, dt, st)
-        stash = getattr(cfg, 'stash_fork', None)
-        if stash is not None and e_in is not None and not deferred_in:
+            c.wst = side.cuda_stream
+        e_in, (rows_after_join, bias_done, dbias_ret) = _BWD[cfg.kind](c)
+        stash = cfg.stash_fork
+        if stash is not None and e_in is not None and not c.deferred_in:
             stash.g2 = e_in                # the other consumer of this layer's input adds it in its own backward (fork_two)
-        dbias_ret = fused_dbias
-        if ctx.has_bias and not (fused_pw and (need_dx or drop_mask is not None)):
-            dbias = _direct_target(p_bias)
-            if link is not None and link.training:
-                # BatchNorm with batch statistics removes any per-channel shift: d(loss)/d(bias) is exactly zero
-                if dbias is None:
-                    dbias_ret = torch.zeros(Cout, dtype=torch.float32, device=dev)
-            elif link is not None:          # frozen statistics: d(bias) = scale * sum(e)
-                tmp = torch.zeros(Cout, dtype=torch.float32, device=dev)
-                _bias_grad_into(e, P, Cout, tmp, dt, st)
-                if dbias is None:
-                    dbias_ret = tmp * link.ga
-                else:
-                    dbias.addcmul_(tmp, link.ga)
-            else:
-                if dbias is None:
-                    dbias = dbias_ret = torch.zeros(Cout, dtype=torch.float32, device=dev)
-                _bias_grad_into(e, P, Cout, dbias, dt, st)
+        if ctx.has_bias and not bias_done:
+            dbias_ret = _bias_backward(c)
         if side is not None:
             main.wait_stream(side)
         if rows_after_join is not None:
-            ws_, rows_, ncols_ = rows_after_join
-            if dw_ret is None and batch_dw_reductions:
-                _defer_dw_reduction(ws_, dw, ncols_, rows_, p_weight)
-            else:
-                _reduce_rows_now(ws_, dw, ncols_, rows_)
-        return e_in, dw_ret, dgamma, dbeta, dbias_ret, None
+            ws, rows, ncols = rows_after_join
+            _add_rows(ws, c.dw, ncols, rows, c.p_weight, c.dw_ret)
+        return e_in, c.dw_ret, dgamma, dbeta, dbias_ret, None
 
 
 # ----------------------------------------------------------------------------- join (materialise / add / relu)
@@ -1673,13 +1863,13 @@ class JoinFn(Function):
     def backward(ctx, dout):
         cfg = ctx.cfg
         a, b, out = ctx.saved_tensors
-        fe = getattr(cfg, 'fused_e', None)
+        fe = cfg.fused_e
         cfg.fused_e = None
         if (fe is not None and dout.data_ptr() == fe.data_ptr() and dout.shape == fe.shape and dout.dtype == fe.dtype
                 and dout.stride() == fe.stride()):
             # the consumer's backward-data launch already did this join's backward on the complete gradient (mask + slab rows written):
             # dout IS e.  (Any other gradient of `out` would have made autograd hand us a different, summed tensor.)
-            fork = getattr(cfg, 'res_fork', None)
+            fork = cfg.res_fork
             if fork is not None and ctx.has_b:
                 fork.g2 = dout
             return dout, (dout if ctx.has_b else None), None
@@ -1694,7 +1884,7 @@ class JoinFn(Function):
                  ptr(e), ld(e) if e is not None else 0, 1.0 / (1.0 - cfg.drop_p) if cfg.drop_p else 1.0,
                  npix(dout), dout.shape[1], N.dtype_code(dout.dtype), stream())
         g = e if e is not None else dout
-        fork = getattr(cfg, 'res_fork', None)
+        fork = cfg.res_fork
         if fork is not None and ctx.has_b:
             fork.g2 = g                    # the skip's gradient, for the epilogue of the block's first layer
         return g, (g if ctx.has_b else None), None
@@ -1860,38 +2050,14 @@ class UpDwFn(Function):
         ho, wo = cfg.size
         link = cfg.out_link
         p_weight, p_gamma, p_beta = cfg.params
-        dgamma = dbeta = None
-        ga = gb = gce = gmu = None
-        if link is not None:
-            acc = 0
-            if ctx.has_affine:
-                dgamma, dbeta = _direct_target(p_gamma), _direct_target(p_beta)
-                if dgamma is not None and dbeta is not None:
-                    acc = 1
-                else:
-                    dgb = torch.empty((2, C), dtype=torch.float32, device=dev)
-                    dgamma, dbeta = dgb[0], dgb[1]
-            _bn_bwd_finalize(link, C, acc, dgamma, dbeta, st)
-            if acc:
-                dgamma = dbeta = None
-            ga, gb, gce, gmu = link.ga, link.gb, link.gce, link.mean
-            if not link.training:
-                y, gb, gce, gmu = None, None, None, None
-        else:
-            y = None
-        dw = _direct_target(p_weight)
-        dw_ret = None
-        if dw is None:
-            dw = dw_ret = torch.zeros_like(weight)
+        dgamma, dbeta, y, ga, gb, gce, gmu = _bn_backward_prologue(link, ctx.has_affine, p_gamma, p_beta, C, y, dev, st)
+        dw, dw_ret = _grad_target(p_weight, weight)
         ws = torch.empty((N.lib().tss_updw_ws_rows(B, Hs, Ws, ho, wo, C, cfg.dil, dt), C * 9), dtype=torch.float32, device=dev)
         e_up = new_nhwc(B, C, ho, wo, e.dtype, dev)
         rows = ctypes.c_int(0)
         call('tss_updw_bwd', ptr(e), ld(e), ptr(y), ld(y) if y is not None else 0, ptr(ga), ptr(gb), ptr(gce), ptr(gmu),
              ptr(weight), ptr(x), ld(x), Hs, Ws, ptr(e_up), ld(e_up), ptr(ws), B, ho, wo, C, cfg.dil, dt, st, ctypes.byref(rows))
-        if dw_ret is None and batch_dw_reductions:
-            _defer_dw_reduction(ws, dw, C * 9, rows.value, p_weight)
-        else:
-            _reduce_rows_now(ws, dw, C * 9, rows.value)
+        _add_rows(ws, dw, C * 9, rows.value, p_weight, dw_ret)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = new_nhwc(B, C, Hs, Ws, e.dtype, dev)
@@ -2357,22 +2523,10 @@ class StandaloneBNFn(Function):
         e = to_nhwc(e)
         C, P = z.shape[1], npix(z)
         st = stream()
-        dgamma = dbeta = None
-        acc = 0
-        if ctx.has_affine:
-            dgamma, dbeta = _direct_target(cfg.params[0]), _direct_target(cfg.params[1])
-            if dgamma is not None and dbeta is not None:
-                acc = 1
-            else:
-                dgb = torch.empty((2, C), dtype=torch.float32, device=z.device)
-                dgamma, dbeta = dgb[0], dgb[1]
-        _bn_bwd_finalize(link, C, acc, dgamma, dbeta, st)
-        if acc:
-            dgamma = dbeta = None
+        dgamma, dbeta, zt, ga, gb, gce, gmu = _bn_backward_prologue(link, ctx.has_affine, cfg.params[0], cfg.params[1], C, z, z.device, st)
         dz = new_nhwc(*z.shape, e.dtype, z.device)
-        tr = link.training
-        call('tss_bn_bwd_apply', ptr(e), ld(e), ptr(z) if tr else None, ld(z), ptr(link.ga), ptr(link.gb) if tr else None,
-             ptr(link.gce) if tr else None, ptr(link.mean) if tr else None, ptr(dz), ld(dz), P, C, N.dtype_code(e.dtype), st)
+        call('tss_bn_bwd_apply', ptr(e), ld(e), ptr(zt), ld(z), ptr(ga), ptr(gb), ptr(gce), ptr(gmu), ptr(dz), ld(dz), P, C,
+             N.dtype_code(e.dtype), st)
         return dz, dgamma, dbeta, None
 
 
@@ -2661,7 +2815,7 @@ class PpmConcatFn(Function):
         call('tss_ppm_concat_bwd', ptr(dout), ld(dout), _hp(raws), _hl([ld(r) for r in raws]), _hi(bins),
              *PpmConcatFn._tables(ctx.cfg), _hp([l.bstats if l is not None else None for l in ctx.cfg.links]),   # (None: sums taken on chip by ppm_arms)
              _hp(es), _hl([ld(e) for e in es]), len(raws), B, H, W, C, ca, N.dtype_code(dout.dtype), stream())
-        stash = getattr(ctx.cfg, 'res_fork', None)
+        stash = ctx.cfg.res_fork
         if stash is not None:
             stash.g2 = dout[:, :C]         # x's other consumer (the pools) adds it in tss_ppm_pool_bwd (fork_two)
         return (dout[:, :C], None, *es)
