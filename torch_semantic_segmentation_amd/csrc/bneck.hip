@@ -44,9 +44,6 @@ __device__ unsigned long long g_bk_timing[8];     // debug builds: cycles of wav
 #define BK_T(var)
 #endif
 
-__device__ __forceinline__ float blo(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bhi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
-
 __device__ __forceinline__ uint4 load_w8(const T* wb, const float* wf, long idx, bool ok) {
   // 8 consecutive weights as bf16 (from the shadow, or converted from f32); zeros when !ok
   uint4 r = make_uint4(0u, 0u, 0u, 0u);

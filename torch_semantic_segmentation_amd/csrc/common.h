@@ -94,6 +94,10 @@ template <> struct V4<bf16_t> {
 
 template <typename T> __device__ __forceinline__ float to_f32(T x) { return (float)x; }
 
+// the two bf16 values of a 32-bit word, widened
+__device__ __forceinline__ float blo(uint32_t u) { return __uint_as_float(u << 16); }
+__device__ __forceinline__ float bhi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
+
 // Branch-free "ReLU and/or zero": clamp(a, lo, hi) as ONE v_med3_f32.
 //   relu, valid  : (0, +inf)     identity, valid : (-inf, +inf)     invalid tap / padding : (0, 0)
 // A runtime relu flag written as `flag ? max(a,0) : a` costs a compare + select per element instead.
@@ -180,6 +184,21 @@ __device__ __forceinline__ float row16_sum(float v) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// The dual-use LDS image of the one-sweep backward kernels (pwsweep.hip, wgsweep.h).
+// byte offset of 16-byte chunk ch (0..15) of row `row` in a [rows][256 B] image that serves ds_read_b128 row reads and
+// ds_read_b64_tr_b16 transposed reads alike (cdna_hip_programming.md T10, image (b))
+__device__ __forceinline__ int img_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
+
+// one MFMA operand (8 values along the contraction axis) out of two transposed 8-byte reads
+typedef __attribute__((ext_vector_type(4))) short v4s;
+__device__ __forceinline__ bf16x8 tr_pair(const unsigned char* lo, const unsigned char* hi) {
+  union { v4s h[2]; bf16x8 v; } u;
+  u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)lo);
+  u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)hi);
+  return u.v;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Host side: error mapping + optional per-kernel profiling (HIP events on the launch stream).
 namespace tss {
 
@@ -214,6 +233,7 @@ struct DevOnce {
 };
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline size_t esz(int dtype) { return dtype == TSS_BF16 ? 2 : 4; }
 
 }  // namespace tss
 

@@ -32,9 +32,6 @@ struct C3Args {
   const T* xm; long ldxm; const float* mm; const float* ms; const float* mb; int m_relu;
 };
 
-__device__ __forceinline__ float bits_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ float bits_lo(uint32_t u) { return __uint_as_float(u << 16); }
-
 template <bool BWD, int NB>
 __global__ __launch_bounds__(NT, 1) void conv3x3_lean_kernel(const C3Args g) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -170,9 +167,9 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_lean_kernel(const C3Args g) {
             float v[8];
 #pragma unroll
             for (int h = 0; h < 4; ++h) {
-              float lo = bits_lo(ua[h]) * k0[2 * h] + kadd[2 * h];
-              float hi = bits_hi(ua[h]) * k0[2 * h + 1] + kadd[2 * h + 1];
-              if (BWD) { lo += bits_lo(ub[h]) * k1[2 * h]; hi += bits_hi(ub[h]) * k1[2 * h + 1]; }
+              float lo = blo(ua[h]) * k0[2 * h] + kadd[2 * h];
+              float hi = bhi(ua[h]) * k0[2 * h + 1] + kadd[2 * h + 1];
+              if (BWD) { lo += blo(ub[h]) * k1[2 * h]; hi += bhi(ub[h]) * k1[2 * h + 1]; }
               v[2 * h] = lo; v[2 * h + 1] = hi;
             }
             if (!BWD) {
@@ -241,7 +238,7 @@ __global__ __launch_bounds__(NT, 1) void conv3x3_lean_kernel(const C3Args g) {
             bf16x4 o;
             if (BWD && g.xm) {
               const uint2 xr = rxm[i][m];
-              const float xc[4] = {bits_lo(xr.x) - cmm[0], bits_hi(xr.x) - cmm[1], bits_lo(xr.y) - cmm[2], bits_hi(xr.y) - cmm[3]};
+              const float xc[4] = {blo(xr.x) - cmm[0], bhi(xr.x) - cmm[1], blo(xr.y) - cmm[2], bhi(xr.y) - cmm[3]};
               if (g.m_relu) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) if (!(xc[q] * cms[q] + cmb[q] > 0.f)) v[q] = 0.f;

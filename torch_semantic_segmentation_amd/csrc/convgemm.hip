@@ -498,8 +498,6 @@ int launch(GemmArgs& g, int dtype, int kernel_id, hipStream_t stream, double alg
   return tss::check_last("convgemm");
 }
 
-inline size_t esz(int dtype) { return dtype == TSS_BF16 ? 2 : 4; }
-
 }  // namespace
 
 extern int g_tss_disable_fast;   // pwfast.hip
@@ -576,7 +574,7 @@ int tss_pwconv_fwd(const void* x, long ldx, const float* in_mean, const float* i
     if (tss_pwfast_fwd(x, ldx, in_mean, in_scale, in_bias, in_relu, w, w_bf16, bias, y, ldy, stats, P, K, N, (hipStream_t)stream))
       return tss::check_last("pwfast_fwd");
   }
-  return launch(g, dtype, TSS_K_PWCONV_FWD, (hipStream_t)stream, (double)P * (K + N) * esz(dtype));
+  return launch(g, dtype, TSS_K_PWCONV_FWD, (hipStream_t)stream, (double)P * (K + N) * tss::esz(dtype));
 }
 
 int tss_pwconv_bwd_data(const void* e, long lde, const void* yraw, long ldyr,
@@ -601,7 +599,7 @@ int tss_pwconv_bwd_data(const void* e, long lde, const void* yraw, long ldyr,
   g.w = w; g.wrs = 1; g.wcs = K; g.wts = 0;  // Wt(k_out, n) = w[n*K + k_out]
   g.y = e_in; g.ldy = ldei; g.stats = bstats;
   g.xm = xraw; g.ldxm = ldx; g.mm = in_mean; g.ms = in_scale; g.mb = in_bias; g.m_relu = in_relu;
-  const double bytes = (double)P * (N * (yraw ? 2 : 1) + K * (xraw ? 2 : 1)) * esz(dtype);
+  const double bytes = (double)P * (N * (yraw ? 2 : 1) + K * (xraw ? 2 : 1)) * tss::esz(dtype);
   if (dtype == TSS_BF16 && !g_tss_disable_fast && yraw && N <= 768 && (N % 8) == 0 && (K % 4) == 0) {
     tss::ProfScope prof(TSS_K_PWCONV_BWD_DATA, (hipStream_t)stream, bytes, 2.0 * (double)P * K * N);
     if (tss_pwfast_bwd_data(e, lde, yraw, ldyr, ga, gb, gce, gmu, w, wT_bf16, xraw, ldx, in_mean, in_scale, in_bias, in_relu,
@@ -675,7 +673,7 @@ int tss_conv3x3_fwd(const void* x, long ldx, const float* in_mean, const float* 
   g.a0 = x; g.lda0 = ldx; g.c0 = in_scale; g.c1 = in_mean; g.c2 = in_bias; g.a_relu = in_relu;
   g.w = w_tnc; g.wrs = Cin; g.wcs = 1; g.wts = (long)N * Cin;  // [tap][n][c]
   g.y = y; g.ldy = ldy; g.stats = stats;
-  const double bytes = ((double)B * Hin * Win * Cin + (double)g.P * N) * esz(dtype);
+  const double bytes = ((double)B * Hin * Win * Cin + (double)g.P * N) * tss::esz(dtype);
   if (dtype == TSS_BF16 && w_tnc_bf16 && !g_tss_disable_fast && tss::aligned16(w_tnc_bf16)) {
     tss::ProfScope prof(TSS_K_CONV3X3_FWD, (hipStream_t)stream, bytes, 18.0 * (double)g.P * Cin * N);
     // a materialised input (no BatchNorm / ReLU pending): activations streamed into the MFMA operand registers, any dilation
@@ -719,7 +717,7 @@ int tss_conv3x3_bwd_data(const void* e, long lde, const void* yraw, long ldyr,
   g.w = w_tcn; g.wrs = N; g.wcs = 1; g.wts = (long)Cin * N;  // [tap][ci][co]
   g.y = e_in; g.ldy = ldei; g.stats = bstats;
   g.xm = xraw; g.ldxm = ldx; g.mm = in_mean; g.ms = in_scale; g.mb = in_bias; g.m_relu = in_relu;
-  const double bytes = (double)g.P * (N * (yraw ? 2 : 1) + Cin * (xraw ? 2 : 1)) * esz(dtype);
+  const double bytes = (double)g.P * (N * (yraw ? 2 : 1) + Cin * (xraw ? 2 : 1)) * tss::esz(dtype);
   if (dtype == TSS_BF16 && w_tcn_bf16 && !g_tss_disable_fast && tss::aligned16(w_tcn_bf16) && tss::aligned16(e) &&
       tss::aligned16(e_in)) {
     tss::ProfScope prof(TSS_K_CONV3X3_BWD_DATA, (hipStream_t)stream, bytes, 18.0 * (double)g.P * Cin * N);
@@ -758,7 +756,7 @@ int tss_conv1d3_fwd(const void* x, long ldx, const float* in_mean, const float* 
   g.a0 = x; g.lda0 = ldx; g.c0 = in_scale; g.c1 = in_mean; g.c2 = in_bias; g.a_relu = in_relu;
   g.w = w_tnc; g.wrs = Cin; g.wcs = 1; g.wts = (long)N * Cin; g.bias = bias;
   g.y = y; g.ldy = ldy; g.stats = stats;
-  return launch(g, dtype, TSS_K_CONV3X3_FWD, (hipStream_t)stream, (double)g.P * (Cin + N) * esz(dtype));
+  return launch(g, dtype, TSS_K_CONV3X3_FWD, (hipStream_t)stream, (double)g.P * (Cin + N) * tss::esz(dtype));
 }
 
 int tss_conv1d3_bwd_data(const void* e, long lde, const void* yraw, long ldyr,
@@ -795,7 +793,7 @@ int tss_conv1d3_bwd_data(const void* e, long lde, const void* yraw, long ldyr,
   g.y = e_in; g.ldy = ldei; g.stats = bstats;
   g.xm = xraw; g.ldxm = ldx; g.mm = in_mean; g.ms = in_scale; g.mb = in_bias; g.m_relu = in_relu;
   return launch(g, dtype, TSS_K_CONV3X3_BWD_DATA, (hipStream_t)stream,
-                (double)g.P * (N * (yraw ? 2 : 1) + Cin * (xraw ? 2 : 1)) * esz(dtype));
+                (double)g.P * (N * (yraw ? 2 : 1) + Cin * (xraw ? 2 : 1)) * tss::esz(dtype));
 }
 
 // ---- general dense convolution: kh x kw taps (odd sides), padding = dilation * (k - 1) / 2 per axis, any stride, optional bias.
@@ -828,7 +826,7 @@ int tss_convkxk_fwd(const void* x, long ldx, const float* in_mean, const float* 
     if (tss_sconv_fwd(x, ldx, in_mean, in_scale, in_bias, in_relu, w_tnc, bias, y, ldy, stats, B, Hin, Win, Cin, N, (hipStream_t)stream))
       return tss::check_last("sconv_fwd");
   }
-  return launch(g, dtype, TSS_K_CONV3X3_FWD, (hipStream_t)stream, ((double)B * Hin * Win * Cin + (double)g.P * N) * esz(dtype));
+  return launch(g, dtype, TSS_K_CONV3X3_FWD, (hipStream_t)stream, ((double)B * Hin * Win * Cin + (double)g.P * N) * tss::esz(dtype));
 }
 
 // e: [B][Hout][Wout][N] (Hout = (Hin - 1) / stride + 1), e_in: [B][Hin][Win][Cin]
@@ -867,7 +865,7 @@ int tss_convkxk_bwd_data(const void* e, long lde, const void* yraw, long ldyr,
   g.y = e_in; g.ldy = ldei; g.stats = bstats;
   g.xm = xraw; g.ldxm = ldx; g.mm = in_mean; g.ms = in_scale; g.mb = in_bias; g.m_relu = in_relu;
   return launch(g, dtype, TSS_K_CONV3X3_BWD_DATA, (hipStream_t)stream,
-                ((double)B * g.Hin * g.Win * N * (yraw ? 2 : 1) + (double)g.P * Cin * (xraw ? 2 : 1)) * esz(dtype));
+                ((double)B * g.Hin * g.Win * N * (yraw ? 2 : 1) + (double)g.P * Cin * (xraw ? 2 : 1)) * tss::esz(dtype));
 }
 
 // nn.ConvTranspose2d(Cin_t, Cout, k, stride, padding = (k - 1) / 2, output_padding = stride - 1) (UpsamplingBlock, TSS/models/esnet.py:71-80):
@@ -893,7 +891,7 @@ int tss_convkxk_transposed_fwd(const void* x, long ldx, const float* w_tcn, cons
     if (tss_sconv_transposed_fwd(x, ldx, w_tcn, bias, y, ldy, B, Hout, Wout, Cout, Cin_t, (hipStream_t)stream))
       return tss::check_last("sconv_transposed_fwd");
   }
-  return launch(g, dtype, TSS_K_CONV3X3_FWD, (hipStream_t)stream, ((double)B * g.Hin * g.Win * Cin_t + (double)g.P * Cout) * esz(dtype));
+  return launch(g, dtype, TSS_K_CONV3X3_FWD, (hipStream_t)stream, ((double)B * g.Hin * g.Win * Cin_t + (double)g.P * Cout) * tss::esz(dtype));
 }
 
 int tss_get_option(int key) { return key == TSS_OPT_DISABLE_FAST_PATHS ? g_tss_disable_fast : -1; }
@@ -915,7 +913,7 @@ int tss_stem3x3_fwd(const void* x_nchw, int x_is_f32, const float* w, void* y, l
   g.a0 = x_nchw; g.a0_f32 = x_is_f32;
   g.w = w; g.wrs = (long)Cin * 9; g.wcs = 1; g.wts = 0;
   g.y = y; g.ldy = ldy; g.stats = stats;
-  const double bytes = (double)B * Cin * Hin * Win * (x_is_f32 ? 4 : esz(dtype)) + (double)g.P * N * esz(dtype);
+  const double bytes = (double)B * Cin * Hin * Win * (x_is_f32 ? 4 : tss::esz(dtype)) + (double)g.P * N * tss::esz(dtype);
   if (dtype == TSS_BF16 && !g_tss_disable_fast && Cin <= 3 && N == 32) {   // performance path: direct VALU kernel (stem.hip)
     tss::ProfScope prof(TSS_K_STEM_FWD, (hipStream_t)stream, bytes, 2.0 * (double)g.P * g.KD * N);
     if (tss_stem_direct_fwd(x_nchw, x_is_f32, w, y, ldy, stats, B, Cin, Hin, Win, N, stride, dtype, (hipStream_t)stream))

@@ -978,8 +978,6 @@ bool launch_strip_fused(const DwArgs& g, int grid, int threads, hipStream_t st) 
   return false;
 }
 
-inline size_t esz(int dtype) { return dtype == TSS_BF16 ? 2 : 4; }
-
 inline bool strip_supported(int stride, int dil) { return (stride == 1 && dil == 1) || (stride == 2 && dil == 1) || (stride == 1 && dil == 4); }
 
 // workspace rows the weight-gradient kernels of this layer write (= their grid); g.NPL / Hout / Wout must be set
@@ -1012,7 +1010,7 @@ int tss_dwconv3x3_fwd(const void* x, long ldx, const float* in_mean, const float
   if (P == 0) return TSS_OK;
   const long U = (long)B * g.Hout * ((g.Wout + SW - 1) / SW);
   tss::ProfScope prof(TSS_K_DWCONV_FWD, (hipStream_t)stream,
-                      ((double)B * Hin * Win + (double)P) * C * esz(dtype), 18.0 * P * C);
+                      ((double)B * Hin * Win + (double)P) * C * tss::esz(dtype), 18.0 * P * C);
   if (tss::dwroll_supported(C, stride, dil, dtype)) {   // bf16, dilation 1: row-pipelined through LDS (dwroll.hip)
     tss::dwroll_fwd(x, ldx, in_mean, in_scale, in_bias, in_relu, w, y, ldy, stats, B, Hin, Win, C, stride, (hipStream_t)stream);
     return tss::check_last("dwconv_fwd");
@@ -1052,7 +1050,7 @@ int tss_dwconv3x3_bwd_data(const void* e, long lde, const void* yraw, long ldyr,
   if (P == 0) return TSS_OK;
   const long Po = (long)B * g.Hout * g.Wout;
   tss::ProfScope prof(TSS_K_DWCONV_BWD_DATA, (hipStream_t)stream,
-                      ((double)Po * (yraw ? 2 : 1) + (double)P * (xraw ? 2 : 1)) * C * esz(dtype), 18.0 * Po * C);
+                      ((double)Po * (yraw ? 2 : 1) + (double)P * (xraw ? 2 : 1)) * C * tss::esz(dtype), 18.0 * Po * C);
   const long U = (long)B * Hin * ((Win + SW - 1) / SW);
   const int sgrid = tss::persistent_blocks((U + g.NPL - 1) / g.NPL, TSS_STAT_SLABS);
   const bool carry = wg_ws && wg_dw && strip_supported(stride, dil);
@@ -1152,7 +1150,7 @@ static int bwd_fused_impl(const void* e, long lde, const void* yraw, long ldyr,
     int rows;
     {
       tss::ProfScope prof(TSS_K_DWCONV_BWD_DATA, (hipStream_t)stream,
-                          ((double)Po * (yraw ? 2 : 1) + (double)P * 2) * C * esz(dtype), 36.0 * Po * C);
+                          ((double)Po * (yraw ? 2 : 1) + (double)P * 2) * C * tss::esz(dtype), 36.0 * Po * C);
       rows = tss::dwroll_bwd_fused(e, lde, yraw, ldyr, ga, gb, gce, gmu, w, x, ldx, in_mean, in_scale, in_bias, in_relu, x_pending,
                                    e_in, ldei, bstats, ws, B, Hin, Win, C, stride, (hipStream_t)stream);
     }
@@ -1164,7 +1162,7 @@ static int bwd_fused_impl(const void* e, long lde, const void* yraw, long ldyr,
   const int sgrid = tss::persistent_blocks((U + g.NPL - 1) / g.NPL, TSS_STAT_SLABS);
   {
     tss::ProfScope prof(TSS_K_DWCONV_BWD_DATA, (hipStream_t)stream,
-                        ((double)Po * (yraw ? 2 : 1) + (double)P * 2) * C * esz(dtype), 36.0 * Po * C);
+                        ((double)Po * (yraw ? 2 : 1) + (double)P * 2) * C * tss::esz(dtype), 36.0 * Po * C);
     launch_strip_fused(g, sgrid, threads, (hipStream_t)stream);
   }
   if (rows_out) *rows_out = sgrid;
@@ -1191,7 +1189,7 @@ int tss_dwconv3x3_bwd_weight(const void* e, long lde, const void* yraw, long ldy
   const long P = (long)B * g.Hout * g.Wout;
   if (P == 0) return TSS_OK;
   tss::ProfScope prof(TSS_K_DWCONV_BWD_WEIGHT, (hipStream_t)stream,
-                      ((double)P * (yraw ? 2 : 1) + (double)B * Hin * Win) * C * esz(dtype), 18.0 * P * C);
+                      ((double)P * (yraw ? 2 : 1) + (double)B * Hin * Win) * C * tss::esz(dtype), 18.0 * P * C);
   const long U = (long)B * g.Hout * ((g.Wout + SW - 1) / SW);
   const int sgrid = tss::persistent_blocks((U + g.NPL - 1) / g.NPL, TSS_STAT_SLABS);
   const bool strip = dtype == TSS_BF16 ? launch_strip<bf16_t>(2, g, sgrid, threads, (hipStream_t)stream)

@@ -7,6 +7,7 @@
 // constants of a lane's channel vectors live in LDS (4 x 24 registers at 128 channels otherwise); 128-channel layers run 8 waves per block so
 // that the 96 KB of weights in LDS are shared by twice as many waves.
 #include "common.h"
+#include "wgsweep.h"
 
 namespace {
 
@@ -20,9 +21,6 @@ struct GArgs {
   T_* y; long ldy; double* stats;
   const T_* xm; long ldxm; const float* mm; const float* ms; const float* mb; int m_relu;
 };
-
-__device__ __forceinline__ float blo(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bhi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
 
 // MODE 0: forward (a = relu?((x - c1) * c0 + c2));  1: backward, g = c0 * e;  2: backward, g = c0 * (e - c2) + c1 * (y - c3)
 // NSPL = 2: a PAIR of waves shares a tile, each owning half of the output channels (the 128-channel backward with two operands per tap:
@@ -299,20 +297,9 @@ bool dispatch_fg(const GArgs& g, int C, int T, hipStream_t stream) {
 
 // ---- weight gradient in one sweep (the scheme of fc1d_wgrad_kernel: pixel-major operands through the transposed-read LDS image),
 // T taps, NW waves: wave w owns output-channel fragment w and all C / 16 x T (input fragment, tap) accumulators
-typedef __attribute__((ext_vector_type(4))) short v4s;
-__device__ __forceinline__ int img_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
-__device__ __forceinline__ bf16x8 tr_pair(const unsigned char* lo, const unsigned char* hi) {
-  union { v4s h[2]; bf16x8 v; } u;
-  u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)lo);
-  u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)hi);
-  return u.v;
-}
-
 struct GwArgs {
   long P; int B, H, W, D, axis;
-  const T_* e; long lde; const T_* y; long ldyr; const float* ga; const float* gb; const float* gce; const float* gmu;
-  const T_* x; long ldx; const float* xm; const float* xs; const float* xb; int x_relu;
-  float* ws;                                           // [gridDim.x][C * C * T], torch's [N][C][taps] order
+  wgs::Operands o;                                     // ws: [gridDim.x][C * C * T], torch's [N][C][taps] order
 };
 
 template <int C, int T, bool HASY>
@@ -321,51 +308,27 @@ __global__ __launch_bounds__(C * 4, 1) void fcg_wgrad_kernel(const GwArgs g) {
   constexpr int BUF = NIMG * PT * 256, NKS = PT / 32;
   static_assert(NTH / 64 == NF && PT == 32, "one wave per output fragment, 32-pixel stages");
   extern __shared__ __align__(16) unsigned char smem[];
+  const wgs::Operands& o = g.o;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
   const int cv = tid % NV, r = tid / NV;
 
-  float ca[8], cb[HASY ? 8 : 1], cc[HASY ? 8 : 1], as[8], ab[8];
-  const bool gplain = !HASY && !g.ga, aplain = !g.xs && !g.xm && !g.xb && !g.x_relu;
-  {
-    const float* safe = reinterpret_cast<const float*>(g.e);
-    float v0[8], v1[8], v2[8], v3[8], w0[8], w1[8], w2[8];
-    const float* p0 = g.ga ? g.ga + cv * 8 : safe; const float* p1 = (HASY && g.gb) ? g.gb + cv * 8 : safe;
-    const float* p2 = (HASY && g.gce) ? g.gce + cv * 8 : safe; const float* p3 = (HASY && g.gmu) ? g.gmu + cv * 8 : safe;
-    const float* q0 = g.xs ? g.xs + cv * 8 : safe; const float* q1 = g.xm ? g.xm + cv * 8 : safe; const float* q2 = g.xb ? g.xb + cv * 8 : safe;
-#pragma unroll
-    for (int h = 0; h < 8; h += 4) {
-      V4<float>::load(p0 + h, v0 + h); V4<float>::load(p1 + h, v1 + h); V4<float>::load(p2 + h, v2 + h); V4<float>::load(p3 + h, v3 + h);
-      V4<float>::load(q0 + h, w0 + h); V4<float>::load(q1 + h, w1 + h); V4<float>::load(q2 + h, w2 + h);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float gav = g.ga ? v0[j] : 1.f;
-      ca[j] = gav;
-      if (HASY) { cb[j] = v1[j]; cc[j] = -(gav * v2[j]) - v1[j] * v3[j]; }
-      const float sc = g.xs ? w0[j] : 1.f;
-      as[j] = sc; ab[j] = (g.xb ? w2[j] : 0.f) - (g.xm ? w1[j] : 0.f) * sc;
-    }
-  }
-  const float relu_lo = g.x_relu ? 0.f : -TSS_INF;
+  wgs::Fold<HASY> f;
+  f.load(o, cv * 8, cv * 8);
 
   const int fi = wave;
   int troffG[2], troffA[T][NF][2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    const int row = fq * 8 + 4 * h + (fr >> 2);
-    troffG[h] = (fi >> 3) * PT * 256 + img_off(row, (fi & 7) * 2 + ((fr & 3) >> 1)) + 8 * (fr & 1);
+    troffG[h] = wgs::tr_off(PT, fr, fq, h, fi);
 #pragma unroll
     for (int t = 0; t < T; ++t)
 #pragma unroll
-      for (int j = 0; j < NF; ++j) {
-        const int F = (1 + t) * NF + j;
-        troffA[t][j][h] = (F >> 3) * PT * 256 + img_off(row, (F & 7) * 2 + ((fr & 3) >> 1)) + 8 * (fr & 1);
-      }
+      for (int j = 0; j < NF; ++j) troffA[t][j][h] = wgs::tr_off(PT, fr, fq, h, (1 + t) * NF + j);
   }
-  const int stG = (cv >> 4) * PT * 256 + img_off(r, cv & 15);
+  const int stG = wgs::st_off(PT, r, cv);
   int stA[T];
 #pragma unroll
-  for (int t = 0; t < T; ++t) { const int gc = (1 + t) * NV + cv; stA[t] = (gc >> 4) * PT * 256 + img_off(r, gc & 15); }
+  for (int t = 0; t < T; ++t) stA[t] = wgs::st_off(PT, r, (1 + t) * NV + cv);
 
   f32x4 acc[T][NF];
 #pragma unroll
@@ -373,11 +336,8 @@ __global__ __launch_bounds__(C * 4, 1) void fcg_wgrad_kernel(const GwArgs g) {
 #pragma unroll
     for (int j = 0; j < NF; ++j) acc[t][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  const long nstage = (g.P + PT - 1) / PT;
-  const long per = (nstage + gridDim.x - 1) / gridDim.x;
-  const long s_begin = (long)blockIdx.x * per;
-  long s_end = s_begin + per;
-  if (s_end > nstage) s_end = nstage;
+  long s_begin, s_end;
+  wgs::stage_range(g.P, PT, &s_begin, &s_end);
   const int lim = g.axis ? g.H : g.W;
   const long pstep = g.axis ? g.W : 1;
 
@@ -391,14 +351,14 @@ __global__ __launch_bounds__(C * 4, 1) void fcg_wgrad_kernel(const GwArgs g) {
     const int xx = (int)(pcl % g.W);                                                                     \
     const int yy = (int)((pcl / g.W) % g.H);                                                             \
     okb = in ? 0x8000u : 0u;                                                                             \
-    re = *reinterpret_cast<const uint4*>(g.e + pcl * g.lde + cv * 8);                                    \
-    if (HASY) ry = *reinterpret_cast<const uint4*>(g.y + pcl * g.ldyr + cv * 8);                         \
+    re = *reinterpret_cast<const uint4*>(o.e + pcl * o.lde + cv * 8);                                    \
+    if (HASY) ry = *reinterpret_cast<const uint4*>(o.y + pcl * o.ldyr + cv * 8);                         \
     _Pragma("unroll") for (int t = 0; t < T; ++t) {                                                     \
       const int sh = (t - T / 2) * g.D;                                                                  \
       const int c1 = (g.axis ? yy : xx) + sh;                                                            \
       const bool ok = in && c1 >= 0 && c1 < lim;                                                         \
       okb |= ok ? (1u << t) : 0u;                                                                        \
-      rx[t] = *reinterpret_cast<const uint4*>(g.x + (ok ? pcl + sh * pstep : pcl) * g.ldx + cv * 8);     \
+      rx[t] = *reinterpret_cast<const uint4*>(o.x + (ok ? pcl + sh * pstep : pcl) * o.ldx + cv * 8);     \
     }                                                                                                    \
   }
 
@@ -406,39 +366,9 @@ __global__ __launch_bounds__(C * 4, 1) void fcg_wgrad_kernel(const GwArgs g) {
   int b = 0;
   for (long s = s_begin; s < s_end; ++s) {
     unsigned char* img = smem + b * BUF;
-    {
-      uint4 og = re;
-      if (!gplain) {
-        const uint32_t* ue = reinterpret_cast<const uint32_t*>(&re);
-        const uint32_t* uy = reinterpret_cast<const uint32_t*>(&ry);
-        bf16x8 o;
+    *reinterpret_cast<uint4*>(img + stG) = wgs::g_row(re, ry, f, okb & 0x8000u);
 #pragma unroll
-        for (int h = 0; h < 4; ++h) {
-          float lo = ca[2 * h] * blo(ue[h]), hi = ca[2 * h + 1] * bhi(ue[h]);
-          if (HASY) { lo += cb[2 * h] * blo(uy[h]) + cc[2 * h]; hi += cb[2 * h + 1] * bhi(uy[h]) + cc[2 * h + 1]; }
-          o[2 * h] = (T_)lo; o[2 * h + 1] = (T_)hi;
-        }
-        og = *reinterpret_cast<const uint4*>(&o);
-      }
-      if (!(okb & 0x8000u)) og = make_uint4(0u, 0u, 0u, 0u);
-      *reinterpret_cast<uint4*>(img + stG) = og;
-#pragma unroll
-      for (int t = 0; t < T; ++t) {
-        uint4 oa = rx[t];
-        if (!aplain) {
-          const uint32_t* ux = reinterpret_cast<const uint32_t*>(&rx[t]);
-          bf16x8 o;
-#pragma unroll
-          for (int h = 0; h < 4; ++h) {
-            o[2 * h] = (T_)fmaxf(blo(ux[h]) * as[2 * h] + ab[2 * h], relu_lo);
-            o[2 * h + 1] = (T_)fmaxf(bhi(ux[h]) * as[2 * h + 1] + ab[2 * h + 1], relu_lo);
-          }
-          oa = *reinterpret_cast<const uint4*>(&o);
-        }
-        if (!((okb >> t) & 1u)) oa = make_uint4(0u, 0u, 0u, 0u);
-        *reinterpret_cast<uint4*>(img + stA[t]) = oa;
-      }
-    }
+    for (int t = 0; t < T; ++t) *reinterpret_cast<uint4*>(img + stA[t]) = wgs::a_row(rx[t], f, (okb >> t) & 1u);
     if (s + 1 < s_end) GW_ISSUE(s + 1);
     __syncthreads();
 #pragma unroll
@@ -456,13 +386,7 @@ __global__ __launch_bounds__(C * 4, 1) void fcg_wgrad_kernel(const GwArgs g) {
     b ^= 1;
   }
 #undef GW_ISSUE
-  float* row = g.ws + (long)blockIdx.x * (T * C * C);
-#pragma unroll
-  for (int t = 0; t < T; ++t)
-#pragma unroll
-    for (int j = 0; j < NF; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) row[((long)(16 * fi + 4 * fq + q) * C + 16 * j + fr) * T + t] = acc[t][j][q];
+  wgs::store_rows<T, NF>(o.ws + (long)blockIdx.x * (T * C * C), acc, fi, 0, fq, fr, C);
 }
 
 template <int C, int T> constexpr int gw_smem() { return 2 * ((((1 + T) * (C / 8) + 15) / 16) * 32 * 256); }
@@ -476,11 +400,7 @@ int gw_rows(long P) {
 
 template <int C, int T, bool HASY>
 void launch_gw(const GwArgs& g, int grid, hipStream_t stream) {
-  constexpr int smem = gw_smem<C, T>();
-  static tss::DevOnce attr;
-  if (attr.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fcg_wgrad_kernel<C, T, HASY>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  hipLaunchKernelGGL((fcg_wgrad_kernel<C, T, HASY>), dim3(grid), dim3(C * 4), smem, stream, g);
+  wgs::launch_with_smem<fcg_wgrad_kernel<C, T, HASY>>(grid, C * 4, gw_smem<C, T>(), stream, g);
 }
 
 bool fg_enabled() {
@@ -540,16 +460,11 @@ extern "C" int tss_convtap_bwd_weight_sweep(const void* e, long lde, const void*
                                             const void* xraw, long ldx, const float* in_mean, const float* in_scale, const float* in_bias,
                                             int in_relu, float* ws, int B, int H, int W, int Cin, int N, int T, int axis, int dil, int dtype,
                                             void* stream) {
-  TSS_REQUIRE(dtype == TSS_BF16, TSS_ERR_DTYPE);
-  TSS_REQUIRE(fg_covered(Cin, N, T) && (lde % 8) == 0 && lde >= N && (ldx % 8) == 0 && ldx >= Cin && dil >= 1 && (axis == 0 || axis == 1) &&
-              e && xraw && ws && (long)B * H * W > 0, TSS_ERR_SHAPE);
-  TSS_REQUIRE(!yraw || ((ldyr % 8) == 0 && ldyr >= N && ga && gb && gce && gmu), TSS_ERR_SHAPE);
-  TSS_REQUIRE(tss::aligned16(e) && tss::aligned16(xraw) && (!yraw || tss::aligned16(yraw)), TSS_ERR_ALIGN);
   GwArgs g = {};
   g.P = (long)B * H * W; g.B = B; g.H = H; g.W = W; g.D = dil; g.axis = axis;
-  g.e = (const T_*)e; g.lde = lde; g.y = (const T_*)yraw; g.ldyr = ldyr; g.ga = ga; g.gb = gb; g.gce = gce; g.gmu = gmu;
-  g.x = (const T_*)xraw; g.ldx = ldx; g.xm = in_mean; g.xs = in_scale; g.xb = in_bias; g.x_relu = in_relu;
-  g.ws = ws;
+  g.o = wgs::operands(e, lde, yraw, ldyr, ga, gb, gce, gmu, xraw, ldx, in_mean, in_scale, in_bias, in_relu, ws);
+  const int err = wgs::check_operands(dtype, fg_covered(Cin, N, T) && dil >= 1 && (axis == 0 || axis == 1) && g.P > 0, g.o, Cin, N);
+  if (err != TSS_OK) return err;
   const int grid = gw_rows(g.P);
   tss::ProfScope prof(TSS_K_CONV3X3_BWD_WEIGHT, (hipStream_t)stream, (double)g.P * N * (yraw ? 3 : 2) * 2.0, 2.0 * g.P * T * N * N);
   if (N == 64) { if (yraw) launch_gw<64, 5, true>(g, grid, (hipStream_t)stream); else launch_gw<64, 5, false>(g, grid, (hipStream_t)stream); }

@@ -80,8 +80,6 @@ __global__ __launch_bounds__(NT) void gate_bwd_reduce_kernel(const float* ws, co
   da[(long)b * ldda + c] = (T)(t * sg * (1.f - sg));
 }
 
-inline size_t esz(int dtype) { return dtype == TSS_BF16 ? 2 : 4; }
-
 }  // namespace
 
 extern "C" {
@@ -105,7 +103,7 @@ int tss_gate_fwd(const void* x, long ldx, const void* a, long lda, void* out, lo
   const long total = P * (C / 8);
   long grid = (total + NT - 1) / NT;
   if (grid > 2048) grid = 2048;
-  tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, 2.0 * P * C * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, 2.0 * P * C * tss::esz(dtype), 0);
   if (dtype == TSS_BF16)
     hipLaunchKernelGGL(gate_fwd_kernel<bf16_t>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, (const bf16_t*)a, lda,
                        (bf16_t*)out, ldo, HW, P, C, add_one);
@@ -123,7 +121,7 @@ int tss_gate_bwd(const void* g, long ldg, const void* x, long ldx, const void* a
   TSS_REQUIRE(tss::aligned16(g) && tss::aligned16(x) && tss::aligned16(a) && tss::aligned16(dx), TSS_ERR_ALIGN);
   if ((long)B * HW == 0) return TSS_OK;
   const int S = tss_gate_slices(B, HW);
-  tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, 3.0 * B * HW * C * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, 3.0 * B * HW * C * tss::esz(dtype), 0);
 #define TSS_GATE_BWD(TT)                                                                                                       \
   hipLaunchKernelGGL(gate_bwd_kernel<TT>, dim3(B * S), dim3(NT), 0, (hipStream_t)stream, (const TT*)g, ldg, (const TT*)x, ldx,   \
                      (const TT*)a, lda, (TT*)dx, lddx, ws, HW, C, S, add_one);                                                 \

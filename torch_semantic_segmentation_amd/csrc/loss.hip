@@ -513,7 +513,6 @@ inline int grid_for(long total) {
   if (g < 1) g = 1;
   return (int)g;
 }
-inline size_t esz(int dtype) { return dtype == TSS_BF16 ? 2 : 4; }
 
 }  // namespace
 
@@ -528,7 +527,7 @@ int tss_cross_entropy_fwd(const void* logits, const long long* target, float* ls
   const long groups = B * (HW / 8);
   if (groups == 0) return TSS_OK;
   {
-    tss::ProfScope prof(TSS_K_CE_FWD, (hipStream_t)stream, (double)B * HW * (C * esz(dtype) + 12.0), 0);
+    tss::ProfScope prof(TSS_K_CE_FWD, (hipStream_t)stream, (double)B * HW * (C * tss::esz(dtype) + 12.0), 0);
     if (dtype == TSS_BF16)
       hipLaunchKernelGGL(ce_fwd_kernel<bf16_t>, dim3(grid_for(groups)), dim3(NT), 0, (hipStream_t)stream,
                          (const bf16_t*)logits, target, lse, acc, B, C, HW, ignore_index);
@@ -548,7 +547,7 @@ int tss_cross_entropy_bwd(const void* logits, const long long* target, const flo
   TSS_REQUIRE(tss::aligned16(logits) && tss::aligned16(dlogits) && tss::aligned16(lse), TSS_ERR_ALIGN);
   const long groups = B * (HW / 8);
   if (groups == 0) return TSS_OK;
-  tss::ProfScope prof(TSS_K_CE_BWD, (hipStream_t)stream, (double)B * HW * (2.0 * C * esz(dtype) + 12.0), 0);
+  tss::ProfScope prof(TSS_K_CE_BWD, (hipStream_t)stream, (double)B * HW * (2.0 * C * tss::esz(dtype) + 12.0), 0);
   if (dtype == TSS_BF16)
     hipLaunchKernelGGL(ce_bwd_kernel<bf16_t>, dim3(grid_for(groups)), dim3(NT), 0, (hipStream_t)stream,
                        (const bf16_t*)logits, target, lse, inv_count, grad_out, (bf16_t*)dlogits, B, C, HW, ignore_index);
@@ -568,7 +567,7 @@ int tss_argmax_confusion(const void* logits, const long long* target, unsigned c
   if (groups == 0) return TSS_OK;
   long grid = grid_for(groups);
   if (grid > 1024) grid = 1024;
-  tss::ProfScope prof(TSS_K_ARGMAX, (hipStream_t)stream, (double)B * HW * (C * esz(dtype) + 9.0), 0);
+  tss::ProfScope prof(TSS_K_ARGMAX, (hipStream_t)stream, (double)B * HW * (C * tss::esz(dtype) + 9.0), 0);
   const size_t sh = (size_t)C * C * sizeof(unsigned int);
   if (dtype == TSS_BF16)
     hipLaunchKernelGGL(argmax_confusion_kernel<bf16_t>, dim3((int)grid), dim3(NT), sh, (hipStream_t)stream,
@@ -590,7 +589,7 @@ int tss_upsample_argmax_confusion(const void* low, long ldl, const long long* ta
   int band_rows = 64;
   while (band_rows > 16 && (long)B * nstrip * ((H + band_rows - 1) / band_rows) < 2048) band_rows /= 2;
   const long grid = (long)B * nstrip * ((H + band_rows - 1) / band_rows);
-  tss::ProfScope prof(TSS_K_ARGMAX, (hipStream_t)stream, (double)B * h * w * C * esz(dtype) + (double)B * H * W * 9.0, 0);
+  tss::ProfScope prof(TSS_K_ARGMAX, (hipStream_t)stream, (double)B * h * w * C * tss::esz(dtype) + (double)B * H * W * 9.0, 0);
   const size_t sh = (size_t)C * C * sizeof(unsigned int);
 #define TSS_AM_LAUNCH(TT, CPV)                                                                                 \
   hipLaunchKernelGGL((upsample_argmax_kernel<TT, CPV>), dim3((int)grid), dim3(NT), sh, (hipStream_t)stream,      \
@@ -640,7 +639,7 @@ int tss_upsample_ce_fwd(const void* low, long ldl, const long long* target, floa
   float* tiles = ws + grid * 4;
   {
     tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream,
-                        (double)B * h * w * C * (esz(dtype) + 8.0) + (double)B * H * W * 8.0, 0);
+                        (double)B * h * w * C * (tss::esz(dtype) + 8.0) + (double)B * H * W * 8.0, 0);
 #define TSS_CE_LAUNCH(TT, CPV)                                                                                   \
     hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 0>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, \
                        (const TT*)low, ldl, target, tiles, lossrows, B, C, h, w, H, W, ignore_index, geo, nullptr, nullptr)
@@ -661,7 +660,7 @@ int tss_upsample_pixel_ce(const void* low, long ldl, const long long* target, fl
   if ((long)B * H * W == 0) return TSS_OK;
   const CeGeom geo = ce_geom(B, h, w, H, W);
   const long grid = (long)B * geo.nstrip * geo.nband;
-  tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream, (double)B * h * w * C * esz(dtype) + (double)B * H * W * 12.0, 0);
+  tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream, (double)B * h * w * C * tss::esz(dtype) + (double)B * H * W * 12.0, 0);
 #define TSS_CE_LAUNCH(TT, CPV)                                                                                       \
   hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 1>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,     \
                      (const TT*)low, ldl, target, nullptr, nullptr, B, C, h, w, H, W, ignore_index, geo, pix, nullptr)
@@ -683,7 +682,7 @@ int tss_upsample_ohem_grad(const void* low, long ldl, const long long* target, c
   const CeGeom geo = ce_geom(B, h, w, H, W);
   const long grid = (long)B * geo.nstrip * geo.nband;
   float* tiles = ws + grid * 4;
-  tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream, (double)B * h * w * C * (esz(dtype) + 8.0) + (double)B * H * W * 12.0, 0);
+  tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream, (double)B * h * w * C * (tss::esz(dtype) + 8.0) + (double)B * H * W * 12.0, 0);
 #define TSS_CE_LAUNCH(TT, CPV)                                                                                       \
   hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 2>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,     \
                      (const TT*)low, ldl, target, tiles, nullptr, B, C, h, w, H, W, ignore_index, geo, const_cast<float*>(pix), sel)
@@ -702,7 +701,7 @@ int tss_upsample_ce_bwd(const float* ws, const float* inv_count, const float* gr
   if (n == 0) return TSS_OK;
   const CeGeom geo = ce_geom(B, h, w, H, W);
   const float* tiles = ws + (long)B * geo.nstrip * geo.nband * 4;
-  tss::ProfScope prof(TSS_K_UPSAMPLE_CE_BWD, (hipStream_t)stream, (double)n * (4.0 + esz(dtype)), 0);
+  tss::ProfScope prof(TSS_K_UPSAMPLE_CE_BWD, (hipStream_t)stream, (double)n * (4.0 + tss::esz(dtype)), 0);
 #define TSS_CE_GATHER(TT, CPV)                                                                                      \
   hipLaunchKernelGGL((upsample_ce_gather_kernel<TT, CPV>), dim3(grid_for(n / 8)), dim3(NT), 0, (hipStream_t)stream, \
                      tiles, inv_count, grad_out, (TT*)dlow, ldl, B, h, w, H, W, geo)

@@ -513,8 +513,6 @@ __global__ __launch_bounds__(NT) void adamw_kernel(float* p, const float* g, flo
   }
 }
 
-inline size_t esz(int dtype) { return dtype == TSS_BF16 ? 2 : 4; }
-
 // bf16 shadows of the 1x1 convolution weights, all layers in one launch: job j = (f32 source [N][K], bf16 copy [N][K],
 // bf16 transpose [K][N]).  The pointwise kernels stage their weight tiles from these with plain 16-byte copies
 // (forward reads the copy, backward-data the transpose) instead of converting f32 per block.
@@ -627,7 +625,7 @@ int tss_join_fwd(const void* a, long lda, const float* ma, const float* sa, cons
   const int rc = join_geometry(g, &threads, &grid, fwd_blocks);
   if (rc) return rc;
   if (P == 0) return TSS_OK;
-  tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, (double)P * C * (b ? 3 : 2) * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, (double)P * C * (b ? 3 : 2) * tss::esz(dtype), 0);
   if (dtype == TSS_BF16) hipLaunchKernelGGL(join_fwd_kernel<bf16_t>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g);
   else hipLaunchKernelGGL(join_fwd_kernel<float>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g);
   return tss::check_last("join_fwd");
@@ -652,7 +650,7 @@ int tss_join_bwd(const void* dout, long lddo, const void* out, long ldo, int rel
   if (rc) return rc;
   if (P == 0) return TSS_OK;
   const int nt = 1 + (relu ? 1 : 0) + (e ? 1 : 0) + (stats_a ? 1 : 0) + (stats_b ? 1 : 0);
-  tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, (double)P * C * nt * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, (double)P * C * nt * tss::esz(dtype), 0);
   if (dtype == TSS_BF16) hipLaunchKernelGGL(join_bwd_kernel<bf16_t>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g);
   else hipLaunchKernelGGL(join_bwd_kernel<float>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g);
   return tss::check_last("join_bwd");
@@ -684,7 +682,7 @@ int tss_dropout(const void* x, long ldx, void* y, long ldy, long P, int C, float
   const long total = P * (C / 8);
   long grid = (total + NT - 1) / NT;
   if (grid > 2048) grid = 2048;
-  tss::ProfScope prof(TSS_K_DROPOUT, (hipStream_t)stream, 2.0 * P * C * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_DROPOUT, (hipStream_t)stream, 2.0 * P * C * tss::esz(dtype), 0);
   if (dtype == TSS_BF16)
     hipLaunchKernelGGL(dropout_kernel<bf16_t>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,
                        (const bf16_t*)x, ldx, (bf16_t*)y, ldy, P, C, p, seed_slot);
@@ -700,7 +698,7 @@ int tss_bias_grad(const void* e, long lde, long P, int N, float* dbias, int dtyp
   if (P == 0) return TSS_OK;
   long grid = (P + 3) / 4;
   if (grid > 1024) grid = 1024;
-  tss::ProfScope prof(TSS_K_BIAS_GRAD, (hipStream_t)stream, (double)P * N * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_BIAS_GRAD, (hipStream_t)stream, (double)P * N * tss::esz(dtype), 0);
   if (dtype == TSS_BF16)
     hipLaunchKernelGGL(colsum_kernel<bf16_t>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)e, lde, P, N, dbias);
   else
@@ -734,7 +732,7 @@ int tss_channel_shuffle(const void* x, long ldx, void* y, long ldy, long P, int 
   const long total = P * (C / 8);
   long grid = (total + NT - 1) / NT;
   if (grid > 2048) grid = 2048;
-  tss::ProfScope prof(TSS_K_COPY, (hipStream_t)stream, 2.0 * P * C * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_COPY, (hipStream_t)stream, 2.0 * P * C * tss::esz(dtype), 0);
   if (dtype == TSS_BF16)
     hipLaunchKernelGGL(channel_shuffle_kernel<bf16_t>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, P, C, groups);
   else

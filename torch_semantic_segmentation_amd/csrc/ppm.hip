@@ -30,9 +30,6 @@ struct ArmsArgs {
   T* ein[MAXA]; long ldei[MAXA];
 };
 
-__device__ __forceinline__ float blo(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bhi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
-
 // ---------------------------------------------------------------------------------------------------------------- forward
 __global__ __launch_bounds__(NT) void ppm_arms_fwd_kernel(const ArmsArgs g) {
   extern __shared__ __align__(16) unsigned char smem[];

@@ -32,9 +32,6 @@ struct PbArgs {
   const unsigned char* dmask; float dinv;
 };
 
-__device__ __forceinline__ float blo(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bhi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
-
 // NT threads (NW waves); TM pixels per tile, TM / NW per wave; FKM = 16-channel fragments of Cin a wave handles (all of them);
 // NFW = 16-channel fragments of Cout whose weight-gradient rows a wave owns (fragments w, w + NW, ...).  Two instances:
 // NSPLIT = 2: the waves pair up over the input-channel fragments of the input gradient (half of FKM each, twice the pixels).
@@ -297,7 +294,6 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 2 : 1)) void pwbwd_kernel(const Pb
             // lane (fr, fq) needs g[pixel px0 + fr][channels kc0 .. kc0 + 7], kc0 = ks*32 + fq*8: two transposed reads of the blocks
             // (rows kc0 + 0..3 | kc0 + 4..7) x (16 pixels from px0) of Gt; lane 4q + p of the group addresses row q, pixels 4p .. 4p+3
             const int px0 = wp * PXW + m * 16, q = fr >> 2, pq = fr & 3;
-            typedef __attribute__((ext_vector_type(4))) short v4s;
             v4s lo, hi;
             {
               const int row = ks * 32 + fq * 8 + q, pg = (px0 >> 2) + pq;

@@ -61,9 +61,6 @@ struct FastArgs {
   const T* jout; long ldjo; const T* jy; long ldjy; const float* jmean;
 };
 
-__device__ __forceinline__ float bits_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ float bits_lo(uint32_t u) { return __uint_as_float(u << 16); }
-
 // Weight chunk -> LDS as bf16: Ws[n][j] for n in [0, nrows), j in [0, kwp); zero outside [0, ncw) x [0, kw).
 //   w_trans == 0: source w[(n0+n)*ldw + kb + j]   (forward: rows are output channels, ldw = K)
 //   w_trans == 1: source w[(kb+j)*ldw + n0 + n]   (backward-data: the same [N][K] tensor read transposed, ldw = conv K)
@@ -339,9 +336,9 @@ __global__ __launch_bounds__(NT, 2) void pwfast_kernel(const FastArgs g) {
             float v[8];
 #pragma unroll
             for (int h = 0; h < 4; ++h) {
-              float lo = bits_lo(ua[h]) * k0[2 * h] + kadd[2 * h];
-              float hi = bits_hi(ua[h]) * k0[2 * h + 1] + kadd[2 * h + 1];
-              if (BWD) { lo += bits_lo(ub[h]) * k1[2 * h]; hi += bits_hi(ub[h]) * k1[2 * h + 1]; }
+              float lo = blo(ua[h]) * k0[2 * h] + kadd[2 * h];
+              float hi = bhi(ua[h]) * k0[2 * h + 1] + kadd[2 * h + 1];
+              if (BWD) { lo += blo(ub[h]) * k1[2 * h]; hi += bhi(ub[h]) * k1[2 * h + 1]; }
               v[2 * h] = lo; v[2 * h + 1] = hi;
             }
             if (!BWD) {
@@ -418,7 +415,7 @@ __global__ __launch_bounds__(NT, 2) void pwfast_kernel(const FastArgs g) {
             }
             if (BWD && g.xm) {
               const uint2 xr = rxm[i][m];
-              const float xc[4] = {bits_lo(xr.x) - cmm[0], bits_hi(xr.x) - cmm[1], bits_lo(xr.y) - cmm[2], bits_hi(xr.y) - cmm[3]};
+              const float xc[4] = {blo(xr.x) - cmm[0], bhi(xr.x) - cmm[1], blo(xr.y) - cmm[2], bhi(xr.y) - cmm[3]};
               if (g.m_relu) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) if (!(xc[q] * cms[q] + cmb[q] > 0.f)) v[q] = 0.f;
@@ -433,7 +430,7 @@ __global__ __launch_bounds__(NT, 2) void pwfast_kernel(const FastArgs g) {
               if (g.radd) {     // bwd: fan-in of a residual block (the other gradient of this tensor); fwd, eval epilogue: the block's skip
                 const long pr = p0 + wm * (TM / 2) + m * 16 + fr;
                 const uint2 rr = *reinterpret_cast<const uint2*>(g.radd + pr * g.ldr + nlane + i * 16);
-                v[0] += bits_lo(rr.x); v[1] += bits_hi(rr.x); v[2] += bits_lo(rr.y); v[3] += bits_hi(rr.y);
+                v[0] += blo(rr.x); v[1] += bhi(rr.x); v[2] += blo(rr.y); v[3] += bhi(rr.y);
               }
               if (!BWD && g.erelu) {
 #pragma unroll
@@ -444,8 +441,8 @@ __global__ __launch_bounds__(NT, 2) void pwfast_kernel(const FastArgs g) {
                 const long pr = p0 + wm * (TM / 2) + m * 16 + fr;
                 const uint2 ov = *reinterpret_cast<const uint2*>(g.jout + pr * g.ldjo + nlane + i * 16);
                 const uint2 yv = *reinterpret_cast<const uint2*>(g.jy + pr * g.ldjy + nlane + i * 16);
-                const float oo[4] = {bits_lo(ov.x), bits_hi(ov.x), bits_lo(ov.y), bits_hi(ov.y)};
-                const float yc[4] = {bits_lo(yv.x) - cmm[0], bits_hi(yv.x) - cmm[1], bits_lo(yv.y) - cmm[2], bits_hi(yv.y) - cmm[3]};
+                const float oo[4] = {blo(ov.x), bhi(ov.x), blo(ov.y), bhi(ov.y)};
+                const float yc[4] = {blo(yv.x) - cmm[0], bhi(yv.x) - cmm[1], blo(yv.y) - cmm[2], bhi(yv.y) - cmm[3]};
 #pragma unroll
                 for (int q = 0; q < 4; ++q) o[q] = (T)(oo[q] > 0.f ? v[q] : 0.f);
 #pragma unroll
@@ -655,9 +652,9 @@ __global__ __launch_bounds__(NT, 2) void pwfast_mc_kernel(const FastArgs g) {
               float v[8];
 #pragma unroll
               for (int h = 0; h < 4; ++h) {
-                float lo = bits_lo(ua[h]) * k0[2 * h] + kadd[2 * h];
-                float hi = bits_hi(ua[h]) * k0[2 * h + 1] + kadd[2 * h + 1];
-                if (BWD) { lo += bits_lo(ub[h]) * k1[2 * h]; hi += bits_hi(ub[h]) * k1[2 * h + 1]; }
+                float lo = blo(ua[h]) * k0[2 * h] + kadd[2 * h];
+                float hi = bhi(ua[h]) * k0[2 * h + 1] + kadd[2 * h + 1];
+                if (BWD) { lo += blo(ub[h]) * k1[2 * h]; hi += bhi(ub[h]) * k1[2 * h + 1]; }
                 v[2 * h] = lo; v[2 * h + 1] = hi;
               }
               if (!BWD) {
@@ -725,7 +722,7 @@ __global__ __launch_bounds__(NT, 2) void pwfast_mc_kernel(const FastArgs g) {
             }
             if (BWD && g.xm) {
               const uint2 xr = *reinterpret_cast<const uint2*>(xrow_m + (long)m * 16 * g.ldxm + i * 16);
-              const float xc[4] = {bits_lo(xr.x) - cmm[0], bits_hi(xr.x) - cmm[1], bits_lo(xr.y) - cmm[2], bits_hi(xr.y) - cmm[3]};
+              const float xc[4] = {blo(xr.x) - cmm[0], bhi(xr.x) - cmm[1], blo(xr.y) - cmm[2], bhi(xr.y) - cmm[3]};
               if (g.m_relu) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) if (!(xc[q] * cms[q] + cmb[q] > 0.f)) v[q] = 0.f;
@@ -740,7 +737,7 @@ __global__ __launch_bounds__(NT, 2) void pwfast_mc_kernel(const FastArgs g) {
               if (g.radd) {     // bwd: fan-in of a residual block (the other gradient of this tensor); fwd, eval epilogue: the block's skip
                 const long pr = p0 + wm * (TM / 2) + m * 16 + fr;
                 const uint2 rr = *reinterpret_cast<const uint2*>(g.radd + pr * g.ldr + nlane + i * 16);
-                v[0] += bits_lo(rr.x); v[1] += bits_hi(rr.x); v[2] += bits_lo(rr.y); v[3] += bits_hi(rr.y);
+                v[0] += blo(rr.x); v[1] += bhi(rr.x); v[2] += blo(rr.y); v[3] += bhi(rr.y);
               }
               if (!BWD && g.erelu) {
 #pragma unroll
@@ -751,8 +748,8 @@ __global__ __launch_bounds__(NT, 2) void pwfast_mc_kernel(const FastArgs g) {
                 const long pr = p0 + wm * (TM / 2) + m * 16 + fr;
                 const uint2 ov = *reinterpret_cast<const uint2*>(g.jout + pr * g.ldjo + nlane + i * 16);
                 const uint2 yv = *reinterpret_cast<const uint2*>(g.jy + pr * g.ldjy + nlane + i * 16);
-                const float oo[4] = {bits_lo(ov.x), bits_hi(ov.x), bits_lo(ov.y), bits_hi(ov.y)};
-                const float yc[4] = {bits_lo(yv.x) - cmm[0], bits_hi(yv.x) - cmm[1], bits_lo(yv.y) - cmm[2], bits_hi(yv.y) - cmm[3]};
+                const float oo[4] = {blo(ov.x), bhi(ov.x), blo(ov.y), bhi(ov.y)};
+                const float yc[4] = {blo(yv.x) - cmm[0], bhi(yv.x) - cmm[1], blo(yv.y) - cmm[2], bhi(yv.y) - cmm[3]};
 #pragma unroll
                 for (int q = 0; q < 4; ++q) o[q] = (T)(oo[q] > 0.f ? v[q] : 0.f);
 #pragma unroll

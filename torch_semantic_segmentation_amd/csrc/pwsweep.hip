@@ -33,7 +33,6 @@ namespace {
 typedef bf16_t T;
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((ext_vector_type(4))) short v4s;
 
 struct SwArgs {
   long P;
@@ -45,26 +44,12 @@ struct SwArgs {
   T* ein; long ldei; double* stats; float* ws; int gslots;
 };
 
-__device__ __forceinline__ float blo(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bhi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
-
 // requests the compiler does not count (see above); base: wave-uniform, off: this lane's byte offset
 __device__ __forceinline__ void req16(u32x4& dst, const void* base, int off) {
   asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(off), "s"(base));
 }
 __device__ __forceinline__ void req8(u32x2& dst, const void* base, int off) {
   asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(dst) : "v"(off), "s"(base));
-}
-
-// byte offset of 16-byte chunk ch (0..15) of row `row` in a [rows][256 B] image that serves ds_read_b128 row reads and
-// ds_read_b64_tr_b16 transposed reads alike (cdna_hip_programming.md T10, image (b))
-__device__ __forceinline__ int img_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
-
-__device__ __forceinline__ bf16x8 tr_pair(const unsigned char* lo, const unsigned char* hi) {
-  union { v4s h[2]; bf16x8 v; } u;
-  u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)lo);
-  u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)hi);
-  return u.v;
 }
 
 // FN / FK: 16-channel fragments of Cout / Cin.  TM: pixels per tile.  NGW: waves that stage g (the other 8 - NGW stage a).

@@ -642,7 +642,6 @@ inline int grid_for(long total) {
   if (g < 1) g = 1;
   return (int)g;
 }
-inline size_t esz(int dtype) { return dtype == TSS_BF16 ? 2 : 4; }
 
 }  // namespace
 
@@ -661,7 +660,7 @@ int tss_bilinear_nhwc_fwd(const void* x, long ldx, void* y, long ldy, int B, int
   TSS_REQUIRE(tss::aligned16(x) && tss::aligned16(y), TSS_ERR_ALIGN);
   const long total = (long)B * Hout * Wout * (C / 8);
   if (total == 0) return TSS_OK;
-  tss::ProfScope prof(TSS_K_BILINEAR_FWD, (hipStream_t)stream, ((double)B * Hin * Win + (double)B * Hout * Wout) * C * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_BILINEAR_FWD, (hipStream_t)stream, ((double)B * Hin * Win + (double)B * Hout * Wout) * C * tss::esz(dtype), 0);
   if (dtype == TSS_BF16)
     hipLaunchKernelGGL(bilinear_nhwc_fwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream,
                        (const bf16_t*)x, ldx, (bf16_t*)y, ldy, B, Hin, Win, Hout, Wout, C);
@@ -680,14 +679,14 @@ int tss_bilinear_nhwc_bwd(const void* dy, long lddy, void* dx, long lddx, float*
   if (t1 == 0) return TSS_OK;
   hipStream_t st = (hipStream_t)stream;
   {
-    tss::ProfScope prof(TSS_K_BILINEAR_BWD, st, (double)B * Hout * Wout * C * esz(dtype) + (double)B * Hin * Wout * C * 4, 0);
+    tss::ProfScope prof(TSS_K_BILINEAR_BWD, st, (double)B * Hout * Wout * C * tss::esz(dtype) + (double)B * Hin * Wout * C * 4, 0);
     if (dtype == TSS_BF16)
       hipLaunchKernelGGL(bilinear_nhwc_bwd_rows_kernel<bf16_t>, dim3(grid_for(t1)), dim3(NT), 0, st, (const bf16_t*)dy, lddy, tmp, B, Hin, Hout, Wout, C);
     else
       hipLaunchKernelGGL(bilinear_nhwc_bwd_rows_kernel<float>, dim3(grid_for(t1)), dim3(NT), 0, st, (const float*)dy, lddy, tmp, B, Hin, Hout, Wout, C);
   }
   {
-    tss::ProfScope prof(TSS_K_BILINEAR_BWD_COLS, st, (double)B * Hin * Wout * C * 4 + (double)B * Hin * Win * C * esz(dtype), 0);
+    tss::ProfScope prof(TSS_K_BILINEAR_BWD_COLS, st, (double)B * Hin * Wout * C * 4 + (double)B * Hin * Win * C * tss::esz(dtype), 0);
     if (dtype == TSS_BF16)
       hipLaunchKernelGGL(bilinear_nhwc_bwd_cols_kernel<bf16_t>, dim3(grid_for(t2)), dim3(NT), 0, st, tmp, (bf16_t*)dx, lddx, B, Hin, Win, Wout, C);
     else
@@ -704,7 +703,7 @@ int tss_bilinear_planar_fwd(const void* x, int x_dtype, void* y, int y_dtype, lo
   if (total == 0) return TSS_OK;
   const int grid = grid_for(total);
   tss::ProfScope prof(TSS_K_BILINEAR_PLANAR_FWD, (hipStream_t)stream,
-                      (double)planes * ((double)Hin * Win * esz(x_dtype) + (double)Hout * Wout * esz(y_dtype)), 0);
+                      (double)planes * ((double)Hin * Win * tss::esz(x_dtype) + (double)Hout * Wout * tss::esz(y_dtype)), 0);
   hipStream_t s = (hipStream_t)stream;
   if (x_dtype == TSS_F32 && y_dtype == TSS_F32)
     hipLaunchKernelGGL((bilinear_planar_fwd_kernel<float, float>), dim3(grid), dim3(NT), 0, s, (const float*)x, (float*)y, planes, Hin, Win, Hout, Wout);
@@ -723,7 +722,7 @@ int tss_upsample_head_fwd(const void* low, long ldl, void* y, int B, int N, int 
   TSS_REQUIRE(N > 0 && ldl >= N && (W % 8) == 0 && h > 0 && w > 0, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(y), TSS_ERR_ALIGN);
   if ((long)B * N * H * W == 0) return TSS_OK;
-  tss::ProfScope prof(TSS_K_UPSAMPLE_HEAD_FWD, (hipStream_t)stream, ((double)B * N * h * w + (double)B * N * H * W) * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_UPSAMPLE_HEAD_FWD, (hipStream_t)stream, ((double)B * N * h * w + (double)B * N * H * W) * tss::esz(dtype), 0);
   // class-vector kernel: needs the 8 outputs of a lane within 4 source columns (7*scale_x < 2, i.e. >= ~x3.5
   // upsampling), 16-byte channel vectors (pitch covers whole groups of 8 classes) and an aligned source
   const float sx = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
@@ -763,7 +762,7 @@ int tss_upsample_head_bwd(const void* dy, const float* gscale, float* tmp /*[B*N
   const long t1 = planes * h * (W / 8), t2 = planes * h * w;
   if (t1 == 0) return TSS_OK;
   {
-    tss::ProfScope prof(TSS_K_UPSAMPLE_HEAD_BWD_ROWS, (hipStream_t)stream, (double)planes * H * W * esz(dtype) + (double)planes * h * W * 4, 0);
+    tss::ProfScope prof(TSS_K_UPSAMPLE_HEAD_BWD_ROWS, (hipStream_t)stream, (double)planes * H * W * tss::esz(dtype) + (double)planes * h * W * 4, 0);
     if (dtype == TSS_BF16)
       hipLaunchKernelGGL(upsample_head_bwd_rows_kernel<bf16_t>, dim3(grid_for(t1)), dim3(NT), 0, (hipStream_t)stream,
                          (const bf16_t*)dy, tmp, gscale, planes, h, H, W);
@@ -772,7 +771,7 @@ int tss_upsample_head_bwd(const void* dy, const float* gscale, float* tmp /*[B*N
                          (const float*)dy, tmp, gscale, planes, h, H, W);
   }
   {
-    tss::ProfScope prof(TSS_K_UPSAMPLE_HEAD_BWD_COLS, (hipStream_t)stream, (double)planes * h * W * 4 + (double)planes * h * w * esz(dtype), 0);
+    tss::ProfScope prof(TSS_K_UPSAMPLE_HEAD_BWD_COLS, (hipStream_t)stream, (double)planes * h * W * 4 + (double)planes * h * w * tss::esz(dtype), 0);
     if (dtype == TSS_BF16)
       hipLaunchKernelGGL(upsample_head_bwd_cols_kernel<bf16_t>, dim3(grid_for(t2)), dim3(NT), 0, (hipStream_t)stream,
                          tmp, (bf16_t*)dlow, ldl, B, N, h, w, W);
@@ -792,7 +791,7 @@ int tss_adaptive_pool_fwd(const void* x, long ldx, void* y, long ldy, int B, int
   const int CV = C / 8, NPL = NT / CV;
   const int threads = (CV * NPL + 63) / 64 * 64;
   const int grid = B * bins * bins;
-  tss::ProfScope prof(TSS_K_POOL_FWD, (hipStream_t)stream, (double)B * H * W * C * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_POOL_FWD, (hipStream_t)stream, (double)B * H * W * C * tss::esz(dtype), 0);
   if (dtype == TSS_BF16)
     hipLaunchKernelGGL(adaptive_pool_fwd_kernel<bf16_t>, dim3(grid), dim3(threads), 0, (hipStream_t)stream,
                        (const bf16_t*)x, ldx, (bf16_t*)y, ldy, H, W, C, bins, CV, NPL);
@@ -809,7 +808,7 @@ int tss_adaptive_pool_bwd(const void* dy, long lddy, void* dx, long lddx, int B,
   TSS_REQUIRE(tss::aligned16(dy) && tss::aligned16(dx), TSS_ERR_ALIGN);
   const long total = (long)B * H * W * (C / 8);
   if (total == 0) return TSS_OK;
-  tss::ProfScope prof(TSS_K_POOL_BWD, (hipStream_t)stream, (double)B * H * W * C * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_POOL_BWD, (hipStream_t)stream, (double)B * H * W * C * tss::esz(dtype), 0);
   if (dtype == TSS_BF16)
     hipLaunchKernelGGL(adaptive_pool_bwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream,
                        (const bf16_t*)dy, lddy, (bf16_t*)dx, lddx, B, H, W, C, bins);
@@ -856,7 +855,7 @@ int tss_ppm_pool_fwd(const void* x, long ldx, void* const* y, const long* ldy, c
   const int threads = (CV * NPL + 63) / 64 * 64;
   const int S = ws ? tss_ppm_pool_slices(B, g.cell0[narms]) : 1;   // ws: B * cells * S * C floats
   const int grid = B * g.cell0[narms] * S;
-  tss::ProfScope prof(TSS_K_POOL_FWD, (hipStream_t)stream, (double)narms * B * H * W * C * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_POOL_FWD, (hipStream_t)stream, (double)narms * B * H * W * C * tss::esz(dtype), 0);
   if (dtype == TSS_BF16) hipLaunchKernelGGL(ppm_pool_fwd_kernel<bf16_t>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g, CV, NPL, S, ws);
   else hipLaunchKernelGGL(ppm_pool_fwd_kernel<float>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g, CV, NPL, S, ws);
   if (S > 1) {
@@ -880,7 +879,7 @@ int tss_ppm_pool_bwd(const void* const* dy, const long* lddy, const int* bins, i
     g.raw[a] = dy[a]; g.ldr[a] = lddy[a];
   }
   const long total = (long)B * H * W * (C / 8);
-  tss::ProfScope prof(TSS_K_POOL_BWD, (hipStream_t)stream, (double)B * H * W * C * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_POOL_BWD, (hipStream_t)stream, (double)B * H * W * C * tss::esz(dtype), 0);
   if (dtype == TSS_BF16) hipLaunchKernelGGL(ppm_pool_bwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, g);
   else hipLaunchKernelGGL(ppm_pool_bwd_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, g);
   return tss::check_last("ppm_pool_bwd");
@@ -902,7 +901,7 @@ int tss_ppm_concat_fwd(const void* x, long ldx, const void* const* raw, const lo
     TSS_REQUIRE((mean[a] != nullptr) == (scale[a] != nullptr) && (beta[a] != nullptr) == (scale[a] != nullptr), TSS_ERR_SHAPE);
   }
   const long total = (long)B * H * W * ((C + narms * ca) / 8);
-  tss::ProfScope prof(TSS_K_BILINEAR_FWD, (hipStream_t)stream, (double)B * H * W * (2 * C + narms * ca) * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_BILINEAR_FWD, (hipStream_t)stream, (double)B * H * W * (2 * C + narms * ca) * tss::esz(dtype), 0);
   if (dtype == TSS_BF16) hipLaunchKernelGGL(ppm_concat_fwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, g);
   else hipLaunchKernelGGL(ppm_concat_fwd_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, g);
   return tss::check_last("ppm_concat_fwd");
@@ -926,7 +925,7 @@ int tss_ppm_concat_bwd(const void* dout, long lddo, const void* const* raw, cons
     g.bstats[a] = bstats[a]; g.e[a] = e[a]; g.lde[a] = lde[a];
   }
   const int grid = B * g.cell0[narms];
-  tss::ProfScope prof(TSS_K_BILINEAR_BWD, (hipStream_t)stream, (double)B * H * W * narms * ca * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_BILINEAR_BWD, (hipStream_t)stream, (double)B * H * W * narms * ca * tss::esz(dtype), 0);
   if (dtype == TSS_BF16) hipLaunchKernelGGL(ppm_concat_bwd_kernel<bf16_t>, dim3(grid), dim3(NT), 0, (hipStream_t)stream, g);
   else hipLaunchKernelGGL(ppm_concat_bwd_kernel<float>, dim3(grid), dim3(NT), 0, (hipStream_t)stream, g);
   return tss::check_last("ppm_concat_bwd");
@@ -938,7 +937,7 @@ int tss_copy_nhwc(const void* x, long ldx, void* y, long ldy, long P, int C, int
   TSS_REQUIRE(tss::aligned16(x) && tss::aligned16(y), TSS_ERR_ALIGN);
   const long total = P * (C / 8);
   if (total == 0) return TSS_OK;
-  tss::ProfScope prof(TSS_K_COPY, (hipStream_t)stream, 2.0 * P * C * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_COPY, (hipStream_t)stream, 2.0 * P * C * tss::esz(dtype), 0);
   if (dtype == TSS_BF16)
     hipLaunchKernelGGL(copy_nhwc_kernel<bf16_t>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, P, C);
   else
@@ -952,7 +951,7 @@ int tss_upsample_head_bwd_cols(const float* tmp, void* dlow, long ldl, int B, in
   TSS_REQUIRE(N > 0 && ldl >= N && h > 0 && w > 0, TSS_ERR_SHAPE);
   const long t2 = (long)B * N * h * w;
   if (t2 == 0) return TSS_OK;
-  tss::ProfScope prof(TSS_K_UPSAMPLE_HEAD_BWD_COLS, (hipStream_t)stream, (double)B * N * h * W * 4 + (double)t2 * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_UPSAMPLE_HEAD_BWD_COLS, (hipStream_t)stream, (double)B * N * h * W * 4 + (double)t2 * tss::esz(dtype), 0);
   if (dtype == TSS_BF16)
     hipLaunchKernelGGL(upsample_head_bwd_cols_kernel<bf16_t>, dim3(grid_for(t2)), dim3(NT), 0, (hipStream_t)stream,
                        tmp, (bf16_t*)dlow, ldl, B, N, h, w, W);

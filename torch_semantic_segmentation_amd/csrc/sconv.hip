@@ -16,6 +16,7 @@
 //   dW      : contraction over output pixels -- g and the nine strided copies of x are written once per stage as [pixel][channel]
 //             rows of the dual-use LDS image (pwsweep.hip) and read back transposed; per-block rows, summed by tss_dw_reduce_many.
 #include "common.h"
+#include "wgsweep.h"
 
 namespace {
 
@@ -31,9 +32,6 @@ struct ScArgs {
   T* y; long ldy; double* stats;
   const T* xm; long ldxm; const float* mm; const float* ms; const float* mb; int m_relu;
 };
-
-__device__ __forceinline__ float blo(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bhi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
 
 // fold the prologue constants of one 8-channel vector: MODE 0: a = relu?((x - c1) * c0 + c2); 1: g = c0 * e; 2: g = c0 (e - c2) + c1 (y - c3)
 template <int MODE>
@@ -459,20 +457,10 @@ __global__ __launch_bounds__(NT, 2) void sc2_bwd_kernel(const ScArgs g) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------- weight gradient
-typedef __attribute__((ext_vector_type(4))) short v4s;
-__device__ __forceinline__ int img_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
-__device__ __forceinline__ bf16x8 tr_pair(const unsigned char* lo, const unsigned char* hi) {
-  union { v4s h[2]; bf16x8 v; } u;
-  u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)lo);
-  u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)hi);
-  return u.v;
-}
-
+// The one-sweep scheme of wgsweep.h with the nine taps of the stride-2 window: tap t of output pixel (yo, xo) reads (2 yo + t / 3 - 1, 2 xo + t % 3 - 1).
 struct SwArgs {
   long P; int B, Hi, Wi, Ho, Wo;                       // P = B * Ho * Wo output pixels
-  const T* e; long lde; const T* y; long ldyr; const float* ga; const float* gb; const float* gce; const float* gmu;
-  const T* x; long ldx; const float* xm; const float* xs; const float* xb; int x_relu;
-  float* ws;                                           // [gridDim.x][C * C * 9], torch's [N][C][3][3] order
+  wgs::Operands o;                                     // ws: [gridDim.x][C * C * 9], torch's [N][C][3][3] order
 };
 
 template <int C, bool HASY>
@@ -485,13 +473,13 @@ __global__ __launch_bounds__(NT, C == 64 ? 1 : 2) void sc2_wgrad_kernel(const Sw
   const int cv = tid % NV, r = tid / NV;
 
   float ca[8], cb[HASY ? 8 : 1], cc[HASY ? 8 : 1], as[8], ab[8];
-  const bool gplain = !HASY && !g.ga, aplain = !g.xs && !g.xm && !g.xb && !g.x_relu;
+  const bool gplain = !HASY && !g.o.ga, aplain = !g.o.xs && !g.o.xm && !g.o.xb && !g.o.x_relu;
   {
-    const float* safe = reinterpret_cast<const float*>(g.e);
+    const float* safe = reinterpret_cast<const float*>(g.o.e);
     float v0[8], v1[8], v2[8], v3[8], w0[8], w1[8], w2[8];
-    const float* p0 = g.ga ? g.ga + cv * 8 : safe; const float* p1 = (HASY && g.gb) ? g.gb + cv * 8 : safe;
-    const float* p2 = (HASY && g.gce) ? g.gce + cv * 8 : safe; const float* p3 = (HASY && g.gmu) ? g.gmu + cv * 8 : safe;
-    const float* q0 = g.xs ? g.xs + cv * 8 : safe; const float* q1 = g.xm ? g.xm + cv * 8 : safe; const float* q2 = g.xb ? g.xb + cv * 8 : safe;
+    const float* p0 = g.o.ga ? g.o.ga + cv * 8 : safe; const float* p1 = (HASY && g.o.gb) ? g.o.gb + cv * 8 : safe;
+    const float* p2 = (HASY && g.o.gce) ? g.o.gce + cv * 8 : safe; const float* p3 = (HASY && g.o.gmu) ? g.o.gmu + cv * 8 : safe;
+    const float* q0 = g.o.xs ? g.o.xs + cv * 8 : safe; const float* q1 = g.o.xm ? g.o.xm + cv * 8 : safe; const float* q2 = g.o.xb ? g.o.xb + cv * 8 : safe;
 #pragma unroll
     for (int h = 0; h < 8; h += 4) {
       V4<float>::load(p0 + h, v0 + h); V4<float>::load(p1 + h, v1 + h); V4<float>::load(p2 + h, v2 + h); V4<float>::load(p3 + h, v3 + h);
@@ -499,14 +487,14 @@ __global__ __launch_bounds__(NT, C == 64 ? 1 : 2) void sc2_wgrad_kernel(const Sw
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float gav = g.ga ? v0[j] : 1.f;
+      const float gav = g.o.ga ? v0[j] : 1.f;
       ca[j] = gav;
       if (HASY) { cb[j] = v1[j]; cc[j] = -(gav * v2[j]) - v1[j] * v3[j]; }
-      const float sc = g.xs ? w0[j] : 1.f;
-      as[j] = sc; ab[j] = (g.xb ? w2[j] : 0.f) - (g.xm ? w1[j] : 0.f) * sc;
+      const float sc = g.o.xs ? w0[j] : 1.f;
+      as[j] = sc; ab[j] = (g.o.xb ? w2[j] : 0.f) - (g.o.xm ? w1[j] : 0.f) * sc;
     }
   }
-  const float relu_lo = g.x_relu ? 0.f : -TSS_INF;
+  const float relu_lo = g.o.x_relu ? 0.f : -TSS_INF;
 
   const int fi = C == 64 ? wave : (wave & 1);
   const int fj0 = C == 64 ? 0 : (wave >> 1);
@@ -552,14 +540,14 @@ __global__ __launch_bounds__(NT, C == 64 ? 1 : 2) void sc2_wgrad_kernel(const Sw
     const int yo = (int)(byo % g.Ho);                                                                    \
     const long bi = (byo / g.Ho) * g.Hi;                                                                 \
     okb = in ? 512u : 0u;                                                                                \
-    re = *reinterpret_cast<const uint4*>(g.e + pcl * g.lde + cv * 8);                                    \
-    if (HASY) ry = *reinterpret_cast<const uint4*>(g.y + pcl * g.ldyr + cv * 8);                         \
+    re = *reinterpret_cast<const uint4*>(g.o.e + pcl * g.o.lde + cv * 8);                                    \
+    if (HASY) ry = *reinterpret_cast<const uint4*>(g.o.y + pcl * g.o.ldyr + cv * 8);                         \
     _Pragma("unroll") for (int t = 0; t < 9; ++t) {                                                     \
       const int yi = 2 * yo + t / 3 - 1, xi = 2 * xo + t % 3 - 1;                                        \
       const bool ok = in && yi >= 0 && yi < g.Hi && xi >= 0 && xi < g.Wi;                                \
       okb |= ok ? (1u << t) : 0u;                                                                        \
       const long q = ok ? (bi + yi) * g.Wi + xi : (bi + 2 * yo) * g.Wi + 2 * xo;                         \
-      rx[t] = *reinterpret_cast<const uint4*>(g.x + q * g.ldx + cv * 8);                                 \
+      rx[t] = *reinterpret_cast<const uint4*>(g.o.x + q * g.o.ldx + cv * 8);                                 \
     }                                                                                                    \
   }
 
@@ -617,7 +605,7 @@ __global__ __launch_bounds__(NT, C == 64 ? 1 : 2) void sc2_wgrad_kernel(const Sw
     b ^= 1;
   }
 #undef SW_ISSUE
-  float* row = g.ws + (long)blockIdx.x * (9 * C * C);
+  float* row = g.o.ws + (long)blockIdx.x * (9 * C * C);
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -642,14 +630,14 @@ __global__ __launch_bounds__(NT, 2) void sc2_wgrad_rect_kernel(const SwArgs g) {
   const int cve = tid % NVE, re_ = tid / NVE, cvx = tid % NVX, rx_ = tid / NVX;
 
   float ca[8], cb[HASY ? 8 : 1], cc[HASY ? 8 : 1], as[8], ab[8];
-  const bool gplain = !HASY && !g.ga, aplain = !g.xs && !g.xm && !g.xb && !g.x_relu;
+  const bool gplain = !HASY && !g.o.ga, aplain = !g.o.xs && !g.o.xm && !g.o.xb && !g.o.x_relu;
   {
-    const float* safe = reinterpret_cast<const float*>(g.e);
+    const float* safe = reinterpret_cast<const float*>(g.o.e);
     const int cx = cvx * 8 < NX ? cvx * 8 : 0;
     float v0[8], v1[8], v2[8], v3[8], w0[8], w1[8], w2[8];
-    const float* p0 = g.ga ? g.ga + cve * 8 : safe; const float* p1 = (HASY && g.gb) ? g.gb + cve * 8 : safe;
-    const float* p2 = (HASY && g.gce) ? g.gce + cve * 8 : safe; const float* p3 = (HASY && g.gmu) ? g.gmu + cve * 8 : safe;
-    const float* q0 = g.xs ? g.xs + cx : safe; const float* q1 = g.xm ? g.xm + cx : safe; const float* q2 = g.xb ? g.xb + cx : safe;
+    const float* p0 = g.o.ga ? g.o.ga + cve * 8 : safe; const float* p1 = (HASY && g.o.gb) ? g.o.gb + cve * 8 : safe;
+    const float* p2 = (HASY && g.o.gce) ? g.o.gce + cve * 8 : safe; const float* p3 = (HASY && g.o.gmu) ? g.o.gmu + cve * 8 : safe;
+    const float* q0 = g.o.xs ? g.o.xs + cx : safe; const float* q1 = g.o.xm ? g.o.xm + cx : safe; const float* q2 = g.o.xb ? g.o.xb + cx : safe;
 #pragma unroll
     for (int h = 0; h < 8; h += 4) {
       V4<float>::load(p0 + h, v0 + h); V4<float>::load(p1 + h, v1 + h); V4<float>::load(p2 + h, v2 + h); V4<float>::load(p3 + h, v3 + h);
@@ -657,14 +645,14 @@ __global__ __launch_bounds__(NT, 2) void sc2_wgrad_rect_kernel(const SwArgs g) {
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float gav = g.ga ? v0[j] : 1.f;
+      const float gav = g.o.ga ? v0[j] : 1.f;
       ca[j] = gav;
       if (HASY) { cb[j] = v1[j]; cc[j] = -(gav * v2[j]) - v1[j] * v3[j]; }
-      const float sc = g.xs ? w0[j] : 1.f;
-      as[j] = sc; ab[j] = (g.xb ? w2[j] : 0.f) - (g.xm ? w1[j] : 0.f) * sc;
+      const float sc = g.o.xs ? w0[j] : 1.f;
+      as[j] = sc; ab[j] = (g.o.xb ? w2[j] : 0.f) - (g.o.xm ? w1[j] : 0.f) * sc;
     }
   }
-  const float relu_lo = g.x_relu ? 0.f : -TSS_INF;
+  const float relu_lo = g.o.x_relu ? 0.f : -TSS_INF;
 
   const int fi = wave % NFE, t0 = wave / NFE;
   int troffG[2], troffA[NTW][NFX][2];
@@ -704,8 +692,8 @@ __global__ __launch_bounds__(NT, 2) void sc2_wgrad_rect_kernel(const SwArgs g) {
       const bool in = rr < PT && p < g.P;                                                                  \
       const long pcl = in ? p : 0;                                                                         \
       oke |= in ? (1u << u) : 0u;                                                                          \
-      re[u] = *reinterpret_cast<const uint4*>(g.e + pcl * g.lde + cve * 8);                                \
-      if (HASY) ry[u] = *reinterpret_cast<const uint4*>(g.y + pcl * g.ldyr + cve * 8);                     \
+      re[u] = *reinterpret_cast<const uint4*>(g.o.e + pcl * g.o.lde + cve * 8);                                \
+      if (HASY) ry[u] = *reinterpret_cast<const uint4*>(g.o.y + pcl * g.o.ldyr + cve * 8);                     \
     }                                                                                                      \
     _Pragma("unroll") for (int u = 0; u < NPX; ++u) {                                                     \
       const int rr = rx_ + u * RPX;                                                                        \
@@ -722,7 +710,7 @@ __global__ __launch_bounds__(NT, 2) void sc2_wgrad_rect_kernel(const SwArgs g) {
         const bool ok = in && yi >= 0 && yi < g.Hi && xi >= 0 && xi < g.Wi;                                \
         okx[u] |= ok ? (1u << t) : 0u;                                                                     \
         const long q = ok ? (bi + yi) * g.Wi + xi : (bi + 2 * yo) * g.Wi + 2 * xo;                         \
-        rx[u][t] = *reinterpret_cast<const uint4*>(g.x + q * g.ldx + (cvx * 8 < NX ? cvx * 8 : 0));       \
+        rx[u][t] = *reinterpret_cast<const uint4*>(g.o.x + q * g.o.ldx + (cvx * 8 < NX ? cvx * 8 : 0));       \
       }                                                                                                    \
     }                                                                                                      \
   }
@@ -795,7 +783,7 @@ __global__ __launch_bounds__(NT, 2) void sc2_wgrad_rect_kernel(const SwArgs g) {
     b ^= 1;
   }
 #undef SR_ISSUE
-  float* row = g.ws + (long)blockIdx.x * (9 * NE * NX);
+  float* row = g.o.ws + (long)blockIdx.x * (9 * NE * NX);
 #pragma unroll
   for (int k = 0; k < NTW; ++k) {
     const int t = t0 + k * TSTEP;
@@ -815,11 +803,7 @@ template <int NE, int NX> constexpr int swr_smem() { return 2 * (((NE / 8 + 9 * 
 
 template <int NE, int NX, bool HASY>
 void launch_swr(const SwArgs& g, int grid, hipStream_t stream) {
-  constexpr int smem = swr_smem<NE, NX>();
-  static tss::DevOnce attr;
-  if (attr.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sc2_wgrad_rect_kernel<NE, NX, HASY>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  hipLaunchKernelGGL((sc2_wgrad_rect_kernel<NE, NX, HASY>), dim3(grid), dim3(NT), smem, stream, g);
+  wgs::launch_with_smem<sc2_wgrad_rect_kernel<NE, NX, HASY>>(grid, NT, swr_smem<NE, NX>(), stream, g);
 }
 
 template <int C> constexpr int sw_smem() { return 2 * (((10 * (C / 8) + 15) / 16) * (C == 64 ? 32 : 64) * 256); }
@@ -877,10 +861,7 @@ void launch_bwd(const ScArgs& g, hipStream_t stream) {
 
 template <int C, bool HASY>
 void launch_sw(const SwArgs& g, int grid, hipStream_t stream) {
-  static tss::DevOnce attr;
-  if (attr.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sc2_wgrad_kernel<C, HASY>), hipFuncAttributeMaxDynamicSharedMemorySize, sw_smem<C>());
-  hipLaunchKernelGGL((sc2_wgrad_kernel<C, HASY>), dim3(grid), dim3(NT), sw_smem<C>(), stream, g);
+  wgs::launch_with_smem<sc2_wgrad_kernel<C, HASY>>(grid, NT, sw_smem<C>(), stream, g);
 }
 
 bool covered(int Hin, int Win, int Cin, int N) { return sc_enabled() && Cin == N && (N == 32 || N == 64) && Hin >= 2 && Win >= 2; }
@@ -955,16 +936,11 @@ extern "C" int tss_sconv_bwd_weight_sweep(const void* e, long lde, const void* y
                                           const float* ga, const float* gb, const float* gce, const float* gmu,
                                           const void* xraw, long ldx, const float* in_mean, const float* in_scale, const float* in_bias,
                                           int in_relu, float* ws, int B, int Hin, int Win, int Cin, int N, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_BF16, TSS_ERR_DTYPE);
-  TSS_REQUIRE((covered(Hin, Win, Cin, N) || rect_covered(Hin, Win, Cin, N)) && (lde % 8) == 0 && lde >= N && (ldx % 8) == 0 && ldx >= Cin && e &&
-              xraw && ws && B > 0, TSS_ERR_SHAPE);
-  TSS_REQUIRE(!yraw || ((ldyr % 8) == 0 && ldyr >= N && ga && gb && gce && gmu), TSS_ERR_SHAPE);
-  TSS_REQUIRE(tss::aligned16(e) && tss::aligned16(xraw) && (!yraw || tss::aligned16(yraw)), TSS_ERR_ALIGN);
   SwArgs g = {};
   g.B = B; g.Hi = Hin; g.Wi = Win; g.Ho = (Hin - 1) / 2 + 1; g.Wo = (Win - 1) / 2 + 1; g.P = (long)B * g.Ho * g.Wo;
-  g.e = (const T*)e; g.lde = lde; g.y = (const T*)yraw; g.ldyr = ldyr; g.ga = ga; g.gb = gb; g.gce = gce; g.gmu = gmu;
-  g.x = (const T*)xraw; g.ldx = ldx; g.xm = in_mean; g.xs = in_scale; g.xb = in_bias; g.x_relu = in_relu;
-  g.ws = ws;
+  g.o = wgs::operands(e, lde, yraw, ldyr, ga, gb, gce, gmu, xraw, ldx, in_mean, in_scale, in_bias, in_relu, ws);
+  const int err = wgs::check_operands(dtype, (covered(Hin, Win, Cin, N) || rect_covered(Hin, Win, Cin, N)) && B > 0, g.o, Cin, N);
+  if (err != TSS_OK) return err;
   const int grid = tss_sconv_bwd_weight_rows(B, Hin, Win, Cin, N, dtype);
   TSS_REQUIRE(grid > 0, TSS_ERR_SHAPE);
   tss::ProfScope prof(TSS_K_CONV3X3_BWD_WEIGHT, (hipStream_t)stream, ((double)g.P * N * (yraw ? 2 : 1) + (double)B * Hin * Win * Cin) * 2.0,

@@ -629,8 +629,6 @@ int launch(WgradArgs& g, int dtype, int kernel_id, hipStream_t stream, double al
   return tss::check_last("wgrad");
 }
 
-inline size_t esz(int dtype) { return dtype == TSS_BF16 ? 2 : 4; }
-
 }  // namespace
 
 bool tss_stem_direct_wgrad(const void* e, long lde, const void* yraw, long ldyr, const float* ga, const float* gb,
@@ -661,7 +659,7 @@ int tss_pwconv_bwd_weight(const void* e, long lde, const void* yraw, long ldyr,
   g.x = xraw; g.ldx = ldx; g.xm = in_mean; g.xs = in_scale; g.xb = in_bias; g.x_relu = in_relu;
   g.Hout = 1; g.Wout = 1;
   g.dw = dw; g.drs = K; g.dcs = 1; g.dts = 0;
-  const double bytes = (double)P * (N * (yraw ? 2 : 1) + K) * esz(dtype);
+  const double bytes = (double)P * (N * (yraw ? 2 : 1) + K) * tss::esz(dtype);
   if (dtype == TSS_BF16 && !g_tss_disable_fast && yraw && (N % 8) == 0 && P > 0) {   // lean pipelined kernel
     tss::ProfScope prof(TSS_K_PWCONV_BWD_WEIGHT, (hipStream_t)stream, bytes, 2.0 * (double)P * N * K);
     g.ws = ws;
@@ -707,7 +705,7 @@ int tss_conv3x3_bwd_weight(const void* e, long lde, const void* yraw, long ldyr,
   g.x = xraw; g.ldx = ldx; g.xm = in_mean; g.xs = in_scale; g.xb = in_bias; g.x_relu = in_relu;
   g.dw = dw; g.drs = (long)Cin * 9; g.dcs = 9; g.dts = 1;  // torch layout [N][Cin][3][3]
   return launch(g, dtype, TSS_K_CONV3X3_BWD_WEIGHT, (hipStream_t)stream,
-                ((double)g.P * N * (yraw ? 2 : 1) + (double)B * Hin * Win * Cin) * esz(dtype));
+                ((double)g.P * N * (yraw ? 2 : 1) + (double)B * Hin * Win * Cin) * tss::esz(dtype));
 }
 
 int tss_conv1d3_bwd_weight(const void* e, long lde, const void* yraw, long ldyr,
@@ -726,7 +724,7 @@ int tss_conv1d3_bwd_weight(const void* e, long lde, const void* yraw, long ldyr,
   g.x = xraw; g.ldx = ldx; g.xm = in_mean; g.xs = in_scale; g.xb = in_bias; g.x_relu = in_relu;
   g.dw = dw; g.drs = (long)Cin * 3; g.dcs = 3; g.dts = 1;  // torch layout [N][Cin][1][3] / [N][Cin][3][1]
   return launch(g, dtype, TSS_K_CONV3X3_BWD_WEIGHT, (hipStream_t)stream,
-                ((double)g.P * N * (yraw ? 2 : 1) + (double)g.P * Cin) * esz(dtype));
+                ((double)g.P * N * (yraw ? 2 : 1) + (double)g.P * Cin) * tss::esz(dtype));
 }
 
 // general dense convolution (tss_convkxk_fwd): dw in the torch layout [N][Cin][kh][kw]
@@ -747,7 +745,7 @@ int tss_convkxk_bwd_weight(const void* e, long lde, const void* yraw, long ldyr,
   g.x = xraw; g.ldx = ldx; g.xm = in_mean; g.xs = in_scale; g.xb = in_bias; g.x_relu = in_relu;
   g.dw = dw; g.drs = (long)Cin * kh * kw; g.dcs = kh * kw; g.dts = 1;
   return launch(g, dtype, TSS_K_CONV3X3_BWD_WEIGHT, (hipStream_t)stream,
-                ((double)g.P * N * (yraw ? 2 : 1) + (double)B * Hin * Win * Cin) * esz(dtype));
+                ((double)g.P * N * (yraw ? 2 : 1) + (double)B * Hin * Win * Cin) * tss::esz(dtype));
 }
 
 int tss_stem3x3_bwd_weight(const void* e, long lde, const void* yraw, long ldyr,
@@ -764,7 +762,7 @@ int tss_stem3x3_bwd_weight(const void* e, long lde, const void* yraw, long ldyr,
   g.e = e; g.lde = lde; g.yraw = yraw; g.ldyr = ldyr; g.ga = ga; g.gb = gb; g.gce = gce; g.gmu = gmu;
   g.x = x_nchw; g.x_f32 = x_is_f32;
   g.dw = dw; g.drs = (long)Cin * 9; g.dcs = 1; g.dts = 0;
-  const double bytes = (double)g.P * N * (yraw ? 2 : 1) * esz(dtype) + (double)B * Cin * Hin * Win * (x_is_f32 ? 4 : esz(dtype));
+  const double bytes = (double)g.P * N * (yraw ? 2 : 1) * tss::esz(dtype) + (double)B * Cin * Hin * Win * (x_is_f32 ? 4 : tss::esz(dtype));
   if (dtype == TSS_BF16 && !g_tss_disable_fast && Cin <= 3 && N == 32 && ws) {   // performance path: direct kernel (stem.hip)
     tss::ProfScope prof(TSS_K_STEM_BWD_WEIGHT, (hipStream_t)stream, bytes, 2.0 * (double)g.P * N * Cin * 9);
     if (tss_stem_direct_wgrad(e, lde, yraw, ldyr, ga, gb, gce, gmu, x_nchw, x_is_f32, dw, ws, B, Cin, Hin, Win, N, stride,

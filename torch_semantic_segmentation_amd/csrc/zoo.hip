@@ -431,7 +431,6 @@ inline int grid_for(long total) {
   long g = (total + NT - 1) / NT;
   return (int)(g > 2048 ? 2048 : (g < 1 ? 1 : g));
 }
-inline size_t esz(int dtype) { return dtype == TSS_BF16 ? 2 : 4; }
 
 }  // namespace
 
@@ -440,7 +439,7 @@ extern "C" {
 int tss_tensor_stats(const void* z, long ldz, long P, int C, double* stats, int dtype, void* stream) {
   TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
   TSS_REQUIRE(P >= 0 && C > 0 && ldz >= C && z && stats, TSS_ERR_SHAPE);
-  tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, (double)P * C * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, (double)P * C * tss::esz(dtype), 0);
   const bool vec = (C % 8) == 0 && C <= NT * 8 / 2 && (ldz % 8) == 0 && tss::aligned16(z) && P >= 4 * TSS_STAT_SLABS;
   if (vec && dtype == TSS_BF16)
     hipLaunchKernelGGL(tensor_stats_vec_kernel<bf16_t>, dim3(TSS_STAT_SLABS), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)z, ldz, P, C, stats);
@@ -460,7 +459,7 @@ int tss_bn_bwd_apply(const void* e, long lde, const void* z, long ldz, const flo
   TSS_REQUIRE(!gb || (z && gce && gmu && (ldz % 8) == 0 && ldz >= C), TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(e) && tss::aligned16(dz) && (!gb || tss::aligned16(z)), TSS_ERR_ALIGN);
   if (P == 0) return TSS_OK;
-  tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, (double)P * C * esz(dtype) * (gb ? 3 : 2), 0);
+  tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, (double)P * C * tss::esz(dtype) * (gb ? 3 : 2), 0);
   if (dtype == TSS_BF16)
     hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, dim3(grid_for(P * (C / 8))), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)e, lde,
                        (const bf16_t*)z, ldz, ga, gb, gce, gmu, (bf16_t*)dz, lddz, P, C);
@@ -478,7 +477,7 @@ int tss_pool_concat_fwd(const void* y1, long ld1, const float* bias, int N1, con
   PoolArgs g = {x, x_f32, sxb, sxc, sxh, sxw, Cin, N1, B, Hin / 2, Win / 2};
   const long total = (long)B * g.Ho * g.Wo * (N1 + Cin);
   if (total == 0) return TSS_OK;
-  tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, (double)B * g.Ho * g.Wo * (2.0 * N1 + 5.0 * Cin) * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, (double)B * g.Ho * g.Wo * (2.0 * N1 + 5.0 * Cin) * tss::esz(dtype), 0);
   // an NHWC activation of the output's dtype, whole vectors everywhere: the vectorised kernel
   const bool vec = (x_f32 != 0) == (dtype == TSS_F32) && sxc == 1 && (N1 % 8) == 0 && (Cin % 8) == 0 && (ld1 % 8) == 0 && (ldz % 8) == 0 &&
                    (sxb % 8) == 0 && (sxh % 8) == 0 && (sxw % 8) == 0 && tss::aligned16(x) && tss::aligned16(z) && (N1 == 0 || tss::aligned16(y1));
@@ -521,7 +520,7 @@ int tss_pool_concat_bwd(const void* dz, long lddz, int N1, const void* x, int x_
   PoolArgs g = {x, x_f32, sxb, sxc, sxh, sxw, Cin, N1, B, Hin / 2, Win / 2};
   const long total = (long)B * g.Ho * g.Wo * Cin;
   if (total == 0) return TSS_OK;
-  tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, (double)total * 9.0 * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, (double)total * 9.0 * tss::esz(dtype), 0);
   const bool vec = (x_f32 != 0) == (dtype == TSS_F32) && sxc == 1 && (N1 % 8) == 0 && (Cin % 8) == 0 && (lddz % 8) == 0 && (lddx % 8) == 0 &&
                    (sxb % 8) == 0 && (sxh % 8) == 0 && (sxw % 8) == 0 && tss::aligned16(x) && tss::aligned16(dz) && tss::aligned16(dx);
   if (vec) {
@@ -558,7 +557,7 @@ int tss_mul_addrows_fwd(const void* u, long ldu, const void* a, long lda, const 
   TSS_REQUIRE(tss::aligned16(u) && tss::aligned16(a) && tss::aligned16(r) && tss::aligned16(out), TSS_ERR_ALIGN);
   const long P = (long)B * HW;
   if (P == 0) return TSS_OK;
-  tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, 3.0 * P * C * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, 3.0 * P * C * tss::esz(dtype), 0);
   if (dtype == TSS_BF16)
     hipLaunchKernelGGL(mul_addrows_fwd_kernel<bf16_t>, dim3(grid_for(P * (C / 8))), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)u, ldu,
                        (const bf16_t*)a, lda, (const bf16_t*)r, ldr, (bf16_t*)out, ldo, HW, P, C);
@@ -576,7 +575,7 @@ int tss_mul_addrows_bwd(const void* g, long ldg, const void* u, long ldu, const 
   TSS_REQUIRE(tss::aligned16(g) && tss::aligned16(u) && tss::aligned16(a) && tss::aligned16(du) && tss::aligned16(da), TSS_ERR_ALIGN);
   if ((long)B * HW == 0) return TSS_OK;
   const int S = tss_rows_slices(B, HW);
-  tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, 5.0 * B * HW * C * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, 5.0 * B * HW * C * tss::esz(dtype), 0);
 #define TSS_MAR_BWD(TT)                                                                                                              \
   hipLaunchKernelGGL(mul_addrows_bwd_kernel<TT>, dim3(B * S), dim3(NT), 0, (hipStream_t)stream, (const TT*)g, ldg, (const TT*)u, ldu,  \
                      (const TT*)a, lda, (TT*)du, lddu, (TT*)da, ldda, ws, HW, C, S);                                                 \
@@ -593,7 +592,7 @@ int tss_cat2_add(const void* gl, long ldl, const void* gr, long ldr, const void*
               gl && gr && out && (!gs || ((lds % 8) == 0 && lds >= 2 * half)), TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(gl) && tss::aligned16(gr) && tss::aligned16(out) && (!gs || tss::aligned16(gs)), TSS_ERR_ALIGN);
   if (P == 0) return TSS_OK;
-  tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, (double)P * half * (gs ? 6.0 : 4.0) * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, (double)P * half * (gs ? 6.0 : 4.0) * tss::esz(dtype), 0);
   if (dtype == TSS_BF16)
     hipLaunchKernelGGL(cat2_add_kernel<bf16_t>, dim3(grid_for(P * (half / 4))), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)gl, ldl,
                        (const bf16_t*)gr, ldr, (const bf16_t*)gs, lds, (bf16_t*)out, ldo, P, half);
@@ -608,7 +607,7 @@ int tss_pad_channels(const void* g, long ldg, int C, void* out, long ldo, int CP
   TSS_REQUIRE(C > 0 && CP >= C && (CP % 8) == 0 && ldg >= C && (ldo % 8) == 0 && ldo >= CP && g && out, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(out), TSS_ERR_ALIGN);
   if (P == 0) return TSS_OK;
-  tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, (double)P * (C + CP) * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, (double)P * (C + CP) * tss::esz(dtype), 0);
   if (dtype == TSS_BF16)
     hipLaunchKernelGGL(pad_channels_kernel<bf16_t>, dim3(grid_for(P * (CP / 8))), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)g, ldg, C,
                        (bf16_t*)out, ldo, CP, P);
@@ -624,7 +623,7 @@ int tss_scale_rows(const void* x, long ldx, const float* m, void* out, long ldo,
   TSS_REQUIRE(tss::aligned16(x) && tss::aligned16(out), TSS_ERR_ALIGN);
   const long P = (long)B * HW;
   if (P == 0) return TSS_OK;
-  tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, 2.0 * P * C * esz(dtype), 0);
+  tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, 2.0 * P * C * tss::esz(dtype), 0);
   if (dtype == TSS_BF16)
     hipLaunchKernelGGL(scale_rows_kernel<bf16_t>, dim3(grid_for(P * (C / 8))), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, m,
                        (bf16_t*)out, ldo, HW, P, C);
