@@ -633,6 +633,21 @@ int tss_ohem_fwd(const void* logits, const long long* target, float* lse, float*
 int tss_ohem_bwd(const void* logits, const long long* target, const float* lse, const float* pixel_loss,
                  const float* params, const float* grad_out, void* dlogits, long B, int C, long HW, int ignore_index,
                  int dtype, void* stream);
+/* Lovasz-Softmax loss (TSS/losses/lovasz_softmax_loss.py:7-59): per present class the errors |fg - softmax| are sorted in
+ * descending order by a segmented stable LSD radix sort (ties: ascending flat pixel index), the foreground counts scanned,
+ * and the Lovasz weights g_r applied in closed form.  variant 0 = the reference's weighting (g_r = J_r - J_0), 1 = Berman et
+ * al.'s (g_r = J_r - J_{r-1}).  has_ignore = 0 keeps every pixel (ignore_index=None).  Labels outside [0,C) that are not
+ * the ignore index are background for every class.  No class present: *loss = 0, zero gradient.  B*HW < 2^31, HW % 8 == 0.
+ * workspace = tss_lovasz_workspace_bytes(B*HW, C) bytes, 256-byte aligned, uninitialised; the forward leaves in it what
+ * the backward reads (g_rank per class and pixel).  The sort buffers inside it are bounded: chunk_classes = 0 sorts as
+ * many classes at a time as fit in 2 GiB of (key, payload) double buffers (16 B per pixel and class), > 0 that many; the
+ * three calls of one loss take the same value. */
+long tss_lovasz_workspace_bytes(long n_pixels, int C, int chunk_classes);
+int tss_lovasz_fwd(const void* logits, const long long* target, void* workspace, float* loss, float* n_present,
+                   long B, int C, long HW, int ignore_index, int has_ignore, int variant, int chunk_classes, int dtype,
+                   void* stream);
+int tss_lovasz_bwd(const void* logits, const long long* target, const void* workspace, const float* n_present,
+                   const float* grad_out, void* dlogits, long B, int C, long HW, int chunk_classes, int dtype, void* stream);
 /* Fused decoder head + loss: cross-entropy (mean over the non-ignored pixels) of the bilinearly upsampled logits,
  * straight from the low-res NHWC logits (replaces F.interpolate TSS/models/fastscnn.py:63-64 + the loss call
  * TSS/engine.py:30 as one operator; the full-resolution logits and their gradient are never materialised).

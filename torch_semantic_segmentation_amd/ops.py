@@ -3026,6 +3026,85 @@ class OHEMLoss(torch.nn.Module):
         return ohem_loss(input, target, self.ignore_index, self.thresh_loss, self.numel_frac)
 
 
+LOVASZ_VARIANTS = {'reference': 0, 'berman': 1}
+lovasz_chunk_classes = 0     # classes sorted at a time; 0: as many as fit in 2 GiB of sort buffers (csrc/lovasz.hip)
+
+
+class LovaszSoftmaxFn(Function):
+    """lovasz_softmax_loss (TSS/losses/lovasz_softmax_loss.py:20-45): a segmented stable radix sort of the per-class errors,
+    a scan of the foreground flags and closed-form Lovasz weights, all on the device (csrc/lovasz.hip); no argsort, no
+    host read-back, graph-capturable and bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, variant):
+        _check_device(logits)
+        logits = logits.contiguous()
+        B, C, H, W = logits.shape
+        if (H * W) % 8:
+            raise NotImplementedError('HIP path: H*W must be a multiple of 8')
+        if B * H * W >= 2 ** 31:
+            raise NotImplementedError('HIP path: lovasz_softmax_loss needs B*H*W < 2**31')
+        if target.dtype != torch.int64 or target.shape != (B, H, W):
+            raise RuntimeError('target must be int64 of shape (B,H,W)')
+        target = target.contiguous()
+        dev = logits.device
+        code = N.dtype_code(logits.dtype)
+        # g_rank per class and pixel (read by backward) + the bounded sort buffers; the caching allocator returns
+        # 512-byte aligned blocks, and inside a graph capture the block comes from the graph's own pool
+        chunk = int(lovasz_chunk_classes)
+        ws = torch.empty(N.lib().tss_lovasz_workspace_bytes(B * H * W, C, chunk), dtype=torch.uint8, device=dev)
+        out = torch.empty(2, dtype=torch.float32, device=dev)              # loss, number of present classes
+        has_ignore = ignore_index is not None
+        call('tss_lovasz_fwd', ptr(logits), ptr(target), ptr(ws), ptr(out[0:1]), ptr(out[1:2]), B, C, H * W,
+             int(ignore_index) if has_ignore else 0, int(has_ignore), LOVASZ_VARIANTS[variant], chunk, code, stream())
+        ctx.chunk = chunk
+        ctx.save_for_backward(logits, target, ws, out)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, target, ws, out = ctx.saved_tensors
+        B, C, H, W = logits.shape
+        gout = gout.to(torch.float32).contiguous()
+        d = torch.empty_like(logits)
+        call('tss_lovasz_bwd', ptr(logits), ptr(target), ptr(ws), ptr(out[1:2]), ptr(gout), ptr(d), B, C, H * W,
+             ctx.chunk, N.dtype_code(logits.dtype), stream())
+        return d, None, None, None
+
+
+def lovasz_softmax_loss(input, target, num_classes, ignore_index=None, variant='reference'):
+    """TSS/losses/lovasz_softmax_loss.py:20-45 for (B,C,H,W) logits and an int64 (B,H,W) target.
+
+    variant='reference' weights rank r >= 1 with J_r - J_0, which is what the reference's lovasz_grad (:15-16) computes
+    (value and gradient are a drop-in for it; the value grows with the number of pixels); variant='berman' uses the
+    published successive difference J_r - J_{r-1} (Berman et al. 2018), a loss in [0, 1].  Pixels with target ==
+    ignore_index are dropped (None keeps all); other labels outside [0, C) are background for every class, as upstream.
+
+    Two documented differences from the reference: equal errors are ordered by ascending flat pixel index (torch.argsort
+    leaves ties unspecified), which keeps the step bit-reproducible; and when no class is present (e.g. every pixel
+    ignored) the loss is 0.0 with a zero gradient, without a host read-back, where the reference raises from
+    torch.stack([])."""
+    if variant not in LOVASZ_VARIANTS:
+        raise ValueError("variant must be 'reference' or 'berman', got %r" % (variant,))
+    if input.dim() != 4 or int(num_classes) != input.shape[1]:
+        raise ValueError('num_classes (%s) must equal the channel count of the (B,C,H,W) logits %s'
+                         % (num_classes, tuple(input.shape)))
+    return LovaszSoftmaxFn.apply(input, target, ignore_index, variant)
+
+
+class LovaszSoftmaxLoss(torch.nn.Module):
+    """Drop-in for TSS.losses.LovaszSoftmaxLoss (TSS/losses/lovasz_softmax_loss.py:48-59); see lovasz_softmax_loss."""
+
+    def __init__(self, num_classes, ignore_index=-100, variant='reference'):
+        super().__init__()
+        if variant not in LOVASZ_VARIANTS:
+            raise ValueError("variant must be 'reference' or 'berman', got %r" % (variant,))
+        self.num_classes, self.ignore_index, self.variant = num_classes, ignore_index, variant
+
+    def forward(self, input, target):
+        return lovasz_softmax_loss(input, target, self.num_classes, self.ignore_index, self.variant)
+
+
 class UpsampleCrossEntropyFn(Function):
     """cross_entropy(F.interpolate(low, scale, bilinear, align_corners=True), target) without the full-res logits:
     one pass yields the loss and the unscaled low-res gradient (per-block tiles in a workspace, no atomics, nothing to
