@@ -21,17 +21,18 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'tss_hip.h')
 
 
 def parse_header(path=HEADER_PATH):
-    """{function name: [ctypes argument types]} for every `int tss_*(...)` declared in include/tss_hip.h.
+    """{function name: (ctypes return type, [ctypes argument types])} for every `tss_*` function declared in include/tss_hip.h.
 
     The binding is generated from the header so the two cannot drift apart; pointer parameters of any
-    pointee type map to c_void_p (callers pass tensor.data_ptr() or None).
+    pointee type map to c_void_p (callers pass tensor.data_ptr(), None, byref(...) or a ctypes array).
     """
     import re
     text = open(path).read()
     text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    scalars = {'int': _I, 'long': _L, 'float': _F, 'double': _D}
     decls = {}
-    for m in re.finditer(r'\bint\s+(tss_\w+)\s*\(([^)]*)\)\s*;', text):
-        name, params = m.group(1), m.group(2).strip()
+    for m in re.finditer(r'\b(int|long|const\s+char\s*\*)\s*(tss_\w+)\s*\(([^)]*)\)\s*;', text):
+        ret, name, params = m.group(1), m.group(2), m.group(3).strip()
         types = []
         if params and params != 'void':
             for prm in params.split(','):
@@ -40,9 +41,8 @@ def parse_header(path=HEADER_PATH):
                     types.append(_P)
                 else:
                     words = prm.split()[:-1]  # drop the parameter name
-                    base = ' '.join(w for w in words if w != 'const')
-                    types.append({'int': _I, 'long': _L, 'float': _F, 'double': _D}[base])
-        decls[name] = types
+                    types.append(scalars[' '.join(w for w in words if w != 'const')])
+        decls[name] = (scalars.get(ret, ctypes.c_char_p), types)
     return decls
 
 
@@ -58,31 +58,10 @@ def lib():
                 'libtss_hip.so is not built (%s). Run `python -m torch_semantic_segmentation_amd.build`; '
                 'this package has no non-HIP fallback.' % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in parse_header().items():
+        for name, (restype, argtypes) in parse_header().items():
             fn = getattr(handle, name)  # AttributeError here = header/library mismatch
             fn.argtypes = argtypes
-            fn.restype = ctypes.c_int
-        handle.tss_last_error.restype = ctypes.c_char_p
-        handle.tss_arch.restype = ctypes.c_char_p
-        handle.tss_prof_name.restype = ctypes.c_char_p
-        handle.tss_prof_name.argtypes = [ctypes.c_int]
-        handle.tss_prof_symbol.restype = ctypes.c_char_p
-        handle.tss_prof_symbol.argtypes = [ctypes.c_int]
-        handle.tss_prof_get.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_double),
-                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
-        handle.tss_prof_records.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double),
-                                            ctypes.POINTER(ctypes.c_double), ctypes.c_long]
-        handle.tss_prof_records.restype = ctypes.c_long
-        handle.tss_pwconv_bwd_weight_ws.argtypes = [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        handle.tss_pwconv_bwd_weight_ws.restype = ctypes.c_long
-        handle.tss_upsample_ce_ws.argtypes = [ctypes.c_int] * 6
-        handle.tss_upsample_ce_ws.restype = ctypes.c_long
-        handle.tss_ohem_workspace_bytes.argtypes = []
-        handle.tss_ohem_workspace_bytes.restype = ctypes.c_long
-        handle.tss_lovasz_workspace_bytes.argtypes = [ctypes.c_long, ctypes.c_int, ctypes.c_int]
-        handle.tss_lovasz_workspace_bytes.restype = ctypes.c_long
-        handle.tss_bn_xchg_bytes.argtypes = []
-        handle.tss_bn_xchg_bytes.restype = ctypes.c_long
+            fn.restype = restype
         _lib = handle
     return _lib
 

@@ -235,6 +235,25 @@ struct DevOnce {
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline size_t esz(int dtype) { return dtype == TSS_BF16 ? 2 : 4; }
 
+// Grid for a grid-stride elementwise kernel: one thread of an nt-thread block per item, at most `cap` blocks.
+inline int grid_for(long total, int nt, long cap = 4096) {
+  long g = (total + nt - 1) / nt;
+  if (g > cap) g = cap;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
 }  // namespace tss
 
 #define TSS_REQUIRE(cond, code) do { if (!(cond)) return (code); } while (0)
+#define TSS_CHECK_DTYPE(dtype) TSS_REQUIRE((dtype) == TSS_F32 || (dtype) == TSS_BF16, TSS_ERR_DTYPE)
+
+// The dtype dispatch of every entry point: runs the statement(s) once with the local alias TT (or NAME) bound to the element type,
+//   TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(k<TT>, dim3(grid), dim3(NT), 0, st, (const TT*)x, (TT*)y, n));
+// Anything but TSS_BF16 selects float: TSS_CHECK_DTYPE comes first.
+#define TSS_WITH_DTYPE_AS(NAME, dtype, ...)          \
+  do {                                               \
+    if ((dtype) == TSS_BF16) { using NAME = bf16_t; __VA_ARGS__; }  \
+    else { using NAME = float; __VA_ARGS__; }        \
+  } while (0)
+#define TSS_WITH_DTYPE(dtype, ...) TSS_WITH_DTYPE_AS(TT, dtype, __VA_ARGS__)

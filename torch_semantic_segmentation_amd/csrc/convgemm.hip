@@ -479,7 +479,7 @@ void launch_typed(const GemmArgs& g, int grid, hipStream_t stream) {
 }
 
 void launch_inst(const GemmArgs& g, int dtype, int grid, hipStream_t stream) {
-  if (dtype == TSS_BF16) launch_typed<bf16_t>(g, grid, stream); else launch_typed<float>(g, grid, stream);
+  TSS_WITH_DTYPE(dtype, launch_typed<TT>(g, grid, stream));
 }
 
 int launch(GemmArgs& g, int dtype, int kernel_id, hipStream_t stream, double alg_bytes) {
@@ -559,7 +559,7 @@ extern "C" {
 int tss_pwconv_fwd(const void* x, long ldx, const float* in_mean, const float* in_scale, const float* in_bias, int in_relu,
                    const float* w, const void* w_bf16, const float* bias, void* y, long ldy, double* stats,
                    long P, int K, int N, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(K > 0 && N > 0 && (K % 8) == 0 && (ldx % 8) == 0 && (ldy % 4) == 0 && ldx >= K && ldy >= (N + 3) / 4 * 4,
               TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(x) && tss::aligned16(y) && tss::aligned16(w), TSS_ERR_ALIGN);
@@ -582,7 +582,7 @@ int tss_pwconv_bwd_data(const void* e, long lde, const void* yraw, long ldyr,
                         const void* xraw, long ldx, const float* in_mean, const float* in_scale, const float* in_bias, int in_relu,
                         void* e_in, long ldei, double* bstats, const float* wg_ws, float* wg_dw, long wg_P, int wg_K, int wg_N,
                         long P, int K, int N, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(K > 0 && N > 0 && (K % 8) == 0 && (lde % 8) == 0 && lde >= (N + 7) / 8 * 8 && (ldei % 4) == 0 && ldei >= K,
               TSS_ERR_SHAPE);
   if (wg_P <= 0) { wg_P = P; wg_K = K; wg_N = N; }      // the slots of this layer's own weight gradient
@@ -662,7 +662,7 @@ int tss_pwconv_bwd_data_joined(const void* e, long lde, const void* yraw, long l
 int tss_conv3x3_fwd(const void* x, long ldx, const float* in_mean, const float* in_scale, const float* in_bias, int in_relu,
                     const float* w_tnc, const void* w_tnc_bf16, void* y, long ldy, double* stats,
                     int B, int Hin, int Win, int Cin, int N, int stride, int dil, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(Cin > 0 && N > 0 && (Cin % 8) == 0 && (ldx % 8) == 0 && ldx >= Cin && (ldy % 4) == 0 && ldy >= N && stride >= 1 && dil >= 1,
               TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(x) && tss::aligned16(y), TSS_ERR_ALIGN);
@@ -704,7 +704,7 @@ int tss_conv3x3_bwd_data(const void* e, long lde, const void* yraw, long ldyr,
                          void* e_in, long ldei, double* bstats,
                          int B, int H, int W, int Cin, int N, int dil, int dtype, void* stream) {
   // stride-1 dense 3x3 only (the hot path has no strided dense conv with Cin > 3)
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(Cin > 0 && N > 0 && (N % 8) == 0 && (Cin % 4) == 0 && (lde % 8) == 0 && lde >= N && (ldei % 4) == 0 && ldei >= Cin,
               TSS_ERR_SHAPE);
   TSS_REQUIRE(!yraw || ((ldyr % 8) == 0 && ldyr >= N), TSS_ERR_SHAPE);
@@ -735,7 +735,7 @@ int tss_conv3x3_bwd_data(const void* e, long lde, const void* yraw, long ldyr,
 int tss_conv1d3_fwd(const void* x, long ldx, const float* in_mean, const float* in_scale, const float* in_bias, int in_relu,
                     const float* w_tnc, const float* bias, void* y, long ldy, double* stats,
                     int B, int H, int W, int Cin, int N, int axis, int dil, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(Cin > 0 && N > 0 && (Cin % 8) == 0 && (ldx % 8) == 0 && ldx >= Cin && (ldy % 4) == 0 && ldy >= N && dil >= 1 &&
               (axis == 0 || axis == 1) && w_tnc, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(x) && tss::aligned16(y), TSS_ERR_ALIGN);
@@ -764,7 +764,7 @@ int tss_conv1d3_bwd_data(const void* e, long lde, const void* yraw, long ldyr,
                          const void* xraw, long ldx, const float* in_mean, const float* in_scale, const float* in_bias, int in_relu,
                          void* e_in, long ldei, double* bstats,
                          int B, int H, int W, int Cin, int N, int axis, int dil, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(Cin > 0 && N > 0 && (N % 8) == 0 && (Cin % 4) == 0 && (lde % 8) == 0 && lde >= N && (ldei % 4) == 0 && ldei >= Cin &&
               (axis == 0 || axis == 1) && w_tcn, TSS_ERR_SHAPE);
   TSS_REQUIRE(!yraw || ((ldyr % 8) == 0 && ldyr >= N), TSS_ERR_SHAPE);
@@ -804,7 +804,7 @@ int tss_conv1d3_bwd_data(const void* e, long lde, const void* yraw, long ldyr,
 int tss_convkxk_fwd(const void* x, long ldx, const float* in_mean, const float* in_scale, const float* in_bias, int in_relu,
                     const float* w_tnc, const float* bias, void* y, long ldy, double* stats,
                     int B, int Hin, int Win, int Cin, int N, int kh, int kw, int stride, int dil, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(Cin > 0 && N > 0 && (Cin % 8) == 0 && (ldx % 8) == 0 && ldx >= Cin && (ldy % 4) == 0 && ldy >= N && stride >= 1 && dil >= 1 &&
               kh >= 1 && kw >= 1 && (kh & 1) && (kw & 1) && kh * kw <= 81 && w_tnc, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(x) && tss::aligned16(y), TSS_ERR_ALIGN);
@@ -835,7 +835,7 @@ int tss_convkxk_bwd_data(const void* e, long lde, const void* yraw, long ldyr,
                          const void* xraw, long ldx, const float* in_mean, const float* in_scale, const float* in_bias, int in_relu,
                          void* e_in, long ldei, double* bstats,
                          int B, int Hin, int Win, int Cin, int N, int kh, int kw, int stride, int dil, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(Cin > 0 && N > 0 && (N % 8) == 0 && (Cin % 4) == 0 && (lde % 8) == 0 && lde >= N && (ldei % 4) == 0 && ldei >= Cin &&
               stride >= 1 && dil >= 1 && kh >= 1 && kw >= 1 && (kh & 1) && (kw & 1) && kh * kw <= 81 && w_tcn, TSS_ERR_SHAPE);
   TSS_REQUIRE(!yraw || ((ldyr % 8) == 0 && ldyr >= N), TSS_ERR_SHAPE);
@@ -873,7 +873,7 @@ int tss_convkxk_bwd_data(const void* e, long lde, const void* yraw, long ldyr,
 // [N][Cin][taps]): x [B][Hout/stride][Wout/stride][Cin_t] -> y [B][Hout][Wout][Cout], w_tcn = [taps][Cout][Cin_t], bias added.
 int tss_convkxk_transposed_fwd(const void* x, long ldx, const float* w_tcn, const float* bias, void* y, long ldy,
                                int B, int Hout, int Wout, int Cout, int Cin_t, int kh, int kw, int stride, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(Cout > 0 && Cin_t > 0 && (Cin_t % 8) == 0 && (Cout % 4) == 0 && (ldx % 8) == 0 && ldx >= Cin_t && (ldy % 4) == 0 && ldy >= Cout &&
               stride >= 1 && (Hout % stride) == 0 && (Wout % stride) == 0 && kh >= 1 && kw >= 1 && (kh & 1) && (kw & 1) && kh * kw <= 81 && w_tcn,
               TSS_ERR_SHAPE);
@@ -903,7 +903,7 @@ int tss_set_option(int key, int value) {
 
 int tss_stem3x3_fwd(const void* x_nchw, int x_is_f32, const float* w, void* y, long ldy, double* stats,
                     int B, int Cin, int Hin, int Win, int N, int stride, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(Cin >= 1 && Cin * 9 <= Mma<float>::KC && N > 0 && (ldy % 4) == 0 && ldy >= N && stride >= 1, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(y), TSS_ERR_ALIGN);
   GemmArgs g = {};

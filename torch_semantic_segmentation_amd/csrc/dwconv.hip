@@ -939,19 +939,18 @@ __global__ __launch_bounds__(NT_MAX, (WG ? WG_WAVES : (D == 1 ? 2 : 1))) void dw
 #endif
 }
 
+// The strip kernels exist for three (stride, dilation) pairs.  For the pair of g, TSS_DW_STRIP_CASES runs the statement(s) with it as
+// constexpr SS, DD and RETURNS TRUE from the enclosing function; for any other pair it falls through.
+#define TSS_DW_STRIP_CASE(S_, D_, ...) \
+  if (g.stride == S_ && g.dil == D_) { constexpr int SS = S_, DD = D_; __VA_ARGS__; return true; }
+#define TSS_DW_STRIP_CASES(...) TSS_DW_STRIP_CASE(1, 1, __VA_ARGS__) TSS_DW_STRIP_CASE(2, 1, __VA_ARGS__) TSS_DW_STRIP_CASE(1, 4, __VA_ARGS__)
+
 template <typename T>
 bool launch_strip(int which, const DwArgs& g, int grid, int threads, hipStream_t st) {
-#define TSS_DW_CASE(SS, DD)                                                                                         \
-  if (g.stride == SS && g.dil == DD) {                                                                              \
-    if (which == 0) hipLaunchKernelGGL((dw_fwd_strip_kernel<T, SS, DD>), dim3(grid), dim3(threads), 0, st, g);        \
-    else if (which == 1) hipLaunchKernelGGL((dw_bwd_data_strip_kernel<T, SS, DD, false>), dim3(grid), dim3(threads), 0, st, g); \
-    else hipLaunchKernelGGL((dw_bwd_weight_strip_kernel<T, SS, DD>), dim3(grid), dim3(threads), 0, st, g);            \
-    return true;                                                                                                    \
-  }
-  TSS_DW_CASE(1, 1)
-  TSS_DW_CASE(2, 1)
-  TSS_DW_CASE(1, 4)
-#undef TSS_DW_CASE
+  TSS_DW_STRIP_CASES(
+    if (which == 0) hipLaunchKernelGGL((dw_fwd_strip_kernel<T, SS, DD>), dim3(grid), dim3(threads), 0, st, g);
+    else if (which == 1) hipLaunchKernelGGL((dw_bwd_data_strip_kernel<T, SS, DD, false>), dim3(grid), dim3(threads), 0, st, g);
+    else hipLaunchKernelGGL((dw_bwd_weight_strip_kernel<T, SS, DD>), dim3(grid), dim3(threads), 0, st, g))
   return false;
 }
 
@@ -966,17 +965,11 @@ int geometry(DwArgs& g, int* threads) {
 
 // backward-data + weight gradient in one sweep (bf16 only: the f32 parity path keeps the two separate kernels)
 bool launch_strip_fused(const DwArgs& g, int grid, int threads, hipStream_t st) {
-#define TSS_DW_CASE(SS, DD)                                                                                         \
-  if (g.stride == SS && g.dil == DD) {                                                                              \
-    hipLaunchKernelGGL((dw_bwd_data_strip_kernel<bf16_t, SS, DD, true>), dim3(grid), dim3(threads), 0, st, g);       \
-    return true;                                                                                                    \
-  }
-  TSS_DW_CASE(1, 1)
-  TSS_DW_CASE(2, 1)
-  TSS_DW_CASE(1, 4)
-#undef TSS_DW_CASE
+  TSS_DW_STRIP_CASES(hipLaunchKernelGGL((dw_bwd_data_strip_kernel<bf16_t, SS, DD, true>), dim3(grid), dim3(threads), 0, st, g))
   return false;
 }
+#undef TSS_DW_STRIP_CASES
+#undef TSS_DW_STRIP_CASE
 
 inline bool strip_supported(int stride, int dil) { return (stride == 1 && dil == 1) || (stride == 2 && dil == 1) || (stride == 1 && dil == 4); }
 
@@ -995,7 +988,7 @@ extern "C" {
 int tss_dwconv3x3_fwd(const void* x, long ldx, const float* in_mean, const float* in_scale, const float* in_bias, int in_relu,
                       const float* w, void* y, long ldy, double* stats,
                       int B, int Hin, int Win, int C, int stride, int dil, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE((ldx % 8) == 0 && (ldy % 8) == 0 && ldx >= C && ldy >= C && stride >= 1 && dil >= 1, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(x) && tss::aligned16(y), TSS_ERR_ALIGN);
   DwArgs g = {};
@@ -1020,8 +1013,7 @@ int tss_dwconv3x3_fwd(const void* x, long ldx, const float* in_mean, const float
                                        : launch_strip<float>(0, g, sgrid, threads, (hipStream_t)stream);
   if (!strip) {
     const int grid = tss::persistent_blocks((P + g.NPL - 1) / g.NPL, TSS_STAT_SLABS);
-    if (dtype == TSS_BF16) hipLaunchKernelGGL(dw_fwd_kernel<bf16_t>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g);
-    else hipLaunchKernelGGL(dw_fwd_kernel<float>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g);
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(dw_fwd_kernel<TT>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g));
   }
   return tss::check_last("dwconv_fwd");
 }
@@ -1031,7 +1023,7 @@ int tss_dwconv3x3_bwd_data(const void* e, long lde, const void* yraw, long ldyr,
                            const void* xraw, long ldx, const float* in_mean, const float* in_scale, const float* in_bias, int in_relu,
                            void* e_in, long ldei, double* bstats, const float* wg_ws, float* wg_dw,
                            int B, int Hin, int Win, int C, int stride, int dil, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE((lde % 8) == 0 && lde >= C && (ldei % 8) == 0 && ldei >= C && stride >= 1 && dil >= 1, TSS_ERR_SHAPE);
   TSS_REQUIRE(!yraw || ((ldyr % 8) == 0 && ldyr >= C && ga && gb && gce && gmu), TSS_ERR_SHAPE);
   TSS_REQUIRE(!xraw || ((ldx % 8) == 0 && ldx >= C), TSS_ERR_SHAPE);
@@ -1064,8 +1056,7 @@ int tss_dwconv3x3_bwd_data(const void* e, long lde, const void* yraw, long ldyr,
                                        : launch_strip<float>(1, g, sgrid + g.lead, threads, (hipStream_t)stream);
   if (!strip) {
     const int grid = tss::persistent_blocks((P + g.NPL - 1) / g.NPL, TSS_STAT_SLABS);
-    if (dtype == TSS_BF16) hipLaunchKernelGGL(dw_bwd_data_kernel<bf16_t>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g);
-    else hipLaunchKernelGGL(dw_bwd_data_kernel<float>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g);
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(dw_bwd_data_kernel<TT>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g));
   }
   return tss::check_last("dwconv_bwd_data");
 }
@@ -1174,7 +1165,7 @@ int tss_dwconv3x3_bwd_weight(const void* e, long lde, const void* yraw, long ldy
                              const float* ga, const float* gb, const float* gce, const float* gmu,
                              const void* xraw, long ldx, const float* in_mean, const float* in_scale, const float* in_bias, int in_relu,
                              float* dw, float* ws, int defer_reduce, int B, int Hin, int Win, int C, int stride, int dil, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE((lde % 8) == 0 && lde >= C && (ldx % 8) == 0 && ldx >= C && stride >= 1 && dil >= 1, TSS_ERR_SHAPE);
   TSS_REQUIRE(!yraw || ((ldyr % 8) == 0 && ldyr >= C && ga && gb && gce && gmu), TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(e) && tss::aligned16(xraw) && ws, TSS_ERR_ALIGN);
@@ -1198,8 +1189,7 @@ int tss_dwconv3x3_bwd_weight(const void* e, long lde, const void* yraw, long ldy
   if (!strip) {
     const int grid = tss::persistent_blocks((P + g.NPL - 1) / g.NPL, TSS_STAT_SLABS);
     rows = grid;
-    if (dtype == TSS_BF16) hipLaunchKernelGGL(dw_bwd_weight_kernel<bf16_t>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g);
-    else hipLaunchKernelGGL(dw_bwd_weight_kernel<float>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g);
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(dw_bwd_weight_kernel<TT>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g));
   }
   if (!defer_reduce)
     hipLaunchKernelGGL(dw_reduce_kernel, dim3((C * 9 + 63) / 64), dim3(RED_WAVES * 64), 0, (hipStream_t)stream, ws, dw, C * 9, rows);

@@ -94,7 +94,7 @@ int tss_gate_slices(int B, long HW) {       // row slices per image of the backw
 
 int tss_gate_fwd(const void* x, long ldx, const void* a, long lda, void* out, long ldo, int B, long HW, int C, float add_one,
                  int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (C % 8) == 0 && C <= 2048 && (ldx % 8) == 0 && ldx >= C && (lda % 8) == 0 && lda >= C && (ldo % 8) == 0 && ldo >= C,
               TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(x) && tss::aligned16(a) && tss::aligned16(out), TSS_ERR_ALIGN);
@@ -104,31 +104,25 @@ int tss_gate_fwd(const void* x, long ldx, const void* a, long lda, void* out, lo
   long grid = (total + NT - 1) / NT;
   if (grid > 2048) grid = 2048;
   tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, 2.0 * P * C * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(gate_fwd_kernel<bf16_t>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, (const bf16_t*)a, lda,
-                       (bf16_t*)out, ldo, HW, P, C, add_one);
-  else
-    hipLaunchKernelGGL(gate_fwd_kernel<float>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const float*)x, ldx, (const float*)a, lda,
-                       (float*)out, ldo, HW, P, C, add_one);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(gate_fwd_kernel<TT>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const TT*)x, ldx, (const TT*)a,
+                                           lda, (TT*)out, ldo, HW, P, C, add_one));
   return tss::check_last("gate_fwd");
 }
 
 int tss_gate_bwd(const void* g, long ldg, const void* x, long ldx, const void* a, long lda, void* dx, long lddx, void* da, long ldda,
                  float* ws, int B, long HW, int C, float add_one, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (C % 8) == 0 && C <= 2048 && (C / 8) <= NT && (ldg % 8) == 0 && ldg >= C && (ldx % 8) == 0 && ldx >= C && (lda % 8) == 0
               && lda >= C && (lddx % 8) == 0 && lddx >= C && ldda >= C && ws, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(g) && tss::aligned16(x) && tss::aligned16(a) && tss::aligned16(dx), TSS_ERR_ALIGN);
   if ((long)B * HW == 0) return TSS_OK;
   const int S = tss_gate_slices(B, HW);
   tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, 3.0 * B * HW * C * tss::esz(dtype), 0);
-#define TSS_GATE_BWD(TT)                                                                                                       \
-  hipLaunchKernelGGL(gate_bwd_kernel<TT>, dim3(B * S), dim3(NT), 0, (hipStream_t)stream, (const TT*)g, ldg, (const TT*)x, ldx,   \
-                     (const TT*)a, lda, (TT*)dx, lddx, ws, HW, C, S, add_one);                                                 \
-  hipLaunchKernelGGL(gate_bwd_reduce_kernel<TT>, dim3((B * C + NT - 1) / NT), dim3(NT), 0, (hipStream_t)stream, ws, (const TT*)a, lda, \
-                     (TT*)da, ldda, B, C, S)
-  if (dtype == TSS_BF16) { TSS_GATE_BWD(bf16_t); } else { TSS_GATE_BWD(float); }
-#undef TSS_GATE_BWD
+  TSS_WITH_DTYPE(dtype,
+    hipLaunchKernelGGL(gate_bwd_kernel<TT>, dim3(B * S), dim3(NT), 0, (hipStream_t)stream, (const TT*)g, ldg, (const TT*)x, ldx,
+                       (const TT*)a, lda, (TT*)dx, lddx, ws, HW, C, S, add_one);
+    hipLaunchKernelGGL(gate_bwd_reduce_kernel<TT>, dim3((B * C + NT - 1) / NT), dim3(NT), 0, (hipStream_t)stream, ws, (const TT*)a, lda,
+                       (TT*)da, ldda, B, C, S));
   return tss::check_last("gate_bwd");
 }
 

@@ -507,33 +507,34 @@ __global__ __launch_bounds__(NT, 3) void upsample_argmax_kernel(const T* low, lo
       if (scm[i]) atomicAdd(cm + i, (unsigned long long)scm[i]);
 }
 
-inline int grid_for(long total) {
-  long g = (total + NT - 1) / NT;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (int)g;
+// What every entry point of the upsampled-CE family asks of its shapes: classes in registers (at most 24), whole class groups per pixel.
+inline bool upsample_ce_shape_ok(int C, long ldl, int h, int w, int H, int W) {
+  return C > 0 && C <= 24 && (ldl % 8) == 0 && ldl >= (C + 3) / 4 * 4 && h > 0 && w > 0 && H >= h && W >= w;
 }
 
 }  // namespace
+
+// The class-register variant of the upsampled-CE kernels: runs the statement(s) with CPV = 20 (up to 20 classes) or 24.
+#define TSS_WITH_CLASS_REGS(C, ...)                           \
+  do {                                                        \
+    if ((C) <= 20) { constexpr int CPV = 20; __VA_ARGS__; }   \
+    else { constexpr int CPV = 24; __VA_ARGS__; }             \
+  } while (0)
 
 extern "C" {
 
 int tss_cross_entropy_fwd(const void* logits, const long long* target, float* lse, double* acc /*[2], zeroed*/,
                           float* loss, float* inv_count, long B, int C, long HW, int ignore_index,
                           int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (HW % 8) == 0, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(logits) && tss::aligned16(lse), TSS_ERR_ALIGN);
   const long groups = B * (HW / 8);
   if (groups == 0) return TSS_OK;
   {
     tss::ProfScope prof(TSS_K_CE_FWD, (hipStream_t)stream, (double)B * HW * (C * tss::esz(dtype) + 12.0), 0);
-    if (dtype == TSS_BF16)
-      hipLaunchKernelGGL(ce_fwd_kernel<bf16_t>, dim3(grid_for(groups)), dim3(NT), 0, (hipStream_t)stream,
-                         (const bf16_t*)logits, target, lse, acc, B, C, HW, ignore_index);
-    else
-      hipLaunchKernelGGL(ce_fwd_kernel<float>, dim3(grid_for(groups)), dim3(NT), 0, (hipStream_t)stream,
-                         (const float*)logits, target, lse, acc, B, C, HW, ignore_index);
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(ce_fwd_kernel<TT>, dim3(tss::grid_for(groups, NT)), dim3(NT), 0, (hipStream_t)stream, (const TT*)logits,
+                                             target, lse, acc, B, C, HW, ignore_index));
   }
   hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, acc, loss, inv_count);
   return tss::check_last("cross_entropy_fwd");
@@ -542,47 +543,39 @@ int tss_cross_entropy_fwd(const void* logits, const long long* target, float* ls
 int tss_cross_entropy_bwd(const void* logits, const long long* target, const float* lse, const float* inv_count,
                           const float* grad_out, void* dlogits, long B, int C, long HW, int ignore_index,
                           int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (HW % 8) == 0, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(logits) && tss::aligned16(dlogits) && tss::aligned16(lse), TSS_ERR_ALIGN);
   const long groups = B * (HW / 8);
   if (groups == 0) return TSS_OK;
   tss::ProfScope prof(TSS_K_CE_BWD, (hipStream_t)stream, (double)B * HW * (2.0 * C * tss::esz(dtype) + 12.0), 0);
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(ce_bwd_kernel<bf16_t>, dim3(grid_for(groups)), dim3(NT), 0, (hipStream_t)stream,
-                       (const bf16_t*)logits, target, lse, inv_count, grad_out, (bf16_t*)dlogits, B, C, HW, ignore_index);
-  else
-    hipLaunchKernelGGL(ce_bwd_kernel<float>, dim3(grid_for(groups)), dim3(NT), 0, (hipStream_t)stream,
-                       (const float*)logits, target, lse, inv_count, grad_out, (float*)dlogits, B, C, HW, ignore_index);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(ce_bwd_kernel<TT>, dim3(tss::grid_for(groups, NT)), dim3(NT), 0, (hipStream_t)stream, (const TT*)logits,
+                                           target, lse, inv_count, grad_out, (TT*)dlogits, B, C, HW, ignore_index));
   return tss::check_last("cross_entropy_bwd");
 }
 
 int tss_argmax_confusion(const void* logits, const long long* target, unsigned char* pred,
                          unsigned long long* confusion /*[C*C] accumulated*/, long B, int C, long HW,
                          int ignore_index, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && C <= 64 && (HW % 8) == 0, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(logits), TSS_ERR_ALIGN);
   const long groups = B * (HW / 8);
   if (groups == 0) return TSS_OK;
-  long grid = grid_for(groups);
+  long grid = tss::grid_for(groups, NT);
   if (grid > 1024) grid = 1024;
   tss::ProfScope prof(TSS_K_ARGMAX, (hipStream_t)stream, (double)B * HW * (C * tss::esz(dtype) + 9.0), 0);
   const size_t sh = (size_t)C * C * sizeof(unsigned int);
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(argmax_confusion_kernel<bf16_t>, dim3((int)grid), dim3(NT), sh, (hipStream_t)stream,
-                       (const bf16_t*)logits, target, pred, confusion, B, C, HW, ignore_index);
-  else
-    hipLaunchKernelGGL(argmax_confusion_kernel<float>, dim3((int)grid), dim3(NT), sh, (hipStream_t)stream,
-                       (const float*)logits, target, pred, confusion, B, C, HW, ignore_index);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(argmax_confusion_kernel<TT>, dim3((int)grid), dim3(NT), sh, (hipStream_t)stream, (const TT*)logits, target,
+                                           pred, confusion, B, C, HW, ignore_index));
   return tss::check_last("argmax_confusion");
 }
 
 int tss_upsample_argmax_confusion(const void* low, long ldl, const long long* target, unsigned char* pred,
                                   unsigned long long* confusion /*[C*C] accumulated*/, int B, int C, int h, int w,
                                   int H, int W, int ignore_index, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
-  TSS_REQUIRE(C > 0 && C <= 24 && (ldl % 8) == 0 && ldl >= (C + 3) / 4 * 4 && h > 0 && w > 0 && H >= h && W >= w, TSS_ERR_SHAPE);
+  TSS_CHECK_DTYPE(dtype);
+  TSS_REQUIRE(upsample_ce_shape_ok(C, ldl, h, w, H, W), TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(low), TSS_ERR_ALIGN);
   if ((long)B * H * W == 0) return TSS_OK;
   const int nstrip = (W + NT - 1) / NT;
@@ -591,12 +584,9 @@ int tss_upsample_argmax_confusion(const void* low, long ldl, const long long* ta
   const long grid = (long)B * nstrip * ((H + band_rows - 1) / band_rows);
   tss::ProfScope prof(TSS_K_ARGMAX, (hipStream_t)stream, (double)B * h * w * C * tss::esz(dtype) + (double)B * H * W * 9.0, 0);
   const size_t sh = (size_t)C * C * sizeof(unsigned int);
-#define TSS_AM_LAUNCH(TT, CPV)                                                                                 \
-  hipLaunchKernelGGL((upsample_argmax_kernel<TT, CPV>), dim3((int)grid), dim3(NT), sh, (hipStream_t)stream,      \
-                     (const TT*)low, ldl, target, pred, confusion, B, C, h, w, H, W, ignore_index, band_rows)
-  if (dtype == TSS_BF16) { if (C <= 20) TSS_AM_LAUNCH(bf16_t, 20); else TSS_AM_LAUNCH(bf16_t, 24); }
-  else { if (C <= 20) TSS_AM_LAUNCH(float, 20); else TSS_AM_LAUNCH(float, 24); }
-#undef TSS_AM_LAUNCH
+  TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
+    hipLaunchKernelGGL((upsample_argmax_kernel<TT, CPV>), dim3((int)grid), dim3(NT), sh, (hipStream_t)stream,
+                       (const TT*)low, ldl, target, pred, confusion, B, C, h, w, H, W, ignore_index, band_rows)));
   return tss::check_last("upsample_argmax_confusion");
 }
 
@@ -622,15 +612,16 @@ long tss_upsample_ce_ws(int B, int C, int h, int w, int H, int W) {
   if (B <= 0 || C <= 0 || C > 24 || h <= 0 || w <= 0 || H < h || W < w) return 0;
   const CeGeom g = ce_geom(B, h, w, H, W);
   const long nblocks = (long)B * g.nband * g.nstrip;
-  const int CP = C <= 20 ? 20 : 24;
+  int CP = 0;
+  TSS_WITH_CLASS_REGS(C, CP = CPV);   // the tiles are CPV floats per cell: the same choice as the kernels that fill them
   return nblocks * 4 /* 2 doubles */ + nblocks * g.tile_rows * g.tile_cells * CP;
 }
 
 int tss_upsample_ce_fwd(const void* low, long ldl, const long long* target, float* ws /* tss_upsample_ce_ws floats, not initialised */,
                         float* loss, float* inv_count,
                         int B, int C, int h, int w, int H, int W, int ignore_index, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
-  TSS_REQUIRE(C > 0 && C <= 24 && (ldl % 8) == 0 && ldl >= (C + 3) / 4 * 4 && h > 0 && w > 0 && H >= h && W >= w, TSS_ERR_SHAPE);
+  TSS_CHECK_DTYPE(dtype);
+  TSS_REQUIRE(upsample_ce_shape_ok(C, ldl, h, w, H, W), TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(low) && tss::aligned16(ws), TSS_ERR_ALIGN);
   if ((long)B * H * W == 0) return TSS_OK;
   const CeGeom geo = ce_geom(B, h, w, H, W);
@@ -640,12 +631,9 @@ int tss_upsample_ce_fwd(const void* low, long ldl, const long long* target, floa
   {
     tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream,
                         (double)B * h * w * C * (tss::esz(dtype) + 8.0) + (double)B * H * W * 8.0, 0);
-#define TSS_CE_LAUNCH(TT, CPV)                                                                                   \
-    hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 0>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, \
-                       (const TT*)low, ldl, target, tiles, lossrows, B, C, h, w, H, W, ignore_index, geo, nullptr, nullptr)
-    if (dtype == TSS_BF16) { if (C <= 20) TSS_CE_LAUNCH(bf16_t, 20); else TSS_CE_LAUNCH(bf16_t, 24); }
-    else { if (C <= 20) TSS_CE_LAUNCH(float, 20); else TSS_CE_LAUNCH(float, 24); }
-#undef TSS_CE_LAUNCH
+    TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
+      hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 0>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,
+                         (const TT*)low, ldl, target, tiles, lossrows, B, C, h, w, H, W, ignore_index, geo, nullptr, nullptr)));
   }
   hipLaunchKernelGGL(ce_finalize_rows_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, lossrows, (int)grid, loss, inv_count);
   return tss::check_last("upsample_ce_fwd");
@@ -654,19 +642,16 @@ int tss_upsample_ce_fwd(const void* low, long ldl, const long long* target, floa
 // Per-pixel cross-entropy of the upsampled logits ([B][H][W] f32, 0 for ignored pixels), straight from the low-res logits.
 int tss_upsample_pixel_ce(const void* low, long ldl, const long long* target, float* pix, int B, int C, int h, int w, int H, int W,
                           int ignore_index, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
-  TSS_REQUIRE(C > 0 && C <= 24 && (ldl % 8) == 0 && ldl >= (C + 3) / 4 * 4 && h > 0 && w > 0 && H >= h && W >= w && pix, TSS_ERR_SHAPE);
+  TSS_CHECK_DTYPE(dtype);
+  TSS_REQUIRE(upsample_ce_shape_ok(C, ldl, h, w, H, W) && pix, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(low), TSS_ERR_ALIGN);
   if ((long)B * H * W == 0) return TSS_OK;
   const CeGeom geo = ce_geom(B, h, w, H, W);
   const long grid = (long)B * geo.nstrip * geo.nband;
   tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream, (double)B * h * w * C * tss::esz(dtype) + (double)B * H * W * 12.0, 0);
-#define TSS_CE_LAUNCH(TT, CPV)                                                                                       \
-  hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 1>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,     \
-                     (const TT*)low, ldl, target, nullptr, nullptr, B, C, h, w, H, W, ignore_index, geo, pix, nullptr)
-  if (dtype == TSS_BF16) { if (C <= 20) TSS_CE_LAUNCH(bf16_t, 20); else TSS_CE_LAUNCH(bf16_t, 24); }
-  else { if (C <= 20) TSS_CE_LAUNCH(float, 20); else TSS_CE_LAUNCH(float, 24); }
-#undef TSS_CE_LAUNCH
+  TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
+    hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 1>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,
+                       (const TT*)low, ldl, target, nullptr, nullptr, B, C, h, w, H, W, ignore_index, geo, pix, nullptr)));
   return tss::check_last("upsample_pixel_ce");
 }
 
@@ -674,41 +659,36 @@ int tss_upsample_pixel_ce(const void* low, long ldl, const long long* target, fl
 // else 0 (sel = the params of tss_ohem_select).  ws as for tss_upsample_ce_fwd; tss_upsample_ce_bwd (inv_count -> 1.0) gathers.
 int tss_upsample_ohem_grad(const void* low, long ldl, const long long* target, const float* pix, const float* sel, float* ws,
                            int B, int C, int h, int w, int H, int W, int ignore_index, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
-  TSS_REQUIRE(C > 0 && C <= 24 && (ldl % 8) == 0 && ldl >= (C + 3) / 4 * 4 && h > 0 && w > 0 && H >= h && W >= w && pix && sel && ws,
-              TSS_ERR_SHAPE);
+  TSS_CHECK_DTYPE(dtype);
+  TSS_REQUIRE(upsample_ce_shape_ok(C, ldl, h, w, H, W) && pix && sel && ws, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(low) && tss::aligned16(ws), TSS_ERR_ALIGN);
   if ((long)B * H * W == 0) return TSS_OK;
   const CeGeom geo = ce_geom(B, h, w, H, W);
   const long grid = (long)B * geo.nstrip * geo.nband;
   float* tiles = ws + grid * 4;
   tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream, (double)B * h * w * C * (tss::esz(dtype) + 8.0) + (double)B * H * W * 12.0, 0);
-#define TSS_CE_LAUNCH(TT, CPV)                                                                                       \
-  hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 2>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,     \
-                     (const TT*)low, ldl, target, tiles, nullptr, B, C, h, w, H, W, ignore_index, geo, const_cast<float*>(pix), sel)
-  if (dtype == TSS_BF16) { if (C <= 20) TSS_CE_LAUNCH(bf16_t, 20); else TSS_CE_LAUNCH(bf16_t, 24); }
-  else { if (C <= 20) TSS_CE_LAUNCH(float, 20); else TSS_CE_LAUNCH(float, 24); }
-#undef TSS_CE_LAUNCH
+  TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
+    hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 2>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,
+                       (const TT*)low, ldl, target, tiles, nullptr, B, C, h, w, H, W, ignore_index, geo, const_cast<float*>(pix), sel)));
   return tss::check_last("upsample_ohem_grad");
 }
 
 int tss_upsample_ce_bwd(const float* ws, const float* inv_count, const float* grad_out, void* dlow, long ldl,
                         int B, int C, int h, int w, int H, int W, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
-  TSS_REQUIRE(C > 0 && C <= 24 && (ldl % 8) == 0 && ldl >= (C + 3) / 4 * 4 && h > 0 && w > 0 && H >= h && W >= w, TSS_ERR_SHAPE);
+  TSS_CHECK_DTYPE(dtype);
+  TSS_REQUIRE(upsample_ce_shape_ok(C, ldl, h, w, H, W), TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(ws) && tss::aligned16(dlow), TSS_ERR_ALIGN);
   const long n = (long)B * h * w * ldl;
   if (n == 0) return TSS_OK;
   const CeGeom geo = ce_geom(B, h, w, H, W);
   const float* tiles = ws + (long)B * geo.nstrip * geo.nband * 4;
   tss::ProfScope prof(TSS_K_UPSAMPLE_CE_BWD, (hipStream_t)stream, (double)n * (4.0 + tss::esz(dtype)), 0);
-#define TSS_CE_GATHER(TT, CPV)                                                                                      \
-  hipLaunchKernelGGL((upsample_ce_gather_kernel<TT, CPV>), dim3(grid_for(n / 8)), dim3(NT), 0, (hipStream_t)stream, \
-                     tiles, inv_count, grad_out, (TT*)dlow, ldl, B, h, w, H, W, geo)
-  if (dtype == TSS_BF16) { if (C <= 20) TSS_CE_GATHER(bf16_t, 20); else TSS_CE_GATHER(bf16_t, 24); }
-  else { if (C <= 20) TSS_CE_GATHER(float, 20); else TSS_CE_GATHER(float, 24); }
-#undef TSS_CE_GATHER
+  TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
+    hipLaunchKernelGGL((upsample_ce_gather_kernel<TT, CPV>), dim3(tss::grid_for(n / 8, NT)), dim3(NT), 0, (hipStream_t)stream,
+                       tiles, inv_count, grad_out, (TT*)dlow, ldl, B, h, w, H, W, geo)));
   return tss::check_last("upsample_ce_bwd");
 }
 
 }  // extern "C"
+
+#undef TSS_WITH_CLASS_REGS

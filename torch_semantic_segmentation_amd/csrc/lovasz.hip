@@ -443,13 +443,6 @@ __global__ __launch_bounds__(NT) void lovasz_bwd_kernel(const T* logits, const l
   }
 }
 
-inline int grid_for(long total) {
-  long g = (total + NT - 1) / NT;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 inline bool shape_ok(long B, int C, long HW) {
   return B > 0 && C > 0 && HW > 0 && (HW % 8) == 0 && B * HW < (1L << 31) && (B * HW + TILE - 1) / TILE <= 0x7FFFFFFFL;
 }
@@ -465,7 +458,7 @@ long tss_lovasz_workspace_bytes(long n_pixels, int C, int chunk_classes) {
 
 int tss_lovasz_fwd(const void* logits, const long long* target, void* workspace, float* loss, float* n_present,
                    long B, int C, long HW, int ignore_index, int has_ignore, int variant, int chunk_classes, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(shape_ok(B, C, HW) && (variant == 0 || variant == 1) && chunk_classes >= 0 && target && loss && n_present, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(logits) && workspace && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, TSS_ERR_ALIGN);
   hipStream_t st = (hipStream_t)stream;
@@ -484,12 +477,8 @@ int tss_lovasz_fwd(const void* logits, const long long* target, void* workspace,
   for (int c0 = 0; c0 < C; c0 += pl.Cc) {
     const int c1 = c0 + pl.Cc < C ? c0 + pl.Cc : C;
     const unsigned int nc = (unsigned int)(c1 - c0);
-    if (dtype == TSS_BF16)
-      hipLaunchKernelGGL(lovasz_key_kernel<bf16_t>, dim3(grid_for(N / 8)), dim3(NT), 0, st, (const bf16_t*)logits, target, key[0], pay[0],
-                         B, C, HW, c0, c1, (long long)ignore_index, has_ignore);
-    else
-      hipLaunchKernelGGL(lovasz_key_kernel<float>, dim3(grid_for(N / 8)), dim3(NT), 0, st, (const float*)logits, target, key[0], pay[0],
-                         B, C, HW, c0, c1, (long long)ignore_index, has_ignore);
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(lovasz_key_kernel<TT>, dim3(tss::grid_for(N / 8, NT)), dim3(NT), 0, st, (const TT*)logits, target,
+                                             key[0], pay[0], B, C, HW, c0, c1, (long long)ignore_index, has_ignore));
     for (int pass = 0; pass < 4; ++pass) {            // 4 passes: the sorted pairs end in buffer 0
       const int src = pass & 1, dst = src ^ 1, shift = 8 * pass;
       hipLaunchKernelGGL(lovasz_hist_kernel, dim3(nt, nc), dim3(NT), 0, st, key[src], hist, N, pl.ntiles, shift);
@@ -507,19 +496,15 @@ int tss_lovasz_fwd(const void* logits, const long long* target, void* workspace,
 
 int tss_lovasz_bwd(const void* logits, const long long* target, const void* workspace, const float* n_present,
                    const float* grad_out, void* dlogits, long B, int C, long HW, int chunk_classes, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(shape_ok(B, C, HW) && chunk_classes >= 0 && target && n_present, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(logits) && tss::aligned16(dlogits) && workspace && (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, TSS_ERR_ALIGN);
   hipStream_t st = (hipStream_t)stream;
   const long N = B * HW;
   const Plan pl = make_plan(N, C, chunk_classes);
   const float* W = reinterpret_cast<const float*>(static_cast<const char*>(workspace) + pl.off_W);
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(lovasz_bwd_kernel<bf16_t>, dim3(grid_for(N / 8)), dim3(NT), 0, st, (const bf16_t*)logits, target, W, n_present, grad_out,
-                       (bf16_t*)dlogits, B, C, HW);
-  else
-    hipLaunchKernelGGL(lovasz_bwd_kernel<float>, dim3(grid_for(N / 8)), dim3(NT), 0, st, (const float*)logits, target, W, n_present, grad_out,
-                       (float*)dlogits, B, C, HW);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(lovasz_bwd_kernel<TT>, dim3(tss::grid_for(N / 8, NT)), dim3(NT), 0, st, (const TT*)logits, target, W,
+                                           n_present, grad_out, (TT*)dlogits, B, C, HW));
   return tss::check_last("lovasz_bwd");
 }
 

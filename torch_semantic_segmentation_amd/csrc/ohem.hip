@@ -192,13 +192,6 @@ __global__ __launch_bounds__(NT) void ohem_bwd_kernel(const T* logits, const lon
   }
 }
 
-inline int grid_for(long total) {
-  long g = (total + NT - 1) / NT;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 }  // namespace
 
 extern "C" {
@@ -208,16 +201,14 @@ long tss_ohem_workspace_bytes(void) { return (long)sizeof(OhemState); }
 int tss_ohem_fwd(const void* logits, const long long* target, float* lse, float* pixel_loss, void* workspace,
                  float* loss, float* params /*[4]*/, long B, int C, long HW, int ignore_index, float thresh_loss,
                  long n_top, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (HW % 8) == 0 && n_top >= 0 && n_top < B * HW, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(logits) && tss::aligned16(lse) && tss::aligned16(pixel_loss) && tss::aligned16(workspace), TSS_ERR_ALIGN);
   const long n = B * HW;
   if (n == 0) return TSS_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(ohem_pixel_kernel<bf16_t>, dim3(grid_for(n / 8)), dim3(NT), 0, st, (const bf16_t*)logits, target, lse, pixel_loss, B, C, HW, ignore_index);
-  else
-    hipLaunchKernelGGL(ohem_pixel_kernel<float>, dim3(grid_for(n / 8)), dim3(NT), 0, st, (const float*)logits, target, lse, pixel_loss, B, C, HW, ignore_index);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(ohem_pixel_kernel<TT>, dim3(tss::grid_for(n / 8, NT)), dim3(NT), 0, st, (const TT*)logits, target, lse,
+                                           pixel_loss, B, C, HW, ignore_index));
   return tss_ohem_select(pixel_loss, workspace, loss, params, n, thresh_loss, n_top, stream);
 }
 
@@ -229,7 +220,7 @@ int tss_ohem_select(const float* pixel_loss, void* workspace, float* loss, float
   TSS_REQUIRE(tss::aligned16(pixel_loss) && tss::aligned16(workspace), TSS_ERR_ALIGN);
   hipStream_t st = (hipStream_t)stream;
   OhemState* ws = reinterpret_cast<OhemState*>(workspace);
-  const int hgrid = grid_for(n / 4) > 1024 ? 1024 : grid_for(n / 4);
+  const int hgrid = tss::grid_for(n / 4, NT, 1024);
   for (int pass = 0; pass < 3; ++pass) {
     hipLaunchKernelGGL(ohem_hist_kernel, dim3(hgrid), dim3(NT), 0, st, pixel_loss, n, ws, pass);
     hipLaunchKernelGGL(ohem_scan_kernel, dim3(1), dim3(NT), 0, st, ws, pass, (long long)n_top);
@@ -242,16 +233,14 @@ int tss_ohem_select(const float* pixel_loss, void* workspace, float* loss, float
 int tss_ohem_bwd(const void* logits, const long long* target, const float* lse, const float* pixel_loss,
                  const float* params, const float* grad_out, void* dlogits, long B, int C, long HW, int ignore_index,
                  int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (HW % 8) == 0, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(logits) && tss::aligned16(dlogits) && tss::aligned16(lse) && tss::aligned16(pixel_loss), TSS_ERR_ALIGN);
   const long groups = B * (HW / 8);
   if (groups == 0) return TSS_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(ohem_bwd_kernel<bf16_t>, dim3(grid_for(groups)), dim3(NT), 0, st, (const bf16_t*)logits, target, lse, pixel_loss, params, grad_out, (bf16_t*)dlogits, B, C, HW, ignore_index);
-  else
-    hipLaunchKernelGGL(ohem_bwd_kernel<float>, dim3(grid_for(groups)), dim3(NT), 0, st, (const float*)logits, target, lse, pixel_loss, params, grad_out, (float*)dlogits, B, C, HW, ignore_index);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(ohem_bwd_kernel<TT>, dim3(tss::grid_for(groups, NT)), dim3(NT), 0, st, (const TT*)logits, target, lse,
+                                           pixel_loss, params, grad_out, (TT*)dlogits, B, C, HW, ignore_index));
   return tss::check_last("ohem_bwd");
 }
 

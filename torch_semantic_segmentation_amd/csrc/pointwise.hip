@@ -610,7 +610,7 @@ int tss_join_fwd(const void* a, long lda, const float* ma, const float* sa, cons
                  const void* b, long ldb, const float* mb, const float* sb, const float* bb,
                  void* out, long ldo, int relu, float drop_p, const unsigned long long* seed_slot,
                  long P, int C, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE((lda % 8) == 0 && lda >= C && (ldo % 8) == 0 && ldo >= C && (!b || ((ldb % 8) == 0 && ldb >= C)), TSS_ERR_SHAPE);
   TSS_REQUIRE(!seed_slot || (relu && drop_p > 0.f && drop_p < 1.f), TSS_ERR_SHAPE);   // the backward relies on out > 0 <=> kept
   TSS_REQUIRE(tss::aligned16(a) && tss::aligned16(out) && tss::aligned16(b), TSS_ERR_ALIGN);
@@ -626,8 +626,7 @@ int tss_join_fwd(const void* a, long lda, const float* ma, const float* sa, cons
   if (rc) return rc;
   if (P == 0) return TSS_OK;
   tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, (double)P * C * (b ? 3 : 2) * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16) hipLaunchKernelGGL(join_fwd_kernel<bf16_t>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g);
-  else hipLaunchKernelGGL(join_fwd_kernel<float>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(join_fwd_kernel<TT>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g));
   return tss::check_last("join_fwd");
 }
 
@@ -635,7 +634,7 @@ int tss_join_bwd(const void* dout, long lddo, const void* out, long ldo, int rel
                  const void* a_raw, long lda, const float* mean_a, double* stats_a,
                  const void* b_raw, long ldb, const float* mean_b, double* stats_b,
                  void* e, long lde, float dout_scale, long P, int C, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE((lddo % 8) == 0 && lddo >= C && (!relu || (out && (ldo % 8) == 0 && ldo >= C)), TSS_ERR_SHAPE);
   TSS_REQUIRE(dout_scale > 0.f && (dout_scale == 1.f || relu), TSS_ERR_SHAPE);
   TSS_REQUIRE((!stats_a || (a_raw && (lda % 8) == 0 && lda >= C)) && (!stats_b || (b_raw && (ldb % 8) == 0 && ldb >= C)), TSS_ERR_SHAPE);
@@ -651,8 +650,7 @@ int tss_join_bwd(const void* dout, long lddo, const void* out, long ldo, int rel
   if (P == 0) return TSS_OK;
   const int nt = 1 + (relu ? 1 : 0) + (e ? 1 : 0) + (stats_a ? 1 : 0) + (stats_b ? 1 : 0);
   tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, (double)P * C * nt * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16) hipLaunchKernelGGL(join_bwd_kernel<bf16_t>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g);
-  else hipLaunchKernelGGL(join_bwd_kernel<float>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(join_bwd_kernel<TT>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g));
   return tss::check_last("join_bwd");
 }
 
@@ -676,33 +674,26 @@ int tss_dropout_mask(const unsigned long long* counter, void* mask, long P, int 
 
 int tss_dropout(const void* x, long ldx, void* y, long ldy, long P, int C, float p,
                 const unsigned long long* seed_slot, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (C % 8) == 0 && (ldx % 8) == 0 && (ldy % 8) == 0 && ldx >= C && ldy >= C && p >= 0.f && p < 1.f, TSS_ERR_SHAPE);
   if (P == 0) return TSS_OK;
   const long total = P * (C / 8);
   long grid = (total + NT - 1) / NT;
   if (grid > 2048) grid = 2048;
   tss::ProfScope prof(TSS_K_DROPOUT, (hipStream_t)stream, 2.0 * P * C * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(dropout_kernel<bf16_t>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,
-                       (const bf16_t*)x, ldx, (bf16_t*)y, ldy, P, C, p, seed_slot);
-  else
-    hipLaunchKernelGGL(dropout_kernel<float>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,
-                       (const float*)x, ldx, (float*)y, ldy, P, C, p, seed_slot);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(dropout_kernel<TT>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const TT*)x, ldx, (TT*)y, ldy, P,
+                                           C, p, seed_slot));
   return tss::check_last("dropout");
 }
 
 int tss_bias_grad(const void* e, long lde, long P, int N, float* dbias, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(N > 0 && N <= 64 && lde >= N, TSS_ERR_SHAPE);
   if (P == 0) return TSS_OK;
   long grid = (P + 3) / 4;
   if (grid > 1024) grid = 1024;
   tss::ProfScope prof(TSS_K_BIAS_GRAD, (hipStream_t)stream, (double)P * N * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(colsum_kernel<bf16_t>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)e, lde, P, N, dbias);
-  else
-    hipLaunchKernelGGL(colsum_kernel<float>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const float*)e, lde, P, N, dbias);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(colsum_kernel<TT>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const TT*)e, lde, P, N, dbias));
   return tss::check_last("bias_grad");
 }
 
@@ -725,7 +716,7 @@ int tss_permute_wtaps(const float* w, float* w_tnc, float* w_tcn, int N, int Cin
 }
 
 int tss_channel_shuffle(const void* x, long ldx, void* y, long ldy, long P, int C, int groups, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (C % 8) == 0 && groups > 0 && (C % groups) == 0 && ldx >= C && (ldy % 8) == 0 && ldy >= C, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(y), TSS_ERR_ALIGN);
   if (P == 0) return TSS_OK;
@@ -733,10 +724,8 @@ int tss_channel_shuffle(const void* x, long ldx, void* y, long ldy, long P, int 
   long grid = (total + NT - 1) / NT;
   if (grid > 2048) grid = 2048;
   tss::ProfScope prof(TSS_K_COPY, (hipStream_t)stream, 2.0 * P * C * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(channel_shuffle_kernel<bf16_t>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, P, C, groups);
-  else
-    hipLaunchKernelGGL(channel_shuffle_kernel<float>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const float*)x, ldx, (float*)y, ldy, P, C, groups);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(channel_shuffle_kernel<TT>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const TT*)x, ldx, (TT*)y,
+                                           ldy, P, C, groups));
   return tss::check_last("channel_shuffle");
 }
 

@@ -636,43 +636,26 @@ __global__ __launch_bounds__(NT) void copy_nhwc_kernel(const T* x, long ldx, T* 
   }
 }
 
-inline int grid_for(long total) {
-  long g = (total + NT - 1) / NT;
-  if (g > 4096) g = 4096;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 }  // namespace
-
-#define TSS_DISPATCH(dtype, KERNEL, grid, stream, ...)                                                    \
-  do {                                                                                                    \
-    if ((dtype) == TSS_BF16) hipLaunchKernelGGL(KERNEL<bf16_t>, dim3(grid), dim3(NT), 0, (hipStream_t)stream, __VA_ARGS__); \
-    else hipLaunchKernelGGL(KERNEL<float>, dim3(grid), dim3(NT), 0, (hipStream_t)stream, __VA_ARGS__);     \
-  } while (0)
 
 extern "C" {
 
 int tss_bilinear_nhwc_fwd(const void* x, long ldx, void* y, long ldy, int B, int Hin, int Win, int Hout, int Wout,
                           int C, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (C % 8) == 0 && (ldx % 8) == 0 && (ldy % 8) == 0 && ldx >= C && ldy >= C && Hin > 0 && Win > 0, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(x) && tss::aligned16(y), TSS_ERR_ALIGN);
   const long total = (long)B * Hout * Wout * (C / 8);
   if (total == 0) return TSS_OK;
   tss::ProfScope prof(TSS_K_BILINEAR_FWD, (hipStream_t)stream, ((double)B * Hin * Win + (double)B * Hout * Wout) * C * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(bilinear_nhwc_fwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream,
-                       (const bf16_t*)x, ldx, (bf16_t*)y, ldy, B, Hin, Win, Hout, Wout, C);
-  else
-    hipLaunchKernelGGL(bilinear_nhwc_fwd_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream,
-                       (const float*)x, ldx, (float*)y, ldy, B, Hin, Win, Hout, Wout, C);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(bilinear_nhwc_fwd_kernel<TT>, dim3(tss::grid_for(total, NT)), dim3(NT), 0, (hipStream_t)stream,
+                                           (const TT*)x, ldx, (TT*)y, ldy, B, Hin, Win, Hout, Wout, C));
   return tss::check_last("bilinear_nhwc_fwd");
 }
 
 int tss_bilinear_nhwc_bwd(const void* dy, long lddy, void* dx, long lddx, float* tmp, int B, int Hin, int Win,
                           int Hout, int Wout, int C, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (C % 8) == 0 && (lddy % 8) == 0 && (lddx % 8) == 0 && lddy >= C && lddx >= C, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(dy) && tss::aligned16(dx) && tss::aligned16(tmp) && tmp, TSS_ERR_ALIGN);
   const long t1 = (long)B * Hin * Wout * (C / 8), t2 = (long)B * Hin * Win * (C / 8);
@@ -680,45 +663,36 @@ int tss_bilinear_nhwc_bwd(const void* dy, long lddy, void* dx, long lddx, float*
   hipStream_t st = (hipStream_t)stream;
   {
     tss::ProfScope prof(TSS_K_BILINEAR_BWD, st, (double)B * Hout * Wout * C * tss::esz(dtype) + (double)B * Hin * Wout * C * 4, 0);
-    if (dtype == TSS_BF16)
-      hipLaunchKernelGGL(bilinear_nhwc_bwd_rows_kernel<bf16_t>, dim3(grid_for(t1)), dim3(NT), 0, st, (const bf16_t*)dy, lddy, tmp, B, Hin, Hout, Wout, C);
-    else
-      hipLaunchKernelGGL(bilinear_nhwc_bwd_rows_kernel<float>, dim3(grid_for(t1)), dim3(NT), 0, st, (const float*)dy, lddy, tmp, B, Hin, Hout, Wout, C);
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(bilinear_nhwc_bwd_rows_kernel<TT>, dim3(tss::grid_for(t1, NT)), dim3(NT), 0, st, (const TT*)dy, lddy,
+                                             tmp, B, Hin, Hout, Wout, C));
   }
   {
     tss::ProfScope prof(TSS_K_BILINEAR_BWD_COLS, st, (double)B * Hin * Wout * C * 4 + (double)B * Hin * Win * C * tss::esz(dtype), 0);
-    if (dtype == TSS_BF16)
-      hipLaunchKernelGGL(bilinear_nhwc_bwd_cols_kernel<bf16_t>, dim3(grid_for(t2)), dim3(NT), 0, st, tmp, (bf16_t*)dx, lddx, B, Hin, Win, Wout, C);
-    else
-      hipLaunchKernelGGL(bilinear_nhwc_bwd_cols_kernel<float>, dim3(grid_for(t2)), dim3(NT), 0, st, tmp, (float*)dx, lddx, B, Hin, Win, Wout, C);
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(bilinear_nhwc_bwd_cols_kernel<TT>, dim3(tss::grid_for(t2, NT)), dim3(NT), 0, st, tmp, (TT*)dx, lddx, B,
+                                             Hin, Win, Wout, C));
   }
   return tss::check_last("bilinear_nhwc_bwd");
 }
 
 int tss_bilinear_planar_fwd(const void* x, int x_dtype, void* y, int y_dtype, long planes, int Hin, int Win,
                             int Hout, int Wout, void* stream) {
-  TSS_REQUIRE((x_dtype == TSS_F32 || x_dtype == TSS_BF16) && (y_dtype == TSS_F32 || y_dtype == TSS_BF16), TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(x_dtype);
+  TSS_CHECK_DTYPE(y_dtype);
   TSS_REQUIRE(Hin > 0 && Win > 0, TSS_ERR_SHAPE);
   const long total = planes * Hout * Wout;
   if (total == 0) return TSS_OK;
-  const int grid = grid_for(total);
+  const int grid = tss::grid_for(total, NT);
   tss::ProfScope prof(TSS_K_BILINEAR_PLANAR_FWD, (hipStream_t)stream,
                       (double)planes * ((double)Hin * Win * tss::esz(x_dtype) + (double)Hout * Wout * tss::esz(y_dtype)), 0);
   hipStream_t s = (hipStream_t)stream;
-  if (x_dtype == TSS_F32 && y_dtype == TSS_F32)
-    hipLaunchKernelGGL((bilinear_planar_fwd_kernel<float, float>), dim3(grid), dim3(NT), 0, s, (const float*)x, (float*)y, planes, Hin, Win, Hout, Wout);
-  else if (x_dtype == TSS_F32)
-    hipLaunchKernelGGL((bilinear_planar_fwd_kernel<float, bf16_t>), dim3(grid), dim3(NT), 0, s, (const float*)x, (bf16_t*)y, planes, Hin, Win, Hout, Wout);
-  else if (y_dtype == TSS_F32)
-    hipLaunchKernelGGL((bilinear_planar_fwd_kernel<bf16_t, float>), dim3(grid), dim3(NT), 0, s, (const bf16_t*)x, (float*)y, planes, Hin, Win, Hout, Wout);
-  else
-    hipLaunchKernelGGL((bilinear_planar_fwd_kernel<bf16_t, bf16_t>), dim3(grid), dim3(NT), 0, s, (const bf16_t*)x, (bf16_t*)y, planes, Hin, Win, Hout, Wout);
+  TSS_WITH_DTYPE_AS(TX, x_dtype, TSS_WITH_DTYPE_AS(TY, y_dtype,
+      hipLaunchKernelGGL((bilinear_planar_fwd_kernel<TX, TY>), dim3(grid), dim3(NT), 0, s, (const TX*)x, (TY*)y, planes, Hin, Win, Hout, Wout)));
   return tss::check_last("bilinear_planar_fwd");
 }
 
 int tss_upsample_head_fwd(const void* low, long ldl, void* y, int B, int N, int h, int w, int H, int W,
                           int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(N > 0 && ldl >= N && (W % 8) == 0 && h > 0 && w > 0, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(y), TSS_ERR_ALIGN);
   if ((long)B * N * H * W == 0) return TSS_OK;
@@ -730,32 +704,22 @@ int tss_upsample_head_fwd(const void* low, long ldl, void* y, int B, int N, int 
   if (fast) {
     const long total = (long)B * ((N + 7) / 8) * H * (W / 8);
     const bool three = 7.f * sx < 0.99f;   // x8 and up: i0 advances at most once over a lane's 8 outputs
-    if (dtype == TSS_BF16) {
-      if (three) hipLaunchKernelGGL((upsample_head_fwd_kernel<bf16_t, 3>), dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream,
-                                    (const bf16_t*)low, ldl, (bf16_t*)y, B, N, h, w, H, W);
-      else hipLaunchKernelGGL((upsample_head_fwd_kernel<bf16_t, 4>), dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream,
-                              (const bf16_t*)low, ldl, (bf16_t*)y, B, N, h, w, H, W);
-    } else {
-      if (three) hipLaunchKernelGGL((upsample_head_fwd_kernel<float, 3>), dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream,
-                                    (const float*)low, ldl, (float*)y, B, N, h, w, H, W);
-      else hipLaunchKernelGGL((upsample_head_fwd_kernel<float, 4>), dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream,
-                              (const float*)low, ldl, (float*)y, B, N, h, w, H, W);
-    }
+    TSS_WITH_DTYPE(dtype,
+      if (three) hipLaunchKernelGGL((upsample_head_fwd_kernel<TT, 3>), dim3(tss::grid_for(total, NT)), dim3(NT), 0, (hipStream_t)stream,
+                                    (const TT*)low, ldl, (TT*)y, B, N, h, w, H, W);
+      else hipLaunchKernelGGL((upsample_head_fwd_kernel<TT, 4>), dim3(tss::grid_for(total, NT)), dim3(NT), 0, (hipStream_t)stream,
+                              (const TT*)low, ldl, (TT*)y, B, N, h, w, H, W));
   } else {
     const long total = (long)B * N * H * (W / 8);
-    if (dtype == TSS_BF16)
-      hipLaunchKernelGGL(upsample_head_fwd_generic_kernel<bf16_t>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream,
-                         (const bf16_t*)low, ldl, (bf16_t*)y, B, N, h, w, H, W);
-    else
-      hipLaunchKernelGGL(upsample_head_fwd_generic_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream,
-                         (const float*)low, ldl, (float*)y, B, N, h, w, H, W);
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(upsample_head_fwd_generic_kernel<TT>, dim3(tss::grid_for(total, NT)), dim3(NT), 0, (hipStream_t)stream,
+                                             (const TT*)low, ldl, (TT*)y, B, N, h, w, H, W));
   }
   return tss::check_last("upsample_head_fwd");
 }
 
 int tss_upsample_head_bwd(const void* dy, const float* gscale, float* tmp /*[B*N*h*W] f32 workspace*/,
                           void* dlow, long ldl, int B, int N, int h, int w, int H, int W, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(N > 0 && ldl >= N && (W % 8) == 0 && h > 0 && w > 0, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(dy) && tss::aligned16(tmp), TSS_ERR_ALIGN);
   const long planes = (long)B * N;
@@ -763,28 +727,20 @@ int tss_upsample_head_bwd(const void* dy, const float* gscale, float* tmp /*[B*N
   if (t1 == 0) return TSS_OK;
   {
     tss::ProfScope prof(TSS_K_UPSAMPLE_HEAD_BWD_ROWS, (hipStream_t)stream, (double)planes * H * W * tss::esz(dtype) + (double)planes * h * W * 4, 0);
-    if (dtype == TSS_BF16)
-      hipLaunchKernelGGL(upsample_head_bwd_rows_kernel<bf16_t>, dim3(grid_for(t1)), dim3(NT), 0, (hipStream_t)stream,
-                         (const bf16_t*)dy, tmp, gscale, planes, h, H, W);
-    else
-      hipLaunchKernelGGL(upsample_head_bwd_rows_kernel<float>, dim3(grid_for(t1)), dim3(NT), 0, (hipStream_t)stream,
-                         (const float*)dy, tmp, gscale, planes, h, H, W);
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(upsample_head_bwd_rows_kernel<TT>, dim3(tss::grid_for(t1, NT)), dim3(NT), 0, (hipStream_t)stream,
+                                             (const TT*)dy, tmp, gscale, planes, h, H, W));
   }
   {
     tss::ProfScope prof(TSS_K_UPSAMPLE_HEAD_BWD_COLS, (hipStream_t)stream, (double)planes * h * W * 4 + (double)planes * h * w * tss::esz(dtype), 0);
-    if (dtype == TSS_BF16)
-      hipLaunchKernelGGL(upsample_head_bwd_cols_kernel<bf16_t>, dim3(grid_for(t2)), dim3(NT), 0, (hipStream_t)stream,
-                         tmp, (bf16_t*)dlow, ldl, B, N, h, w, W);
-    else
-      hipLaunchKernelGGL(upsample_head_bwd_cols_kernel<float>, dim3(grid_for(t2)), dim3(NT), 0, (hipStream_t)stream,
-                         tmp, (float*)dlow, ldl, B, N, h, w, W);
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(upsample_head_bwd_cols_kernel<TT>, dim3(tss::grid_for(t2, NT)), dim3(NT), 0, (hipStream_t)stream, tmp,
+                                             (TT*)dlow, ldl, B, N, h, w, W));
   }
   return tss::check_last("upsample_head_bwd");
 }
 
 int tss_adaptive_pool_fwd(const void* x, long ldx, void* y, long ldy, int B, int H, int W, int C, int bins,
                           int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (C % 8) == 0 && C <= NT * 8 && (ldx % 8) == 0 && ldx >= C && ldy >= C && bins >= 1, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(x), TSS_ERR_ALIGN);
   if (B == 0) return TSS_OK;
@@ -792,29 +748,21 @@ int tss_adaptive_pool_fwd(const void* x, long ldx, void* y, long ldy, int B, int
   const int threads = (CV * NPL + 63) / 64 * 64;
   const int grid = B * bins * bins;
   tss::ProfScope prof(TSS_K_POOL_FWD, (hipStream_t)stream, (double)B * H * W * C * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(adaptive_pool_fwd_kernel<bf16_t>, dim3(grid), dim3(threads), 0, (hipStream_t)stream,
-                       (const bf16_t*)x, ldx, (bf16_t*)y, ldy, H, W, C, bins, CV, NPL);
-  else
-    hipLaunchKernelGGL(adaptive_pool_fwd_kernel<float>, dim3(grid), dim3(threads), 0, (hipStream_t)stream,
-                       (const float*)x, ldx, (float*)y, ldy, H, W, C, bins, CV, NPL);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(adaptive_pool_fwd_kernel<TT>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, (const TT*)x, ldx, (TT*)y,
+                                           ldy, H, W, C, bins, CV, NPL));
   return tss::check_last("adaptive_pool_fwd");
 }
 
 int tss_adaptive_pool_bwd(const void* dy, long lddy, void* dx, long lddx, int B, int H, int W, int C, int bins,
                           int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (C % 8) == 0 && (lddy % 8) == 0 && lddy >= C && (lddx % 8) == 0 && lddx >= C && bins >= 1, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(dy) && tss::aligned16(dx), TSS_ERR_ALIGN);
   const long total = (long)B * H * W * (C / 8);
   if (total == 0) return TSS_OK;
   tss::ProfScope prof(TSS_K_POOL_BWD, (hipStream_t)stream, (double)B * H * W * C * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(adaptive_pool_bwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream,
-                       (const bf16_t*)dy, lddy, (bf16_t*)dx, lddx, B, H, W, C, bins);
-  else
-    hipLaunchKernelGGL(adaptive_pool_bwd_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream,
-                       (const float*)dy, lddy, (float*)dx, lddx, B, H, W, C, bins);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(adaptive_pool_bwd_kernel<TT>, dim3(tss::grid_for(total, NT)), dim3(NT), 0, (hipStream_t)stream,
+                                           (const TT*)dy, lddy, (TT*)dx, lddx, B, H, W, C, bins));
   return tss::check_last("adaptive_pool_bwd");
 }
 
@@ -844,7 +792,7 @@ int tss_ppm_pool_slices(int B, int ncells) {   // row slices per window: > 1 onl
 
 int tss_ppm_pool_fwd(const void* x, long ldx, void* const* y, const long* ldy, const int* bins, int narms, float* ws,
                      int B, int H, int W, int C, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C <= NT * 8 && (ldx % 8) == 0 && ldx >= C && tss::aligned16(x), TSS_ERR_SHAPE);
   PpmArgs g = {};
   const int rc = ppm_fill(g, narms, bins, B, H, W, C, C);
@@ -856,18 +804,16 @@ int tss_ppm_pool_fwd(const void* x, long ldx, void* const* y, const long* ldy, c
   const int S = ws ? tss_ppm_pool_slices(B, g.cell0[narms]) : 1;   // ws: B * cells * S * C floats
   const int grid = B * g.cell0[narms] * S;
   tss::ProfScope prof(TSS_K_POOL_FWD, (hipStream_t)stream, (double)narms * B * H * W * C * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16) hipLaunchKernelGGL(ppm_pool_fwd_kernel<bf16_t>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g, CV, NPL, S, ws);
-  else hipLaunchKernelGGL(ppm_pool_fwd_kernel<float>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g, CV, NPL, S, ws);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(ppm_pool_fwd_kernel<TT>, dim3(grid), dim3(threads), 0, (hipStream_t)stream, g, CV, NPL, S, ws));
   if (S > 1) {
-    if (dtype == TSS_BF16) hipLaunchKernelGGL(ppm_pool_combine_kernel<bf16_t>, dim3(B * g.cell0[narms]), dim3(128), 0, (hipStream_t)stream, g, S, ws);
-    else hipLaunchKernelGGL(ppm_pool_combine_kernel<float>, dim3(B * g.cell0[narms]), dim3(128), 0, (hipStream_t)stream, g, S, ws);
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(ppm_pool_combine_kernel<TT>, dim3(B * g.cell0[narms]), dim3(128), 0, (hipStream_t)stream, g, S, ws));
   }
   return tss::check_last("ppm_pool_fwd");
 }
 
 int tss_ppm_pool_bwd(const void* const* dy, const long* lddy, const int* bins, int narms, void* dx, long lddx,
                      const void* radd, long ldr, int B, int H, int W, int C, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE((lddx % 8) == 0 && lddx >= C && tss::aligned16(dx), TSS_ERR_SHAPE);
   TSS_REQUIRE(!radd || ((ldr % 8) == 0 && ldr >= C && tss::aligned16(radd)), TSS_ERR_SHAPE);
   PpmArgs g = {};
@@ -880,15 +826,14 @@ int tss_ppm_pool_bwd(const void* const* dy, const long* lddy, const int* bins, i
   }
   const long total = (long)B * H * W * (C / 8);
   tss::ProfScope prof(TSS_K_POOL_BWD, (hipStream_t)stream, (double)B * H * W * C * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16) hipLaunchKernelGGL(ppm_pool_bwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, g);
-  else hipLaunchKernelGGL(ppm_pool_bwd_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, g);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(ppm_pool_bwd_kernel<TT>, dim3(tss::grid_for(total, NT)), dim3(NT), 0, (hipStream_t)stream, g));
   return tss::check_last("ppm_pool_bwd");
 }
 
 int tss_ppm_concat_fwd(const void* x, long ldx, const void* const* raw, const long* ldr, const int* bins,
                        const float* const* mean, const float* const* scale, const float* const* beta, const int* relu,
                        int narms, void* out, long ldo, int B, int H, int W, int C, int ca, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(ca > 0 && (ca % 8) == 0 && (ldx % 8) == 0 && ldx >= C && (ldo % 8) == 0 && ldo >= C + narms * ca, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(x) && tss::aligned16(out), TSS_ERR_ALIGN);
   PpmArgs g = {};
@@ -902,8 +847,7 @@ int tss_ppm_concat_fwd(const void* x, long ldx, const void* const* raw, const lo
   }
   const long total = (long)B * H * W * ((C + narms * ca) / 8);
   tss::ProfScope prof(TSS_K_BILINEAR_FWD, (hipStream_t)stream, (double)B * H * W * (2 * C + narms * ca) * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16) hipLaunchKernelGGL(ppm_concat_fwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, g);
-  else hipLaunchKernelGGL(ppm_concat_fwd_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, g);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(ppm_concat_fwd_kernel<TT>, dim3(tss::grid_for(total, NT)), dim3(NT), 0, (hipStream_t)stream, g));
   return tss::check_last("ppm_concat_fwd");
 }
 
@@ -911,7 +855,7 @@ int tss_ppm_concat_bwd(const void* dout, long lddo, const void* const* raw, cons
                        const float* const* mean, const float* const* scale, const float* const* beta, const int* relu,
                        double* const* bstats, void* const* e, const long* lde, int narms,
                        int B, int H, int W, int C, int ca, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(ca > 0 && (ca % 8) == 0 && ca <= 256 && (NT % (ca / 8)) == 0 && (lddo % 8) == 0 && lddo >= C + narms * ca, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(dout), TSS_ERR_ALIGN);
   PpmArgs g = {};
@@ -926,38 +870,31 @@ int tss_ppm_concat_bwd(const void* dout, long lddo, const void* const* raw, cons
   }
   const int grid = B * g.cell0[narms];
   tss::ProfScope prof(TSS_K_BILINEAR_BWD, (hipStream_t)stream, (double)B * H * W * narms * ca * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16) hipLaunchKernelGGL(ppm_concat_bwd_kernel<bf16_t>, dim3(grid), dim3(NT), 0, (hipStream_t)stream, g);
-  else hipLaunchKernelGGL(ppm_concat_bwd_kernel<float>, dim3(grid), dim3(NT), 0, (hipStream_t)stream, g);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(ppm_concat_bwd_kernel<TT>, dim3(grid), dim3(NT), 0, (hipStream_t)stream, g));
   return tss::check_last("ppm_concat_bwd");
 }
 
 int tss_copy_nhwc(const void* x, long ldx, void* y, long ldy, long P, int C, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (C % 8) == 0 && (ldx % 8) == 0 && (ldy % 8) == 0 && ldx >= C && ldy >= C, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(x) && tss::aligned16(y), TSS_ERR_ALIGN);
   const long total = P * (C / 8);
   if (total == 0) return TSS_OK;
   tss::ProfScope prof(TSS_K_COPY, (hipStream_t)stream, 2.0 * P * C * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(copy_nhwc_kernel<bf16_t>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, P, C);
-  else
-    hipLaunchKernelGGL(copy_nhwc_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, (const float*)x, ldx, (float*)y, ldy, P, C);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(copy_nhwc_kernel<TT>, dim3(tss::grid_for(total, NT)), dim3(NT), 0, (hipStream_t)stream, (const TT*)x, ldx,
+                                           (TT*)y, ldy, P, C));
   return tss::check_last("copy_nhwc");
 }
 
 int tss_upsample_head_bwd_cols(const float* tmp, void* dlow, long ldl, int B, int N, int h, int w, int W,
                                int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(N > 0 && ldl >= N && h > 0 && w > 0, TSS_ERR_SHAPE);
   const long t2 = (long)B * N * h * w;
   if (t2 == 0) return TSS_OK;
   tss::ProfScope prof(TSS_K_UPSAMPLE_HEAD_BWD_COLS, (hipStream_t)stream, (double)B * N * h * W * 4 + (double)t2 * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(upsample_head_bwd_cols_kernel<bf16_t>, dim3(grid_for(t2)), dim3(NT), 0, (hipStream_t)stream,
-                       tmp, (bf16_t*)dlow, ldl, B, N, h, w, W);
-  else
-    hipLaunchKernelGGL(upsample_head_bwd_cols_kernel<float>, dim3(grid_for(t2)), dim3(NT), 0, (hipStream_t)stream,
-                       tmp, (float*)dlow, ldl, B, N, h, w, W);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(upsample_head_bwd_cols_kernel<TT>, dim3(tss::grid_for(t2, NT)), dim3(NT), 0, (hipStream_t)stream, tmp,
+                                           (TT*)dlow, ldl, B, N, h, w, W));
   return tss::check_last("upsample_head_bwd_cols");
 }
 

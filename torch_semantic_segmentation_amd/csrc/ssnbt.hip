@@ -189,7 +189,7 @@ extern "C" {
 int tss_ssnbt_tail_fwd(const void* left, long ldl, const float* mean_l, const float* scale_l, const float* shift_l,
                        const void* right, long ldr, const float* mean_r, const float* scale_r, const float* shift_r,
                        const void* x, long ldx, const float* m, void* out, long ldo, int B, long HW, int C, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (C % 16) == 0 && C <= 512 && (ldl % 8) == 0 && ldl >= C / 2 && (ldr % 8) == 0 && ldr >= C / 2 && (ldx % 8) == 0 && ldx >= C &&
               (ldo % 8) == 0 && ldo >= C && left && right && x && out && B > 0 && HW > 0, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(left) && tss::aligned16(right) && tss::aligned16(x) && tss::aligned16(out), TSS_ERR_ALIGN);
@@ -201,8 +201,7 @@ int tss_ssnbt_tail_fwd(const void* left, long ldl, const float* mean_l, const fl
   long grid = (HW + npl - 1) / npl;
   if (grid > 2048) grid = 2048;
   tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, 3.0 * B * HW * C * (dtype == TSS_BF16 ? 2 : 4), 0);
-  if (dtype == TSS_BF16) hipLaunchKernelGGL(ssnbt_tail_fwd_kernel<bf16_t>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, g);
-  else hipLaunchKernelGGL(ssnbt_tail_fwd_kernel<float>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, g);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(ssnbt_tail_fwd_kernel<TT>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, g));
   return tss::check_last("ssnbt_tail_fwd");
 }
 
@@ -212,7 +211,7 @@ int tss_ssnbt_tail_bwd(const void* dout, long lddo, const void* out, long ldo,
                        const void* left, long ldl, const float* mean_l, const void* right, long ldr, const float* mean_r,
                        const float* m, void* e, long lde, void* gs, long ldgs, double* stats_l, double* stats_r,
                        int B, long HW, int C, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (C % 16) == 0 && C <= 512 && (lddo % 8) == 0 && lddo >= C && (ldo % 8) == 0 && ldo >= C && (ldgs % 8) == 0 && ldgs >= C &&
               dout && out && gs && B > 0 && HW > 0 && (!e || ((lde % 8) == 0 && lde >= C)) && ((stats_l != nullptr) == (stats_r != nullptr)), TSS_ERR_SHAPE);
   TSS_REQUIRE(!stats_l || (left && right && mean_l && mean_r && (ldl % 8) == 0 && ldl >= C / 2 && (ldr % 8) == 0 && ldr >= C / 2), TSS_ERR_SHAPE);
@@ -227,8 +226,7 @@ int tss_ssnbt_tail_bwd(const void* dout, long lddo, const void* out, long ldo,
   if (grid > TSS_STAT_SLABS) grid = TSS_STAT_SLABS;    // one statistics slab row per block
   const int nt = 2 + 1 + (e ? 1 : 0) + (stats_l ? 1 : 0);
   tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, (double)nt * B * HW * C * (dtype == TSS_BF16 ? 2 : 4), 0);
-  if (dtype == TSS_BF16) hipLaunchKernelGGL(ssnbt_tail_bwd_kernel<bf16_t>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, g);
-  else hipLaunchKernelGGL(ssnbt_tail_bwd_kernel<float>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, g);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(ssnbt_tail_bwd_kernel<TT>, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, g));
   return tss::check_last("ssnbt_tail_bwd");
 }
 

@@ -624,8 +624,7 @@ int launch(WgradArgs& g, int dtype, int kernel_id, hipStream_t stream, double al
   g.nsplit = (int)ns;
   const int grid = tiles * (int)ns;
   tss::ProfScope prof(kernel_id, stream, alg_bytes, 2.0 * (double)g.P * g.ND * g.KD * g.ntaps);
-  if (dtype == TSS_BF16) hipLaunchKernelGGL(wgrad_kernel<bf16_t>, dim3(grid), dim3(NT), 0, stream, g);
-  else hipLaunchKernelGGL(wgrad_kernel<float>, dim3(grid), dim3(NT), 0, stream, g);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(wgrad_kernel<TT>, dim3(grid), dim3(NT), 0, stream, g));
   return tss::check_last("wgrad");
 }
 
@@ -648,7 +647,7 @@ int tss_pwconv_bwd_weight(const void* e, long lde, const void* yraw, long ldyr,
                           const void* xraw, long ldx, const float* in_mean, const float* in_scale, const float* in_bias, int in_relu,
                           float* dw, float* ws, int defer_reduce, long P, int K, int N, int dtype, const tss_bn_bwd_job* fin,
                           void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(!fin || (fin->C > 0 && fin->count >= 1.0 && fin->bstats && fin->invstd && fin->ga && fin->gb && fin->gce), TSS_ERR_SHAPE);
   TSS_REQUIRE(K > 0 && N > 0 && (K % 8) == 0 && (lde % 8) == 0 && lde >= (N + 7) / 8 * 8 && (ldx % 8) == 0 && ldx >= K, TSS_ERR_SHAPE);
   TSS_REQUIRE(!yraw || ((ldyr % 8) == 0 && ldyr >= (N + 7) / 8 * 8 && ga && gb && gce && gmu), TSS_ERR_SHAPE);
@@ -693,7 +692,7 @@ int tss_conv3x3_bwd_weight(const void* e, long lde, const void* yraw, long ldyr,
                            const void* xraw, long ldx, const float* in_mean, const float* in_scale, const float* in_bias, int in_relu,
                            float* dw, int B, int Hin, int Win, int Cin, int N, int stride, int dil,
                            int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(Cin > 0 && N > 0 && (Cin % 8) == 0 && (N % 8) == 0 && (lde % 8) == 0 && lde >= N && (ldx % 8) == 0 && ldx >= Cin,
               TSS_ERR_SHAPE);
   TSS_REQUIRE(!yraw || ((ldyr % 8) == 0 && ldyr >= N && ga && gb && gce && gmu), TSS_ERR_SHAPE);
@@ -712,7 +711,7 @@ int tss_conv1d3_bwd_weight(const void* e, long lde, const void* yraw, long ldyr,
                            const float* ga, const float* gb, const float* gce, const float* gmu,
                            const void* xraw, long ldx, const float* in_mean, const float* in_scale, const float* in_bias, int in_relu,
                            float* dw, int B, int H, int W, int Cin, int N, int axis, int dil, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(Cin > 0 && N > 0 && (Cin % 8) == 0 && (N % 8) == 0 && (lde % 8) == 0 && lde >= N && (ldx % 8) == 0 && ldx >= Cin &&
               (axis == 0 || axis == 1) && dil >= 1, TSS_ERR_SHAPE);
   TSS_REQUIRE(!yraw || ((ldyr % 8) == 0 && ldyr >= N && ga && gb && gce && gmu), TSS_ERR_SHAPE);
@@ -733,7 +732,7 @@ int tss_convkxk_bwd_weight(const void* e, long lde, const void* yraw, long ldyr,
                            const void* xraw, long ldx, const float* in_mean, const float* in_scale, const float* in_bias, int in_relu,
                            float* dw, int B, int Hin, int Win, int Cin, int N, int kh, int kw, int stride, int dil,
                            int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(Cin > 0 && N > 0 && (Cin % 8) == 0 && (N % 8) == 0 && (lde % 8) == 0 && lde >= N && (ldx % 8) == 0 && ldx >= Cin &&
               stride >= 1 && dil >= 1 && kh >= 1 && kw >= 1 && (kh & 1) && (kw & 1) && kh * kw <= 81, TSS_ERR_SHAPE);
   TSS_REQUIRE(!yraw || ((ldyr % 8) == 0 && ldyr >= N && ga && gb && gce && gmu), TSS_ERR_SHAPE);
@@ -752,7 +751,7 @@ int tss_stem3x3_bwd_weight(const void* e, long lde, const void* yraw, long ldyr,
                            const float* ga, const float* gb, const float* gce, const float* gmu,
                            const void* x_nchw, int x_is_f32, float* dw, float* ws,
                            int B, int Cin, int Hin, int Win, int N, int stride, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(Cin >= 1 && Cin * 9 <= TK && N > 0 && (N % 8) == 0 && (lde % 8) == 0 && lde >= N, TSS_ERR_SHAPE);
   TSS_REQUIRE(!yraw || ((ldyr % 8) == 0 && ldyr >= N && ga && gb && gce && gmu), TSS_ERR_SHAPE);
   WgradArgs g = {};

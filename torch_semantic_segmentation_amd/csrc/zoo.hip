@@ -427,51 +427,38 @@ __global__ __launch_bounds__(NT) void pad_channels_kernel(const T* g, long ldg, 
   }
 }
 
-inline int grid_for(long total) {
-  long g = (total + NT - 1) / NT;
-  return (int)(g > 2048 ? 2048 : (g < 1 ? 1 : g));
-}
-
 }  // namespace
 
 extern "C" {
 
 int tss_tensor_stats(const void* z, long ldz, long P, int C, double* stats, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(P >= 0 && C > 0 && ldz >= C && z && stats, TSS_ERR_SHAPE);
   tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, (double)P * C * tss::esz(dtype), 0);
   const bool vec = (C % 8) == 0 && C <= NT * 8 / 2 && (ldz % 8) == 0 && tss::aligned16(z) && P >= 4 * TSS_STAT_SLABS;
-  if (vec && dtype == TSS_BF16)
-    hipLaunchKernelGGL(tensor_stats_vec_kernel<bf16_t>, dim3(TSS_STAT_SLABS), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)z, ldz, P, C, stats);
-  else if (vec)
-    hipLaunchKernelGGL(tensor_stats_vec_kernel<float>, dim3(TSS_STAT_SLABS), dim3(NT), 0, (hipStream_t)stream, (const float*)z, ldz, P, C, stats);
-  else if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(tensor_stats_kernel<bf16_t>, dim3(TSS_STAT_SLABS), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)z, ldz, P, C, stats);
+  if (vec)
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(tensor_stats_vec_kernel<TT>, dim3(TSS_STAT_SLABS), dim3(NT), 0, (hipStream_t)stream, (const TT*)z, ldz, P, C, stats));
   else
-    hipLaunchKernelGGL(tensor_stats_kernel<float>, dim3(TSS_STAT_SLABS), dim3(NT), 0, (hipStream_t)stream, (const float*)z, ldz, P, C, stats);
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(tensor_stats_kernel<TT>, dim3(TSS_STAT_SLABS), dim3(NT), 0, (hipStream_t)stream, (const TT*)z, ldz, P, C, stats));
   return tss::check_last("tensor_stats");
 }
 
 int tss_bn_bwd_apply(const void* e, long lde, const void* z, long ldz, const float* ga, const float* gb, const float* gce,
                      const float* gmu, void* dz, long lddz, long P, int C, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (C % 8) == 0 && (lde % 8) == 0 && lde >= C && (lddz % 8) == 0 && lddz >= C && ga && e && dz, TSS_ERR_SHAPE);
   TSS_REQUIRE(!gb || (z && gce && gmu && (ldz % 8) == 0 && ldz >= C), TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(e) && tss::aligned16(dz) && (!gb || tss::aligned16(z)), TSS_ERR_ALIGN);
   if (P == 0) return TSS_OK;
   tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, (double)P * C * tss::esz(dtype) * (gb ? 3 : 2), 0);
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, dim3(grid_for(P * (C / 8))), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)e, lde,
-                       (const bf16_t*)z, ldz, ga, gb, gce, gmu, (bf16_t*)dz, lddz, P, C);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(grid_for(P * (C / 8))), dim3(NT), 0, (hipStream_t)stream, (const float*)e, lde,
-                       (const float*)z, ldz, ga, gb, gce, gmu, (float*)dz, lddz, P, C);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(bn_bwd_apply_kernel<TT>, dim3(tss::grid_for(P * (C / 8), NT, 2048)), dim3(NT), 0, (hipStream_t)stream,
+                                           (const TT*)e, lde, (const TT*)z, ldz, ga, gb, gce, gmu, (TT*)dz, lddz, P, C));
   return tss::check_last("bn_bwd_apply");
 }
 
 int tss_pool_concat_fwd(const void* y1, long ld1, const float* bias, int N1, const void* x, int x_f32, long sxb, long sxc, long sxh,
                         long sxw, int Cin, void* z, long ldz, int B, int Hin, int Win, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(N1 >= 0 && Cin > 0 && B >= 0 && Hin > 0 && Win > 0 && (Hin % 2) == 0 && (Win % 2) == 0 && ldz >= N1 + Cin && x && z &&
               (N1 == 0 || (y1 && ld1 >= N1)), TSS_ERR_SHAPE);
   PoolArgs g = {x, x_f32, sxb, sxc, sxh, sxw, Cin, N1, B, Hin / 2, Win / 2};
@@ -483,38 +470,26 @@ int tss_pool_concat_fwd(const void* y1, long ld1, const float* bias, int N1, con
                    (sxb % 8) == 0 && (sxh % 8) == 0 && (sxw % 8) == 0 && tss::aligned16(x) && tss::aligned16(z) && (N1 == 0 || tss::aligned16(y1));
   if (vec) {
     const long tv = total / 8;
-    if (dtype == TSS_BF16)
-      hipLaunchKernelGGL(pool_concat_fwd_vec_kernel<bf16_t>, dim3(grid_for(tv)), dim3(NT), 0, (hipStream_t)stream, g, (const bf16_t*)y1, ld1, bias,
-                         (bf16_t*)z, ldz);
-    else
-      hipLaunchKernelGGL(pool_concat_fwd_vec_kernel<float>, dim3(grid_for(tv)), dim3(NT), 0, (hipStream_t)stream, g, (const float*)y1, ld1, bias,
-                         (float*)z, ldz);
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(pool_concat_fwd_vec_kernel<TT>, dim3(tss::grid_for(tv, NT, 2048)), dim3(NT), 0, (hipStream_t)stream, g,
+                                             (const TT*)y1, ld1, bias, (TT*)z, ldz));
     return tss::check_last("pool_concat_fwd");
   }
   const bool img = x_f32 != 0 && ((N1 + Cin) % 8) == 0 && (ldz % 8) == 0 && tss::aligned16(z) && N1 > 0 && (ld1 % 8) == 0 && ld1 >= (N1 + 7) / 8 * 8 &&
                    tss::aligned16(y1);
   if (img) {
     const long tv = total / 8;
-    if (dtype == TSS_BF16)
-      hipLaunchKernelGGL(pool_concat_fwd_img_kernel<bf16_t>, dim3(grid_for(tv)), dim3(NT), 0, (hipStream_t)stream, g, (const bf16_t*)y1, ld1, bias,
-                         (bf16_t*)z, ldz);
-    else
-      hipLaunchKernelGGL(pool_concat_fwd_img_kernel<float>, dim3(grid_for(tv)), dim3(NT), 0, (hipStream_t)stream, g, (const float*)y1, ld1, bias,
-                         (float*)z, ldz);
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(pool_concat_fwd_img_kernel<TT>, dim3(tss::grid_for(tv, NT, 2048)), dim3(NT), 0, (hipStream_t)stream, g,
+                                             (const TT*)y1, ld1, bias, (TT*)z, ldz));
     return tss::check_last("pool_concat_fwd");
   }
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(pool_concat_fwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, g, (const bf16_t*)y1, ld1, bias,
-                       (bf16_t*)z, ldz);
-  else
-    hipLaunchKernelGGL(pool_concat_fwd_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, g, (const float*)y1, ld1, bias,
-                       (float*)z, ldz);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(pool_concat_fwd_kernel<TT>, dim3(tss::grid_for(total, NT, 2048)), dim3(NT), 0, (hipStream_t)stream, g,
+                                           (const TT*)y1, ld1, bias, (TT*)z, ldz));
   return tss::check_last("pool_concat_fwd");
 }
 
 int tss_pool_concat_bwd(const void* dz, long lddz, int N1, const void* x, int x_f32, long sxb, long sxc, long sxh, long sxw, int Cin,
                         void* dx, long lddx, int B, int Hin, int Win, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(N1 >= 0 && Cin > 0 && B >= 0 && Hin > 0 && Win > 0 && (Hin % 2) == 0 && (Win % 2) == 0 && lddz >= N1 + Cin && lddx >= Cin &&
               x && dz && dx, TSS_ERR_SHAPE);
   PoolArgs g = {x, x_f32, sxb, sxc, sxh, sxw, Cin, N1, B, Hin / 2, Win / 2};
@@ -524,20 +499,12 @@ int tss_pool_concat_bwd(const void* dz, long lddz, int N1, const void* x, int x_
   const bool vec = (x_f32 != 0) == (dtype == TSS_F32) && sxc == 1 && (N1 % 8) == 0 && (Cin % 8) == 0 && (lddz % 8) == 0 && (lddx % 8) == 0 &&
                    (sxb % 8) == 0 && (sxh % 8) == 0 && (sxw % 8) == 0 && tss::aligned16(x) && tss::aligned16(dz) && tss::aligned16(dx);
   if (vec) {
-    if (dtype == TSS_BF16)
-      hipLaunchKernelGGL(pool_concat_bwd_vec_kernel<bf16_t>, dim3(grid_for(total / 8)), dim3(NT), 0, (hipStream_t)stream, g, (const bf16_t*)dz, lddz,
-                         (bf16_t*)dx, lddx);
-    else
-      hipLaunchKernelGGL(pool_concat_bwd_vec_kernel<float>, dim3(grid_for(total / 8)), dim3(NT), 0, (hipStream_t)stream, g, (const float*)dz, lddz,
-                         (float*)dx, lddx);
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(pool_concat_bwd_vec_kernel<TT>, dim3(tss::grid_for(total / 8, NT, 2048)), dim3(NT), 0,
+                                             (hipStream_t)stream, g, (const TT*)dz, lddz, (TT*)dx, lddx));
     return tss::check_last("pool_concat_bwd");
   }
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(pool_concat_bwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, g, (const bf16_t*)dz, lddz,
-                       (bf16_t*)dx, lddx);
-  else
-    hipLaunchKernelGGL(pool_concat_bwd_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, g, (const float*)dz, lddz,
-                       (float*)dx, lddx);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(pool_concat_bwd_kernel<TT>, dim3(tss::grid_for(total, NT, 2048)), dim3(NT), 0, (hipStream_t)stream, g,
+                                           (const TT*)dz, lddz, (TT*)dx, lddx));
   return tss::check_last("pool_concat_bwd");
 }
 
@@ -551,85 +518,67 @@ int tss_rows_slices(int B, long HW) {       // pixel slices per image of tss_mul
 
 int tss_mul_addrows_fwd(const void* u, long ldu, const void* a, long lda, const void* r, long ldr, void* out, long ldo, int B, long HW,
                         int C, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (C % 8) == 0 && (ldu % 8) == 0 && ldu >= C && (lda % 8) == 0 && lda >= C && (ldr % 8) == 0 && ldr >= C &&
               (ldo % 8) == 0 && ldo >= C, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(u) && tss::aligned16(a) && tss::aligned16(r) && tss::aligned16(out), TSS_ERR_ALIGN);
   const long P = (long)B * HW;
   if (P == 0) return TSS_OK;
   tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, 3.0 * P * C * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(mul_addrows_fwd_kernel<bf16_t>, dim3(grid_for(P * (C / 8))), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)u, ldu,
-                       (const bf16_t*)a, lda, (const bf16_t*)r, ldr, (bf16_t*)out, ldo, HW, P, C);
-  else
-    hipLaunchKernelGGL(mul_addrows_fwd_kernel<float>, dim3(grid_for(P * (C / 8))), dim3(NT), 0, (hipStream_t)stream, (const float*)u, ldu,
-                       (const float*)a, lda, (const float*)r, ldr, (float*)out, ldo, HW, P, C);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(mul_addrows_fwd_kernel<TT>, dim3(tss::grid_for(P * (C / 8), NT, 2048)), dim3(NT), 0, (hipStream_t)stream,
+                                           (const TT*)u, ldu, (const TT*)a, lda, (const TT*)r, ldr, (TT*)out, ldo, HW, P, C));
   return tss::check_last("mul_addrows_fwd");
 }
 
 int tss_mul_addrows_bwd(const void* g, long ldg, const void* u, long ldu, const void* a, long lda, void* du, long lddu, void* da,
                         long ldda, void* dr, long lddr, float* ws, int B, long HW, int C, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (C % 8) == 0 && (C / 8) <= NT && (ldg % 8) == 0 && ldg >= C && (ldu % 8) == 0 && ldu >= C && (lda % 8) == 0 && lda >= C &&
               (lddu % 8) == 0 && lddu >= C && (ldda % 8) == 0 && ldda >= C && lddr >= C && ws && dr, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(g) && tss::aligned16(u) && tss::aligned16(a) && tss::aligned16(du) && tss::aligned16(da), TSS_ERR_ALIGN);
   if ((long)B * HW == 0) return TSS_OK;
   const int S = tss_rows_slices(B, HW);
   tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, 5.0 * B * HW * C * tss::esz(dtype), 0);
-#define TSS_MAR_BWD(TT)                                                                                                              \
-  hipLaunchKernelGGL(mul_addrows_bwd_kernel<TT>, dim3(B * S), dim3(NT), 0, (hipStream_t)stream, (const TT*)g, ldg, (const TT*)u, ldu,  \
-                     (const TT*)a, lda, (TT*)du, lddu, (TT*)da, ldda, ws, HW, C, S);                                                 \
-  hipLaunchKernelGGL(rows_reduce_kernel<TT>, dim3((B * C + NT - 1) / NT), dim3(NT), 0, (hipStream_t)stream, ws, (TT*)dr, lddr, B, C, S)
-  if (dtype == TSS_BF16) { TSS_MAR_BWD(bf16_t); } else { TSS_MAR_BWD(float); }
-#undef TSS_MAR_BWD
+  TSS_WITH_DTYPE(dtype,
+    hipLaunchKernelGGL(mul_addrows_bwd_kernel<TT>, dim3(B * S), dim3(NT), 0, (hipStream_t)stream, (const TT*)g, ldg, (const TT*)u, ldu,
+                       (const TT*)a, lda, (TT*)du, lddu, (TT*)da, ldda, ws, HW, C, S);
+    hipLaunchKernelGGL(rows_reduce_kernel<TT>, dim3((B * C + NT - 1) / NT), dim3(NT), 0, (hipStream_t)stream, ws, (TT*)dr, lddr, B, C, S));
   return tss::check_last("mul_addrows_bwd");
 }
 
 int tss_cat2_add(const void* gl, long ldl, const void* gr, long ldr, const void* gs, long lds, void* out, long ldo, long P, int half,
                  int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(half > 0 && (half % 8) == 0 && (ldl % 8) == 0 && ldl >= half && (ldr % 8) == 0 && ldr >= half && (ldo % 8) == 0 && ldo >= 2 * half &&
               gl && gr && out && (!gs || ((lds % 8) == 0 && lds >= 2 * half)), TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(gl) && tss::aligned16(gr) && tss::aligned16(out) && (!gs || tss::aligned16(gs)), TSS_ERR_ALIGN);
   if (P == 0) return TSS_OK;
   tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, (double)P * half * (gs ? 6.0 : 4.0) * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(cat2_add_kernel<bf16_t>, dim3(grid_for(P * (half / 4))), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)gl, ldl,
-                       (const bf16_t*)gr, ldr, (const bf16_t*)gs, lds, (bf16_t*)out, ldo, P, half);
-  else
-    hipLaunchKernelGGL(cat2_add_kernel<float>, dim3(grid_for(P * (half / 4))), dim3(NT), 0, (hipStream_t)stream, (const float*)gl, ldl,
-                       (const float*)gr, ldr, (const float*)gs, lds, (float*)out, ldo, P, half);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(cat2_add_kernel<TT>, dim3(tss::grid_for(P * (half / 4), NT, 2048)), dim3(NT), 0, (hipStream_t)stream,
+                                           (const TT*)gl, ldl, (const TT*)gr, ldr, (const TT*)gs, lds, (TT*)out, ldo, P, half));
   return tss::check_last("cat2_add");
 }
 
 int tss_pad_channels(const void* g, long ldg, int C, void* out, long ldo, int CP, long P, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && CP >= C && (CP % 8) == 0 && ldg >= C && (ldo % 8) == 0 && ldo >= CP && g && out, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(out), TSS_ERR_ALIGN);
   if (P == 0) return TSS_OK;
   tss::ProfScope prof(TSS_K_JOIN_BWD, (hipStream_t)stream, (double)P * (C + CP) * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(pad_channels_kernel<bf16_t>, dim3(grid_for(P * (CP / 8))), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)g, ldg, C,
-                       (bf16_t*)out, ldo, CP, P);
-  else
-    hipLaunchKernelGGL(pad_channels_kernel<float>, dim3(grid_for(P * (CP / 8))), dim3(NT), 0, (hipStream_t)stream, (const float*)g, ldg, C,
-                       (float*)out, ldo, CP, P);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(pad_channels_kernel<TT>, dim3(tss::grid_for(P * (CP / 8), NT, 2048)), dim3(NT), 0, (hipStream_t)stream,
+                                           (const TT*)g, ldg, C, (TT*)out, ldo, CP, P));
   return tss::check_last("pad_channels");
 }
 
 int tss_scale_rows(const void* x, long ldx, const float* m, void* out, long ldo, int B, long HW, int C, int dtype, void* stream) {
-  TSS_REQUIRE(dtype == TSS_F32 || dtype == TSS_BF16, TSS_ERR_DTYPE);
+  TSS_CHECK_DTYPE(dtype);
   TSS_REQUIRE(C > 0 && (C % 8) == 0 && (ldx % 8) == 0 && ldx >= C && (ldo % 8) == 0 && ldo >= C && m, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(x) && tss::aligned16(out), TSS_ERR_ALIGN);
   const long P = (long)B * HW;
   if (P == 0) return TSS_OK;
   tss::ProfScope prof(TSS_K_JOIN_FWD, (hipStream_t)stream, 2.0 * P * C * tss::esz(dtype), 0);
-  if (dtype == TSS_BF16)
-    hipLaunchKernelGGL(scale_rows_kernel<bf16_t>, dim3(grid_for(P * (C / 8))), dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, m,
-                       (bf16_t*)out, ldo, HW, P, C);
-  else
-    hipLaunchKernelGGL(scale_rows_kernel<float>, dim3(grid_for(P * (C / 8))), dim3(NT), 0, (hipStream_t)stream, (const float*)x, ldx, m,
-                       (float*)out, ldo, HW, P, C);
+  TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(scale_rows_kernel<TT>, dim3(tss::grid_for(P * (C / 8), NT, 2048)), dim3(NT), 0, (hipStream_t)stream,
+                                           (const TT*)x, ldx, m, (TT*)out, ldo, HW, P, C));
   return tss::check_last("scale_rows");
 }
 

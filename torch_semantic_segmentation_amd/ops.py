@@ -73,14 +73,19 @@ unfold_1d_wgrad = os.environ.get('TSS_FC1D_WGRAD', '1') != '0'
 _CONST_ROWS = {}
 
 
+def _per_device(cache, dev, make, stale=lambda got: False):
+    """cache[dev], filled by make() on first use (and again when stale(entry)): one entry per (device type, index)."""
+    key = (dev.type, dev.index)
+    if key not in cache or stale(cache[key]):
+        cache[key] = make()
+    return cache[key]
+
+
 def _const_rows(dev, n):
     """(ones, zeros) f32 rows of at least n channels on `dev`: BatchNorm-backward coefficients of a layer that has none."""
-    key = (dev.type, dev.index)
-    got = _CONST_ROWS.get(key)
-    if got is None or got[0].numel() < n:
-        m = max(768, n)
-        got = _CONST_ROWS[key] = (torch.ones(m, dtype=torch.float32, device=dev), torch.zeros(m, dtype=torch.float32, device=dev))
-    return got
+    m = max(768, n)
+    return _per_device(_CONST_ROWS, dev, lambda: (torch.ones(m, dtype=torch.float32, device=dev), torch.zeros(m, dtype=torch.float32, device=dev)),
+                       stale=lambda got: got[0].numel() < n)
 # Layers that run inside a two-stream region of the forward pass (ContextNet's branches, `overlap_region`) are not postponed: there
 # the other stream's kernels already fill the launch gaps, and what postponing leaves for the end of the pass (a weight gradient and
 # its slot reduction per stream, un-overlapped) costs more than the finalize launches it saves (measured: 6.32 vs 6.21 ms per step).
@@ -1896,11 +1901,8 @@ _dropout_counters = {}
 
 
 def _dropout_counter(device):
-    key = (device.type, device.index)
-    if key not in _dropout_counters:
-        seed = torch.initial_seed() & 0x7FFFFFFFFFFFFFFF
-        _dropout_counters[key] = torch.tensor([seed], dtype=torch.int64, device=device)
-    return _dropout_counters[key]
+    return _per_device(_dropout_counters, device,
+                       lambda: torch.tensor([torch.initial_seed() & 0x7FFFFFFFFFFFFFFF], dtype=torch.int64, device=device))
 
 
 def dropout(x, p, training):
@@ -2922,17 +2924,23 @@ class PpmArmsFn(Function):
 
 # ----------------------------------------------------------------------------- loss / metrics (caller side)
 
+def _check_logits_target(logits, target):
+    """The common opening of the losses on full-resolution logits: (B,C,H,W) logits and (B,H,W) int64 target, both contiguous."""
+    _check_device(logits)
+    logits = logits.contiguous()
+    B, C, H, W = logits.shape
+    if (H * W) % 8:
+        raise NotImplementedError('HIP path: H*W must be a multiple of 8')
+    if target.dtype != torch.int64 or target.shape != (B, H, W):
+        raise RuntimeError('target must be int64 of shape (B,H,W)')
+    return logits, target.contiguous()
+
+
 class CrossEntropyFn(Function):
     @staticmethod
     def forward(ctx, logits, target, ignore_index):
-        _check_device(logits)
-        logits = logits.contiguous()
+        logits, target = _check_logits_target(logits, target)
         B, C, H, W = logits.shape
-        if (H * W) % 8:
-            raise NotImplementedError('HIP path: H*W must be a multiple of 8')
-        if target.dtype != torch.int64 or target.shape != (B, H, W):
-            raise RuntimeError('target must be int64 of shape (B,H,W)')
-        target = target.contiguous()
         dev = logits.device
         lse = torch.empty((B, H, W), dtype=torch.float32, device=dev)
         acc = torch.zeros(2, dtype=torch.float64, device=dev)
@@ -2975,24 +2983,19 @@ class OHEMFn(Function):
     _ws = {}
 
     @staticmethod
+    def workspace(dev):          # zeroed once; every call leaves it zeroed
+        return _per_device(OHEMFn._ws, dev, lambda: torch.zeros(N.lib().tss_ohem_workspace_bytes(), dtype=torch.uint8, device=dev))
+
+    @staticmethod
     def forward(ctx, logits, target, ignore_index, thresh_loss, numel_frac):
-        _check_device(logits)
-        logits = logits.contiguous()
+        logits, target = _check_logits_target(logits, target)
         B, C, H, W = logits.shape
-        if (H * W) % 8:
-            raise NotImplementedError('HIP path: H*W must be a multiple of 8')
-        if target.dtype != torch.int64 or target.shape != (B, H, W):
-            raise RuntimeError('target must be int64 of shape (B,H,W)')
-        target = target.contiguous()
         dev = logits.device
-        key = (dev.type, dev.index)
-        if key not in OHEMFn._ws:          # zeroed once; every call leaves it zeroed
-            OHEMFn._ws[key] = torch.zeros(N.lib().tss_ohem_workspace_bytes(), dtype=torch.uint8, device=dev)
         lse = torch.empty((B, H, W), dtype=torch.float32, device=dev)
         pix = torch.empty((B, H, W), dtype=torch.float32, device=dev)
         out = torch.empty(5, dtype=torch.float32, device=dev)              # loss, then the 4 selection parameters
         n_top = int(B * H * W * float(numel_frac))
-        call('tss_ohem_fwd', ptr(logits), ptr(target), ptr(lse), ptr(pix), ptr(OHEMFn._ws[key]), ptr(out[0:1]),
+        call('tss_ohem_fwd', ptr(logits), ptr(target), ptr(lse), ptr(pix), ptr(OHEMFn.workspace(dev)), ptr(out[0:1]),
              ptr(out[1:5]), B, C, H * W, int(ignore_index), float(thresh_loss), n_top, N.dtype_code(logits.dtype),
              stream())
         ctx.ignore_index = int(ignore_index)
@@ -3037,16 +3040,10 @@ class LovaszSoftmaxFn(Function):
 
     @staticmethod
     def forward(ctx, logits, target, ignore_index, variant):
-        _check_device(logits)
-        logits = logits.contiguous()
+        logits, target = _check_logits_target(logits, target)
         B, C, H, W = logits.shape
-        if (H * W) % 8:
-            raise NotImplementedError('HIP path: H*W must be a multiple of 8')
         if B * H * W >= 2 ** 31:
             raise NotImplementedError('HIP path: lovasz_softmax_loss needs B*H*W < 2**31')
-        if target.dtype != torch.int64 or target.shape != (B, H, W):
-            raise RuntimeError('target must be int64 of shape (B,H,W)')
-        target = target.contiguous()
         dev = logits.device
         code = N.dtype_code(logits.dtype)
         # g_rank per class and pixel (read by backward) + the bounded sort buffers; the caching allocator returns
@@ -3162,14 +3159,11 @@ class UpsampleOHEMFn(Function):
         B, C, h, w = low.shape
         dev = low.device
         target = target.contiguous()
-        key = (dev.type, dev.index)
-        if key not in OHEMFn._ws:          # zeroed once; every call leaves it zeroed
-            OHEMFn._ws[key] = torch.zeros(N.lib().tss_ohem_workspace_bytes(), dtype=torch.uint8, device=dev)
         pix = torch.empty((B, ho, wo), dtype=torch.float32, device=dev)
         out = torch.empty(8, dtype=torch.float32, device=dev)              # loss, 3 pad, the 4 selection parameters (16 B aligned)
         code = N.dtype_code(low.dtype)
         call('tss_upsample_pixel_ce', ptr(low), ld(low), ptr(target), ptr(pix), B, C, h, w, ho, wo, int(ignore_index), code, stream())
-        call('tss_ohem_select', ptr(pix), ptr(OHEMFn._ws[key]), ptr(out[0:1]), ptr(out[4:8]), B * ho * wo, float(thresh_loss),
+        call('tss_ohem_select', ptr(pix), ptr(OHEMFn.workspace(dev)), ptr(out[0:1]), ptr(out[4:8]), B * ho * wo, float(thresh_loss),
              int(B * ho * wo * float(numel_frac)), stream())
         ctx.geom = (B, C, h, w, ho, wo, ld(low), low.dtype, int(ignore_index))
         ctx.save_for_backward(low, target, pix, out)
@@ -3194,10 +3188,7 @@ _UNIT = {}
 
 
 def _unit(dev):
-    key = (dev.type, dev.index)
-    if key not in _UNIT:
-        _UNIT[key] = torch.ones(1, dtype=torch.float32, device=dev)
-    return _UNIT[key]
+    return _per_device(_UNIT, dev, lambda: torch.ones(1, dtype=torch.float32, device=dev))
 
 
 def upsample_ohem_loss(low, target, scale_factor=None, size=None, ignore_index=-100, thresh_loss=0.35667494393873245,
