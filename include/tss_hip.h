@@ -648,6 +648,30 @@ int tss_lovasz_fwd(const void* logits, const long long* target, void* workspace,
                    void* stream);
 int tss_lovasz_bwd(const void* logits, const long long* target, const void* workspace, const float* n_present,
                    const float* grad_out, void* dlogits, long B, int C, long HW, int chunk_classes, int dtype, void* stream);
+/* Focal loss (TSS/losses/focal_loss.py:8-15) and soft Dice loss (TSS/losses/dice_loss.py:8-26) on NCHW-planar logits,
+ * HW % 8 == 0.  A pixel counts iff target != ignore_index (has_ignore = 0: no ignore index) and 0 <= target < C.
+ * Neither uses atomics: every block writes its partial sums into a row of its own in `workspace` (tss_*_workspace_bytes
+ * bytes, 16-byte aligned, NOT initialised by the caller) and a one-block kernel adds the rows in a fixed order, so two
+ * runs give the same bits.  max_blocks caps the grid, 0 = the default; the calls of one loss take the same value.
+ * No valid pixel: *loss = 0 and a zero gradient.
+ * focal: per valid pixel p = softmax_t, q = sum of the other classes' probabilities (summed, not 1 - p),
+ *   w = exp(q^gamma) (variant 0, what the reference computes) or q^gamma (variant 1, Lin et al. 2017), gamma >= 0;
+ *   *loss = -alpha * sum w log p / #valid, *scale = alpha / #valid.  The forward saves the per-pixel lse and the per-pixel
+ *   gradient coefficient (`pixel_coef`, [B][HW] f32 each); the backward is one sweep over the planes.
+ * dice: loss = mean over all C classes of 1 - (2 I_c + smooth) / (U_c + smooth), I_c = sum p_c [t == c],
+ *   U_c = sum p_c + sum [t == c] over the valid pixels; 1 <= C <= 256, smooth >= 0.  The forward leaves the 2C backward
+ *   coefficients at the head of the workspace, which the backward reads. */
+long tss_focal_workspace_bytes(long B, long HW, int max_blocks);
+int tss_focal_fwd(const void* logits, const long long* target, float* lse, float* pixel_coef, void* workspace, float* loss,
+                  float* scale, long B, int C, long HW, int ignore_index, int has_ignore, float alpha, float gamma, int variant,
+                  int max_blocks, int dtype, void* stream);
+int tss_focal_bwd(const void* logits, const long long* target, const float* lse, const float* pixel_coef, const float* scale,
+                  const float* grad_out, void* dlogits, long B, int C, long HW, int max_blocks, int dtype, void* stream);
+long tss_dice_workspace_bytes(long B, int C, long HW, int max_blocks);
+int tss_dice_fwd(const void* logits, const long long* target, float* lse, void* workspace, float* loss, long B, int C, long HW,
+                 int ignore_index, int has_ignore, float smooth, int max_blocks, int dtype, void* stream);
+int tss_dice_bwd(const void* logits, const long long* target, const float* lse, const void* workspace, const float* grad_out,
+                 void* dlogits, long B, int C, long HW, int ignore_index, int has_ignore, int max_blocks, int dtype, void* stream);
 /* Fused decoder head + loss: cross-entropy (mean over the non-ignored pixels) of the bilinearly upsampled logits,
  * straight from the low-res NHWC logits (replaces F.interpolate TSS/models/fastscnn.py:63-64 + the loss call
  * TSS/engine.py:30 as one operator; the full-resolution logits and their gradient are never materialised).

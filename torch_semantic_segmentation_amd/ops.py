@@ -3102,6 +3102,142 @@ class LovaszSoftmaxLoss(torch.nn.Module):
         return lovasz_softmax_loss(input, target, self.num_classes, self.ignore_index, self.variant)
 
 
+FOCAL_VARIANTS = {'reference': 0, 'lin': 1}
+softloss_max_blocks = 0      # block cap of the focal / Dice kernels; 0: their default (csrc/softloss.hip)
+
+
+class FocalFn(Function):
+    """focal_loss (TSS/losses/focal_loss.py:8-15) on csrc/softloss.hip: one sweep over the class planes per direction, per-block
+    partial rows and a fixed-order finalize (no atomics, no host read-back): graph-capturable and bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, logits, target, alpha, gamma, ignore_index, variant):
+        logits, target = _check_logits_target(logits, target)
+        B, C, H, W = logits.shape
+        dev = logits.device
+        cap = int(softloss_max_blocks)
+        lse = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        coef = torch.empty((B, H, W), dtype=torch.float32, device=dev)     # per-pixel gradient coefficient, 0 outside the valid set
+        ws = torch.empty(N.lib().tss_focal_workspace_bytes(B, H * W, cap), dtype=torch.uint8, device=dev)
+        out = torch.empty(2, dtype=torch.float32, device=dev)              # loss, alpha / number of valid pixels
+        has_ignore = ignore_index is not None
+        call('tss_focal_fwd', ptr(logits), ptr(target), ptr(lse), ptr(coef), ptr(ws), ptr(out[0:1]), ptr(out[1:2]), B, C, H * W,
+             int(ignore_index) if has_ignore else 0, int(has_ignore), float(alpha), float(gamma), FOCAL_VARIANTS[variant], cap,
+             N.dtype_code(logits.dtype), stream())
+        ctx.cap = cap
+        ctx.save_for_backward(logits, target, lse, coef, out)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, target, lse, coef, out = ctx.saved_tensors
+        B, C, H, W = logits.shape
+        gout = gout.to(torch.float32).contiguous()
+        d = torch.empty_like(logits)
+        call('tss_focal_bwd', ptr(logits), ptr(target), ptr(lse), ptr(coef), ptr(out[1:2]), ptr(gout), ptr(d), B, C, H * W,
+             ctx.cap, N.dtype_code(logits.dtype), stream())
+        return d, None, None, None, None, None
+
+
+def focal_loss(input, target, alpha=0.25, gamma=2.0, ignore_index=-100, variant='reference'):
+    """TSS/losses/focal_loss.py:8-15 for (B,C,H,W) logits and an int64 (B,H,W) target: -alpha * mean over the valid pixels of
+    w * log p_t, with q = 1 - p_t evaluated as the sum of the other classes' probabilities.
+
+    variant='reference' weights a pixel with w = exp(q^gamma), which is what the reference computes (torch.exp(factor) *
+    log_softmax; value and gradient are a drop-in for it); variant='lin' uses the published w = q^gamma (Lin et al. 2017).
+    A pixel is valid iff target != ignore_index and 0 <= target < C (the rule of cross_entropy here).
+
+    Two documented differences from the reference: ignore_index=None keeps every in-range pixel, where the reference
+    raises a TypeError from nll_loss; and with no valid pixel the loss is 0.0 with a zero gradient, without a host
+    read-back, where the reference returns nan."""
+    if variant not in FOCAL_VARIANTS:
+        raise ValueError("variant must be 'reference' or 'lin', got %r" % (variant,))
+    if not float(gamma) >= 0.0:
+        raise ValueError('gamma must be >= 0, got %r' % (gamma,))
+    return FocalFn.apply(input, target, alpha, gamma, ignore_index, variant)
+
+
+class FocalLoss(torch.nn.Module):
+    """Drop-in for TSS.losses.FocalLoss (TSS/losses/focal_loss.py:18-32), constructor defaults included; the default
+    ignore_index=None keeps every in-range pixel (the reference raises there).  See focal_loss."""
+
+    def __init__(self, alpha=0.25, gamma=2.0, ignore_index=None, variant='reference'):
+        super().__init__()
+        if variant not in FOCAL_VARIANTS:
+            raise ValueError("variant must be 'reference' or 'lin', got %r" % (variant,))
+        self.alpha, self.gamma, self.ignore_index, self.variant = alpha, gamma, ignore_index, variant
+
+    def forward(self, input, target):
+        return focal_loss(input, target, self.alpha, self.gamma, self.ignore_index, self.variant)
+
+
+DICE_MAX_CLASSES = 256
+
+
+class DiceFn(Function):
+    """dice_loss (TSS/losses/dice_loss.py:8-26) on csrc/softloss.hip: per-class sums in registers, per-block partial rows and a
+    fixed-order finalize that also leaves the 2C backward coefficients (no atomics, no one_hot, no boolean-mask indexing, no
+    host read-back): graph-capturable and bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, logits, target, smooth, ignore_index):
+        logits, target = _check_logits_target(logits, target)
+        B, C, H, W = logits.shape
+        if C > DICE_MAX_CLASSES:
+            raise NotImplementedError('HIP path: dice_loss supports at most %d classes, got %d' % (DICE_MAX_CLASSES, C))
+        dev = logits.device
+        cap = int(softloss_max_blocks)
+        lse = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        ws = torch.empty(N.lib().tss_dice_workspace_bytes(B, C, H * W, cap), dtype=torch.uint8, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        has_ignore = ignore_index is not None
+        ign = (int(ignore_index) if has_ignore else 0, int(has_ignore))
+        call('tss_dice_fwd', ptr(logits), ptr(target), ptr(lse), ptr(ws), ptr(loss), B, C, H * W, ign[0], ign[1], float(smooth), cap,
+             N.dtype_code(logits.dtype), stream())
+        ctx.cap, ctx.ign = cap, ign
+        ctx.save_for_backward(logits, target, lse, ws)
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, target, lse, ws = ctx.saved_tensors
+        B, C, H, W = logits.shape
+        gout = gout.to(torch.float32).contiguous()
+        d = torch.empty_like(logits)
+        call('tss_dice_bwd', ptr(logits), ptr(target), ptr(lse), ptr(ws), ptr(gout), ptr(d), B, C, H * W, ctx.ign[0], ctx.ign[1],
+             ctx.cap, N.dtype_code(logits.dtype), stream())
+        return d, None, None, None
+
+
+def dice_loss(input, target, num_classes, smooth=1.0, ignore_index=-100):
+    """The soft Dice loss TSS/losses/dice_loss.py:8-26 intends, for (B,C,H,W) logits and an int64 (B,H,W) target: over the
+    valid pixels, I_c = sum p_c [t == c], U_c = sum p_c + sum [t == c], loss = mean over all num_classes classes (an absent
+    class counts) of 1 - (2 I_c + smooth) / (U_c + smooth).
+
+    The reference itself raises on every call (the chained `&` of its mask line, :15), so there is no reference number;
+    its evident intent is built.  Reading taken of that line: `target > 0` is read as the range check `target >= 0`, so
+    a pixel is valid iff target != ignore_index and 0 <= target < num_classes, the rule of every loss here
+    (ignore_index=None: every in-range pixel).  With no valid pixel the loss is 0.0 with a zero gradient (also for
+    smooth=0), without a host read-back.  num_classes must equal the channel count, at most 256."""
+    if input.dim() != 4 or int(num_classes) != input.shape[1]:
+        raise ValueError('num_classes (%s) must equal the channel count of the (B,C,H,W) logits %s'
+                         % (num_classes, tuple(input.shape)))
+    if not float(smooth) >= 0.0:
+        raise ValueError('smooth must be >= 0, got %r' % (smooth,))
+    return DiceFn.apply(input, target, smooth, ignore_index)
+
+
+class DiceLoss(torch.nn.Module):
+    """Drop-in for TSS.losses.DiceLoss (TSS/losses/dice_loss.py:29-42), which cannot run upstream; see dice_loss."""
+
+    def __init__(self, num_classes, smooth=1.0, ignore_index=-100):
+        super().__init__()
+        self.num_classes, self.smooth, self.ignore_index = num_classes, smooth, ignore_index
+
+    def forward(self, input, target):
+        return dice_loss(input, target, self.num_classes, self.smooth, self.ignore_index)
+
+
 class UpsampleCrossEntropyFn(Function):
     """cross_entropy(F.interpolate(low, scale, bilinear, align_corners=True), target) without the full-res logits:
     one pass yields the loss and the unscaled low-res gradient (per-block tiles in a workspace, no atomics, nothing to
