@@ -672,6 +672,12 @@ int tss_dice_fwd(const void* logits, const long long* target, float* lse, void* 
                  int ignore_index, int has_ignore, float smooth, int max_blocks, int dtype, void* stream);
 int tss_dice_bwd(const void* logits, const long long* target, const float* lse, const void* workspace, const float* grad_out,
                  void* dlogits, long B, int C, long HW, int ignore_index, int has_ignore, int max_blocks, int dtype, void* stream);
+/* counts[c] += the number of labels equal to c among the n int64 labels of `target`, c in [0, C), the labels equal to
+ * ignore_index left out (has_ignore = 0: none are).  Integer arithmetic only: exact, and `counts` (int64 [C], owned and
+ * initialised by the caller) accumulates over calls.  C <= tss_label_histogram_max_classes() (per-block LDS counters). */
+int tss_label_histogram_max_classes(void);
+int tss_label_histogram(const long long* target, long long* counts, long n, int C, int ignore_index, int has_ignore, int max_blocks,
+                        void* stream);
 /* Fused decoder head + loss: cross-entropy (mean over the non-ignored pixels) of the bilinearly upsampled logits,
  * straight from the low-res NHWC logits (replaces F.interpolate TSS/models/fastscnn.py:63-64 + the loss call
  * TSS/engine.py:30 as one operator; the full-resolution logits and their gradient are never materialised).

@@ -2978,6 +2978,38 @@ class CrossEntropyLoss(torch.nn.Module):
         return cross_entropy(input, target, self.ignore_index)
 
 
+def label_histogram(target, num_classes, ignore_index=255, out=None):
+    """Number of labels per class in an int64 label tensor of any shape, on the device: int64 [num_classes].  Labels equal to
+    ignore_index (None: no ignore index) or outside [0, num_classes) are not counted.  With `out` (int64 [num_classes] on the
+    target's device) the counts are ADDED to it, so a loop over a dataset accumulates; integer arithmetic only, exact.
+    No bincount over a masked copy, no host sync."""
+    _check_device(target)
+    C = int(num_classes)
+    if target.dtype != torch.int64:
+        raise RuntimeError('target must be int64')
+    if not 0 < C <= N.lib().tss_label_histogram_max_classes():
+        raise NotImplementedError('HIP path: label_histogram supports 1..%d classes, got %d' % (N.lib().tss_label_histogram_max_classes(), C))
+    if out is None:
+        out = torch.zeros(C, dtype=torch.int64, device=target.device)
+    elif out.dtype != torch.int64 or out.shape != (C,) or out.device != target.device or not out.is_contiguous():
+        raise RuntimeError('out must be a contiguous int64 tensor of shape (%d,) on %s' % (C, target.device))
+    target = target.contiguous()
+    has_ignore = ignore_index is not None
+    call('tss_label_histogram', ptr(target), ptr(out), target.numel(), C, int(ignore_index) if has_ignore else 0, int(has_ignore), 0, stream())
+    return out
+
+
+def enet_class_weights(counts_or_freq, c=1.02):
+    """The ENet / ERFNet class balancing 1 / log(c + frequency) (Paszke et al. 2016), the recipe of
+    scripts/contextnet/train_contextnet.py:123-124: float32 weights on the input's device.  An integer tensor is taken as
+    counts (label_histogram's output) and normalized to frequencies first; a floating one is taken as frequencies."""
+    freq = counts_or_freq
+    if not freq.is_floating_point():
+        freq = freq.to(torch.float64)
+        freq = freq / freq.sum()
+    return (1.0 / torch.log(c + freq)).to(torch.float32)
+
+
 class OHEMFn(Function):
     """ohem_loss (TSS/losses/ohem_loss.py:10-21): per-pixel CE, the (n+1)-th largest found by a device-side radix select."""
     _ws = {}
