@@ -716,6 +716,21 @@ int tss_argmax_confusion(const void* logits, const long long* target, unsigned c
  *           buffers the step reads.  mean3 / std3 are HOST arrays of C floats (NULL: 0 / 1); either tensor may be NULL. */
 int tss_decode_batch_u8(const unsigned char* image, int image_is_hwc, const float* mean3, const float* std3, float* image_out,
                         const unsigned char* target, long long* target_out, long B, int C, long HW, void* stream);
+/* The train augmentation of the same recipe on the device (albumentations RandomScale -> RandomCrop -> HorizontalFlip ->
+ * Normalize -> ToTensor, scripts/train_fastscnn.py:62-68): the loader ships the full uint8 frame [B][H][W][C] (or [B][C][H][W])
+ * and the uint8 label map [B][H][W]; one gather kernel writes image_out [B][C][crop_h][crop_w] (f32) and target_out
+ * [B][crop_h][crop_w] (int64).  params: DEVICE int32 [B][6] rows (Hs, Ws, oy, ox, flip, 0) = scaled size, crop origin inside
+ * the scaled image, flip flag -- read by the kernel, so one captured graph serves every draw; the rows are NOT validated
+ * (the caller guarantees crop_h <= Hs <= 8192, crop_w <= Ws <= 8192, 0 <= oy <= Hs - crop_h, 0 <= ox <= Ws - crop_w; the
+ * source reads of a bad row are clamped into the sample, the result is then unspecified).  Output pixel (y, x) takes
+ * scaled-image pixel Y = oy + y, X = ox + (flip ? crop_w-1-x : x).  Image: bilinear, half-pixel centres, clamped edges
+ * (cv2.INTER_LINEAR / F.interpolate(align_corners=False)) with integer coordinates, n = (2X+1) W - Ws, x0 = floor(n / 2Ws),
+ * weight (n - x0 2Ws) / 2Ws; the four texels are blended in f32 and not re-quantised to uint8 (cv2 is: <= half a grey level
+ * apart), then normalized as above.  Labels: nearest as cv2.INTER_NEAREST, xs = min(floor(X W / Ws), W-1), exact, 255 kept.
+ * crop_w % 8 == 0, 1 <= C <= 3, H, W, crop_h, crop_w <= 8192, outputs 16-byte aligned; either tensor may be NULL. */
+int tss_augment_batch_u8(const unsigned char* image, int image_is_hwc, const float* mean3, const float* std3, float* image_out,
+                         const unsigned char* target, long long* target_out, const int* params /* device, [B][6] */,
+                         long B, int C, int H, int W, int crop_h, int crop_w, void* stream);
 
 #ifdef __cplusplus
 }

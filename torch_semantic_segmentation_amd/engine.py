@@ -421,6 +421,12 @@ class HostBatchPipeline:
     wire = 'u8' : uint8 image (CHW, or HWC as decoded: image_hwc=True) + uint8 target (67 MB); `mean` / `std` are the
            albumentations.Normalize constants (scripts/train_fastscnn.py:62-68), applied on the device by tss_decode_batch_u8
            at the top of the (captured) step.
+    augment = ops.TrainAugment(...) (wire 'u8' only), with source_size = (H, W): the loader ships the FULL uint8 frame and label
+           map, undecorated; put() draws one (scale, crop origin, flip) row per sample on the host (`generator`: a
+           torch.Generator for reproducible draws) and copies the rows with the batch, and tss_augment_batch_u8 writes the
+           normalized float32 crop and the int64 target crop at the top of the (captured) step.  example_x / example_y keep the
+           CROP shape (what the step reads); mean / std default to the augmentation's.  The rows live in device memory, so one
+           captured graph serves every draw.
 
         pipe = HostBatchPipeline(trainer, example_x_f32, example_y_i64, wire='u8', mean=..., std=...)
         pipe.put(x0, y0)
@@ -429,9 +435,15 @@ class HostBatchPipeline:
             loss = pipe.step()             # waits for the oldest staged batch only, runs the step on it
     """
 
-    def __init__(self, trainer, example_x, example_y, wire='f32', mean=None, std=None, image_hwc=False, depth=2, device=None):
+    def __init__(self, trainer, example_x, example_y, wire='f32', mean=None, std=None, image_hwc=False, depth=2, device=None,
+                 augment=None, source_size=None, generator=None):
         if wire not in ('f32', 'u8'):
             raise ValueError("wire must be 'f32' or 'u8'")
+        if augment is not None and wire != 'u8':
+            raise ValueError("augment needs wire='u8': the device augmentation reads the uint8 frame")
+        if augment is not None and source_size is None:
+            raise ValueError('augment needs source_size=(H, W), the size of the frames the loader ships')
+        self.augment, self.generator, self.params = augment, generator, []
         self.trainer, self.wire, self.image_hwc, self.depth = trainer, wire, bool(image_hwc), int(depth)
         dev = device if device is not None else (trainer.device if trainer.device is not None else torch.device('cuda', torch.cuda.current_device()))
         self.device = torch.device(dev)
@@ -441,8 +453,18 @@ class HostBatchPipeline:
                        torch.empty((B, H, W), dtype=torch.int64, device=self.device))
         if wire == 'u8':
             import ctypes
-            xs = (B, H, W, C) if image_hwc else (B, C, H, W)
-            self.stage = [(torch.empty(xs, dtype=torch.uint8, device=self.device), torch.empty((B, H, W), dtype=torch.uint8, device=self.device))
+            SH, SW = H, W                    # size of the staged frame: the step's own, or the source of the augmentation
+            if augment is not None:
+                SH, SW = int(source_size[0]), int(source_size[1])
+                if tuple(augment.crop_size) != (H, W):
+                    raise ValueError('augment.crop_size %s differs from the example batch %s' % (tuple(augment.crop_size), (H, W)))
+                augment.check_source((SH, SW))
+                mean = augment.mean if mean is None else mean
+                std = augment.std if std is None else std
+                self.source_size = (SH, SW)
+                self.params = [torch.zeros((B, 6), dtype=torch.int32, device=self.device) for _ in range(depth)]
+            xs = (B, SH, SW, C) if image_hwc else (B, C, SH, SW)
+            self.stage = [(torch.empty(xs, dtype=torch.uint8, device=self.device), torch.empty((B, SH, SW), dtype=torch.uint8, device=self.device))
                           for _ in range(depth)]
             self._mean = (ctypes.c_float * 3)(*([float(v) for v in mean] + [0.0] * 3)[:3]) if mean is not None else None
             self._std = (ctypes.c_float * 3)(*([float(v) for v in std] + [1.0] * 3)[:3]) if std is not None else None
@@ -471,11 +493,16 @@ class HostBatchPipeline:
             x = x.pin_memory()
         if not y.is_cuda and not y.is_pinned():
             y = y.pin_memory()
-        self._keep[slot] = (x, y)
+        rows = None
+        if self.augment is not None:         # this batch's (scale, crop origin, flip) rows travel with it
+            rows = self.augment.draw(self.geom[0], self.source_size, generator=self.generator).pin_memory()
+        self._keep[slot] = (x, y, rows)
         with torch.cuda.stream(self.copy_stream):
             self.copy_stream.wait_event(self.consumed[slot])      # the step that read this slot last has finished with it
             sx.copy_(x, non_blocking=True)
             sy.copy_(y, non_blocking=True)
+            if rows is not None:
+                self.params[slot].copy_(rows, non_blocking=True)
             self.ready[slot].record(self.copy_stream)
         self._count += 1
 
@@ -487,11 +514,17 @@ class HostBatchPipeline:
         for s in self.slots:
             self.trainer.release_slot(s)
         self.slots, self.stage, self.decoded, self._keep, self._count = [], [], None, [], 0
+        self.params = []
 
     def _decode(self, slot):
         sx, sy = self.stage[slot]
         dx, dy = self.decoded
         B, C, H, W = self.geom
+        if self.augment is not None:
+            SH, SW = self.source_size
+            N.call('tss_augment_batch_u8', N.ptr(sx), int(self.image_hwc), self._mean, self._std, N.ptr(dx), N.ptr(sy), N.ptr(dy),
+                   N.ptr(self.params[slot]), B, C, SH, SW, H, W, N.stream())
+            return
         N.call('tss_decode_batch_u8', N.ptr(sx), int(self.image_hwc), self._mean, self._std, N.ptr(dx), N.ptr(sy), N.ptr(dy),
                B, C, H * W, N.stream())
 

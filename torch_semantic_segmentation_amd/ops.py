@@ -14,6 +14,7 @@ There is no torch/ATen fallback here: every operator calls the C ABI and raises 
 """
 import collections
 import ctypes
+import math
 import os
 import threading
 
@@ -3008,6 +3009,158 @@ def enet_class_weights(counts_or_freq, c=1.02):
         freq = freq.to(torch.float64)
         freq = freq / freq.sum()
     return (1.0 / torch.log(c + freq)).to(torch.float32)
+
+
+AUGMENT_MAX_SIZE = 8192      # source and scaled sizes for which every index of tss_augment_batch_u8 fits in int32
+
+
+def _float3(values, fill):
+    """HOST array of 3 floats for the mean3 / std3 arguments of the wire-format entries (None -> NULL)."""
+    if values is None:
+        return None
+    return (ctypes.c_float * 3)(*([float(v) for v in values] + [fill] * 3)[:3])
+
+
+def _pair(v):
+    return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+def check_augment_params(params, source_size, crop_size):
+    """Raise ValueError unless every (Hs, Ws, oy, ox, flip, 0) row of the CPU tensor `params` keeps its crop inside its scaled
+    image: crop <= scaled size <= 8192 and 0 <= origin <= scaled size - crop.  The kernel does not validate the rows."""
+    (H, W), (ch, cw) = _pair(source_size), _pair(crop_size)
+    if params.dtype != torch.int32 or params.dim() != 2 or params.shape[1] != 6:
+        raise ValueError('augmentation parameters must be int32 [B, 6], got %s %s' % (params.dtype, tuple(params.shape)))
+    Hs, Ws, oy, ox, flip, _ = params.long().unbind(1)
+    ok = ((Hs >= ch) & (Hs <= AUGMENT_MAX_SIZE) & (Ws >= cw) & (Ws <= AUGMENT_MAX_SIZE) & (oy >= 0) & (oy <= Hs - ch)
+          & (ox >= 0) & (ox <= Ws - cw) & ((flip == 0) | (flip == 1)))
+    if not bool(ok.all()):
+        raise ValueError('augmentation parameter row %d = %s does not keep a %dx%d crop inside its scaled image'
+                         % (int((~ok).nonzero()[0]), params[int((~ok).nonzero()[0])].tolist(), ch, cw))
+
+
+class TrainAugment:
+    """The reference's train-time augmentation (scripts/train_fastscnn.py:62-68), drawn on the host and applied on the device:
+
+        albu.RandomScale -> albu.RandomCrop(crop_size) -> albu.HorizontalFlip(p=flip_p) -> albu.Normalize(mean, std) -> ToTensor()
+
+    crop_size = (height, width), width a multiple of 8.  `scale_range` is the range of the MULTIPLICATIVE factor itself
+    (albumentations versions differ on whether a `scale_limit` tuple gets 1 added: pass the factors you mean, (0.5, 2.0) for
+    the recipe).  `mean` / `std` are the Normalize constants (None: 0 / 1, i.e. x / 255).
+
+    draw() produces one int32 row (Hs, Ws, oy, ox, flip, 0) per sample on the CPU: s uniform in scale_range,
+    Hs = max(crop height, floor(H s + 0.5)), Ws likewise, the crop origin uniform over the positions that keep the crop inside
+    the scaled image, flip Bernoulli(flip_p).  augment_batch / tss_augment_batch_u8 apply the rows: bilinear (half-pixel centres,
+    clamped edges, as cv2.INTER_LINEAR) for the image, nearest (as cv2.INTER_NEAREST) for the labels.  The image is blended in
+    float32 from the four uint8 texels and NOT rounded back to uint8 before Normalize as cv2 does: at most half a grey level
+    away from the reference's pixel, on purpose (one rounding fewer, and no quantisation noise added to the input).
+
+    The reference's RandomCrop raises when the scaled image is smaller than the crop; check_source() / draw() (and
+    engine.HostBatchPipeline at construction) raise ValueError when scale_range[0] makes that possible for the source size."""
+
+    def __init__(self, crop_size, scale_range=(0.5, 2.0), flip_p=0.5, mean=None, std=None):
+        self.crop_size = _pair(crop_size)
+        self.scale_range = (float(scale_range[0]), float(scale_range[1]))
+        self.flip_p = float(flip_p)
+        self.mean = None if mean is None else tuple(float(v) for v in mean)
+        self.std = None if std is None else tuple(float(v) for v in std)
+        ch, cw = self.crop_size
+        if ch < 1 or cw < 8 or cw % 8 or max(ch, cw) > AUGMENT_MAX_SIZE:
+            raise ValueError('crop_size must be (height >= 1, width a multiple of 8), at most %d: got %s' % (AUGMENT_MAX_SIZE, (ch, cw)))
+        if not 0.0 < self.scale_range[0] <= self.scale_range[1]:
+            raise ValueError('scale_range must be 0 < low <= high, got %s' % (self.scale_range,))
+        if not 0.0 <= self.flip_p <= 1.0:
+            raise ValueError('flip_p must be a probability, got %r' % flip_p)
+
+    @staticmethod
+    def _scaled(n, s):
+        return int(math.floor(n * s + 0.5))
+
+    def check_source(self, source_size):
+        """ValueError when some scale of the range gives a scaled image smaller than the crop or larger than 8192."""
+        H, W = _pair(source_size)
+        ch, cw = self.crop_size
+        lo, hi = self.scale_range
+        if not (1 <= H <= AUGMENT_MAX_SIZE and 1 <= W <= AUGMENT_MAX_SIZE):
+            raise ValueError('source size %s outside 1..%d' % ((H, W), AUGMENT_MAX_SIZE))
+        if self._scaled(H, lo) < ch or self._scaled(W, lo) < cw:
+            raise ValueError('scale_range[0] = %g shrinks a %dx%d source to %dx%d, smaller than the %dx%d crop (RandomCrop would raise)'
+                             % (lo, H, W, self._scaled(H, lo), self._scaled(W, lo), ch, cw))
+        if self._scaled(H, hi) > AUGMENT_MAX_SIZE or self._scaled(W, hi) > AUGMENT_MAX_SIZE:
+            raise ValueError('scale_range[1] = %g grows a %dx%d source past %d' % (hi, H, W, AUGMENT_MAX_SIZE))
+
+    def draw(self, B, source_size, generator=None):
+        """int32 [B, 6] rows (Hs, Ws, oy, ox, flip, 0) on the CPU; deterministic for a given torch.Generator state."""
+        self.check_source(source_size)
+        H, W = _pair(source_size)
+        ch, cw = self.crop_size
+        lo, hi = self.scale_range
+        u = torch.rand((int(B), 4), generator=generator, dtype=torch.float64)
+        s = lo + (hi - lo) * u[:, 0]
+        Hs = torch.floor(H * s + 0.5).long().clamp_(min=ch)
+        Ws = torch.floor(W * s + 0.5).long().clamp_(min=cw)
+        oy = torch.minimum(torch.floor(u[:, 1] * (Hs - ch + 1)).long(), Hs - ch)      # uniform integers in [0, Hs - ch]
+        ox = torch.minimum(torch.floor(u[:, 2] * (Ws - cw + 1)).long(), Ws - cw)
+        flip = (u[:, 3] < self.flip_p).long()
+        rows = torch.stack([Hs, Ws, oy, ox, flip, torch.zeros_like(flip)], 1).to(torch.int32)
+        check_augment_params(rows, (H, W), (ch, cw))
+        return rows
+
+
+def augment_batch(image_u8, target_u8, params, crop_size, mean=None, std=None, image_hwc=False, out=None):
+    """Scale + crop + flip + Normalize + ToTensor of a uint8 batch on the device (tss_augment_batch_u8; semantics: TrainAugment).
+
+    image_u8 [B, H, W, C] (image_hwc=True) or [B, C, H, W], C <= 3; target_u8 [B, H, W]; either may be None.  params: int32
+    [B, 6] rows (Hs, Ws, oy, ox, flip, 0) as TrainAugment.draw returns them -- a CPU tensor is validated and copied to the
+    device, a device tensor is used as it is (not validated: no host sync).  Returns (float32 [B, C, ch, cw], int64 [B, ch, cw]);
+    with out=(image_out, target_out) the results are written there."""
+    first = image_u8 if image_u8 is not None else target_u8
+    if first is None:
+        raise ValueError('augment_batch needs an image or a target')
+    _check_device(first)
+    ch, cw = _pair(crop_size)
+    dev = first.device
+    B = first.shape[0]
+    C, size = 1, None
+    if image_u8 is not None:
+        if image_u8.dtype != torch.uint8 or image_u8.dim() != 4 or not image_u8.is_contiguous():
+            raise ValueError('image must be a contiguous uint8 [B, H, W, C] or [B, C, H, W] tensor')
+        (H, W, C) = image_u8.shape[1:] if image_hwc else (image_u8.shape[2], image_u8.shape[3], image_u8.shape[1])
+        size = (H, W)
+    if target_u8 is not None:
+        _check_device(target_u8)
+        if target_u8.dtype != torch.uint8 or target_u8.dim() != 3 or not target_u8.is_contiguous() or target_u8.shape[0] != B:
+            raise ValueError('target must be a contiguous uint8 [B, H, W] tensor')
+        if size is not None and tuple(target_u8.shape[1:]) != size:
+            raise ValueError('image is %dx%d but target is %s' % (size[0], size[1], tuple(target_u8.shape[1:])))
+        size = tuple(target_u8.shape[1:])
+    H, W = size
+    if not 1 <= C <= 3:
+        raise ValueError('HIP path: augment_batch supports 1..3 channels, got %d' % C)
+    if cw % 8 or cw < 8 or ch < 1 or max(H, W, ch, cw) > AUGMENT_MAX_SIZE:
+        raise ValueError('crop width must be a multiple of 8 and every size at most %d: source %dx%d, crop %dx%d'
+                         % (AUGMENT_MAX_SIZE, H, W, ch, cw))
+    if tuple(params.shape) != (B, 6) or params.dtype != torch.int32:
+        raise ValueError('params must be int32 [%d, 6], got %s %s' % (B, params.dtype, tuple(params.shape)))
+    if not params.is_cuda:
+        check_augment_params(params, (H, W), (ch, cw))
+        params = params.to(dev)
+    params = params.contiguous()
+    ox, oy = out if out is not None else (None, None)
+    if image_u8 is not None:
+        if ox is None:
+            ox = torch.empty((B, C, ch, cw), dtype=torch.float32, device=dev)
+        elif ox.dtype != torch.float32 or tuple(ox.shape) != (B, C, ch, cw) or not ox.is_contiguous() or ox.device != dev or ox.data_ptr() % 16:
+            raise ValueError('out[0] must be a contiguous, 16-byte aligned float32 %s tensor on %s' % ((B, C, ch, cw), dev))
+    if target_u8 is not None:
+        if oy is None:
+            oy = torch.empty((B, ch, cw), dtype=torch.int64, device=dev)
+        elif oy.dtype != torch.int64 or tuple(oy.shape) != (B, ch, cw) or not oy.is_contiguous() or oy.device != dev or oy.data_ptr() % 16:
+            raise ValueError('out[1] must be a contiguous, 16-byte aligned int64 %s tensor on %s' % ((B, ch, cw), dev))
+    call('tss_augment_batch_u8', ptr(image_u8), int(bool(image_hwc)), _float3(mean, 0.0), _float3(std, 1.0),
+         ptr(ox) if image_u8 is not None else None, ptr(target_u8), ptr(oy) if target_u8 is not None else None, ptr(params),
+         B, C, H, W, ch, cw, stream())
+    return (ox if image_u8 is not None else None), (oy if target_u8 is not None else None)
 
 
 class OHEMFn(Function):
