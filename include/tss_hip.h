@@ -61,6 +61,7 @@ enum {
   TSS_K_UPSAMPLE_HEAD_FWD, TSS_K_UPSAMPLE_HEAD_BWD_ROWS, TSS_K_UPSAMPLE_HEAD_BWD_COLS,
   TSS_K_POOL_FWD, TSS_K_POOL_BWD, TSS_K_COPY,
   TSS_K_CE_FWD, TSS_K_CE_BWD, TSS_K_ARGMAX, TSS_K_UPSAMPLE_CE_FWD, TSS_K_UPSAMPLE_CE_BWD,
+  TSS_K_RESIZE_FLIP_PLANAR, TSS_K_MULTISCALE_ARGMAX,
   TSS_K_COUNT
 };
 
@@ -731,6 +732,31 @@ int tss_decode_batch_u8(const unsigned char* image, int image_is_hwc, const floa
 int tss_augment_batch_u8(const unsigned char* image, int image_is_hwc, const float* mean3, const float* std3, float* image_out,
                          const unsigned char* target, long long* target_out, const int* params /* device, [B][6] */,
                          long B, int C, int H, int W, int crop_h, int crop_w, void* stream);
+
+/* ---- multi-scale + horizontal-flip evaluation (csrc/msflip.hip) --------------------------------------------------------
+ * The inference protocol of the published Cityscapes numbers: the image at several scales, each plain and mirrored, class
+ * scores summed at full resolution, arg-max of the sum.  No full-resolution float tensor is written.
+ *
+ * tss_resize_flip_planar: bilinear (align_corners=True, any ratio) resize of the f32 NCHW batch x [B][C][Hin][Win] to
+ * y [2B][C][Hout][Wout] (flip != 0) or [B][C][Hout][Wout] (flip == 0), y_dtype TSS_F32 | TSS_BF16, one launch.  Samples
+ * 0..B-1 are bit-identical to tss_bilinear_planar_fwd; y[B+b][c][yy][xx] = y[b][c][yy][Wout-1-xx] exactly. */
+int tss_resize_flip_planar(const float* x, void* y, int y_dtype, long B, int C, int Hin, int Win, int Hout, int Wout,
+                           int flip, void* stream);
+/* One low-resolution logit map of tss_multiscale_argmax_confusion: NHWC [.][h][w][ldl] of the call's dtype, of which samples
+ * first .. first+B-1 are used (the two halves of a 2B forward are two descriptors into one tensor); flip != 0: the map was
+ * computed from the mirrored image and is mirrored back after its upsample. */
+typedef struct tss_msmap { const void* low; long ldl; int h; int w; int flip; int first; } tss_msmap;
+/* maps: HOST array of K descriptors (copied into the kernel arguments: no device memory, no synchronisation).  For output pixel
+ * (b, y, x): z_k[c] = U_k[c][y][flip_k ? W-1-x : x], U_k the align_corners=True bilinear upsample of map k to H x W (f32
+ * arithmetic, the taps of tss_upsample_argmax_confusion), i.e. F.interpolate(...).flip(-1).  mode 0: score[c] = sum_k
+ * softmax_c(z_k) (max-subtracted); mode 1: score[c] = sum_k z_k[c]; maps are summed in descriptor order.  pred (uint8 [B][H][W],
+ * may be NULL) = arg-max over c < C, lowest index wins ties; confusion (u64 [C*C], rows = truth, ACCUMULATED; may be NULL, as may
+ * target int64 [B][H][W]) skips targets equal to ignore_index or outside 0..C-1.  Integer counts: bit-reproducible.
+ * Contract (else TSS_ERR_SHAPE, nothing launched): 1 <= K <= 16, 1 <= C <= 24, ldl % 8 == 0, 1 <= h_k <= H, 1 <= w_k <= W;
+ * a map pointer off 16 bytes: TSS_ERR_ALIGN; B*H*W == 0: TSS_OK without a launch. */
+int tss_multiscale_argmax_confusion(const tss_msmap* maps, int K, const long long* target, unsigned char* pred,
+                                    unsigned long long* confusion, int B, int C, int H, int W,
+                                    int ignore_index, int mode, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,7 @@ from .ops import LovaszSoftmaxFn, LovaszSoftmaxLoss, lovasz_softmax_loss  # noqa
 from .ops import FocalFn, FocalLoss, focal_loss, DiceFn, DiceLoss, dice_loss  # noqa: F401
 from .ops import label_histogram, enet_class_weights  # noqa: F401
 from .ops import TrainAugment, augment_batch  # noqa: F401
-from .engine import benchmark_model, GraphedInference  # noqa: F401
+from .ops import multiscale_argmax_confusion, resize_flip_image  # noqa: F401
+from .engine import benchmark_model, GraphedInference, MultiScaleEvaluator  # noqa: F401
 
 __version__ = '0.1.0'

@@ -107,7 +107,7 @@ def dtype_code(dtype):
 
 # ----------------------------------------------------------------------------- profiler helpers
 
-K_COUNT = 33
+K_COUNT = 35
 
 
 def prof_enable(on=True):

@@ -156,6 +156,14 @@ __device__ __forceinline__ Tap ac_tap(float scale, int dst, int in) {
   t.l0 = 1.f - t.l1;
   return t;
 }
+// One sample of a planar H x W image at the taps (ty, tx): the blend every planar resize shares, so that two kernels
+// that resize the same image agree bit for bit.
+template <typename TI>
+__device__ __forceinline__ float planar_bilinear(const TI* base, int Win, const Tap ty, const Tap tx) {
+  const float v00 = (float)base[(long)ty.i0 * Win + tx.i0], v01 = (float)base[(long)ty.i0 * Win + tx.i1];
+  const float v10 = (float)base[(long)ty.i1 * Win + tx.i0], v11 = (float)base[(long)ty.i1 * Win + tx.i1];
+  return ty.l0 * (tx.l0 * v00 + tx.l1 * v01) + ty.l1 * (tx.l0 * v10 + tx.l1 * v11);
+}
 // outputs whose taps can include source index i: a conservative window [lo, hi]
 __device__ __forceinline__ void ac_window(float scale, int i, int out, int* lo, int* hi) {
   if (scale <= 0.f) { *lo = 0; *hi = out - 1; return; }
@@ -257,3 +265,11 @@ inline int grid_for(long total, int nt, long cap = 4096) {
     else { using NAME = float; __VA_ARGS__; }        \
   } while (0)
 #define TSS_WITH_DTYPE(dtype, ...) TSS_WITH_DTYPE_AS(TT, dtype, __VA_ARGS__)
+
+// The class-register variant of the upsampled-logits kernels (loss.hip, msflip.hip): runs the statement(s) with CPV = 20
+// (up to 20 classes) or 24.
+#define TSS_WITH_CLASS_REGS(C, ...)                           \
+  do {                                                        \
+    if ((C) <= 20) { constexpr int CPV = 20; __VA_ARGS__; }   \
+    else { constexpr int CPV = 24; __VA_ARGS__; }             \
+  } while (0)

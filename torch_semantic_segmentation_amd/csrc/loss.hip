@@ -514,13 +514,6 @@ inline bool upsample_ce_shape_ok(int C, long ldl, int h, int w, int H, int W) {
 
 }  // namespace
 
-// The class-register variant of the upsampled-CE kernels: runs the statement(s) with CPV = 20 (up to 20 classes) or 24.
-#define TSS_WITH_CLASS_REGS(C, ...)                           \
-  do {                                                        \
-    if ((C) <= 20) { constexpr int CPV = 20; __VA_ARGS__; }   \
-    else { constexpr int CPV = 24; __VA_ARGS__; }             \
-  } while (0)
-
 extern "C" {
 
 int tss_cross_entropy_fwd(const void* logits, const long long* target, float* lse, double* acc /*[2], zeroed*/,
@@ -690,5 +683,3 @@ int tss_upsample_ce_bwd(const float* ws, const float* inv_count, const float* gr
 }
 
 }  // extern "C"
-
-#undef TSS_WITH_CLASS_REGS

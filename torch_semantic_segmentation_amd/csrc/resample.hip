@@ -129,10 +129,7 @@ __global__ __launch_bounds__(NT) void bilinear_planar_fwd_kernel(const TI* x, TO
     const int oy = (int)(p % Hout);
     const long pl = p / Hout;
     const Tap ty = ac_tap(sy, oy, Hin), tx = ac_tap(sx, ox, Win);
-    const TI* base = x + pl * Hin * (long)Win;
-    const float v00 = (float)base[(long)ty.i0 * Win + tx.i0], v01 = (float)base[(long)ty.i0 * Win + tx.i1];
-    const float v10 = (float)base[(long)ty.i1 * Win + tx.i0], v11 = (float)base[(long)ty.i1 * Win + tx.i1];
-    y[i] = (TO)(ty.l0 * (tx.l0 * v00 + tx.l1 * v01) + ty.l1 * (tx.l0 * v10 + tx.l1 * v11));
+    y[i] = (TO)planar_bilinear(x + pl * Hin * (long)Win, Win, ty, tx);
   }
 }
 

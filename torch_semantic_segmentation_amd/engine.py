@@ -646,8 +646,92 @@ def confusion_metrics(cm):
             'dice': 2 * tp / (cm.sum(0) + cm.sum(1) + 1e-15)}
 
 
-def create_segmentation_evaluator(model, device, num_classes=19, loss_fn=None, non_blocking=True):
-    return Evaluator(model, device, num_classes=num_classes, loss_fn=loss_fn, non_blocking=non_blocking)
+class MultiScaleEvaluator:
+    """Multi-scale + horizontal-flip evaluation, the protocol of the published Cityscapes numbers: per batch, the image is resized to
+    every scale (sides rounded to a multiple of `size_multiple`), each scale runs once through `model.forward_lowres` as a 2B batch of
+    the plain and the mirrored image (ops.resize_flip_image), and ONE ops.multiscale_argmax_confusion call upsamples the maps to
+    the target's size, mirrors the flipped ones back, sums the per-map softmax (average='softmax') or logits ('logits') and updates
+    the confusion matrix.  No full-resolution logits, no ATen arithmetic, no host synchronisation inside a batch.
+    Same run(data) and metric dict as Evaluator; predict(x) returns the uint8 label map."""
+
+    def __init__(self, model, device=None, num_classes=19, scales=(0.5, 0.75, 1.0, 1.25, 1.5, 1.75), flip=True, size_multiple=32,
+                 average='softmax', ignore_index=255, non_blocking=True):
+        if not (hasattr(model, 'forward_lowres') and hasattr(model, 'logit_scale')):
+            raise NotImplementedError('MultiScaleEvaluator needs a model with forward_lowres() and logit_scale (the low-resolution '
+                                      'logits of the decoder head); %s has none' % type(model).__name__)
+        scales = tuple(float(s) for s in scales)
+        if not scales or min(scales) <= 0:
+            raise ValueError('scales must be a non-empty sequence of positive factors, got %r' % (scales,))
+        if len(scales) * (2 if flip else 1) > ops.MULTISCALE_MAX_MAPS:
+            raise ValueError('%d scales%s are more than the %d maps one fused call takes'
+                             % (len(scales), ' with flip' if flip else '', ops.MULTISCALE_MAX_MAPS))
+        if average not in ('softmax', 'logits'):
+            raise ValueError("average must be 'softmax' or 'logits', got %r" % (average,))
+        self.model, self.device, self.num_classes = model, device, num_classes
+        self.scales, self.flip, self.size_multiple = scales, bool(flip), int(size_multiple)
+        self.average, self.ignore_index, self.non_blocking = average, ignore_index, non_blocking
+        self._prep = None
+        self.confusion = None      # the int64 [C, C] matrix of the last run(), on the device
+
+    def scaled_size(self, H, W, s):
+        m = self.size_multiple
+        return max(m, int(round(H * s / m)) * m), max(m, int(round(W * s / m)) * m)
+
+    @torch.no_grad()
+    def lowres_maps(self, x):
+        """(lows, flips) as ops.multiscale_argmax_confusion takes them: the low-resolution logits of the device batch x at every
+        scale (a 2B batch each with flip), under the shared EvalPrep."""
+        H, W = x.shape[-2:]
+        if self._prep is None:
+            self._prep = EvalPrep(self.model)
+        lows = []
+        with self._prep:
+            for s in self.scales:
+                xs = ops.resize_flip_image(x, self.scaled_size(H, W, s), flip=self.flip)   # float32, as Evaluator feeds the image
+                low = self.model.forward_lowres(xs)
+                if low.shape[1] != self.num_classes:
+                    raise ValueError('the model scores %d classes, the evaluator was built for num_classes=%d'
+                                     % (low.shape[1], self.num_classes))
+                lows.append(low)
+        return lows, [(False, True) if self.flip else False] * len(lows)
+
+    @torch.no_grad()
+    def predict(self, x):
+        self.model.eval()
+        if self.device is not None:
+            x = x.to(self.device, non_blocking=self.non_blocking)
+        lows, flips = self.lowres_maps(x)
+        pred, _ = ops.multiscale_argmax_confusion(lows, flips, size=tuple(x.shape[-2:]), ignore_index=self.ignore_index,
+                                                  average=self.average)
+        return pred
+
+    @torch.no_grad()
+    def run(self, data):
+        self.model.eval()
+        cm = None
+        for x, y in data:
+            if self.device is not None:
+                x = x.to(self.device, non_blocking=self.non_blocking)
+                y = y.to(self.device, non_blocking=self.non_blocking)
+            lows, flips = self.lowres_maps(x)
+            _, cm = ops.multiscale_argmax_confusion(lows, flips, y, size=tuple(y.shape[-2:]), ignore_index=self.ignore_index,
+                                                    confusion=cm, want_pred=False, average=self.average)
+        if cm is None:
+            raise ValueError('MultiScaleEvaluator.run got no batches: there is nothing to score')
+        self.confusion = cm
+        return confusion_metrics(cm.cpu().double())
+
+
+def create_segmentation_evaluator(model, device, num_classes=19, loss_fn=None, non_blocking=True, scales=None, flip=False,
+                                  size_multiple=32, average='softmax', ignore_index=255):
+    """`scales` given: the multi-scale (+ `flip`) protocol (MultiScaleEvaluator, which also takes `size_multiple` and `average`; it
+    reports no loss); otherwise the single forward."""
+    if scales is not None:
+        if loss_fn is not None:
+            raise ValueError('the multi-scale evaluator has no full-resolution logits to feed a loss_fn')
+        return MultiScaleEvaluator(model, device, num_classes=num_classes, scales=scales, flip=flip, size_multiple=size_multiple,
+                                   average=average, ignore_index=ignore_index, non_blocking=non_blocking)
+    return Evaluator(model, device, num_classes=num_classes, loss_fn=loss_fn, ignore_index=ignore_index, non_blocking=non_blocking)
 
 
 # ----------------------------------------------------------------------------- deep supervision (row S)

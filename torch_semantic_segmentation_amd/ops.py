@@ -3532,6 +3532,7 @@ def upsample_argmax_confusion(low, target=None, scale_factor=None, size=None, ig
     """argmax_confusion(F.interpolate(low, scale, bilinear, align_corners=True), ...) without the full-resolution logits
     (the evaluator's decoder head + metric update as one operator).  Returns (pred uint8 or None, confusion)."""
     low = to_nhwc(materialize(low))
+    _check_device(low)
     ho, wo = _out_size(low, size, scale_factor)
     B, C, h, w = low.shape
     if C > 24 or ho < h or wo < w:
@@ -3546,6 +3547,92 @@ def upsample_argmax_confusion(low, target=None, scale_factor=None, size=None, ig
             confusion = torch.zeros((C, C), dtype=torch.int64, device=low.device)
     call('tss_upsample_argmax_confusion', ptr(low), ld(low), ptr(target.contiguous()) if target is not None else None,
          ptr(pred), ptr(confusion), B, C, h, w, ho, wo, int(ignore_index), N.dtype_code(low.dtype), stream())
+    return pred, confusion
+
+
+class _MsMap(ctypes.Structure):
+    """tss_msmap of include/tss_hip.h."""
+    _fields_ = [('low', ctypes.c_void_p), ('ldl', ctypes.c_long), ('h', ctypes.c_int), ('w', ctypes.c_int),
+                ('flip', ctypes.c_int), ('first', ctypes.c_int)]
+
+
+MULTISCALE_MAX_MAPS = 16
+_MS_AVERAGE = {'softmax': 0, 'logits': 1}
+
+
+def resize_flip_image(x, size, flip=True, out_dtype=None):
+    """The input of one scale of multi-scale + flip inference, one launch: the float32 NCHW batch x resized (bilinear,
+    align_corners=True, up or down) to `size`, followed -- with `flip` -- by its horizontal mirror as samples B..2B-1.  The first
+    half is bit-identical to resize_image(x, size, out_dtype=...), the second to its .flip(-1)."""
+    _check_device(x)
+    if x.dtype != torch.float32:
+        raise TypeError('resize_flip_image takes the float32 image, got %s' % x.dtype)
+    x = x.contiguous()
+    ho, wo = _out_size(x, size, None)
+    B, C, H, W = x.shape
+    out_dtype = out_dtype or x.dtype
+    y = torch.empty((2 * B if flip else B, C, ho, wo), dtype=out_dtype, device=x.device)
+    call('tss_resize_flip_planar', ptr(x), ptr(y), N.dtype_code(out_dtype), B, C, H, W, ho, wo, 1 if flip else 0, stream())
+    return y
+
+
+def multiscale_argmax_confusion(lows, flips, target=None, size=None, ignore_index=255, confusion=None, want_pred=True,
+                                average='softmax'):
+    """Multi-scale + flip fusion of low-resolution logit maps (tss_multiscale_argmax_confusion): every map is upsampled to `size`
+    (bilinear, align_corners=True), mirrored back where its `flips` entry says it came from the mirrored image (the flip is taken
+    AFTER the upsample: F.interpolate(...).flip(-1)), the per-map softmax (average='softmax') or the raw logits ('logits') are summed
+    in list order, and the arg-max of the sum is scored against `target`.  No full-resolution float tensor exists.
+    lows[i]: logits [B,C,h,w] with flips[i] a bool, or [2B,C,h,w] with flips[i] == (False, True): the plain and the mirrored half of
+    one forward (two maps).  At most 16 maps, C <= 24, no map larger than `size`.  Returns (pred uint8 or None, confusion)."""
+    if average not in _MS_AVERAGE:
+        raise ValueError("average must be 'softmax' or 'logits', got %r" % (average,))
+    lows, flips = list(lows), list(flips)
+    if not lows:
+        raise ValueError('multiscale_argmax_confusion needs at least one map')
+    if len(lows) != len(flips):
+        raise ValueError('%d maps but %d flips entries' % (len(lows), len(flips)))
+    lows = [materialize(low) for low in lows]
+    first = lows[0]
+    C = first.shape[1]
+    for low in lows:
+        if low.dtype != first.dtype or low.device != first.device or low.shape[1] != C:
+            raise ValueError('the maps must share dtype, device and class count: got %s %s C=%d after %s %s C=%d'
+                             % (low.dtype, low.device, low.shape[1], first.dtype, first.device, C))
+    _check_device(first)        # one device for all (above); to_nhwc passes a channels-last tensor on unchecked, wherever it lives
+    lows = [to_nhwc(low) for low in lows]
+    first = lows[0]
+    if target is not None:
+        B = target.shape[0]
+    else:
+        B = first.shape[0] // 2 if isinstance(flips[0], (tuple, list)) else first.shape[0]
+    if size is None:
+        if target is None:
+            raise ValueError('multiscale_argmax_confusion needs `size` or a target')
+        size = tuple(target.shape[-2:])
+    ho, wo = _out_size(first, size, None)
+    descs = []
+    for low, f in zip(lows, flips):
+        halves = tuple(bool(v) for v in f) if isinstance(f, (tuple, list)) else (bool(f),)
+        if low.shape[0] != len(halves) * B:
+            raise ValueError('a map of batch %d does not match flips entry %r at batch size %d' % (low.shape[0], f, B))
+        h, w = low.shape[2], low.shape[3]
+        if h > ho or w > wo:
+            raise ValueError('map %dx%d is larger than the output %dx%d (maps are upsampled, never reduced)' % (h, w, ho, wo))
+        descs += [_MsMap(low.data_ptr(), ld(low), h, w, int(fl), i * B) for i, fl in enumerate(halves)]
+    if len(descs) > MULTISCALE_MAX_MAPS:
+        raise ValueError('at most %d maps per call, got %d' % (MULTISCALE_MAX_MAPS, len(descs)))
+    if C > 24:
+        raise ValueError('at most 24 classes (the scores live in registers), got %d' % C)
+    pred = torch.empty((B, ho, wo), dtype=torch.uint8, device=first.device) if want_pred else None
+    if target is not None:
+        if target.dtype != torch.int64 or tuple(target.shape) != (B, ho, wo):
+            raise RuntimeError('target must be int64 of shape (B,H,W) = %s' % ((B, ho, wo),))
+        _check_device(target)
+        target = target.contiguous()
+        if confusion is None:
+            confusion = torch.zeros((C, C), dtype=torch.int64, device=first.device)
+    call('tss_multiscale_argmax_confusion', (_MsMap * len(descs))(*descs), len(descs), ptr(target), ptr(pred), ptr(confusion),
+         B, C, ho, wo, int(ignore_index), _MS_AVERAGE[average], N.dtype_code(first.dtype), stream())
     return pred, confusion
 
 
