@@ -732,6 +732,26 @@ int tss_decode_batch_u8(const unsigned char* image, int image_is_hwc, const floa
 int tss_augment_batch_u8(const unsigned char* image, int image_is_hwc, const float* mean3, const float* std3, float* image_out,
                          const unsigned char* target, long long* target_out, const int* params /* device, [B][6] */,
                          long B, int C, int H, int W, int crop_h, int crop_w, void* stream);
+/* The same launch with the two per-pixel steps of the other recipe (scripts/contextnet/train_contextnet.py: ... HorizontalFlip
+ * -> HueSaturationValue -> Normalize ...) and of both dataset classes (TRAIN_MAPPING[label]).  Both pointers are optional; with
+ * both NULL the results are bit-identical to tss_augment_batch_u8.
+ * color: DEVICE int32 [B][4] rows (apply, dh, ds, dv), read by the kernel like params (one captured graph serves every draw) and
+ *   NOT validated (the caller guarantees |dh| <= 180).  Needs C == 3 (else TSS_ERR_SHAPE).  A row with apply != 0 transforms the
+ *   blended float32 (r, g, b) of every output pixel of its sample, in grey levels, before the normalization: albumentations'
+ *   additive HueSaturationValue on cv2's 8-bit HSV scale, kept continuous (H, S, V and the result are NOT rounded to uint8):
+ *   V = max, D = V - min, S = 255 D / V (0 at V = 0); H in [0, 180) in units of 2 degrees: 0 at D = 0, else 30 (g-b)/D when
+ *   V == r, else 60 + 30 (b-r)/D when V == g, else 120 + 30 (r-g)/D, plus 180 when negative.  H' = H + dh wrapped once into
+ *   [0, 180), S' = clamp(S + ds, 0, 255), V' = clamp(V + dv, 0, 255).  Back with h = H'/30, i = floor(h), f = h - i,
+ *   p = V'(1 - S'/255), q = V'(1 - f S'/255), t = V'(1 - (1-f) S'/255) and the sector table (V',t,p) (q,V',p) (p,V',t) (p,q,V')
+ *   (t,p,V') (V',p,q).  IEEE float32 divisions.  A grey pixel has H = 0: ds > 0 tints it red, as in the reference.
+ * label_lut: DEVICE 256 bytes; target_out = (int64) label_lut[nearest-sampled byte].  Exact. */
+int tss_augment_batch_u8_ex(const unsigned char* image, int image_is_hwc, const float* mean3, const float* std3, float* image_out,
+                            const unsigned char* target, long long* target_out, const int* params /* device, [B][6] */,
+                            const int* color /* device, [B][4], or NULL */, const unsigned char* label_lut /* device, [256], or NULL */,
+                            long B, int C, int H, int W, int crop_h, int crop_w, void* stream);
+/* The label table alone, for the evaluation loader: out[i] = (int64) label_lut[target[i]], i < n.  target 8-byte aligned, out
+ * 16-byte aligned. */
+int tss_remap_labels_u8(const unsigned char* target, const unsigned char* label_lut, long long* out, long n, void* stream);
 
 /* ---- multi-scale + horizontal-flip evaluation (csrc/msflip.hip) --------------------------------------------------------
  * The inference protocol of the published Cityscapes numbers: the image at several scales, each plain and mirrored, class

@@ -5,6 +5,11 @@ F.interpolate (bilinear for the image, nearest for the labels) of the whole fram
 Writes one JSON file (default profiles/augment_time.json) and prints it.
 
     python tools/augment_time.py [--source 1024 2048] [--crop 512 768] [--batch 8] [--iters 20] [--rounds 5] [--out FILE]
+    python tools/augment_time.py --hsv       # the plain entry next to tss_augment_batch_u8_ex -> profiles/augment_hsv_time.json
+
+--hsv times, on the same batch and rows: the plain entry; the _ex entry with both pointers NULL (the same work through the other
+instantiation), with the label table alone, with HueSaturationValue on EVERY sample alone, and with both (the headline:
+hsv_lut_over_plain).
 
 Every candidate is warmed up, then timed with device events over `iters` calls; the candidates are visited `rounds` times in turn
 (alternating, so drift hits all of them alike); the per-round times are all reported, the median is the headline.
@@ -67,9 +72,11 @@ def main():
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--skip-stock', action='store_true')
+    ap.add_argument('--hsv', action='store_true', help='time tss_augment_batch_u8_ex (HSV on every sample + label table) next to the plain entry')
     ap.add_argument('--commit', default=None, help='recorded in the file (default: git rev-parse of the checkout, if it is one)')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'augment_time.json'))
+    ap.add_argument('--out', default=None, help='default profiles/augment_time.json, with --hsv profiles/augment_hsv_time.json')
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, 'profiles', 'augment_hsv_time.json' if a.hsv else 'augment_time.json')
     B, (H, W), (ch, cw) = a.batch, a.source, a.crop
     dev = 'cuda:0'
     g = torch.Generator().manual_seed(0)
@@ -92,8 +99,22 @@ def main():
         N.call('tss_decode_batch_u8', N.ptr(crop_u8[0]), 1, mean3, std3, N.ptr(out[0]), N.ptr(crop_u8[1]), N.ptr(out[1]),
                B, 3, ch * cw, N.stream())
 
+    color = tssa.TrainAugment((ch, cw), hsv_p=1.0).draw_color(B, generator=g)
+    lut = torch.randint(0, 20, (256,), generator=g).to(torch.uint8)
+    color_dev, lut_dev = color.to(dev), lut.to(dev)
+
+    def hip_augment_ex(color_rows, table):
+        def run():
+            N.call('tss_augment_batch_u8_ex', N.ptr(image), 1, mean3, std3, N.ptr(out[0]), N.ptr(target), N.ptr(out[1]), N.ptr(params),
+                   N.ptr(color_rows), N.ptr(table), B, 3, H, W, ch, cw, N.stream())
+        return run
+
     cands = [('hip_augment', hip_augment), ('hip_decode_same_output', hip_decode)]
-    if not a.skip_stock:
+    if a.hsv:
+        cands = [('hip_augment', hip_augment), ('hip_augment_ex_null', hip_augment_ex(None, None)),
+                 ('hip_augment_ex_lut', hip_augment_ex(None, lut_dev)), ('hip_augment_ex_hsv', hip_augment_ex(color_dev, None)),
+                 ('hip_augment_ex_hsv_lut', hip_augment_ex(color_dev, lut_dev))]
+    elif not a.skip_stock:
         cands.append(('stock_interpolate_slice_flip_normalize', lambda: stock_augment(image, target, row_list, (ch, cw), mean_t, std_t)))
     for _name, fn in cands:                                # warm-up: code objects, allocator blocks
         one_round(fn, 2)
@@ -115,9 +136,14 @@ def main():
         med = sorted(us[name])[len(us[name]) // 2]
         res[name] = {'us_rounds': us[name], 'us_median': med}
     res['hip_augment']['GBps'] = round(need / res['hip_augment']['us_median'] / 1e3, 1)
-    res['hip_decode_same_output']['GBps'] = round((out_bytes + B * ch * cw * 4) / res['hip_decode_same_output']['us_median'] / 1e3, 1)
-    res['augment_over_decode'] = round(res['hip_augment']['us_median'] / res['hip_decode_same_output']['us_median'], 2)
-    if not a.skip_stock:
+    if a.hsv:
+        res['color_rows'] = color.tolist()
+        for name, _ in cands[1:]:
+            res[name.replace('hip_augment_ex_', '') + '_over_plain'] = round(res[name]['us_median'] / res['hip_augment']['us_median'], 3)
+    else:
+        res['hip_decode_same_output']['GBps'] = round((out_bytes + B * ch * cw * 4) / res['hip_decode_same_output']['us_median'] / 1e3, 1)
+        res['augment_over_decode'] = round(res['hip_augment']['us_median'] / res['hip_decode_same_output']['us_median'], 2)
+    if not a.skip_stock and not a.hsv:
         res['stock_over_augment'] = round(res['stock_interpolate_slice_flip_normalize']['us_median'] / res['hip_augment']['us_median'], 2)
     text = json.dumps(res)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -8,7 +8,7 @@ from .ops import OHEMLoss, ohem_loss, Upsample  # noqa: F401
 from .ops import LovaszSoftmaxFn, LovaszSoftmaxLoss, lovasz_softmax_loss  # noqa: F401
 from .ops import FocalFn, FocalLoss, focal_loss, DiceFn, DiceLoss, dice_loss  # noqa: F401
 from .ops import label_histogram, enet_class_weights  # noqa: F401
-from .ops import TrainAugment, augment_batch  # noqa: F401
+from .ops import TrainAugment, augment_batch, remap_labels  # noqa: F401
 from .ops import multiscale_argmax_confusion, resize_flip_image  # noqa: F401
 from .engine import benchmark_model, GraphedInference, MultiScaleEvaluator  # noqa: F401
 

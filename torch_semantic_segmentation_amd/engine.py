@@ -426,7 +426,10 @@ class HostBatchPipeline:
            torch.Generator for reproducible draws) and copies the rows with the batch, and tss_augment_batch_u8 writes the
            normalized float32 crop and the int64 target crop at the top of the (captured) step.  example_x / example_y keep the
            CROP shape (what the step reads); mean / std default to the augmentation's.  The rows live in device memory, so one
-           captured graph serves every draw.
+           captured graph serves every draw.  An augmentation with hsv_p > 0 or a label_map goes through
+           tss_augment_batch_u8_ex instead: with hsv_p > 0 put() also draws the batch's colour rows (TrainAugment.draw_color,
+           after its geometry rows, from the same generator) into a [B, 4] device buffer per slot; the label table is copied
+           to the device once, here.
 
         pipe = HostBatchPipeline(trainer, example_x_f32, example_y_i64, wire='u8', mean=..., std=...)
         pipe.put(x0, y0)
@@ -444,6 +447,7 @@ class HostBatchPipeline:
         if augment is not None and source_size is None:
             raise ValueError('augment needs source_size=(H, W), the size of the frames the loader ships')
         self.augment, self.generator, self.params = augment, generator, []
+        self.color, self._lut = [], None     # colour rows per slot / the label table: the _ex entry when either is there
         self.trainer, self.wire, self.image_hwc, self.depth = trainer, wire, bool(image_hwc), int(depth)
         dev = device if device is not None else (trainer.device if trainer.device is not None else torch.device('cuda', torch.cuda.current_device()))
         self.device = torch.device(dev)
@@ -463,6 +467,12 @@ class HostBatchPipeline:
                 std = augment.std if std is None else std
                 self.source_size = (SH, SW)
                 self.params = [torch.zeros((B, 6), dtype=torch.int32, device=self.device) for _ in range(depth)]
+                if augment.hsv_p > 0:
+                    if C != 3:
+                        raise ValueError('augment.hsv_p > 0 needs a 3-channel image, the example batch has %d' % C)
+                    self.color = [torch.zeros((B, 4), dtype=torch.int32, device=self.device) for _ in range(depth)]
+                if augment.label_map is not None:
+                    self._lut = augment.label_map.to(self.device)
             xs = (B, SH, SW, C) if image_hwc else (B, C, SH, SW)
             self.stage = [(torch.empty(xs, dtype=torch.uint8, device=self.device), torch.empty((B, SH, SW), dtype=torch.uint8, device=self.device))
                           for _ in range(depth)]
@@ -493,16 +503,20 @@ class HostBatchPipeline:
             x = x.pin_memory()
         if not y.is_cuda and not y.is_pinned():
             y = y.pin_memory()
-        rows = None
+        rows = crows = None
         if self.augment is not None:         # this batch's (scale, crop origin, flip) rows travel with it
             rows = self.augment.draw(self.geom[0], self.source_size, generator=self.generator).pin_memory()
-        self._keep[slot] = (x, y, rows)
+            if self.color:                   # ... and its (apply, dh, ds, dv) rows
+                crows = self.augment.draw_color(self.geom[0], generator=self.generator).pin_memory()
+        self._keep[slot] = (x, y, rows, crows)
         with torch.cuda.stream(self.copy_stream):
             self.copy_stream.wait_event(self.consumed[slot])      # the step that read this slot last has finished with it
             sx.copy_(x, non_blocking=True)
             sy.copy_(y, non_blocking=True)
             if rows is not None:
                 self.params[slot].copy_(rows, non_blocking=True)
+            if crows is not None:
+                self.color[slot].copy_(crows, non_blocking=True)
             self.ready[slot].record(self.copy_stream)
         self._count += 1
 
@@ -514,7 +528,7 @@ class HostBatchPipeline:
         for s in self.slots:
             self.trainer.release_slot(s)
         self.slots, self.stage, self.decoded, self._keep, self._count = [], [], None, [], 0
-        self.params = []
+        self.params, self.color, self._lut = [], [], None
 
     def _decode(self, slot):
         sx, sy = self.stage[slot]
@@ -522,8 +536,12 @@ class HostBatchPipeline:
         B, C, H, W = self.geom
         if self.augment is not None:
             SH, SW = self.source_size
-            N.call('tss_augment_batch_u8', N.ptr(sx), int(self.image_hwc), self._mean, self._std, N.ptr(dx), N.ptr(sy), N.ptr(dy),
-                   N.ptr(self.params[slot]), B, C, SH, SW, H, W, N.stream())
+            head = (N.ptr(sx), int(self.image_hwc), self._mean, self._std, N.ptr(dx), N.ptr(sy), N.ptr(dy), N.ptr(self.params[slot]))
+            if self.color or self._lut is not None:
+                N.call('tss_augment_batch_u8_ex', *head, N.ptr(self.color[slot]) if self.color else None, N.ptr(self._lut),
+                       B, C, SH, SW, H, W, N.stream())
+            else:
+                N.call('tss_augment_batch_u8', *head, B, C, SH, SW, H, W, N.stream())
             return
         N.call('tss_decode_batch_u8', N.ptr(sx), int(self.image_hwc), self._mean, self._std, N.ptr(dx), N.ptr(sy), N.ptr(dy),
                B, C, H * W, N.stream())

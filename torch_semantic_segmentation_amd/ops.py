@@ -3039,6 +3039,32 @@ def check_augment_params(params, source_size, crop_size):
                          % (int((~ok).nonzero()[0]), params[int((~ok).nonzero()[0])].tolist(), ch, cw))
 
 
+def check_color_params(color):
+    """Raise ValueError unless the CPU tensor `color` holds int32 [B, 4] rows (apply, dh, ds, dv) with apply in {0, 1}, |dh| <= 180
+    (the kernel wraps the hue once) and |ds|, |dv| <= 255.  The kernel does not validate the rows."""
+    if color.dtype != torch.int32 or color.dim() != 2 or color.shape[1] != 4:
+        raise ValueError('colour rows must be int32 [B, 4], got %s %s' % (color.dtype, tuple(color.shape)))
+    apply, dh, ds, dv = color.long().unbind(1)
+    ok = ((apply == 0) | (apply == 1)) & (dh.abs() <= 180) & (ds.abs() <= 255) & (dv.abs() <= 255)
+    if not bool(ok.all()):
+        raise ValueError('colour row %d = %s: need apply in {0, 1}, |dh| <= 180, |ds| <= 255, |dv| <= 255'
+                         % (int((~ok).nonzero()[0]), color[int((~ok).nonzero()[0])].tolist()))
+
+
+def label_lut(label_map, device=None):
+    """The 256-byte table of augment_batch / remap_labels as a uint8 tensor (on `device` if given): `label_map` is a sequence or
+    tensor of 256 integers in 0..255, entry i = the train id of raw label i.  A uint8 tensor already on the device is returned
+    as it is, so build the table once and pass it on."""
+    t = label_map if torch.is_tensor(label_map) else torch.as_tensor(list(label_map))
+    if t.dim() != 1 or t.numel() != 256 or t.is_floating_point() or t.is_complex():
+        raise ValueError('label_map must hold 256 integers, got %s %s' % (t.dtype, tuple(t.shape)))
+    if t.dtype != torch.uint8:
+        if bool(((t < 0) | (t > 255)).any()):
+            raise ValueError('label_map entries must lie in 0..255')
+        t = t.to(torch.uint8)
+    return t.contiguous() if device is None else t.to(device).contiguous()
+
+
 class TrainAugment:
     """The reference's train-time augmentation (scripts/train_fastscnn.py:62-68), drawn on the host and applied on the device:
 
@@ -3056,9 +3082,18 @@ class TrainAugment:
     away from the reference's pixel, on purpose (one rounding fewer, and no quantisation noise added to the input).
 
     The reference's RandomCrop raises when the scaled image is smaller than the crop; check_source() / draw() (and
-    engine.HostBatchPipeline at construction) raise ValueError when scale_range[0] makes that possible for the source size."""
+    engine.HostBatchPipeline at construction) raise ValueError when scale_range[0] makes that possible for the source size.
 
-    def __init__(self, crop_size, scale_range=(0.5, 2.0), flip_p=0.5, mean=None, std=None):
+    hsv_p > 0 adds the other recipe's colour step (scripts/contextnet/train_contextnet.py: ... HorizontalFlip ->
+    albu.HueSaturationValue(p=hsv_p) -> Normalize ...; the limits default to albumentations'): draw_color() produces one int32 row
+    (apply, dh, ds, dv) per sample, and the kernel shifts the blended float32 (r, g, b) of a sample with apply = 1 in HSV, on
+    cv2's 8-bit scale (H in [0, 180), S and V in [0, 255]) kept CONTINUOUS: neither H, S, V nor the RGB result is rounded to
+    uint8 as cv2 does (include/tss_hip.h, tss_augment_batch_u8_ex, has the formulas).  A grey pixel has hue 0, so ds > 0 tints it
+    red, as in the reference.  `label_map` (256 integers in 0..255, e.g. the dataset's TRAIN_MAPPING; none ships with the
+    package) sends the raw label byte through a table on the device, so the loader ships the label PNG as decoded."""
+
+    def __init__(self, crop_size, scale_range=(0.5, 2.0), flip_p=0.5, mean=None, std=None, hsv_p=0.0, hue_shift_limit=20,
+                 sat_shift_limit=30, val_shift_limit=20, label_map=None):
         self.crop_size = _pair(crop_size)
         self.scale_range = (float(scale_range[0]), float(scale_range[1]))
         self.flip_p = float(flip_p)
@@ -3071,6 +3106,13 @@ class TrainAugment:
             raise ValueError('scale_range must be 0 < low <= high, got %s' % (self.scale_range,))
         if not 0.0 <= self.flip_p <= 1.0:
             raise ValueError('flip_p must be a probability, got %r' % flip_p)
+        self.hsv_p = float(hsv_p)
+        self.shift_limits = (int(hue_shift_limit), int(sat_shift_limit), int(val_shift_limit))
+        self.label_map = None if label_map is None else label_lut(label_map).cpu()
+        if not 0.0 <= self.hsv_p <= 1.0:
+            raise ValueError('hsv_p must be a probability, got %r' % hsv_p)
+        if not (0 <= self.shift_limits[0] <= 180 and 0 <= self.shift_limits[1] <= 255 and 0 <= self.shift_limits[2] <= 255):
+            raise ValueError('shift limits must be 0 <= hue <= 180, 0 <= sat <= 255, 0 <= val <= 255, got %s' % (self.shift_limits,))
 
     @staticmethod
     def _scaled(n, s):
@@ -3106,14 +3148,31 @@ class TrainAugment:
         check_augment_params(rows, (H, W), (ch, cw))
         return rows
 
+    def draw_color(self, B, generator=None):
+        """int32 [B, 4] rows (apply, dh, ds, dv) on the CPU: apply Bernoulli(hsv_p), every shift a uniform integer in
+        [-limit, limit], drawn whether or not the row applies; deterministic for a given torch.Generator state.  Call it after
+        draw(): the pipeline draws the geometry rows of a batch first, then its colour rows, from one generator."""
+        u = torch.rand((int(B), 4), generator=generator, dtype=torch.float64)
+        cols = [(u[:, 0] < self.hsv_p).long()]
+        for k, lim in enumerate(self.shift_limits):
+            cols.append(torch.floor(u[:, k + 1] * (2 * lim + 1)).long().clamp_(max=2 * lim) - lim)
+        rows = torch.stack(cols, 1).to(torch.int32)
+        check_color_params(rows)
+        return rows
 
-def augment_batch(image_u8, target_u8, params, crop_size, mean=None, std=None, image_hwc=False, out=None):
+
+def augment_batch(image_u8, target_u8, params, crop_size, mean=None, std=None, image_hwc=False, out=None, color=None, label_map=None):
     """Scale + crop + flip + Normalize + ToTensor of a uint8 batch on the device (tss_augment_batch_u8; semantics: TrainAugment).
 
     image_u8 [B, H, W, C] (image_hwc=True) or [B, C, H, W], C <= 3; target_u8 [B, H, W]; either may be None.  params: int32
     [B, 6] rows (Hs, Ws, oy, ox, flip, 0) as TrainAugment.draw returns them -- a CPU tensor is validated and copied to the
     device, a device tensor is used as it is (not validated: no host sync).  Returns (float32 [B, C, ch, cw], int64 [B, ch, cw]);
-    with out=(image_out, target_out) the results are written there."""
+    with out=(image_out, target_out) the results are written there.
+
+    color: int32 [B, 4] rows (apply, dh, ds, dv) as TrainAugment.draw_color returns them (CPU: validated and copied; device:
+    used as it is): HueSaturationValue between the blend and Normalize, C == 3 only.  label_map: 256 integers in 0..255 (see
+    label_lut; a uint8 device tensor is used as it is), applied to the label bytes.  With either, the call goes to
+    tss_augment_batch_u8_ex; with both None it is the plain entry, as before."""
     first = image_u8 if image_u8 is not None else target_u8
     if first is None:
         raise ValueError('augment_batch needs an image or a target')
@@ -3146,6 +3205,16 @@ def augment_batch(image_u8, target_u8, params, crop_size, mean=None, std=None, i
         check_augment_params(params, (H, W), (ch, cw))
         params = params.to(dev)
     params = params.contiguous()
+    if color is not None:
+        if C != 3 or image_u8 is None:
+            raise ValueError('color needs a 3-channel image (hue is defined on r, g, b), got %s' % ('no image' if image_u8 is None else 'C = %d' % C))
+        if tuple(color.shape) != (B, 4) or color.dtype != torch.int32:
+            raise ValueError('color must be int32 [%d, 4], got %s %s' % (B, color.dtype, tuple(color.shape)))
+        if not color.is_cuda:
+            check_color_params(color)
+            color = color.to(dev)
+        color = color.contiguous()
+    lut = None if label_map is None else label_lut(label_map, dev)
     ox, oy = out if out is not None else (None, None)
     if image_u8 is not None:
         if ox is None:
@@ -3157,10 +3226,30 @@ def augment_batch(image_u8, target_u8, params, crop_size, mean=None, std=None, i
             oy = torch.empty((B, ch, cw), dtype=torch.int64, device=dev)
         elif oy.dtype != torch.int64 or tuple(oy.shape) != (B, ch, cw) or not oy.is_contiguous() or oy.device != dev or oy.data_ptr() % 16:
             raise ValueError('out[1] must be a contiguous, 16-byte aligned int64 %s tensor on %s' % ((B, ch, cw), dev))
-    call('tss_augment_batch_u8', ptr(image_u8), int(bool(image_hwc)), _float3(mean, 0.0), _float3(std, 1.0),
-         ptr(ox) if image_u8 is not None else None, ptr(target_u8), ptr(oy) if target_u8 is not None else None, ptr(params),
-         B, C, H, W, ch, cw, stream())
+    head = (ptr(image_u8), int(bool(image_hwc)), _float3(mean, 0.0), _float3(std, 1.0), ptr(ox) if image_u8 is not None else None,
+            ptr(target_u8), ptr(oy) if target_u8 is not None else None, ptr(params))
+    if color is None and lut is None:
+        call('tss_augment_batch_u8', *head, B, C, H, W, ch, cw, stream())
+    else:
+        call('tss_augment_batch_u8_ex', *head, ptr(color), ptr(lut), B, C, H, W, ch, cw, stream())
     return (ox if image_u8 is not None else None), (oy if target_u8 is not None else None)
+
+
+def remap_labels(target_u8, label_map, out=None):
+    """int64 [B, H, W] = label_map[target_u8] on the device (tss_remap_labels_u8): the dataset's raw-id -> train-id table for the
+    evaluation path, where no augmentation launch carries it.  target_u8: contiguous uint8 tensor (any shape; the result has its
+    shape); label_map as in augment_batch; out: a contiguous int64 tensor of that shape to write into."""
+    _check_device(target_u8)
+    if target_u8.dtype != torch.uint8 or not target_u8.is_contiguous() or target_u8.data_ptr() % 8:
+        raise ValueError('target must be a contiguous, 8-byte aligned uint8 tensor')
+    lut = label_lut(label_map, target_u8.device)
+    if out is None:
+        out = torch.empty(target_u8.shape, dtype=torch.int64, device=target_u8.device)
+    elif (out.dtype != torch.int64 or out.shape != target_u8.shape or not out.is_contiguous() or out.device != target_u8.device
+          or out.data_ptr() % 16):
+        raise ValueError('out must be a contiguous, 16-byte aligned int64 %s tensor on %s' % (tuple(target_u8.shape), target_u8.device))
+    call('tss_remap_labels_u8', ptr(target_u8), ptr(lut), ptr(out), target_u8.numel(), stream())
+    return out
 
 
 class OHEMFn(Function):
