@@ -251,6 +251,12 @@ inline int grid_for(long total, int nt, long cap = 4096) {
   return (int)g;
 }
 
+// What the kernels over NCHW-planar (B, C, HW) logits (losssweep.h) ask of a shape: whole 8-pixel lane groups.  `empty_ok`: the
+// entry point takes an empty batch (and returns before it launches).
+inline bool planar_shape_ok(long B, int C, long HW, bool empty_ok = false) {
+  return C > 0 && (HW % 8) == 0 && (empty_ok || (B > 0 && HW > 0));
+}
+
 }  // namespace tss
 
 #define TSS_REQUIRE(cond, code) do { if (!(cond)) return (code); } while (0)

@@ -1,58 +1,33 @@
 // Cross-entropy over NCHW-planar logits (the caller side of the hot path: nn.CrossEntropyLoss(ignore_index)
 // as the training scripts use it), plus the argmax / confusion-matrix pass of the evaluator.
-// One lane owns 8 consecutive pixels of a row: every class plane is read/written as 16-byte vectors.
-// forward : online log-sum-exp over the C planes -> per-pixel lse (saved), sum of losses + valid count (f64 atomics)
+// The planar kernels are instances of the class-plane sweep of losssweep.h (lane layout, labels, validity rule, reductions).
+// forward: online log-sum-exp over the C planes -> per-pixel lse (saved), sum of losses + valid count (f64 atomics)
 // backward: dlogits[c] = (exp(l_c - lse) - [c == t]) * grad_out / count, recomputed from the saved lse
-#include "common.h"
+#include "losssweep.h"
 
 namespace {
 
-constexpr int NT = 256;
+constexpr int NT = lsw::NT;
 
 template <typename T>
 __global__ __launch_bounds__(NT) void ce_fwd_kernel(const T* logits, const long long* target, float* lse_out,
                                                     double* acc /*[2]: loss sum, valid count*/, long B, int C,
                                                     long HW, int ignore_index) {
-  __shared__ double red[2][NT / 64];
-  const long groups = B * (HW / 8);
   double lsum = 0.0, lcnt = 0.0;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
-    const long b = i / (HW / 8);
-    const long off = (i - b * (HW / 8)) * 8;
-    const T* base = logits + b * C * HW + off;
-    float m[8], s[8], lt[8];
-    long long t[8];
+  for (lsw::Groups g(B, HW); g.more(); g.next()) {
+    const long b = g.b(), off = g.off();
+    int tv[8];
+    float l[8], lt[8];
+    lsw::load_labels(target + b * HW + off, C, ignore_index, 1, tv);
+    lsw::lse8<true>(logits + b * C * HW + off, C, HW, tv, l, lt);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { m[j] = -INFINITY; s[j] = 0.f; lt[j] = 0.f; t[j] = target[b * HW + off + j]; }
-    for (int c = 0; c < C; ++c) {
-      float v[8];
-      V8<T>::load(base + (long)c * HW, v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float mn = fmaxf(m[j], v[j]);
-        s[j] = s[j] * __expf(m[j] - mn) + __expf(v[j] - mn);
-        m[j] = mn;
-        if (t[j] == c) lt[j] = v[j];
-      }
-    }
-    float l[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      l[j] = m[j] + __logf(s[j]);
-      if (t[j] != ignore_index && t[j] >= 0 && t[j] < C) { lsum += (double)(l[j] - lt[j]); lcnt += 1.0; }   // same validity rule as the fused head
-    }
+    for (int j = 0; j < 8; ++j)
+      if (tv[j] >= 0) { lsum += (double)(l[j] - lt[j]); lcnt += 1.0; }
     V8<float>::store(lse_out + b * HW + off, l);
   }
-  lsum = wave_sum(lsum);
-  lcnt = wave_sum(lcnt);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[0][wave] = lsum; red[1][wave] = lcnt; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = 0.0, c = 0.0;
-    for (int w = 0; w < NT / 64; ++w) { a += red[0][w]; c += red[1][w]; }
-    atomicAdd(acc, a);
-    atomicAdd(acc + 1, c);
+  if (lsw::block_sum2(lsum, lcnt)) {
+    atomicAdd(acc, lsum);
+    atomicAdd(acc + 1, lcnt);
   }
 }
 
@@ -68,23 +43,16 @@ template <typename T>
 __global__ __launch_bounds__(NT) void ce_bwd_kernel(const T* logits, const long long* target, const float* lse,
                                                     const float* inv_count, const float* grad_out, T* dlogits,
                                                     long B, int C, long HW, int ignore_index) {
-  const long groups = B * (HW / 8);
   const float gs = (*inv_count) * (grad_out ? *grad_out : 1.f);
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
-    const long b = i / (HW / 8);
-    const long off = (i - b * (HW / 8)) * 8;
+  for (lsw::Groups g(B, HW); g.more(); g.next()) {
+    const long b = g.b(), off = g.off();
+    int tv[8];
     float l[8], w[8];
-    long long t[8];
+    lsw::load_labels(target + b * HW + off, C, 0, 0, tv);
     V8<float>::load(lse + b * HW + off, l);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { t[j] = target[b * HW + off + j]; w[j] = (t[j] != ignore_index && t[j] >= 0 && t[j] < C) ? gs : 0.f; }
-    for (int c = 0; c < C; ++c) {
-      float v[8], d[8];
-      V8<T>::load(logits + (b * C + c) * HW + off, v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) d[j] = (__expf(v[j] - l[j]) - (t[j] == c ? 1.f : 0.f)) * w[j];
-      V8<T>::store(dlogits + (b * C + c) * HW + off, d);
-    }
+    for (int j = 0; j < 8; ++j) w[j] = lsw::counts(tv[j], ignore_index) ? gs : 0.f;
+    lsw::grad8<false>(logits + b * C * HW + off, dlogits + b * C * HW + off, C, HW, tv, l, w);
   }
 }
 
@@ -324,20 +292,11 @@ __global__ __launch_bounds__(NT, (CP <= 20 ? 3 : 2)) void upsample_ce_onepass_ke
   }
 }
 
-// loss = sum(rows[.][0]) / sum(rows[.][1]) in a fixed order (one block; thread t takes rows t, t + NT, ...)
+// loss = sum(rows[.][0]) / sum(rows[.][1]) in a fixed order (one block)
 __global__ __launch_bounds__(NT) void ce_finalize_rows_kernel(const double* rows, int nrows, float* loss, float* inv_count) {
-  __shared__ double red[2][NT];
-  double a = 0.0, c = 0.0;
-  for (int i = threadIdx.x; i < nrows; i += NT) { a += rows[2 * (long)i]; c += rows[2 * (long)i + 1]; }
-  red[0][threadIdx.x] = a; red[1][threadIdx.x] = c;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) { red[0][threadIdx.x] += red[0][threadIdx.x + s]; red[1][threadIdx.x] += red[1][threadIdx.x + s]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const double n = red[1][0];
-    *loss = (float)(red[0][0] / n);          // n == 0 -> nan, like torch
+  double sum, n;
+  if (lsw::row_sum2(rows, nrows, sum, n)) {
+    *loss = (float)(sum / n);          // n == 0 -> nan, like torch
     *inv_count = n > 0.0 ? (float)(1.0 / n) : 0.f;
   }
 }
@@ -405,12 +364,10 @@ __global__ __launch_bounds__(NT) void argmax_confusion_kernel(const T* logits, c
   extern __shared__ unsigned int scm[];  // [C*C]
   for (int i = threadIdx.x; i < C * C; i += blockDim.x) scm[i] = 0u;
   __syncthreads();
-  const long groups = B * (HW / 8);
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
-    const long b = i / (HW / 8);
-    const long off = (i - b * (HW / 8)) * 8;
+  for (lsw::Groups g(B, HW); g.more(); g.next()) {
+    const long b = g.b(), off = g.off();
     float best[8];
-    int arg[8];
+    int arg[8], tv[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { best[j] = -INFINITY; arg[j] = 0; }
     for (int c = 0; c < C; ++c) {
@@ -420,13 +377,12 @@ __global__ __launch_bounds__(NT) void argmax_confusion_kernel(const T* logits, c
       for (int j = 0; j < 8; ++j)
         if (v[j] > best[j] || (c == 0)) { best[j] = v[j]; arg[j] = c; }
     }
+    const bool score = cm && target;
+    if (score) lsw::load_labels(target + b * HW + off, C, ignore_index, 1, tv);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       if (pred_out) pred_out[b * HW + off + j] = (unsigned char)arg[j];
-      if (cm && target) {
-        const long long t = target[b * HW + off + j];
-        if (t != ignore_index && t >= 0 && t < C) atomicAdd(&scm[(int)t * C + arg[j]], 1u);
-      }
+      if (score && tv[j] >= 0) atomicAdd(&scm[tv[j] * C + arg[j]], 1u);
     }
   }
   __syncthreads();
@@ -520,7 +476,7 @@ int tss_cross_entropy_fwd(const void* logits, const long long* target, float* ls
                           float* loss, float* inv_count, long B, int C, long HW, int ignore_index,
                           int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(C > 0 && (HW % 8) == 0, TSS_ERR_SHAPE);
+  TSS_REQUIRE(tss::planar_shape_ok(B, C, HW, true), TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(logits) && tss::aligned16(lse), TSS_ERR_ALIGN);
   const long groups = B * (HW / 8);
   if (groups == 0) return TSS_OK;
@@ -537,7 +493,7 @@ int tss_cross_entropy_bwd(const void* logits, const long long* target, const flo
                           const float* grad_out, void* dlogits, long B, int C, long HW, int ignore_index,
                           int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(C > 0 && (HW % 8) == 0, TSS_ERR_SHAPE);
+  TSS_REQUIRE(tss::planar_shape_ok(B, C, HW, true), TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(logits) && tss::aligned16(dlogits) && tss::aligned16(lse), TSS_ERR_ALIGN);
   const long groups = B * (HW / 8);
   if (groups == 0) return TSS_OK;
@@ -551,7 +507,7 @@ int tss_argmax_confusion(const void* logits, const long long* target, unsigned c
                          unsigned long long* confusion /*[C*C] accumulated*/, long B, int C, long HW,
                          int ignore_index, int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(C > 0 && C <= 64 && (HW % 8) == 0, TSS_ERR_SHAPE);
+  TSS_REQUIRE(tss::planar_shape_ok(B, C, HW, true) && C <= 64, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(logits), TSS_ERR_ALIGN);
   const long groups = B * (HW / 8);
   if (groups == 0) return TSS_OK;

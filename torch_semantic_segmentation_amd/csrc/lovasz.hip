@@ -18,11 +18,11 @@
 // The softmax is evaluated in f64 and the error rounded once, into the key, so the order is that of the exact errors to
 // 2^-24 relative at both ends (an f32 softmax swaps near-equal errors, and a swapped pair moves g by O(1/U)); ranks and
 // counts are integers, g is f64.
-#include "common.h"
+#include "losssweep.h"
 
 namespace {
 
-constexpr int NT = 256;
+constexpr int NT = lsw::NT;
 constexpr int WAVES = NT / 64;
 constexpr int ITEMS = 16;                 // elements per lane and tile: 48 VGPRs of (key, payload, rank) in the scatter
 constexpr int TILE = NT * ITEMS;          // 4096 pairs per block; a wave owns 1024 consecutive ones
@@ -122,16 +122,14 @@ __device__ __forceinline__ double key_error(unsigned int key) {
 template <typename T>
 __global__ __launch_bounds__(NT) void lovasz_key_kernel(const T* logits, const long long* target, unsigned int* keys,
                                                         unsigned int* pay, long B, int C, long HW, int c0, int c1,
-                                                        long long ignore, int has_ignore) {
-  const long groups = B * (HW / 8), N = B * HW;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
-    const long b = i / (HW / 8);
-    const long off = (i - b * (HW / 8)) * 8;
+                                                        int ignore_index, int has_ignore) {
+  const long N = B * HW;
+  for (lsw::Groups g(B, HW); g.more(); g.next()) {
+    const long b = g.b(), off = g.off();
     const long pix = b * HW + off;
     const T* base = logits + b * C * HW + off;
-    long long t[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t[j] = target[pix + j];
+    int tv[8];
+    lsw::load_labels(target + pix, C, ignore_index, has_ignore, tv);
     float m[8];
     double inv[8];
     softmax_stats(base, C, HW, m, inv);
@@ -142,8 +140,8 @@ __global__ __launch_bounds__(NT) void lovasz_key_kernel(const T* logits, const l
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const double p = exp((double)v[j] - (double)m[j]) * inv[j];
-        const unsigned int fg = t[j] == c ? 1u : 0u;
-        const bool kept = !(has_ignore && t[j] == ignore);
+        const unsigned int fg = tv[j] == c ? 1u : 0u;
+        const bool kept = tv[j] != lsw::IGNORED;       // an out-of-range label is background, not dropped
         k[j] = kept ? error_key(fabs((double)fg - p)) : DROPPED;
         q[j] = (unsigned int)(pix + j) | ((kept ? fg : 0u) << 31);
       }
@@ -399,17 +397,15 @@ __global__ __launch_bounds__(NT) void lovasz_final_kernel(const double* partial,
 template <typename T>
 __global__ __launch_bounds__(NT) void lovasz_bwd_kernel(const T* logits, const long long* target, const float* W, const float* n_present,
                                                         const float* grad_out, T* dlogits, long B, int C, long HW) {
-  const long groups = B * (HW / 8), N = B * HW;
+  const long N = B * HW;
   const double np = (double)*n_present;
   const double scale = np > 0.0 ? (double)(grad_out ? *grad_out : 1.f) / np : 0.0;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
-    const long b = i / (HW / 8);
-    const long off = (i - b * (HW / 8)) * 8;
+  for (lsw::Groups g(B, HW); g.more(); g.next()) {
+    const long b = g.b(), off = g.off();
     const long pix = b * HW + off;
     const T* base = logits + b * C * HW + off;
-    long long t[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t[j] = target[pix + j];
+    int tv[8];
+    lsw::load_labels(target + pix, C, 0, 0, tv);         // the foreground term only: a dropped pixel has weight 0 in W
     float m[8];
     double inv[8], dot[8];
     softmax_stats(base, C, HW, m, inv);
@@ -422,7 +418,7 @@ __global__ __launch_bounds__(NT) void lovasz_bwd_kernel(const T* logits, const l
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const double p = exp((double)v[j] - (double)m[j]) * inv[j];
-        const double diff = (t[j] == c ? 1.0 : 0.0) - p;
+        const double diff = (tv[j] == c ? 1.0 : 0.0) - p;
         const double D = diff > 0.0 ? -(double)w[j] : (diff < 0.0 ? (double)w[j] : 0.0);
         dot[j] += D * p;
       }
@@ -434,7 +430,7 @@ __global__ __launch_bounds__(NT) void lovasz_bwd_kernel(const T* logits, const l
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const double p = exp((double)v[j] - (double)m[j]) * inv[j];
-        const double diff = (t[j] == c ? 1.0 : 0.0) - p;
+        const double diff = (tv[j] == c ? 1.0 : 0.0) - p;
         const double D = diff > 0.0 ? -(double)w[j] : (diff < 0.0 ? (double)w[j] : 0.0);
         d[j] = (float)(p * (D - dot[j]) * scale);
       }
@@ -443,8 +439,9 @@ __global__ __launch_bounds__(NT) void lovasz_bwd_kernel(const T* logits, const l
   }
 }
 
+// the planar rule, and pixel indices and tile counts that fit the 31-bit payload / an int grid
 inline bool shape_ok(long B, int C, long HW) {
-  return B > 0 && C > 0 && HW > 0 && (HW % 8) == 0 && B * HW < (1L << 31) && (B * HW + TILE - 1) / TILE <= 0x7FFFFFFFL;
+  return tss::planar_shape_ok(B, C, HW) && B * HW < (1L << 31) && (B * HW + TILE - 1) / TILE <= 0x7FFFFFFFL;
 }
 
 }  // namespace
@@ -478,7 +475,7 @@ int tss_lovasz_fwd(const void* logits, const long long* target, void* workspace,
     const int c1 = c0 + pl.Cc < C ? c0 + pl.Cc : C;
     const unsigned int nc = (unsigned int)(c1 - c0);
     TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(lovasz_key_kernel<TT>, dim3(tss::grid_for(N / 8, NT)), dim3(NT), 0, st, (const TT*)logits, target,
-                                             key[0], pay[0], B, C, HW, c0, c1, (long long)ignore_index, has_ignore));
+                                             key[0], pay[0], B, C, HW, c0, c1, ignore_index, has_ignore));
     for (int pass = 0; pass < 4; ++pass) {            // 4 passes: the sorted pairs end in buffer 0
       const int src = pass & 1, dst = src ^ 1, shift = 8 * pass;
       hipLaunchKernelGGL(lovasz_hist_kernel, dim3(nt, nc), dim3(NT), 0, st, key[src], hist, N, pl.ntiles, shift);

@@ -6,11 +6,11 @@
 // one-block scan between the passes, everything on the device (graph-capturable, no sort, no host round trip).
 // Ties at v share the remaining weight evenly (the reference takes an arbitrary subset of them; the loss value is the
 // same, and exact ties of positive losses do not occur in practice).
-#include "common.h"
+#include "losssweep.h"
 
 namespace {
 
-constexpr int NT = 256;
+constexpr int NT = lsw::NT;
 
 struct OhemState {            // device workspace, zero-initialised by the caller
   unsigned int hist[2048];
@@ -20,35 +20,20 @@ struct OhemState {            // device workspace, zero-initialised by the calle
   double acc[5];              // sum(l > thresh), count(l > thresh), sum(l > v), count(l > v), count(l == v)
 };
 
+// per-pixel CE (0 for a pixel that does not count) and lse: the forward sweep of losssweep.h
 template <typename T>
 __global__ __launch_bounds__(NT) void ohem_pixel_kernel(const T* logits, const long long* target, float* lse_out,
                                                         float* pix, long B, int C, long HW, int ignore_index) {
-  const long groups = B * (HW / 8);
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
-    const long b = i / (HW / 8);
-    const long off = (i - b * (HW / 8)) * 8;
-    const T* base = logits + b * C * HW + off;
-    float m[8], s[8], lt[8];
-    long long t[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { m[j] = -INFINITY; s[j] = 0.f; lt[j] = 0.f; t[j] = target[b * HW + off + j]; }
-    for (int c = 0; c < C; ++c) {
-      float v[8];
-      V8<T>::load(base + (long)c * HW, v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float mn = fmaxf(m[j], v[j]);
-        s[j] = s[j] * __expf(m[j] - mn) + __expf(v[j] - mn);
-        m[j] = mn;
-        if (t[j] == c) lt[j] = v[j];
-      }
-    }
-    float l[8], p[8];
+  for (lsw::Groups g(B, HW); g.more(); g.next()) {
+    const long b = g.b(), off = g.off();
+    int tv[8];
+    float l[8], lt[8], p[8];
+    lsw::load_labels(target + b * HW + off, C, ignore_index, 1, tv);
+    lsw::lse8<true>(logits + b * C * HW + off, C, HW, tv, l, lt);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      l[j] = m[j] + __logf(s[j]);
       const float d = l[j] - lt[j];
-      p[j] = (t[j] != ignore_index && t[j] >= 0 && t[j] < C) ? fmaxf(d, 0.f) : 0.f;     // a CE value is >= 0 (rounding may give -1e-7)
+      p[j] = tv[j] >= 0 ? fmaxf(d, 0.f) : 0.f;     // a CE value is >= 0 (rounding may give -1e-7)
     }
     V8<float>::store(lse_out + b * HW + off, l);
     V8<float>::store(pix + b * HW + off, p);
@@ -166,29 +151,21 @@ template <typename T>
 __global__ __launch_bounds__(NT) void ohem_bwd_kernel(const T* logits, const long long* target, const float* lse,
                                                       const float* pix, const float* params, const float* grad_out,
                                                       T* dlogits, long B, int C, long HW, int ignore_index) {
-  const long groups = B * (HW / 8);
   const float cut = params[1], wgt = params[2], weq = params[0] != 0.f ? 0.f : params[3];
   const float gs = grad_out ? *grad_out : 1.f;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
-    const long b = i / (HW / 8);
-    const long off = (i - b * (HW / 8)) * 8;
+  for (lsw::Groups g(B, HW); g.more(); g.next()) {
+    const long b = g.b(), off = g.off();
+    int tv[8];
     float l[8], p[8], w[8];
-    long long t[8];
+    lsw::load_labels(target + b * HW + off, C, 0, 0, tv);
     V8<float>::load(lse + b * HW + off, l);
     V8<float>::load(pix + b * HW + off, p);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      t[j] = target[b * HW + off + j];
       const float sel = p[j] > cut ? wgt : (p[j] == cut ? weq : 0.f);
-      w[j] = (t[j] != ignore_index && t[j] >= 0 && t[j] < C) ? sel * gs : 0.f;
+      w[j] = lsw::counts(tv[j], ignore_index) ? sel * gs : 0.f;
     }
-    for (int c = 0; c < C; ++c) {
-      float v[8], d[8];
-      V8<T>::load(logits + (b * C + c) * HW + off, v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) d[j] = (__expf(v[j] - l[j]) - (t[j] == c ? 1.f : 0.f)) * w[j];
-      V8<T>::store(dlogits + (b * C + c) * HW + off, d);
-    }
+    lsw::grad8<false>(logits + b * C * HW + off, dlogits + b * C * HW + off, C, HW, tv, l, w);
   }
 }
 
@@ -202,7 +179,7 @@ int tss_ohem_fwd(const void* logits, const long long* target, float* lse, float*
                  float* loss, float* params /*[4]*/, long B, int C, long HW, int ignore_index, float thresh_loss,
                  long n_top, int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(C > 0 && (HW % 8) == 0 && n_top >= 0 && n_top < B * HW, TSS_ERR_SHAPE);
+  TSS_REQUIRE(tss::planar_shape_ok(B, C, HW, true) && n_top >= 0 && n_top < B * HW, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(logits) && tss::aligned16(lse) && tss::aligned16(pixel_loss) && tss::aligned16(workspace), TSS_ERR_ALIGN);
   const long n = B * HW;
   if (n == 0) return TSS_OK;
@@ -234,7 +211,7 @@ int tss_ohem_bwd(const void* logits, const long long* target, const float* lse, 
                  const float* params, const float* grad_out, void* dlogits, long B, int C, long HW, int ignore_index,
                  int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(C > 0 && (HW % 8) == 0, TSS_ERR_SHAPE);
+  TSS_REQUIRE(tss::planar_shape_ok(B, C, HW, true), TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(logits) && tss::aligned16(dlogits) && tss::aligned16(lse) && tss::aligned16(pixel_loss), TSS_ERR_ALIGN);
   const long groups = B * (HW / 8);
   if (groups == 0) return TSS_OK;

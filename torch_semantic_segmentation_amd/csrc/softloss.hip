@@ -1,7 +1,6 @@
 // Focal loss (TSS/losses/focal_loss.py:8-15) and soft Dice loss (TSS/losses/dice_loss.py:8-26) over NCHW-planar logits.
-// Same lane layout as ce_fwd_kernel / ce_bwd_kernel (loss.hip): one lane owns 8 consecutive pixels, every class plane is
-// read / written as 16-byte vectors, the per-pixel log-sum-exp comes from an online sweep over the planes and is saved in f32.
-// Validity as everywhere in loss.hip: a pixel counts iff target != ignore_index (when there is one) and 0 <= target < C.
+// Instances of the class-plane sweep of losssweep.h: its lane layout, group loop, labels and validity rule (a pixel counts iff
+// target != ignore_index, when there is one, and 0 <= target < C), its reductions; the per-pixel log-sum-exp is saved in f32.
 //
 // No atomics: every block stores its partial sums (f64) into a row of its own in the caller's workspace (plain stores, every
 // element that is read was written, nothing zero-filled) and a one-block finalize kernel adds the rows in a fixed order, so
@@ -13,7 +12,7 @@
 //         dloss/dx_c = A ([c == t] - s_c) alpha grad_out / |V|,  A = -(p w' lp + w),  w' = dw/dp = -gamma q^(gamma-1) w
 //         (variant 1: -gamma q^(gamma-1)); gamma == 0: w' = 0; q == 0: the term p w' lp is taken as 0 (its limit).
 //         The forward has p, q and lp of a pixel in registers, so it saves A per pixel (0 for a pixel outside V) next to
-//         the lse, and the backward is one sweep over the planes like ce_bwd_kernel: s_c is recomputed from the saved lse.
+//         the lse, and the backward is the gradient sweep of losssweep.h (sign reversed): s_c is recomputed from the saved lse.
 // dice:   I_c = sum_V p_c [t == c], U_c = sum_V p_c + sum_V [t == c], loss = mean_c 1 - (2 I_c + smooth) / (U_c + smooth)
 //         over all C classes (an absent class counts).  Per-class sums live in registers, DICE_CP classes at a time: the sweep
 //         reads the planes a second time right after the lse sweep of the same 8 pixels (C <= DICE_CP: once per plane and
@@ -22,11 +21,11 @@
 //         backward is dx_k = p_k (G_k - sum_c p_c G_c) grad_out on V (coefficients in LDS, two sweeps), 0 elsewhere.
 // V empty: loss 0, zero gradient (both losses; no host read-back).  A class with U_c + smooth == 0 contributes 1 (the
 // limit of 0 / U) and zero coefficients.
-#include "common.h"
+#include "losssweep.h"
 
 namespace {
 
-constexpr int NT = 256;
+constexpr int NT = lsw::NT;
 constexpr int WAVES = NT / 64;
 constexpr int DICE_CP = 24;               // class sums held in registers per sweep (3 accumulators each)
 constexpr int DICE_MAX_C = 256;
@@ -39,29 +38,17 @@ inline int grid_of(long groups, int max_blocks, long default_cap) {
   return tss::grid_for(groups, NT, max_blocks > 0 ? (long)max_blocks : default_cap);
 }
 
-// the 8 labels of a lane as ints: the class of a valid pixel, -1 for every other one
-__device__ __forceinline__ void load_labels(const long long* target, int C, int ignore_index, int has_ignore, int tv[8]) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const long long t = target[j];
-    tv[j] = ((!has_ignore || t != (long long)ignore_index) && t >= 0 && t < C) ? (int)t : -1;
-  }
-}
-
 // ------------------------------------------------------------------------------------------------------------ focal
 template <typename T>
 __global__ __launch_bounds__(NT) void focal_fwd_kernel(const T* logits, const long long* target, float* lse_out, float* pixw,
                                                        double* rows /*[gridDim.x][2]: sum of w lp, valid count*/, long B, int C,
                                                        long HW, int ignore_index, int has_ignore, float gamma, int variant) {
-  __shared__ double red[2][WAVES];
-  const long groups = B * (HW / 8);
   double lsum = 0.0, lcnt = 0.0;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
-    const long b = i / (HW / 8);
-    const long off = (i - b * (HW / 8)) * 8;
+  for (lsw::Groups g(B, HW); g.more(); g.next()) {
+    const long b = g.b(), off = g.off();
     const T* base = logits + b * C * HW + off;
     int tv[8];
-    load_labels(target + b * HW + off, C, ignore_index, has_ignore, tv);
+    lsw::load_labels(target + b * HW + off, C, ignore_index, has_ignore, tv);
     float m[8], so[8], xt[8];           // running maximum over all classes, sum of exp over the classes != t, the target's logit
 #pragma unroll
     for (int j = 0; j < 8; ++j) { m[j] = -INFINITY; so[j] = 0.f; xt[j] = 0.f; }
@@ -105,33 +92,17 @@ __global__ __launch_bounds__(NT) void focal_fwd_kernel(const T* logits, const lo
     V8<float>::store(lse_out + b * HW + off, l);
     V8<float>::store(pixw + b * HW + off, a);
   }
-  lsum = wave_sum(lsum);
-  lcnt = wave_sum(lcnt);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[0][wave] = lsum; red[1][wave] = lcnt; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0, n = 0.0;
-    for (int w = 0; w < WAVES; ++w) { s += red[0][w]; n += red[1][w]; }
-    rows[2 * (long)blockIdx.x] = s;
-    rows[2 * (long)blockIdx.x + 1] = n;
+  if (lsw::block_sum2(lsum, lcnt)) {
+    rows[2 * (long)blockIdx.x] = lsum;
+    rows[2 * (long)blockIdx.x + 1] = lcnt;
   }
 }
 
 // loss = -alpha * sum(rows[.][0]) / n, scale = alpha / n with n = sum(rows[.][1]); n == 0: both 0.  One block, fixed tree.
 __global__ __launch_bounds__(NT) void focal_finalize_kernel(const double* rows, int nrows, float alpha, float* loss, float* scale) {
-  __shared__ double red[2][NT];
-  double s = 0.0, n = 0.0;
-  for (int i = threadIdx.x; i < nrows; i += NT) { s += rows[2 * (long)i]; n += rows[2 * (long)i + 1]; }
-  red[0][threadIdx.x] = s; red[1][threadIdx.x] = n;
-  __syncthreads();
-  for (int k = NT / 2; k > 0; k >>= 1) {
-    if ((int)threadIdx.x < k) { red[0][threadIdx.x] += red[0][threadIdx.x + k]; red[1][threadIdx.x] += red[1][threadIdx.x + k]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const double cnt = red[1][0];
-    *loss = cnt > 0.0 ? (float)(-(double)alpha * red[0][0] / cnt) : 0.f;
+  double sum, cnt;
+  if (lsw::row_sum2(rows, nrows, sum, cnt)) {
+    *loss = cnt > 0.0 ? (float)(-(double)alpha * sum / cnt) : 0.f;
     *scale = cnt > 0.0 ? (float)((double)alpha / cnt) : 0.f;
   }
 }
@@ -139,24 +110,17 @@ __global__ __launch_bounds__(NT) void focal_finalize_kernel(const double* rows, 
 template <typename T>
 __global__ __launch_bounds__(NT) void focal_bwd_kernel(const T* logits, const long long* target, const float* lse, const float* pixw,
                                                        const float* scale, const float* grad_out, T* dlogits, long B, int C, long HW) {
-  const long groups = B * (HW / 8);
   const float gs = (*scale) * (grad_out ? *grad_out : 1.f);
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
-    const long b = i / (HW / 8);
-    const long off = (i - b * (HW / 8)) * 8;
+  for (lsw::Groups g(B, HW); g.more(); g.next()) {
+    const long b = g.b(), off = g.off();
+    int tv[8];
     float l[8], a[8];
-    long long t[8];
+    lsw::load_labels(target + b * HW + off, C, 0, 0, tv);      // the one-hot term only: a == 0 outside the valid set
     V8<float>::load(lse + b * HW + off, l);
     V8<float>::load(pixw + b * HW + off, a);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { t[j] = target[b * HW + off + j]; a[j] *= gs; }      // a == 0 outside the valid set
-    for (int c = 0; c < C; ++c) {
-      float v[8], d[8];
-      V8<T>::load(logits + (b * C + c) * HW + off, v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) d[j] = ((t[j] == c ? 1.f : 0.f) - __expf(v[j] - l[j])) * a[j];
-      V8<T>::store(dlogits + (b * C + c) * HW + off, d);
-    }
+    for (int j = 0; j < 8; ++j) a[j] *= gs;
+    lsw::grad8<true>(logits + b * C * HW + off, dlogits + b * C * HW + off, C, HW, tv, l, a);
   }
 }
 
@@ -166,36 +130,20 @@ template <typename T>
 __global__ __launch_bounds__(NT) void dice_fwd_kernel(const T* logits, const long long* target, float* lse_out, double* rows,
                                                       long B, int C, long HW, int ignore_index, int has_ignore) {
   __shared__ double red[WAVES][3 * DICE_CP];
-  const long groups = B * (HW / 8);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double* row = rows + (long)blockIdx.x * 3 * C;
   for (int c0 = 0; c0 < C; c0 += DICE_CP) {
     float aP[DICE_CP], aI[DICE_CP], aN[DICE_CP];
 #pragma unroll
     for (int k = 0; k < DICE_CP; ++k) { aP[k] = 0.f; aI[k] = 0.f; aN[k] = 0.f; }
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
-      const long b = i / (HW / 8);
-      const long off = (i - b * (HW / 8)) * 8;
+    for (lsw::Groups g(B, HW); g.more(); g.next()) {
+      const long b = g.b(), off = g.off();
       const T* base = logits + b * C * HW + off;
       int tv[8];
-      load_labels(target + b * HW + off, C, ignore_index, has_ignore, tv);
+      lsw::load_labels(target + b * HW + off, C, ignore_index, has_ignore, tv);
       float l[8];
       if (c0 == 0) {
-        float m[8], s[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { m[j] = -INFINITY; s[j] = 0.f; }
-        for (int c = 0; c < C; ++c) {
-          float v[8];
-          V8<T>::load(base + (long)c * HW, v);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float mn = fmaxf(m[j], v[j]);
-            s[j] = s[j] * __expf(m[j] - mn) + __expf(v[j] - mn);
-            m[j] = mn;
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) l[j] = m[j] + __logf(s[j]);
+        lsw::lse8<false>(base, C, HW, nullptr, l, nullptr);
         V8<float>::store(lse_out + b * HW + off, l);
       } else {
         V8<float>::load(lse_out + b * HW + off, l);      // this lane's own store of the first sweep
@@ -279,18 +227,16 @@ __global__ __launch_bounds__(NT) void dice_bwd_kernel(const T* logits, const lon
   __shared__ float sa[DICE_MAX_C], sb[DICE_MAX_C];
   for (int c = threadIdx.x; c < C; c += NT) { sa[c] = coef[c]; sb[c] = coef[C + c]; }
   __syncthreads();
-  const long groups = B * (HW / 8);
-  const float g = grad_out ? *grad_out : 1.f;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < groups; i += (long)gridDim.x * blockDim.x) {
-    const long b = i / (HW / 8);
-    const long off = (i - b * (HW / 8)) * 8;
+  const float go = grad_out ? *grad_out : 1.f;
+  for (lsw::Groups g(B, HW); g.more(); g.next()) {
+    const long b = g.b(), off = g.off();
     const T* base = logits + b * C * HW + off;
     int tv[8];
-    load_labels(target + b * HW + off, C, ignore_index, has_ignore, tv);
+    lsw::load_labels(target + b * HW + off, C, ignore_index, has_ignore, tv);
     float l[8], dot[8], gv[8];
     V8<float>::load(lse + b * HW + off, l);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { dot[j] = 0.f; gv[j] = tv[j] >= 0 ? g : 0.f; }
+    for (int j = 0; j < 8; ++j) { dot[j] = 0.f; gv[j] = tv[j] >= 0 ? go : 0.f; }
     for (int c = 0; c < C; ++c) {                        // sum_c p_c G_c
       float v[8];
       V8<T>::load(base + (long)c * HW, v);
@@ -309,7 +255,6 @@ __global__ __launch_bounds__(NT) void dice_bwd_kernel(const T* logits, const lon
   }
 }
 
-inline bool shape_ok(long B, int C, long HW) { return B > 0 && C > 0 && HW > 0 && (HW % 8) == 0; }
 inline size_t dice_coef_bytes(int C) { return up256(sizeof(float) * 2 * (size_t)C); }
 
 }  // namespace
@@ -325,7 +270,7 @@ int tss_focal_fwd(const void* logits, const long long* target, float* lse, float
                   long B, int C, long HW, int ignore_index, int has_ignore, float alpha, float gamma, int variant, int max_blocks,
                   int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(shape_ok(B, C, HW) && gamma >= 0.f && (variant == 0 || variant == 1) && max_blocks >= 0, TSS_ERR_SHAPE);
+  TSS_REQUIRE(tss::planar_shape_ok(B, C, HW) && gamma >= 0.f && (variant == 0 || variant == 1) && max_blocks >= 0, TSS_ERR_SHAPE);
   TSS_REQUIRE(target && lse && pixel_coef && workspace && loss && scale, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(logits) && tss::aligned16(lse) && tss::aligned16(pixel_coef) && tss::aligned16(workspace), TSS_ERR_ALIGN);
   hipStream_t st = (hipStream_t)stream;
@@ -341,7 +286,7 @@ int tss_focal_fwd(const void* logits, const long long* target, float* lse, float
 int tss_focal_bwd(const void* logits, const long long* target, const float* lse, const float* pixel_coef, const float* scale,
                   const float* grad_out, void* dlogits, long B, int C, long HW, int max_blocks, int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(shape_ok(B, C, HW) && max_blocks >= 0 && target && lse && pixel_coef && scale, TSS_ERR_SHAPE);
+  TSS_REQUIRE(tss::planar_shape_ok(B, C, HW) && max_blocks >= 0 && target && lse && pixel_coef && scale, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(logits) && tss::aligned16(dlogits) && tss::aligned16(lse) && tss::aligned16(pixel_coef), TSS_ERR_ALIGN);
   const long groups = B * (HW / 8);
   TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(focal_bwd_kernel<TT>, dim3(grid_of(groups, max_blocks, 4096)), dim3(NT), 0, (hipStream_t)stream,
@@ -357,7 +302,7 @@ long tss_dice_workspace_bytes(long B, int C, long HW, int max_blocks) {
 int tss_dice_fwd(const void* logits, const long long* target, float* lse, void* workspace, float* loss, long B, int C, long HW,
                  int ignore_index, int has_ignore, float smooth, int max_blocks, int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(shape_ok(B, C, HW) && C <= DICE_MAX_C && smooth >= 0.f && max_blocks >= 0, TSS_ERR_SHAPE);
+  TSS_REQUIRE(tss::planar_shape_ok(B, C, HW) && C <= DICE_MAX_C && smooth >= 0.f && max_blocks >= 0, TSS_ERR_SHAPE);
   TSS_REQUIRE(target && lse && workspace && loss, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(logits) && tss::aligned16(lse) && tss::aligned16(workspace), TSS_ERR_ALIGN);
   hipStream_t st = (hipStream_t)stream;
@@ -374,7 +319,7 @@ int tss_dice_fwd(const void* logits, const long long* target, float* lse, void* 
 int tss_dice_bwd(const void* logits, const long long* target, const float* lse, const void* workspace, const float* grad_out,
                  void* dlogits, long B, int C, long HW, int ignore_index, int has_ignore, int max_blocks, int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(shape_ok(B, C, HW) && C <= DICE_MAX_C && max_blocks >= 0 && target && lse && workspace, TSS_ERR_SHAPE);
+  TSS_REQUIRE(tss::planar_shape_ok(B, C, HW) && C <= DICE_MAX_C && max_blocks >= 0 && target && lse && workspace, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(logits) && tss::aligned16(dlogits) && tss::aligned16(lse) && tss::aligned16(workspace), TSS_ERR_ALIGN);
   const long groups = B * (HW / 8);
   TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(dice_bwd_kernel<TT>, dim3(grid_of(groups, max_blocks, 4096)), dim3(NT), 0, (hipStream_t)stream,

@@ -2937,6 +2937,28 @@ def _check_logits_target(logits, target):
     return logits, target.contiguous()
 
 
+def _ignore_pair(ignore_index):
+    """(ignore value, has_ignore) as the entry points take them; ignore_index=None: no label is ignored."""
+    return (int(ignore_index), 1) if ignore_index is not None else (0, 0)
+
+
+def _open_backward(logits, gout):
+    """The common opening of the loss backwards: grad_out as contiguous float32, the uninitialised dlogits, (B, C, H*W)."""
+    B, C, H, W = logits.shape
+    return gout.to(torch.float32).contiguous(), torch.empty_like(logits), (B, C, H * W)
+
+
+def _check_variant(variant, variants):
+    if variant not in variants:
+        raise ValueError('variant must be %s, got %r' % (' or '.join(repr(v) for v in variants), variant))
+
+
+def _check_num_classes(input, num_classes):
+    if input.dim() != 4 or int(num_classes) != input.shape[1]:
+        raise ValueError('num_classes (%s) must equal the channel count of the (B,C,H,W) logits %s'
+                         % (num_classes, tuple(input.shape)))
+
+
 class CrossEntropyFn(Function):
     @staticmethod
     def forward(ctx, logits, target, ignore_index):
@@ -2955,11 +2977,9 @@ class CrossEntropyFn(Function):
     @staticmethod
     def backward(ctx, gout):
         logits, target, lse, scal = ctx.saved_tensors
-        B, C, H, W = logits.shape
-        gout = gout.to(torch.float32).contiguous()
-        d = torch.empty_like(logits)
+        gout, d, dims = _open_backward(logits, gout)
         call('tss_cross_entropy_bwd', ptr(logits), ptr(target), ptr(lse), ptr(scal[1:2]), ptr(gout), ptr(d),
-             B, C, H * W, ctx.ignore_index, N.dtype_code(logits.dtype), stream())
+             *dims, ctx.ignore_index, N.dtype_code(logits.dtype), stream())
         return d, None, None
 
 
@@ -3279,11 +3299,9 @@ class OHEMFn(Function):
     @staticmethod
     def backward(ctx, gout):
         logits, target, lse, pix, out = ctx.saved_tensors
-        B, C, H, W = logits.shape
-        gout = gout.to(torch.float32).contiguous()
-        d = torch.empty_like(logits)
+        gout, d, dims = _open_backward(logits, gout)
         call('tss_ohem_bwd', ptr(logits), ptr(target), ptr(lse), ptr(pix), ptr(out[1:5]), ptr(gout), ptr(d),
-             B, C, H * W, ctx.ignore_index, N.dtype_code(logits.dtype), stream())
+             *dims, ctx.ignore_index, N.dtype_code(logits.dtype), stream())
         return d, None, None, None, None
 
 
@@ -3325,9 +3343,8 @@ class LovaszSoftmaxFn(Function):
         chunk = int(lovasz_chunk_classes)
         ws = torch.empty(N.lib().tss_lovasz_workspace_bytes(B * H * W, C, chunk), dtype=torch.uint8, device=dev)
         out = torch.empty(2, dtype=torch.float32, device=dev)              # loss, number of present classes
-        has_ignore = ignore_index is not None
         call('tss_lovasz_fwd', ptr(logits), ptr(target), ptr(ws), ptr(out[0:1]), ptr(out[1:2]), B, C, H * W,
-             int(ignore_index) if has_ignore else 0, int(has_ignore), LOVASZ_VARIANTS[variant], chunk, code, stream())
+             *_ignore_pair(ignore_index), LOVASZ_VARIANTS[variant], chunk, code, stream())
         ctx.chunk = chunk
         ctx.save_for_backward(logits, target, ws, out)
         return out[0].clone()
@@ -3335,10 +3352,8 @@ class LovaszSoftmaxFn(Function):
     @staticmethod
     def backward(ctx, gout):
         logits, target, ws, out = ctx.saved_tensors
-        B, C, H, W = logits.shape
-        gout = gout.to(torch.float32).contiguous()
-        d = torch.empty_like(logits)
-        call('tss_lovasz_bwd', ptr(logits), ptr(target), ptr(ws), ptr(out[1:2]), ptr(gout), ptr(d), B, C, H * W,
+        gout, d, dims = _open_backward(logits, gout)
+        call('tss_lovasz_bwd', ptr(logits), ptr(target), ptr(ws), ptr(out[1:2]), ptr(gout), ptr(d), *dims,
              ctx.chunk, N.dtype_code(logits.dtype), stream())
         return d, None, None, None
 
@@ -3355,11 +3370,8 @@ def lovasz_softmax_loss(input, target, num_classes, ignore_index=None, variant='
     leaves ties unspecified), which keeps the step bit-reproducible; and when no class is present (e.g. every pixel
     ignored) the loss is 0.0 with a zero gradient, without a host read-back, where the reference raises from
     torch.stack([])."""
-    if variant not in LOVASZ_VARIANTS:
-        raise ValueError("variant must be 'reference' or 'berman', got %r" % (variant,))
-    if input.dim() != 4 or int(num_classes) != input.shape[1]:
-        raise ValueError('num_classes (%s) must equal the channel count of the (B,C,H,W) logits %s'
-                         % (num_classes, tuple(input.shape)))
+    _check_variant(variant, LOVASZ_VARIANTS)
+    _check_num_classes(input, num_classes)
     return LovaszSoftmaxFn.apply(input, target, ignore_index, variant)
 
 
@@ -3368,8 +3380,7 @@ class LovaszSoftmaxLoss(torch.nn.Module):
 
     def __init__(self, num_classes, ignore_index=-100, variant='reference'):
         super().__init__()
-        if variant not in LOVASZ_VARIANTS:
-            raise ValueError("variant must be 'reference' or 'berman', got %r" % (variant,))
+        _check_variant(variant, LOVASZ_VARIANTS)
         self.num_classes, self.ignore_index, self.variant = num_classes, ignore_index, variant
 
     def forward(self, input, target):
@@ -3394,10 +3405,8 @@ class FocalFn(Function):
         coef = torch.empty((B, H, W), dtype=torch.float32, device=dev)     # per-pixel gradient coefficient, 0 outside the valid set
         ws = torch.empty(N.lib().tss_focal_workspace_bytes(B, H * W, cap), dtype=torch.uint8, device=dev)
         out = torch.empty(2, dtype=torch.float32, device=dev)              # loss, alpha / number of valid pixels
-        has_ignore = ignore_index is not None
         call('tss_focal_fwd', ptr(logits), ptr(target), ptr(lse), ptr(coef), ptr(ws), ptr(out[0:1]), ptr(out[1:2]), B, C, H * W,
-             int(ignore_index) if has_ignore else 0, int(has_ignore), float(alpha), float(gamma), FOCAL_VARIANTS[variant], cap,
-             N.dtype_code(logits.dtype), stream())
+             *_ignore_pair(ignore_index), float(alpha), float(gamma), FOCAL_VARIANTS[variant], cap, N.dtype_code(logits.dtype), stream())
         ctx.cap = cap
         ctx.save_for_backward(logits, target, lse, coef, out)
         return out[0].clone()
@@ -3405,10 +3414,8 @@ class FocalFn(Function):
     @staticmethod
     def backward(ctx, gout):
         logits, target, lse, coef, out = ctx.saved_tensors
-        B, C, H, W = logits.shape
-        gout = gout.to(torch.float32).contiguous()
-        d = torch.empty_like(logits)
-        call('tss_focal_bwd', ptr(logits), ptr(target), ptr(lse), ptr(coef), ptr(out[1:2]), ptr(gout), ptr(d), B, C, H * W,
+        gout, d, dims = _open_backward(logits, gout)
+        call('tss_focal_bwd', ptr(logits), ptr(target), ptr(lse), ptr(coef), ptr(out[1:2]), ptr(gout), ptr(d), *dims,
              ctx.cap, N.dtype_code(logits.dtype), stream())
         return d, None, None, None, None, None
 
@@ -3424,8 +3431,7 @@ def focal_loss(input, target, alpha=0.25, gamma=2.0, ignore_index=-100, variant=
     Two documented differences from the reference: ignore_index=None keeps every in-range pixel, where the reference
     raises a TypeError from nll_loss; and with no valid pixel the loss is 0.0 with a zero gradient, without a host
     read-back, where the reference returns nan."""
-    if variant not in FOCAL_VARIANTS:
-        raise ValueError("variant must be 'reference' or 'lin', got %r" % (variant,))
+    _check_variant(variant, FOCAL_VARIANTS)
     if not float(gamma) >= 0.0:
         raise ValueError('gamma must be >= 0, got %r' % (gamma,))
     return FocalFn.apply(input, target, alpha, gamma, ignore_index, variant)
@@ -3437,8 +3443,7 @@ class FocalLoss(torch.nn.Module):
 
     def __init__(self, alpha=0.25, gamma=2.0, ignore_index=None, variant='reference'):
         super().__init__()
-        if variant not in FOCAL_VARIANTS:
-            raise ValueError("variant must be 'reference' or 'lin', got %r" % (variant,))
+        _check_variant(variant, FOCAL_VARIANTS)
         self.alpha, self.gamma, self.ignore_index, self.variant = alpha, gamma, ignore_index, variant
 
     def forward(self, input, target):
@@ -3464,9 +3469,8 @@ class DiceFn(Function):
         lse = torch.empty((B, H, W), dtype=torch.float32, device=dev)
         ws = torch.empty(N.lib().tss_dice_workspace_bytes(B, C, H * W, cap), dtype=torch.uint8, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        has_ignore = ignore_index is not None
-        ign = (int(ignore_index) if has_ignore else 0, int(has_ignore))
-        call('tss_dice_fwd', ptr(logits), ptr(target), ptr(lse), ptr(ws), ptr(loss), B, C, H * W, ign[0], ign[1], float(smooth), cap,
+        ign = _ignore_pair(ignore_index)
+        call('tss_dice_fwd', ptr(logits), ptr(target), ptr(lse), ptr(ws), ptr(loss), B, C, H * W, *ign, float(smooth), cap,
              N.dtype_code(logits.dtype), stream())
         ctx.cap, ctx.ign = cap, ign
         ctx.save_for_backward(logits, target, lse, ws)
@@ -3475,10 +3479,8 @@ class DiceFn(Function):
     @staticmethod
     def backward(ctx, gout):
         logits, target, lse, ws = ctx.saved_tensors
-        B, C, H, W = logits.shape
-        gout = gout.to(torch.float32).contiguous()
-        d = torch.empty_like(logits)
-        call('tss_dice_bwd', ptr(logits), ptr(target), ptr(lse), ptr(ws), ptr(gout), ptr(d), B, C, H * W, ctx.ign[0], ctx.ign[1],
+        gout, d, dims = _open_backward(logits, gout)
+        call('tss_dice_bwd', ptr(logits), ptr(target), ptr(lse), ptr(ws), ptr(gout), ptr(d), *dims, *ctx.ign,
              ctx.cap, N.dtype_code(logits.dtype), stream())
         return d, None, None, None
 
@@ -3493,9 +3495,7 @@ def dice_loss(input, target, num_classes, smooth=1.0, ignore_index=-100):
     a pixel is valid iff target != ignore_index and 0 <= target < num_classes, the rule of every loss here
     (ignore_index=None: every in-range pixel).  With no valid pixel the loss is 0.0 with a zero gradient (also for
     smooth=0), without a host read-back.  num_classes must equal the channel count, at most 256."""
-    if input.dim() != 4 or int(num_classes) != input.shape[1]:
-        raise ValueError('num_classes (%s) must equal the channel count of the (B,C,H,W) logits %s'
-                         % (num_classes, tuple(input.shape)))
+    _check_num_classes(input, num_classes)
     if not float(smooth) >= 0.0:
         raise ValueError('smooth must be >= 0, got %r' % (smooth,))
     return DiceFn.apply(input, target, smooth, ignore_index)
