@@ -1,4 +1,5 @@
-"""Exact-operand f64 references for the bf16 convolution kernels (tests/test_exact_bounds.py, tests/test_gpu_zoo_exact.py).
+"""Exact-operand f64 references for the bf16 convolution kernels (tests/test_exact_bounds.py, tests/test_gpu_zoo_exact.py,
+tests/test_gpu_dw_exact.py).
 
 Every operand is a DYADIC bf16 value, +-(1 + k/128) * 2^e with e in [-4, 2): 8 significant bits.  BatchNorm scales are powers of two in
 [1/2, 4], the backward pair (ga, gb) powers of two in [1/4, 2] and [2^-6, 2^-3].  Then the on-load transforms of the kernels
@@ -11,9 +12,16 @@ than 24 bits.  The only rounding before the MFMA is then the f32 -> bf16 convers
 reproduce bit for bit.  What is left between a kernel and the f64 reference is its f32 accumulation order and the final bf16 rounding,
 which the bounds below cover as worst cases, elementwise.
 
-Unit roundoff: u = 2^-24 for f32, 2^-9 for bf16 (half an ulp of an 8-bit significand).  For n terms summed in f32 in ANY order (a chain,
+Unit roundoff: u = 2^-24 for f32, 2^-8 for bf16 (half an ulp of an 8-bit significand, relative to the value).  For n terms summed in f32 in ANY order (a chain,
 a tree, MFMA partial sums, atomics) |fl(sum) - sum| <= gamma_n * sum|terms| with gamma_n = n u / (1 - n u) <= 2 n u = 2^-23 n for
-n u <= 1/2, n the longest chain of roundings a term goes through."""
+n u <= 1/2, n the longest chain of roundings a term goes through.
+
+The depthwise 3x3 family (csrc/dwconv.hip, dwroll.hip, updw.hip; tests/test_gpu_dw_exact.py) does not feed the matrix unit: its
+activated operand a and backward operand g stay f32 and its weights are f32.  Its references therefore use the UNROUNDED f64 a and g
+(act_f32 / gcomb_f32, still exact in f32 under the dyadic premise), its products are no longer exact (24 x 8 bits forward, up to
+24 x 24 in the weight gradient: one more rounding per term unless the compiler contracts it into an FMA, which no bound relies on), and
+the chain helpers at the end of this file restate each kernel's planner.  tss_updw_* rounds the interpolated pixel to bf16 as the
+materialised upsampled tensor would have been: bilinear_ref / upsampled_operand."""
 import math
 
 import torch
@@ -83,6 +91,29 @@ def gcomb(e, y=None, ga=None, gb=None, gce=None, gmu=None):
     return e
 
 
+def exact_f32(v):
+    """v (f64) as it is, after checking that f32 holds it exactly (the dyadic premise of the unrounded operands)"""
+    assert torch.equal(v.float().double(), v), 'operand not exact in f32: the dyadic premise is broken'
+    return v
+
+
+def act_f32(x, mean=None, scale=None, bias=None, relu=False):
+    """the activated operand of the depthwise kernels: the f64 transform (exact in f32) and ReLU, NOT rounded to bf16"""
+    a = pre_act(x, mean, scale, bias)
+    if relu:
+        a = a.clamp_min(0.0)
+    return exact_f32(a)
+
+
+def gcomb_f32(e, y=None, ga=None, gb=None, gce=None, gmu=None):
+    """the backward operand of the depthwise kernels: ga (e - gce) + gb (y - gmu) (or ga e, or e), exact in f32, NOT rounded"""
+    if y is not None:
+        return exact_f32(ga * (e - gce) + gb * (y - gmu))
+    if ga is not None:
+        return exact_f32(ga * e)
+    return e
+
+
 def plant_zeros(x, mean, scale, bias, gen, frac=0.03):
     """set a fraction of x to mean - bias / scale where that is a dyadic bf16 value: the pre-activation is an exact 0 there"""
     z = mean - bias / scale
@@ -106,10 +137,20 @@ def nchw_to_rows(t):
 def conv_excess(out, ref, S, K):
     """forward / backward-data / transposed: |out - ref| <= 2^-8 |ref| + 2^-22 K S elementwise (S includes |bias|).
     The kernel's f32 sum v of K products (exact: 8 x 8-bit significands) and the bias obeys |v - ref| <= gamma_(K+1) S <= 2^-23 (K+1) S; the
-    bf16 rounding adds at most 2^-9 |v| <= 2^-9 (|ref| + 2^-23 (K+1) S).  Together <= 2^-9 |ref| + 2^-22 K S for K >= 2 -- the bound
-    keeps a factor 2 on the |ref| term, which no rounding consumes.  Returns max(|out - ref| - bound) (<= 0: within the bound)."""
+    bf16 rounding adds at most 2^-8 |v| <= 2^-8 (|ref| + 2^-23 (K+1) S).  Together <= 2^-8 |ref| + 2^-22 K S for K >= 2.
+    Returns max(|out - ref| - bound) (<= 0: within the bound).
+    Depthwise kernels (K = 9 taps, f32 weights, f32 a / g): a product is rounded too, so a term goes through at most 1 + 9 roundings
+    (2 K = 18 if every partial sum of a split accumulation is counted): |v - ref| <= gamma_18 S, and rounding v to bf16 (8 significant
+    bits: half an ulp is at most 2^-8 |v|) adds <= 2^-8 |ref| + 2^-8 gamma_18 S.  Together <= 2^-8 |ref| + gamma_18 (1 + 2^-8) S, and
+    gamma_18 (1 + 2^-8) = 18 u (1 + 2^-8) / (1 - 18 u) < 2^-24 18.1 < 2^-22 9: conv_excess(out, ref, S, 9) still holds, with nothing
+    to spare on the |ref| term (a result off by one bf16 ulp where the exact value is not near a tie fails)."""
     bound = 2.0 ** -8 * ref.abs() + 2.0 ** -22 * K * S
     return ((out - ref).abs() - bound).max().item()
+
+
+def f32_excess(out, ref, S, K):
+    """an f32 instance of a depthwise kernel (f32 activations, nothing rounded to bf16): |out - ref| <= gamma_2K S <= 2^-22 K S"""
+    return ((out - ref).abs() - 2.0 ** -22 * K * S).max().item()
 
 
 def wgrad_excess(dw, ref, S, chain):
@@ -166,23 +207,29 @@ def generic_wgrad_chain(P, K, N, ntaps):
 
 
 # ---------------------------------------------------------------------------------------------------------- references
-def conv_ref(a, w, stride=1, padding=0, dilation=1):
+def conv_ref(a, w, stride=1, padding=0, dilation=1, groups=1):
     """(reference, its absolute twin) of conv2d in f64"""
     F = torch.nn.functional
-    return (F.conv2d(a, w, stride=stride, padding=padding, dilation=dilation),
-            F.conv2d(a.abs(), w.abs(), stride=stride, padding=padding, dilation=dilation))
+    return (F.conv2d(a, w, stride=stride, padding=padding, dilation=dilation, groups=groups),
+            F.conv2d(a.abs(), w.abs(), stride=stride, padding=padding, dilation=dilation, groups=groups))
 
 
-def conv_input_ref(shape, w, g, stride=1, padding=0, dilation=1):
+def conv_input_ref(shape, w, g, stride=1, padding=0, dilation=1, groups=1):
     G = torch.nn.grad
-    return (G.conv2d_input(shape, w, g, stride=stride, padding=padding, dilation=dilation),
-            G.conv2d_input(shape, w.abs(), g.abs(), stride=stride, padding=padding, dilation=dilation))
+    return (G.conv2d_input(shape, w, g, stride=stride, padding=padding, dilation=dilation, groups=groups),
+            G.conv2d_input(shape, w.abs(), g.abs(), stride=stride, padding=padding, dilation=dilation, groups=groups))
 
 
-def conv_weight_ref(a, wshape, g, stride=1, padding=0, dilation=1):
+def conv_weight_ref(a, wshape, g, stride=1, padding=0, dilation=1, groups=1):
     G = torch.nn.grad
-    return (G.conv2d_weight(a, wshape, g, stride=stride, padding=padding, dilation=dilation),
-            G.conv2d_weight(a.abs(), wshape, g.abs(), stride=stride, padding=padding, dilation=dilation))
+    return (G.conv2d_weight(a, wshape, g, stride=stride, padding=padding, dilation=dilation, groups=groups),
+            G.conv2d_weight(a.abs(), wshape, g.abs(), stride=stride, padding=padding, dilation=dilation, groups=groups))
+
+
+def dw_refs(a, w, gop, xshape, stride, dil):
+    """((forward, S), (input gradient, S), (weight gradient, S)) of a depthwise 3x3 layer, padding = dilation, in f64"""
+    kw = dict(stride=stride, padding=dil, dilation=dil, groups=w.shape[0])
+    return conv_ref(a, w, **kw), conv_input_ref(xshape, w, gop, **kw), conv_weight_ref(a, w.shape, gop, **kw)
 
 
 def convT_ref(x, w, stride=2, padding=1, output_padding=1):
@@ -195,3 +242,190 @@ def tap_geom(T, axis, dil):
     """(kernel shape, padding, dilation) of a T-tap layer along W (axis 0) or H (axis 1), padding = dilation (T - 1) / 2"""
     p = dil * (T - 1) // 2
     return ((1, T), (0, p), (1, dil)) if axis == 0 else ((T, 1), (p, 0), (dil, 1))
+
+
+# ---------------------------------------------------------------------------------------------------------- depthwise 3x3 family
+STAT_SLABS = 512          # TSS_STAT_SLABS (csrc/common.h): statistics slab rows, and the grid cap of the depthwise kernels
+DW_NT = 256               # NT_MAX of csrc/dwconv.hip, NT of dwroll.hip / updw.hip
+DW_SW = 4                 # SW: pixels of a strip (csrc/dwconv.hip)
+RED_WAVES = 16            # waves of dw_reduce_kernel / dw_reduce_many_kernel
+
+
+def reduce_chain(rows, waves=RED_WAVES):
+    """dw_reduce_block / dw_reduce_block4 (csrc/dwconv.hip): a lane of wave w adds rows w, w + waves, ... (ceil(rows / waves)
+    additions), one thread adds the waves' partial sums, and the total is added to dw"""
+    return cdiv(rows, waves) + waves + 1
+
+
+def dw_sweep(B, H, W, C, strip, dil=1):
+    """geometry() + tss::persistent_blocks + xcd_tiles (csrc/dwconv.hip, common.h) of a launch over a [B][H][W] grid: (NPL lane items
+    per tile, grid = workspace / slab rows written, tiles per block, waves per block).  Lane items are pixels (generic kernels) or
+    4-pixel strips; the host sizes the grid by B H ceil(W / 4) strips, the stride-1 strip kernels walk ceil(W / 4 dil) dil interleaved
+    strips per row (more at dilation 4 when W is ragged).  The tiles are dealt to 8 XCD ranges of ceil(ntiles / 8), each shared by
+    grid / 8 blocks"""
+    CV = C // 8
+    NPL = DW_NT // CV
+    host_units = B * H * (cdiv(W, DW_SW) if strip else W)
+    units = B * H * cdiv(W, DW_SW * dil) * dil if strip else host_units
+    grid = cdiv(min(max(cdiv(host_units, NPL), 1), STAT_SLABS), 8) * 8
+    return NPL, grid, cdiv(cdiv(cdiv(units, NPL), 8), grid // 8), cdiv(CV * NPL, 64)
+
+
+def dw_strip_pair(stride, dil):
+    """strip_supported (csrc/dwconv.hip)"""
+    return (stride, dil) in ((1, 1), (2, 1), (1, 4))
+
+
+def dw_stats_chain(B, H, W, C, strip, dil=1):
+    """f32 chain of one lane's statistics in dw_fwd_kernel / dw_bwd_data_kernel / their strip forms (bf16 instances; the f32
+    instances add in f64): one value per pixel of every tile the block owns, 4 per strip; flush_stats then adds in f64"""
+    _, _, tpb, _ = dw_sweep(B, H, W, C, strip, dil)
+    return tpb * (DW_SW if strip else 1)
+
+
+def dw_wgrad_chain(B, Ho, Wo, C, strip, dil=1, lead_waves=None, rows=None):
+    """dw_bwd_weight_kernel / dw_bwd_weight_strip_kernel / dw_bwd_data_strip_kernel<WG> (the latter over the INPUT grid) + the row
+    reduction: a lane adds one product per pixel it owns to each tap's accumulator (2 roundings each: the product, the addition), the
+    block adds its NPL lanes through LDS, and the rows are added by dw_reduce_kernel (16 waves), tss_dw_reduce_many (16) or the lead
+    blocks of tss_dwconv3x3_bwd_data (lead_waves = the sweeping kernel's waves per block)"""
+    NPL, grid, tpb, _ = dw_sweep(B, Ho, Wo, C, strip, dil)
+    return 2 * tpb * (DW_SW if strip else 1) + NPL + reduce_chain(grid if rows is None else rows, lead_waves or RED_WAVES)
+
+
+def roll_plan(B, Ho, Wo, C, stride, lanes_per_slice=8, rpj=1):
+    """plan (lanes_per_slice 8: dw_fwd_roll_kernel, 8 channels per lane) and plan_bwd (16: the backward kernels, 4 channels per lane;
+    rpj = input rows per step) of csrc/dwroll.hip: column strips of PXL pixels x row segments of RS output rows x 64-channel slices;
+    rows_used blocks per slice, each owning k = ceil(units / rows_used) units"""
+    cv = C // (64 // lanes_per_slice)
+    nsl = cdiv(C, 64)
+    CVS = min(cv, lanes_per_slice)
+    PXL = DW_NT // CVS
+    nstrips = cdiv(Wo, PXL)
+    cap = max(STAT_SLABS // nsl, 1)
+    halo = 2 if stride == 1 else 1
+    best = None
+    for nseg in range(1, Ho + 1):
+        RS = cdiv(Ho, nseg)
+        if RS < 4 and nseg > 1:
+            break
+        segs = cdiv(Ho, RS)
+        units = B * nstrips * segs
+        k = cdiv(units, cap)
+        cost = k * (cdiv(RS + halo, rpj) * rpj) + 6
+        if best is None or cost < best['cost']:
+            best = dict(cost=cost, RS=RS, nseg=segs, units=units, k=k, rows_used=cdiv(units, k))
+    best.update(nsl=nsl, CVS=CVS, PXL=PXL, nstrips=nstrips)
+    best['k'] = cdiv(best['units'], best['rows_used'])
+    return best
+
+
+def roll_stats_chain(plan, channels_per_lane, per_row=1):
+    """a lane of a row-pipelined kernel adds one value per output row of every unit it owns (per_row = 4 in dw_bwd_roll_s2_kernel: the
+    2 x 2 input pixels under an output pixel), then flush_slab adds ceil(PXL / share) lanes in f32, share = 256 / (2 CVS channels
+    per lane) threads per column, before the f64 sum"""
+    share = DW_NT // (2 * plan['CVS'] * channels_per_lane)
+    return plan['k'] * plan['RS'] * per_row + cdiv(plan['PXL'], share)
+
+
+def roll_wgrad_chain(plan, rows=None):
+    """dw_bwd_roll_s1_kernel / dw_bwd_roll_s2_kernel: per tap one product per owned output row of every unit (2 roundings each), PXL
+    lanes through LDS, then the rows_used rows by dw_reduce_kernel / tss_dw_reduce_many"""
+    return 2 * plan['k'] * plan['RS'] + plan['PXL'] + reduce_chain(plan['rows_used'] if rows is None else rows)
+
+
+def updw_geometry(B, Hs, Ws, Ho, Wo, C, D, px, halo, budgets, max_units):
+    """geometry() of csrc/updw.hip (px = 32, halo = D, budgets 40 K then 56 K, 512 units forward; px = 16, halo 0, 36 K, 8192 units
+    backward): segments per residue class such that a unit's source tile fits the LDS budget.  Its two scales are f32 quotients"""
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+    sy = (f32(Hs - 1) / f32(Ho - 1)) if Ho > 1 else f32(0.0)
+    sx = (f32(Ws - 1) / f32(Wo - 1)) if Wo > 1 else f32(0.0)
+    nstrips = cdiv(Wo, px)
+    ncols = min(int(f32(px + 2 * halo - 1) * sx) + 4, Ws)
+    njmax = cdiv(Ho, D)
+    for budget in budgets:
+        for nseg in range(1, njmax + 1):
+            steps = cdiv(njmax, nseg)
+            nrows = min(int(f32((steps + 3) * D) * sy) + 4, Hs)
+            units = B * nstrips * D * nseg
+            if units > max_units:
+                break
+            if nrows * ncols * 128 <= budget:
+                return dict(nseg=nseg, seg_steps=steps, nunits=units, nstrips=nstrips)
+    return None
+
+
+def updw_fwd_geometry(B, Hs, Ws, Ho, Wo, C, D):
+    return updw_geometry(B, Hs, Ws, Ho, Wo, C, D, 32, D, (40 * 1024, 56 * 1024), STAT_SLABS)
+
+
+def updw_bwd_geometry(B, Hs, Ws, Ho, Wo, C, D):
+    return updw_geometry(B, Hs, Ws, Ho, Wo, C, D, 16, 0, (36 * 1024,), 8192)
+
+
+def updw_stats_chain(geo):
+    """updw_fwd_kernel: a lane adds the seg_steps rows its unit owns in f32; the unit's 32 pixel lanes meet in f64"""
+    return geo['seg_steps']
+
+
+def updw_wgrad_chain(geo):
+    """updw_bwd_kernel + tss_dw_reduce_many: per tap one product per owned class row (2 roundings each), BPX = 16 pixel lanes through
+    LDS, then the nunits workspace rows"""
+    return 2 * geo['seg_steps'] + 16 + reduce_chain(geo['nunits'])
+
+
+def bilinear_matrix(n_in, n_out):
+    """[n_out][n_in] f64 weights of bilinear interpolation with align_corners=True: source coordinate dst (n_in - 1) / (n_out - 1)"""
+    M = torch.zeros(n_out, n_in, dtype=torch.float64)
+    for d in range(n_out):
+        src = d * (n_in - 1) / (n_out - 1) if n_out > 1 else 0.0
+        i0 = min(int(math.floor(src)), n_in - 1)
+        i1 = min(i0 + 1, n_in - 1)
+        M[d, i0] += 1.0 - (src - i0)
+        M[d, i1] += src - i0
+    return M
+
+
+def ac_taps_f32(n_in, n_out):
+    """ac_scale / ac_tap of csrc/common.h, as updw.hip's lerp_store and lerp use them, step by step in f32: [(i0, i1, l0, l1)] per
+    destination index"""
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+    scale = f32(n_in - 1) / f32(n_out - 1) if n_out > 1 else f32(0.0)
+    taps = []
+    for dst in range(n_out):
+        src = scale * f32(dst)
+        i0 = min(int(src), n_in - 1)
+        i1 = i0 + (1 if i0 < n_in - 1 else 0)
+        l1 = src - f32(i0)
+        taps.append((i0, i1, f32(1.0) - l1, l1))
+    return taps
+
+
+def dyadic_resize(n_in, n_out):
+    """n_out - 1 = 2^k (n_in - 1): then ac_scale / ac_tap (csrc/common.h) -- scale = fl((n_in - 1) / (n_out - 1)) = 2^-k, src = scale *
+    dst, i0 = (int)src, l1 = src - i0, l0 = 1 - l1 -- are all exact in f32 and equal bilinear_matrix's weights (multiples of 2^-k):
+    ac_taps_f32 against bilinear_matrix in tests/test_exact_bounds.py"""
+    if n_in == 1:
+        return True
+    q, r = divmod(n_out - 1, n_in - 1)
+    return r == 0 and q >= 1 and (q & (q - 1)) == 0
+
+
+def upsampled_operand(x, Ho, Wo):
+    """(bf16-rounded upsampled map, its unrounded f64 value) of x [B][C][Hs][Ws]: the operand bits tss_updw_* forms on load"""
+    My, Mx = bilinear_matrix(x.shape[2], Ho), bilinear_matrix(x.shape[3], Wo)
+    v = torch.einsum('oh,bchw,pw->bcop', My, x, Mx)
+    return v.float().to(torch.bfloat16).double(), v
+
+
+def bilinear_f32_slack(x, Ho, Wo):
+    """bound on |v_kernel - v| of one interpolated pixel BEFORE its bf16 rounding when the size pair is not dyadic, from ac_tap /
+    lerp_store (csrc/common.h, updw.hip), u = 2^-24, M = max|x|:
+      coordinates  scale = fl((n_in - 1) / (n_out - 1)) and src = fl(scale dst) are off by <= 2 u src (1 + u) = 2^-23 (1 + u) src, taken
+                   as <= 2^-22 (n_in - 1) (a deliberate factor 2: it is dwarfed by the 2^-8 rounding of the operand that follows); the
+                   blend is continuous and piecewise linear in src with slope <= 2 M per axis (|x[i + 1] - x[i]| <= 2 M), also across
+                   an integer, where (int)src changes and l1 jumps between ~1 and ~0: <= 2^-21 M (n_in - 1) per axis;
+      weights      l1 = src - i0 is exact (Sterbenz), l0 = fl(1 - l1) is off by <= u;
+      blend        l0y (l0x a + l1x b) + l1y (l0x c + l1x d): every value goes through <= 5 roundings (two products, two sums, or an
+                   FMA fewer) plus the weight's: <= gamma_6 sum of |weight products| M <= 2^-21 M (the weights sum to <= 1 + 2 u).
+    Together <= 2^-21 M (Hs + Ws)"""
+    return 2.0 ** -21 * float(x.abs().max()) * (x.shape[2] + x.shape[3])

@@ -185,3 +185,190 @@ def test_statistics_slabs_meet_the_bound_and_a_row_not_zeroed_fails():
     assert not (X.stats_excess(slabs.sum(0), terms, chain) <= 0)
     slabs[rows + 3] = slabs[0]                                                  # a stale row from an earlier call
     assert X.stats_excess(slabs.sum(0), terms, chain) > 0
+
+
+# ---------------------------------------------------------------------------------------------------------- depthwise 3x3 family
+# f32 emulation of csrc/dwconv.hip / dwroll.hip: unrounded f32 operands a and g, f32 weights, every product rounded on its own (no FMA)
+# and added to a running f32 sum tap by tap; the weight gradient per (image, row segment) block -- a lane per column adds its rows, the
+# block adds its lanes one after the other, the rows are added one after the other onto dW
+def _dw_tap(a, ky, kx, stride, dil, Ho, Wo):
+    """a [B][C][H][W] read at (oy stride + (ky - 1) dil, ox stride + (kx - 1) dil) for every output pixel, zero outside"""
+    B, C, H, W = a.shape
+    pad = torch.zeros(B, C, H + 2 * dil, W + 2 * dil, dtype=a.dtype)
+    pad[:, :, dil:dil + H, dil:dil + W] = a
+    y0, x0 = ky * dil, kx * dil
+    return pad[:, :, y0:y0 + (Ho - 1) * stride + 1:stride, x0:x0 + (Wo - 1) * stride + 1:stride]
+
+
+def _dw_case(seed, B=2, C=16, H=11, W=19, stride=1, relu=True):
+    g = _gen(seed)
+    mean, bias, scale = X.dyadic((1, C, 1, 1), g), X.dyadic((1, C, 1, 1), g), X.pow2((1, C, 1, 1), g, 0.5, 4)
+    x = X.plant_zeros(X.dyadic((B, C, H, W), g), mean, scale, bias, g, 0.05)
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    w = (torch.randn((C, 1, 3, 3), generator=g) * 0.25).double()                       # f32 weights with all 24 bits in use
+    e, y = X.dyadic((B, C, Ho, Wo), g), X.dyadic((B, C, Ho, Wo), g)
+    ga, gb = X.pow2((1, C, 1, 1), g, 0.25, 2), X.pow2((1, C, 1, 1), g, 2.0 ** -6, 2.0 ** -3)
+    gce, gmu = X.dyadic((1, C, 1, 1), g), X.dyadic((1, C, 1, 1), g)
+    a = X.act_f32(x, mean, scale, bias, relu)
+    gop = X.gcomb_f32(e, y, ga, gb, gce, gmu)
+    mask = (X.pre_act(x, mean, scale, bias) > 0).double() if relu else torch.ones_like(x)
+    mask_ge = (X.pre_act(x, mean, scale, bias) >= 0).double()
+    return dict(x=x, a=a, w=w, gop=gop, mask=mask, mask_ge=mask_ge, Ho=Ho, Wo=Wo, C=C, stride=stride)
+
+
+def _dw_fwd_emulated(a, w, stride, dil, Ho, Wo, defect=None, strip=8):
+    a32, w32 = a.float(), w.float()
+    acc = torch.zeros(a.shape[0], a.shape[1], Ho, Wo)
+    for ky in range(3):
+        for kx in range(3):
+            src = _dw_tap(a32, ky, kx, stride, dil, Ho, Wo).clone()
+            if defect == 'halo' and kx == 2:
+                # the right halo column of the last, ragged strip: clamped to the row's last pixel and not masked
+                assert Wo % strip != 0 and stride == 1 and dil == 1
+                src[..., Wo - 1] = _dw_tap(a32, ky, 1, stride, dil, Ho, Wo)[..., Wo - 1]
+            acc = acc + src * w32[:, 0, ky, kx].view(1, -1, 1, 1)
+    return acc
+
+
+def _dw_bwd_data_emulated(gop, w, shape, stride, dil, mask, defect=None):
+    """input gradient as the kernels gather it: per input pixel, the flipped taps over the output pixels that reach it"""
+    B, C, H, W = shape
+    Ho, Wo = gop.shape[2:]
+    g32, w32 = gop.float(), w.float().clone()
+    if defect == 'mirror_tap':
+        w32[:, 0, 1, 0], w32[:, 0, 1, 2] = w32[:, 0, 1, 2].clone(), w32[:, 0, 1, 0].clone()
+    up = torch.zeros(B, C, (Ho - 1) * stride + 1 + 2 * dil, (Wo - 1) * stride + 1 + 2 * dil)      # g on the input grid, zero between
+    up[:, :, dil:dil + (Ho - 1) * stride + 1:stride, dil:dil + (Wo - 1) * stride + 1:stride] = g32
+    full = torch.zeros(B, C, max(H, (Ho - 1) * stride + 1) + 2 * dil, max(W, (Wo - 1) * stride + 1) + 2 * dil)
+    full[:, :, :up.shape[2], :up.shape[3]] = up
+    acc = torch.zeros(B, C, H, W)
+    for ky in range(3):
+        for kx in range(3):
+            y0, x0 = (2 - ky) * dil, (2 - kx) * dil                     # input pixel (iy, ix) sees output position iy - (ky - 1) dil
+            acc = acc + full[:, :, y0:y0 + H, x0:x0 + W] * w32[:, 0, ky, kx].view(1, -1, 1, 1)
+    return acc * mask.float()
+
+
+def _dw_wgrad_emulated(a, gop, stride, dil, RS, defect=None):
+    """(dW [C][1][3][3] in f32, its chain): blocks = (image, segment of RS output rows); a lane per output column"""
+    B, C, Ho, Wo = gop.shape
+    a32, g32 = a.float(), gop.float()
+    nseg = -(-Ho // RS)
+    rows = []
+    for b in range(B):
+        for s in range(nseg):
+            o0, o1 = s * RS, min(Ho, (s + 1) * RS)
+            if defect == 'row_twice' and s > 0:
+                o0 -= 1                                                  # the boundary row of the segment above is counted again
+            part = torch.zeros(C, 3, 3)
+            for ky in range(3):
+                for kx in range(3):
+                    src = _dw_tap(a32, ky, kx, stride, dil, Ho, Wo)[b]
+                    lane = torch.zeros(C, Wo)
+                    for o in range(o0, o1):
+                        lane = lane + g32[b, :, o] * src[:, o]
+                    tot = torch.zeros(C)
+                    for p in range(Wo):
+                        tot = tot + lane[:, p]
+                    part[:, ky, kx] = tot
+            rows.append(part)
+    dw = torch.zeros(C, 3, 3)
+    for r in rows:
+        dw = dw + r
+    return dw.reshape(C, 1, 3, 3), 2 * RS + Wo + len(rows)
+
+
+def _dw_refs(c, dil):
+    return X.dw_refs(c['a'], c['w'], c['gop'], c['x'].shape, c['stride'], dil)
+
+
+DW_GEOMS = [(1, 1), (2, 1), (1, 4), (2, 2), (1, 3)]
+
+
+@pytest.mark.parametrize('stride,dil', DW_GEOMS)
+def test_f32_emulation_of_the_depthwise_layer_meets_the_unrounded_operand_bounds(stride, dil):
+    c = _dw_case(stride * 10 + dil, stride=stride)
+    (ref, S), (rin, Sin), (rw, Sw) = _dw_refs(c, dil)
+    out = _dw_fwd_emulated(c['a'], c['w'], stride, dil, c['Ho'], c['Wo'])
+    assert X.f32_excess(out.double(), ref, S, 9) <= 0
+    assert X.conv_excess(X.rne_bf16(out.double()), ref, S, 9) <= 0
+    ein = _dw_bwd_data_emulated(c['gop'], c['w'], c['x'].shape, stride, dil, c['mask'])
+    assert X.f32_excess(ein.double(), rin * c['mask'], Sin * c['mask'], 9) <= 0
+    assert X.conv_excess(X.rne_bf16(ein.double()), rin * c['mask'], Sin * c['mask'], 9) <= 0
+    dw, chain = _dw_wgrad_emulated(c['a'], c['gop'], stride, dil, 4)
+    assert X.wgrad_excess(dw.double(), rw, Sw, chain) <= 0
+    # statistics of the stored bf16 outputs, a lane per column adding its rows in f32, lanes and blocks meeting in f64
+    o = X.rne_bf16(out.double())
+    terms = torch.cat([X.nchw_to_rows(o), X.nchw_to_rows(o * o)], 1)
+    lanes = torch.cat([o.float().sum(2), (o.float() * o.float()).sum(2)], 1)               # [B][2C][Wo]: f32 over the rows
+    assert X.stats_excess(lanes.double().sum((0, 2)), terms, c['Ho']) <= 0
+
+
+@pytest.mark.parametrize('defect', ['halo', 'row_twice', 'mask_ge', 'mirror_tap', 'stats_row'])
+def test_one_realistic_depthwise_defect_fails_the_bound(defect):
+    stride = 2 if defect == 'mirror_tap' else 1
+    c = _dw_case(40 + len(defect), stride=stride)
+    (ref, S), (rin, Sin), (rw, Sw) = _dw_refs(c, 1)
+    if defect == 'halo':
+        out = _dw_fwd_emulated(c['a'], c['w'], 1, 1, c['Ho'], c['Wo'], defect=defect)
+        ex = X.conv_excess(X.rne_bf16(out.double()), ref, S, 9)
+    elif defect == 'row_twice':
+        dw, chain = _dw_wgrad_emulated(c['a'], c['gop'], 1, 1, 4, defect=defect)
+        ex = X.wgrad_excess(dw.double(), rw, Sw, chain)
+    elif defect == 'mask_ge':
+        assert (c['mask_ge'] - c['mask']).sum() > 0                      # exact zeros of the pre-activation are planted
+        ein = _dw_bwd_data_emulated(c['gop'], c['w'], c['x'].shape, 1, 1, c['mask_ge'])
+        ex = X.conv_excess(X.rne_bf16(ein.double()), rin * c['mask'], Sin * c['mask'], 9)
+    elif defect == 'mirror_tap':
+        ein = _dw_bwd_data_emulated(c['gop'], c['w'], c['x'].shape, 2, 1, c['mask'], defect=defect)
+        ex = X.conv_excess(X.rne_bf16(ein.double()), rin * c['mask'], Sin * c['mask'], 9)
+    else:
+        o = X.rne_bf16(_dw_fwd_emulated(c['a'], c['w'], 1, 1, c['Ho'], c['Wo']).double())
+        terms = torch.cat([X.nchw_to_rows(o), X.nchw_to_rows(o * o)], 1)
+        lanes = torch.cat([o.float().sum(2), (o.float() * o.float()).sum(2)], 1)
+        slabs = lanes.double().sum(2)                                     # one slab row per image
+        ex = X.stats_excess(slabs[1:].sum(0), terms, c['Ho'])             # the first block's row never arrives
+    print(defect, 'excess over the bound', ex)
+    assert ex > 0
+
+
+def test_dyadic_transforms_are_exact_in_f32_in_the_depthwise_kernels_orders():
+    """the orders of csrc/dwconv.hip / dwroll.hip / updw.hip that test_dyadic_transforms_are_exact_in_f32_in_every_order does not list:
+    sh' = fma(-mean, scale, bias) then x scale + sh' (strip and roll kernels), g = ga e + (gb y + kd) with kd = -(ga gce) - gb gmu,
+    the mask's (x - mean) scale + bias > 0 and x scale + sh' > 0, and the dyadic bilinear blend of tss_updw_*"""
+    g = _gen(11)
+    n = 1 << 18
+    f = lambda t: t.float()
+    x, mean, bias = X.dyadic((n,), g), X.dyadic((n,), g), X.dyadic((n,), g)
+    scale = X.pow2((n,), g, 0.5, 4)
+    ref = (x - mean) * scale + bias
+    shp = torch.addcmul(f(bias), -f(mean), f(scale))                       # one rounding at most: exact here
+    assert torch.equal((f(x) * f(scale) + shp).double(), ref)
+    e, y, gce, gmu = X.dyadic((n,), g), X.dyadic((n,), g), X.dyadic((n,), g), X.dyadic((n,), g)
+    ga, gb = X.pow2((n,), g, 0.25, 2), X.pow2((n,), g, 2.0 ** -6, 2.0 ** -3)
+    kd = -(f(ga) * f(gce)) - f(gb) * f(gmu)
+    assert torch.equal((f(ga) * f(e) + (f(gb) * f(y) + kd)).double(), ga * (e - gce) + gb * (y - gmu))
+    # tss_updw_*'s own coordinate formula (ac_scale / ac_tap in f32) gives exactly the f64 weights at every dyadic size pair the GPU cases
+    # use (x4, x8, x2, x1, a source of one pixel), and does not at a non-dyadic one
+    for n_in, n_out in [(5, 17), (19, 73), (42, 165), (6, 41), (3, 9), (9, 33), (4, 25), (3, 17), (5, 33), (1, 9), (1, 21), (1, 7)]:
+        assert X.dyadic_resize(n_in, n_out)
+        M = torch.zeros(n_out, n_in, dtype=torch.float64)
+        for d, (i0, i1, l0, l1) in enumerate(X.ac_taps_f32(n_in, n_out)):
+            M[d, i0] += l0.double()
+            M[d, i1] += l1.double()
+        assert torch.equal(M, X.bilinear_matrix(n_in, n_out)), (n_in, n_out)
+    assert not X.dyadic_resize(5, 18) and not X.dyadic_resize(9, 30) and not X.dyadic_resize(6, 22) and not X.dyadic_resize(7, 50)
+    M = torch.zeros(18, 5, dtype=torch.float64)
+    for d, (i0, i1, l0, l1) in enumerate(X.ac_taps_f32(5, 18)):
+        M[d, i0] += l0.double()
+        M[d, i1] += l1.double()
+    assert not torch.equal(M, X.bilinear_matrix(5, 18)) and (M - X.bilinear_matrix(5, 18)).abs().max() < 2.0 ** -20
+    # the blend at a dyadic size pair (3 -> 9 rows, 5 -> 33 columns) with the kernel's own f32 weights, in lerp_store's order
+    xs = X.dyadic((2, 3, 3, 5), g)
+    _, v = X.upsampled_operand(xs, 9, 33)
+    X.exact_f32(v)
+    for oy, (i0, i1, l0y, l1y) in enumerate(X.ac_taps_f32(3, 9)):
+        for ox, (j0, j1, l0x, l1x) in enumerate(X.ac_taps_f32(5, 33)):
+            a, b_, c_, d = (f(xs[:, :, r, q]) for r, q in ((i0, j0), (i0, j1), (i1, j0), (i1, j1)))
+            o = l0y * (l0x * a + l1x * b_) + l1y * (l0x * c_ + l1x * d)
+            assert torch.equal(o.double(), v[:, :, oy, ox])
