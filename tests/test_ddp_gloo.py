@@ -76,6 +76,25 @@ def _worker(rank, world, port, out):
     dist.destroy_process_group()
 
 
+def _group_key_worker(rank, port):
+    dist.init_process_group('gloo', init_method='tcp://127.0.0.1:%d' % port, rank=rank, world_size=1)
+    try:
+        group = dist.group.WORLD
+        assert group is dist.group.WORLD
+        assert hash(group) == hash(dist.group.WORLD)
+        table = {(group, 0): 'exchange'}
+        assert table[(dist.group.WORLD, 0)] == 'exchange' and (dist.group.WORLD, 1) not in table
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.timeout(120)
+def test_process_group_object_is_a_stable_dictionary_key():
+    """ops._XCHG is keyed by (process group, device index) with the group object itself in the key (it keeps the group alive, so
+    the key cannot alias a later group): the default group hashes, and is the same object on every access.  No IPC call is made."""
+    mp.spawn(_group_key_worker, args=(_free_port(),), nprocs=1, join=True)
+
+
 @pytest.mark.timeout(300)
 def test_two_rank_gradient_average_equals_single_process(tmp_path):
     out = str(tmp_path / 'r0.pt')

@@ -495,35 +495,153 @@ def test_half_model_runs_and_tracks_f32(name, dtype):
 def test_residual_fan_in_folded_into_the_first_layers_backward_matches_autograds_add():
     """The block input of a residual bottleneck has two consumers; ops.residual_fork hands the skip's gradient to the epilogue of
     conv1's backward-data kernel (tss_pwconv_bwd_data_radd) instead of letting autograd add the two tensors with a launch of its
-    own.  Same gradients as the unfolded graph (TSS_FOLD_RESIDUAL=0), up to one bf16 rounding of the sum."""
+    own.  Same gradients as the unfolded graph (TSS_FOLD_RESIDUAL=0), up to one bf16 rounding of the sum.  The folded run launches an
+    entry point that takes the skip's gradient, and nothing is left behind: a fork of the forward dies with the tensors and the graph."""
+    import gc
     import importlib
+    import weakref
     import torch_semantic_segmentation_amd as tssa
     from torch_semantic_segmentation_amd import ops
     F_ = importlib.import_module('torch_semantic_segmentation_amd.models.fastscnn')
+    # the entry points with a residual operand: ops._bwd_pw_sweep (radd_s) and the two folded branches of ops._pw_data_grad (radd)
+    takes_residual = {'tss_pwconv_bwd_sweep', 'tss_pwconv_bwd_data_joined', 'tss_pwconv_bwd_data_radd'}
+    sequences = []
 
     def run(fold):
         torch.manual_seed(37)
         m = F_.BottleneckModule(32, 32, expansion=6, repeats=3, stride=1).to(DEV)
         tssa.set_compute_dtype(m, torch.bfloat16)
         m.train()
-        x = torch.randn(2, 32, 24, 40, device=DEV).requires_grad_(True)
-        old = ops.fold_residual_adds
-        ops.fold_residual_adds = fold
+        x = torch.randn(2, 32, 24, 40, device=DEV).to(torch.bfloat16).requires_grad_(True)     # (a float32 input folds nothing)
+        old, orig_fork, orig_call = ops.fold_residual_adds, ops.residual_fork, ops.call
+        forks, names = [], []
+
+        def fork_spy(t):
+            r = orig_fork(t)
+            if r[2] is not None:
+                forks.append(weakref.ref(r[2]))
+            return r
+
+        def call_spy(name, *a):
+            names.append(name)
+            return orig_call(name, *a)
+        ops.fold_residual_adds, ops.residual_fork, ops.call = fold, fork_spy, call_spy
         try:
             out = ops.materialize(m(x))
             out.float().backward(torch.randn_like(out, dtype=torch.float32))
         finally:
-            ops.fold_residual_adds = old
-        assert not ops._pending_forks
-        return out.float(), x.grad.float(), {k: p.grad.float() for k, p in m.named_parameters()}
+            ops.fold_residual_adds, ops.residual_fork, ops.call = old, orig_fork, orig_call
+        res = out.detach().float(), x.grad.float(), {k: p.grad.float() for k, p in m.named_parameters()}
+        assert len(forks) == (3 if fold else 0)
+        if fold:
+            assert takes_residual & set(names), names
+        # ... of which only tss_pwconv_bwd_data_radd never runs without a fork's gradient: the first block's input is a leaf (no join
+        # in front of it), so its conv1 takes that branch of ops._pw_data_grad exactly when it took the fork off its input
+        assert (names.count('tss_pwconv_bwd_data_radd') >= 1) == fold, names
+        sequences.append(names)
+        del out
+        gc.collect()
+        assert all(ref() is None for ref in forks)       # nothing outlives the pass (there is no registry to leave an entry in)
+        return res
     o1, dx1, g1 = run(True)
     o0, dx0, g0 = run(False)
     assert torch.equal(o1, o0)
+    assert sequences[0] != sequences[1]          # the fold changes what is launched: the autograd fallback alone would not
     l2 = lambda a, b: ((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-30)).item()
     assert l2(dx1, dx0) < 1e-2
     for k in g0:
         if g0[k].norm() > 1e-3:
-            assert l2(g1[k], g0[k]) < 2e-2, k
+            ref = g0[k]
+            if k.endswith('conv1.1.weight'):
+                # the gradient of conv1's BatchNorm weight is analytically zero: a per-channel scale passes the ReLU (beta = 0) and the
+                # depthwise convolution and is removed by conv2's per-channel BatchNorm.  Both runs hold the rounding noise of
+                # sum(e * xhat) there, so the difference is held against the scale of that sum's terms, the same layer's
+                # sum(e) -- its bias gradient -- and not against the noise itself; and each run's own value, whose exact
+                # counterpart is 0, is held to the same bound (a wrong e in the folded sum would show at that scale).
+                ref = g0[k[:-len('weight')] + 'bias']
+                assert max(g1[k].double().norm().item(), g0[k].double().norm().item()) < 2e-2 * ref.double().norm().item(), k
+            assert (g1[k].double() - g0[k].double()).norm().item() < 2e-2 * ref.double().norm().item(), k
+
+
+def _bf16_nhwc_leaf(*shape):
+    from torch_semantic_segmentation_amd import ops
+    return ops.to_nhwc(torch.randn(*shape, device=DEV).to(torch.bfloat16)).requires_grad_(True)
+
+
+@pytest.mark.parametrize('maker', ['residual_fork', 'fork_two'])
+def test_an_abandoned_fork_note_dies_with_its_tensor(maker):
+    """A fork whose handles nobody consumes (a layer raised, a consumer outside the envelope) is gone when the handles are: the notes
+    ride on the tensors, there is no table an entry could stay in.  A convolution unit on fresh tensors of the same shape (which may
+    well get the ids of the dead ones) therefore finds no fork, no stash and no join."""
+    import gc
+    import importlib
+    import weakref
+    import torch_semantic_segmentation_amd as tssa
+    from torch_semantic_segmentation_amd import ops
+    F_ = importlib.import_module('torch_semantic_segmentation_amd.models.fastscnn')
+    xa, xb, fork = getattr(ops, maker)(_bf16_nhwc_leaf(1, 8, 4, 8))
+    assert fork is not None and xa is not xb
+    ref = weakref.ref(fork)
+    del xa, xb, fork
+    gc.collect()
+    assert ref() is None
+    torch.manual_seed(71)
+    block = F_.Conv2dBlock(8, 8, kernel_size=1).to(DEV)
+    tssa.set_compute_dtype(block, torch.bfloat16)
+    block.train()
+    for _ in range(2):
+        y = block.unit(_bf16_nhwc_leaf(1, 8, 4, 8))
+        cfg = y.raw.grad_fn.cfg
+        assert isinstance(cfg, ops.UnitCfg)
+        assert cfg.res_fork is None and cfg.stash_fork is None and cfg.prev_join is None
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize('maker', ['residual_fork', 'fork_two'])
+def test_a_note_never_references_the_tensor_that_carries_it(maker):
+    """The rule stated at ops._hand: with the collector switched off, reference counting alone frees an abandoned fork together with
+    its handles -- there is no cycle through a note."""
+    import gc
+    import weakref
+    from torch_semantic_segmentation_amd import ops
+    xa, xb, fork = getattr(ops, maker)(_bf16_nhwc_leaf(1, 8, 4, 8))
+    assert fork is not None
+    ref = weakref.ref(fork)
+    gc.disable()
+    try:
+        del xa, xb, fork
+        dead = ref() is None
+    finally:
+        gc.enable()
+    assert dead
+
+
+def test_a_join_note_is_single_use_and_keeps_nothing_alive(monkeypatch):
+    """The output of a block's ReLU join carries the join's configuration for the next layer's backward-data epilogue: the first taker
+    gets it, a second one gets nothing, and once the output and the taker's handle are dropped the configuration is gone."""
+    import gc
+    import importlib
+    import weakref
+    import torch_semantic_segmentation_amd as tssa
+    from torch_semantic_segmentation_amd import ops
+    F_ = importlib.import_module('torch_semantic_segmentation_amd.models.fastscnn')
+
+    class WatchedJoinCfg(ops.JoinCfg):           # JoinCfg has __slots__ without __weakref__: this test alone needs to watch one die
+        __slots__ = ('__weakref__',)
+    monkeypatch.setattr(ops, 'JoinCfg', WatchedJoinCfg)
+    torch.manual_seed(73)
+    m = F_.BottleneckBlock(32, 32, expansion=6).to(DEV)
+    tssa.set_compute_dtype(m, torch.bfloat16)
+    m.train()
+    h = m(_bf16_nhwc_leaf(2, 32, 8, 8))
+    cfg = ops._take_join(h)
+    assert isinstance(cfg, WatchedJoinCfg) and cfg.j_a is not None
+    assert ops._take_join(h) is None
+    ref = weakref.ref(cfg)
+    del h, cfg
+    gc.collect()
+    assert ref() is None
+    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize('family,cin,cout,stride,shape', [('fastscnn', 64, 64, 1, (2, 24, 40)), ('fastscnn', 64, 96, 2, (2, 24, 40)),
@@ -753,8 +871,8 @@ def test_autograd_grad_inside_a_backward_hook_does_not_touch_the_outer_pass():
 
 
 def test_two_trainers_in_two_threads_do_not_share_scheduling_state():
-    """Two models stepping concurrently from two host threads (each with its own stream): the forward-pass registries are per thread
-    and the backward-pass state per graph task, so both produce the gradients of their single-threaded runs."""
+    """Two models stepping concurrently from two host threads (each with its own stream): the backward-pass state is per graph task,
+    so both produce the gradients of their single-threaded runs."""
     import threading
     from torch_semantic_segmentation_amd import ops
     g = torch.Generator().manual_seed(7)

@@ -66,8 +66,6 @@ class BottleneckBlock(nn.Module):
         residual = tuple(c2.stride) == (1, 1) and c1.in_channels == c3.out_channels and not has_hooks(self.conv1)
         xa, xb, fork = ops.residual_fork(x) if residual else (x, x, None)
         d = run(self.conv2, run(self.conv1, xa))
-        if fork is not None:
-            ops._pending_forks.pop(id(xa), None)
         if fork is None and not has_hooks(self.conv3):
             # model.eval(), no gradient: the frozen BatchNorm, the skip and the ReLU ride in conv3's epilogue -- no join pass
             same_shape = (d.shape[0], c3.out_channels) + tuple(d.shape[2:]) == tuple(x.shape)

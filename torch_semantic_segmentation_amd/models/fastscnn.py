@@ -67,11 +67,7 @@ class BottleneckBlock(nn.Module):
         c1, c2, c3 = self.conv1[0], self.conv2[0], self.conv3[0]
         residual = tuple(c2.stride) == (1, 1) and c1.in_channels == c3.out_channels and not has_hooks(self.conv1)
         xa, xb, fork = ops.residual_fork(x) if residual else (x, x, None)
-        try:
-            d = run(self.conv2, run(self.conv1, xa))
-        finally:                                   # (also when a layer raises: ids are recycled, a stale entry would be picked up later)
-            if fork is not None:
-                ops._pending_forks.pop(id(xa), None)
+        d = run(self.conv2, run(self.conv1, xa))
         if fork is None and not has_hooks(self.conv3):
             # model.eval(), no gradient: the frozen BatchNorm, the skip and the ReLU ride in conv3's epilogue -- no join pass
             same_shape = (d.shape[0], c3.out_channels) + tuple(d.shape[2:]) == tuple(x.shape)
@@ -110,20 +106,17 @@ class PyramidPoolingModule(nn.Module):
             and isinstance(a[0].output_size, int) and not has_hooks(a) for a in arms)
         if plain:
             # x feeds the pools and the concat: the concat's gradient of x is added inside the pools' backward kernel (ops.fork_two)
-            xp, xc, fork = ops.fork_two(x)
-            try:
-                pooled = ops.adaptive_avg_pool_multi(xp, [a[0].output_size for a in arms])
-                x = xc
-                # the arms' 1x1 convolutions + BatchNorm statistics: one launch for all arms (csrc/ppm.hip), else unit by unit
-                ds = ops.ppm_arms([a[1] for a in arms], pooled)
-                if ds is None:
-                    ds = [run(a[1], Deferred(p)) for a, p in zip(arms, pooled)]
-                if ops.ppm_arms_fusable(x, ds):
-                    cat = ops.concat_upsampled_arms(x, ds)
-                else:
-                    cat = ops.concat_upsampled(x, ds)
-            finally:
-                ops.drop_fork(xp, xc)
+            xp, xc, _ = ops.fork_two(x)
+            pooled = ops.adaptive_avg_pool_multi(xp, [a[0].output_size for a in arms])
+            x = xc
+            # the arms' 1x1 convolutions + BatchNorm statistics: one launch for all arms (csrc/ppm.hip), else unit by unit
+            ds = ops.ppm_arms([a[1] for a in arms], pooled)
+            if ds is None:
+                ds = [run(a[1], Deferred(p)) for a, p in zip(arms, pooled)]
+            if ops.ppm_arms_fusable(x, ds):
+                cat = ops.concat_upsampled_arms(x, ds)
+            else:
+                cat = ops.concat_upsampled(x, ds)
             return self.conv(cat)
         pools = [pool(x) for pool in arms]
         return self.conv(ops.concat_upsampled(x, pools))
@@ -193,16 +186,12 @@ class FastSCNN(HipModel):
         # `downsample` has two consumers (the feature extractor and the fusion module's high-resolution layer): the gradient of the
         # latter is added in the epilogue of the former's first backward-data kernel, not by an elementwise launch (ops.fork_two)
         hooked = has_hooks(self.features) or has_hooks(self.fusion)
-        da, db, fork = (downsample, downsample, None) if hooked else ops.fork_two(downsample)
-        try:
-            features = self.features(da)
-            # (the fusion module's high-resolution 1x1 layer only needs `downsample` and could run on a side stream under the feature
-            # extractor, as ContextNet's context branch does: measured, 5.58 vs 5.45 ms per step -- it competes with, rather than hides
-            # under, the 1/16-resolution kernels; not done)
-            fusion = self.fusion(features, db)
-        finally:
-            if fork is not None:
-                ops.drop_fork(da, db)
+        da, db, _ = (downsample, downsample, None) if hooked else ops.fork_two(downsample)
+        features = self.features(da)
+        # (the fusion module's high-resolution 1x1 layer only needs `downsample` and could run on a side stream under the feature
+        # extractor, as ContextNet's context branch does: measured, 5.58 vs 5.45 ms per step -- it competes with, rather than hides
+        # under, the 1/16-resolution kernels; not done)
+        fusion = self.fusion(features, db)
         return self.classifier(fusion)
 
     def forward(self, input):

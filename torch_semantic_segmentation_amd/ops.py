@@ -320,54 +320,33 @@ def _add_rows(ws, target, ncols, nrows, param, returned):
         _reduce_rows_now(ws, target, ncols, nrows)
 
 
-class _PerThread:
-    """A dict private to the calling thread.  The forward-pass registries below (keyed by id() of a tensor between the operator that
-    registers an entry and the operator that picks it up, both in the same forward call) are per thread, so two models running their
-    forward passes in two threads never see -- or steal -- each other's entries."""
-
-    def __init__(self):
-        self._tl = threading.local()
-
-    def _d(self):
-        d = getattr(self._tl, 'd', None)
-        if d is None:
-            d = self._tl.d = {}
-        return d
-
-    def __bool__(self):
-        return bool(self._d())
-
-    def __len__(self):
-        return len(self._d())
-
-    def __setitem__(self, k, v):
-        self._d()[k] = v
-
-    def __contains__(self, k):
-        return k in self._d()
-
-    def pop(self, k, default=None):
-        return self._d().pop(k, default)
-
-    def get(self, k, default=None):
-        return self._d().get(k, default)
-
-    def clear(self):
-        self._d().clear()
-
-
 # Residual blocks: the block input has two consumers (the first 1x1 layer and the skip), so its gradient is a sum of two tensors.
 # Autograd would add them with an elementwise launch of its own; instead the skip's gradient (produced first, by the join's
 # backward) is handed to the first layer's backward-data kernel, which adds it in its epilogue (tss_pwconv_bwd_data_radd).
 fold_residual_adds = os.environ.get('TSS_FOLD_RESIDUAL', '1') != '0'
-_pending_forks = _PerThread()
 
 
 class _Fork:
-    __slots__ = ('g2', 'consumed', 'prev_join')
+    __slots__ = ('g2', 'consumed', 'prev_join', '__weakref__')      # (__weakref__: only the tests use it, to watch a fork die)
 
     def __init__(self):
         self.g2, self.consumed, self.prev_join = None, False, None
+
+
+# A producer's note for the operator that consumes its output travels ON the tensor, as a private attribute: it dies with the
+# tensor, and no other tensor, operator or thread can see it.  (Views, detach() and copies do not inherit it.)
+_FORK, _STASH, _JOIN = '_tss_fork', '_tss_stash', '_tss_join'
+
+
+def _hand(t, key, value):
+    """Leave `value` on tensor `t` for its consumer.  `value` may hold other tensors (a join's j_a, a fork's g2) but must never
+    reference `t` itself: the pair would then only die when the garbage collector runs."""
+    setattr(t, key, value)
+
+
+def _take(t, key):
+    """The note left on `t` under `key`, removed from it (a second consumer of `t` finds nothing), or None."""
+    return t.__dict__.pop(key, None)
 
 
 class ForkFn(Function):
@@ -392,54 +371,43 @@ class ForkFn(Function):
 
 
 def residual_fork(x):
-    """(handle for the convolution path, handle for the skip, fork) of a residual block's input; (x, x, None) when nothing is folded."""
+    """(handle for the convolution path, handle for the skip, fork) of a residual block's input; (x, x, None) when nothing is folded.
+    The fork rides on the first handle as a note for the operator that consumes it; a handle nobody consumes takes its note with it."""
     if not (fold_residual_adds and torch.is_grad_enabled() and torch.is_tensor(x) and x.requires_grad and x.is_cuda
             and x.dtype == torch.bfloat16 and not N.fast_paths_disabled()):
         return x, x, None
     fork = _Fork()
     fork.prev_join = _take_join(x)         # x is a block output: its join's backward can ride in the first layer's backward-data launch
     xa, xb = ForkFn.apply(x, fork)
-    _pending_forks[id(xa)] = fork          # picked up by the first conv unit that consumes xa (conv_unit)
+    _hand(xa, _FORK, fork)                 # taken by the first operator that consumes xa (conv_unit, adaptive_avg_pool_multi)
     return xa, xb, fork
 
 
 # A relu join whose output feeds a 1x1 layer (block output -> the next block's expand conv): the join's backward (ReLU mask of its
 # output + the BatchNorm-backward sums) can run in the epilogue of that layer's backward-data launch (tss_pwconv_bwd_data_joined).
-# join() registers its configuration here, keyed by the output tensor; the consuming conv unit picks it up.
+# join() leaves its configuration on the output tensor; the consuming conv unit takes it.
 fuse_join_backward = os.environ.get('TSS_FUSE_JOIN_BWD', '1') != '0'
 # ... for block outputs up to this many elements: the two extra loads of the epilogue drain the next tile's prefetch, which costs a long
 # layer more than the join launch it saves (262 k pixels x 64 channels: +48 us against a 28 us join; 65 k x 64: +10 against 14;
 # 16 k x 96-128: +2 against 9)
 fuse_join_backward_max = int(os.environ.get('TSS_FUSE_JOIN_BWD_MAX', '4000000'))
-_join_ctx = _PerThread()
 
 
 def _take_join(x):
-    if not _join_ctx or not torch.is_tensor(x):
-        return None
-    ref = _join_ctx.pop(id(x), None)
-    cfg = ref() if ref is not None else None
-    return cfg if (cfg is not None and cfg.j_ptr == x.data_ptr()) else None
-
-
-_pending_stash = _PerThread()
+    return _take(x, _JOIN) if torch.is_tensor(x) else None
 
 
 def fork_two(x):
     """(xa, xb, fork) for a materialised activation with TWO consumers whose gradients would otherwise meet in an elementwise launch of
     autograd's: the consumer of xb (created later, so its backward runs first) leaves its input gradient in fork.g2, the 1x1 layer
     that consumes xa adds it in the epilogue of its backward-data kernel (tss_pwconv_bwd_data_radd) -- or, for pooled maps,
-    tss_ppm_pool_bwd does.  Falls back to autograd's add whenever a side cannot take part.  (x, x, None) when nothing is folded."""
+    tss_ppm_pool_bwd does.  Falls back to autograd's add whenever a side cannot take part.  (x, x, None) when nothing is folded.
+    Both requests ride on the handles themselves (the fork on xa, the stash on xb): a consumer outside the envelope leaves its note
+    where it is, and the note goes with the handle."""
     xa, xb, fork = residual_fork(x)
     if fork is not None:
-        _pending_stash[id(xb)] = fork          # picked up by the operator that consumes xb
+        _hand(xb, _STASH, fork)                # taken by the operator that consumes xb (conv_unit, concat_upsampled_arms)
     return xa, xb, fork
-
-
-def drop_fork(xa, xb):
-    """Forget fork registrations nobody picked up (a consumer outside the envelope): ids may be recycled."""
-    _pending_forks.pop(id(xa), None)
-    _pending_stash.pop(id(xb), None)
 
 
 # independent branches of a model (ContextNet's spatial / context branches) on two streams: parallel branches of the captured graph
@@ -478,18 +446,33 @@ def _side_stream(device):
     return _side_streams[key]
 
 
+class _Scoped:
+    """`with obj:` installs obj.entries in the module-level table obj._table; leaving the block restores what the table held before."""
+    _table = None
+
+    def __enter__(self):
+        self.prev = dict(self._table)
+        self._table.update(self.entries)
+        return self
+
+    def __exit__(self, *exc):
+        self._table.clear()
+        self._table.update(self.prev)
+        return False
+
 
 # bf16 shadows of the 1x1 convolution weights (WeightShadows below): {weight.data_ptr(): (copy [N][K], transpose [K][N])},
 # only populated while a `with shadows:` block is active, i.e. while somebody guarantees they are current.
 _SHADOWS = {}
 
 
-class WeightShadows:
+class WeightShadows(_Scoped):
     """bf16 copies (and transposes) of every 1x1 convolution weight of a model, refreshed by ONE kernel launch
     (`tss_cast_weights`).  The pointwise kernels then stage their weight tiles with plain 16-byte copies instead of
     converting f32 in every block.  Opt-in and explicit: the owner calls refresh() whenever the weights changed
     (Trainer: at the top of every step, inside the captured graph) and wraps the pass in `with shadows:`; outside such
     a block the kernels read the f32 weights as before, so a stale shadow can never be used."""
+    _table = _SHADOWS
 
     def __init__(self, module):
         ws = [p for p in module.parameters() if p.dim() == 4 and p.shape[2] == 1 and p.shape[3] == 1
@@ -528,25 +511,16 @@ class WeightShadows:
             return fold
         return False
 
-    def __enter__(self):
-        self.prev = dict(_SHADOWS)
-        _SHADOWS.update(self.entries)
-        return self
-
-    def __exit__(self, *exc):
-        _SHADOWS.clear()
-        _SHADOWS.update(self.prev)
-        return False
-
 
 # bf16 tap-major copies of dense 3x3 weights prepared ahead of a forward (Dense3x3Shadows below): {weight.data_ptr(): [9][N][K] bf16}
 _W3X3 = {}
 
 
-class Dense3x3Shadows:
+class Dense3x3Shadows(_Scoped):
     """The bf16 [tap][output][input] copies of every dense 3x3 weight of a model that the matrix-core 3x3 kernels read (wstat.hip,
     atrous.hip, conv3x3.hip), written ahead of the forward instead of by one tss_permute_w3x3_bf16 launch per layer inside it.  Same
     contract as WeightShadows: refresh() rewrites them from the live weights; only visible inside `with shadows:`."""
+    _table = _W3X3
 
     def __init__(self, module):
         self.items = []
@@ -563,28 +537,19 @@ class Dense3x3Shadows:
                 raise RuntimeError('Dense3x3Shadows: a parameter was reallocated; rebuild the shadows')
             call('tss_permute_w3x3_bf16', ptr(w), ptr(t), None, w.shape[0], w.shape[1], stream())
 
-    def __enter__(self):
-        self.prev = dict(_W3X3)
-        _W3X3.update(self.entries)
-        return self
-
-    def __exit__(self, *exc):
-        _W3X3.clear()
-        _W3X3.update(self.prev)
-        return False
-
 
 # eval-mode BatchNorm affines computed for a whole model by one launch (EvalAffines below): {id(bn): [3][C] f32 view},
 # only populated inside a `with affines:` block, for the forward that follows its refresh().
 _EVAL_AFFINES = {}
 
 
-class EvalAffines:
+class EvalAffines(_Scoped):
     """(mean, invstd, gamma*invstd) of every BatchNorm of a model that normalises with its running statistics, written
     by ONE kernel (`tss_bn_eval_affine_batched`) instead of one tiny launch per layer (44 in FastSCNN: 15 % of an
     eval-mode forward at 2048 x 4096).  Same contract as WeightShadows: the owner calls refresh() at the top of each
     forward (inside a captured graph it is replayed with it, so the values always follow the live parameters and
     buffers) and wraps the forward in `with affines:`; outside such a block every layer computes its own."""
+    _table = _EVAL_AFFINES
 
     def __init__(self, module):
         import struct
@@ -618,16 +583,6 @@ class EvalAffines:
                     or m.running_var.data_ptr() != rv:
                 raise RuntimeError('EvalAffines: a BatchNorm tensor was reallocated; rebuild the affines')
         call('tss_bn_eval_affine_batched', ptr(self.table), self.table.shape[0], self.max_c, stream())
-
-    def __enter__(self):
-        self.prev = dict(_EVAL_AFFINES)
-        _EVAL_AFFINES.update(self.entries)
-        return self
-
-    def __exit__(self, *exc):
-        _EVAL_AFFINES.clear()
-        _EVAL_AFFINES.update(self.prev)
-        return False
 
 
 # The LDS-halo dense 3x3 kernel handles dilation <= 18, but it restages its nine 32 KB weight taps for every 64-pixel tile: on
@@ -865,7 +820,7 @@ def _exchange(group, device):
     """The IPC exchange of `group` on `device`, or None (switched off, set-up failed: the caller uses dist.all_reduce)."""
     if not syncbn_ipc:
         return None
-    key = (id(group), device.index)
+    key = (group, device.index)        # the group object itself: the entry keeps it alive, so no later group can alias it
     if key not in _XCHG:
         try:
             _XCHG[key] = _Exchange(group, device)
@@ -1004,8 +959,8 @@ def conv_unit(x, conv, bn=None, relu=False, out_dtype=None, weight=None, bias=_K
         cfg.in_link, cfg.in_relu = d.link, d.relu
         cfg.image_f32 = False
         cfg.out_dtype = x_raw.dtype
-        cfg.res_fork = _pending_forks.pop(id(x_raw), None) if _pending_forks else None
-        cfg.stash_fork = _pending_stash.pop(id(x_raw), None) if _pending_stash else None
+        cfg.res_fork = _take(x_raw, _FORK)
+        cfg.stash_fork = _take(x_raw, _STASH)
         cfg.prev_join = cfg.res_fork.prev_join if cfg.res_fork is not None else (_take_join(x_raw) if d.link is None and not d.relu else None)
     if x_raw.shape[1] != conv.in_channels:
         raise RuntimeError('expected %d input channels, got %d' % (conv.in_channels, x_raw.shape[1]))
@@ -1507,7 +1462,7 @@ def _pw_data_grad(c, e_in, red):
     pj = c.cfg.prev_join
     if (pj is not None and (radd is None or radd_ok) and not deferred_in and y is not None and e.dtype == torch.bfloat16
             and P * Cin <= fuse_join_backward_max
-            and pj.j_a is not None and pj.j_ptr == x.data_ptr() and tuple(pj.j_a.shape) == tuple(x.shape)
+            and pj.j_a is not None and tuple(pj.j_a.shape) == tuple(x.shape)
             and is_nhwc(pj.j_a) and N.lib().tss_pwconv_bwd_data_radd_supported(P, Cin, Cout, dt)):
         # this layer's input is a block output: that join's backward (ReLU mask + BatchNorm-backward sums) in the epilogue
         jl = pj.a_link
@@ -1811,7 +1766,18 @@ class ConvUnitFn(Function):
 # ----------------------------------------------------------------------------- join (materialise / add / relu)
 
 class JoinCfg:
-    __slots__ = ('a_link', 'b_link', 'relu', 'links', 'relus', 'drop_p', 'res_fork', 'j_a', 'j_ptr', 'fused_e', '__weakref__')
+    __slots__ = ('a_link', 'b_link', 'relu', 'drop_p', 'res_fork', 'j_a', 'fused_e')
+
+
+class BranchCfg:
+    """Pending BatchNorm links and ReLU flags of the branches that ssnbt_tail, concat_joined and concat_upsampled_arms write into
+    one buffer; res_fork: the stash of concat_upsampled_arms' first operand (fork_two)."""
+    __slots__ = ('links', 'relus', 'res_fork')
+
+
+class PpmArmsCfg:
+    """The modules of the arms that ppm_arms runs in one launch, and the links their BatchNorms leave pending."""
+    __slots__ = ('convs', 'bns', 'links')
 
 
 def join(a, b=None, relu=False, dropout_p=0.0, fork=None):
@@ -1836,15 +1802,12 @@ def join(a, b=None, relu=False, dropout_p=0.0, fork=None):
             raise RuntimeError('join: operands differ in shape/dtype: %s vs %s' % (a.raw.shape, b.raw.shape))
         braw, cfg.b_link = b.raw, b.link
     cfg.res_fork = fork if b is not None else None
-    cfg.j_a = cfg.j_ptr = cfg.fused_e = None
+    cfg.j_a = cfg.fused_e = None
     out = JoinFn.apply(a.raw, braw, cfg)
     if (fuse_join_backward and cfg.relu and not cfg.drop_p and cfg.a_link is not None and cfg.b_link is None and out.requires_grad
             and out.dtype == torch.bfloat16 and not N.fast_paths_disabled()):
-        import weakref
-        cfg.j_a, cfg.j_ptr = a.raw, out.data_ptr()
-        if len(_join_ctx) > 256:          # outputs nobody picked up (consumed by something other than a conv unit)
-            _join_ctx.clear()
-        _join_ctx[id(out)] = weakref.ref(cfg)
+        cfg.j_a = a.raw
+        _hand(out, _JOIN, cfg)            # taken by the conv unit (or residual_fork) that consumes `out`, if one does
     return out
 
 
@@ -2314,7 +2277,7 @@ def ssnbt_tail(left, right, x, drop_p, training):
         m = (torch.rand((x.shape[0], x.shape[1]), device=x.device) < keep).to(torch.float32)
         if keep > 0.0:
             m = m / keep
-    cfg = JoinCfg()
+    cfg = BranchCfg()
     cfg.links = [dl.link, dr.link]
     return SSnbtTailFn.apply(cfg, dl.raw, dr.raw, x, m)
 
@@ -2386,7 +2349,7 @@ def concat_joined(branches, relu=True):
     if any(d.raw.shape[1] % 8 or d.raw.shape[0] != ds[0].raw.shape[0] or d.raw.shape[2:] != ds[0].raw.shape[2:]
            or d.raw.dtype != ds[0].raw.dtype for d in ds):
         raise RuntimeError('concat_joined: branches must share batch / spatial size / dtype, channels multiples of 8')
-    cfg = JoinCfg()
+    cfg = BranchCfg()
     cfg.links = [d.link for d in ds]
     cfg.relus = [bool(relu) or bool(d.relu) for d in ds]
     return ConcatJoinFn.apply(cfg, *[d.raw for d in ds])
@@ -2735,7 +2698,7 @@ def _hi(vals):
 def adaptive_avg_pool_multi(x, bins):
     """[AdaptiveAvgPool2d(b)(x) for b in bins] from one launch (and one launch for the summed gradient)."""
     x = to_nhwc(materialize(x))
-    fork = _pending_forks.pop(id(x), None) if _pending_forks else None      # x has another consumer (fork_two): its gradient is added in our backward
+    fork = _take(x, _FORK)      # x has another consumer (fork_two): its gradient is added in our backward
     return PoolMultiFn.apply(x, tuple(int(b) for b in bins), fork)
 
 
@@ -2783,8 +2746,8 @@ def concat_upsampled_arms(x, arms):
     per bilinear tap, all arms in one launch; backward hands every arm its masked gradient and BatchNorm-backward sums."""
     x = to_nhwc(materialize(x))
     ds = [a.take() for a in arms]
-    cfg = JoinCfg()
-    cfg.res_fork = _pending_stash.pop(id(x), None) if _pending_stash else None
+    cfg = BranchCfg()
+    cfg.res_fork = _take(x, _STASH)
     cfg.links = [d.link for d in ds]
     cfg.relus = [bool(d.relu) for d in ds]
     return PpmConcatFn.apply(x, cfg, *[d.raw for d in ds])
@@ -2845,7 +2808,7 @@ def ppm_arms(blocks, pooled):
         if (c.kernel_size != (1, 1) or c.groups != 1 or c.bias is not None or c.stride != (1, 1) or c.padding != (0, 0)
                 or c.weight.dtype != torch.float32 or bn.weight is None or bn.weight.dtype != torch.float32
                 or (bn.training and (bn.momentum is None or not bn.track_running_stats)) or _sync_group(bn) is not None
-                or (bn.running_mean is not None and bn.running_mean.dtype != torch.float32)
+                or bn.running_mean is None or bn.running_mean.dtype != torch.float32
                 or getattr(blk, 'act_dtype', None) not in (None, torch.bfloat16)):
             return None
         convs.append(c); bns.append(bn); relus.append(len(mods) == 3)
@@ -2862,9 +2825,9 @@ def ppm_arms(blocks, pooled):
         return None                     # conv_unit raises torch's "Expected more than 1 value per channel"
     if not N.lib().tss_ppm_arms_supported(len(ps), C, Ca, _hi(counts), N.TSS_BF16):
         return None
-    cfg = JoinCfg()
+    cfg = PpmArmsCfg()
     cfg.links = [None] * len(ps)
-    cfg.relus = (convs, bns)
+    cfg.convs, cfg.bns = convs, bns
     ys = PpmArmsFn.apply(cfg, *ps, *[c.weight for c in convs], *[bn.weight for bn in bns], *[bn.bias for bn in bns])
     return [Deferred(y, link, relu) for y, link, relu in zip(ys, cfg.links, relus)]
 
@@ -2872,7 +2835,7 @@ def ppm_arms(blocks, pooled):
 class PpmArmsFn(Function):
     @staticmethod
     def forward(ctx, cfg, *ts):
-        convs, bns = cfg.relus
+        convs, bns = cfg.convs, cfg.bns
         n = len(convs)
         ps, ws, gammas, betas = ts[:n], ts[n:2 * n], ts[2 * n:3 * n], ts[3 * n:4 * n]
         dev = ps[0].device
@@ -2887,13 +2850,8 @@ class PpmArmsFn(Function):
              _hi(counts), n, C, Ca, int(training), float(bns[0].eps), float(bns[0].momentum if bns[0].momentum is not None else 0.0),
              N.TSS_BF16, stream())
         if not training:
-            for bn, link in zip(bns, links):
-                pre = _EVAL_AFFINES.get(id(bn)) if _EVAL_AFFINES else None
-                if pre is not None:
-                    link.mean, link.invstd, link.scale = pre.unbind(0)
-                else:
-                    call('tss_bn_eval_affine', ptr(bn.weight), ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps),
-                         ptr(link.mean), ptr(link.invstd), ptr(link.scale), Ca, stream())
+            for bn, link, cnt, g_ in zip(bns, links, counts, gammas):
+                _finalize_forward(link, bn, False, cnt, Ca, g_, stream())
         cfg.links = links
         ctx.cfg, ctx.n, ctx.geom = cfg, n, (C, Ca, counts, training)
         ctx.save_for_backward(*ps, *ws, *ys)
@@ -2904,8 +2862,7 @@ class PpmArmsFn(Function):
         n = ctx.n
         saved = ctx.saved_tensors
         ps, ws, ys = saved[:n], saved[n:2 * n], saved[2 * n:3 * n]
-        convs, bns = ctx.cfg.relus
-        links = ctx.cfg.links
+        convs, bns, links = ctx.cfg.convs, ctx.cfg.bns, ctx.cfg.links
         C, Ca, counts, training = ctx.geom
         dev = ps[0].device
         es = [to_nhwc(e) if e is not None else new_nhwc(*y.shape, y.dtype, dev).zero_() for e, y in zip(es, ys)]
