@@ -62,6 +62,7 @@ enum {
   TSS_K_POOL_FWD, TSS_K_POOL_BWD, TSS_K_COPY,
   TSS_K_CE_FWD, TSS_K_CE_BWD, TSS_K_ARGMAX, TSS_K_UPSAMPLE_CE_FWD, TSS_K_UPSAMPLE_CE_BWD,
   TSS_K_RESIZE_FLIP_PLANAR, TSS_K_MULTISCALE_ARGMAX,
+  TSS_K_SGD, TSS_K_GRAD_NORM,
   TSS_K_COUNT
 };
 
@@ -537,6 +538,41 @@ int tss_cast_weights(const long long* table, int njobs, int blocks_per_job, floa
 int tss_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n,
                    const float* lr, float beta1, float beta2, float eps, float weight_decay,
                    float* state, float grad_scale, float lr_host, long step_host, void* stream);
+
+/* ---- flat optimizers with parameter groups (csrc/optim.hip) -------------------------------------------------------------
+ * replaces: torch.optim.AdamW(groups) / torch.optim.SGD(groups) .step() and torch.nn.utils.clip_grad_norm_ on the flat buffers.
+ * One row per parameter group: elements begin .. end-1 of the flat buffers take the row's hyper-parameters.  AdamW reads beta1,
+ * beta2, eps; SGD reads beta1 as the momentum, beta2 as the dampening and flags & TSS_OPT_NESTEROV (eps unused). */
+#define TSS_OPT_MAX_GROUPS 8
+#define TSS_OPT_NESTEROV 1
+typedef struct tss_optgroup { long begin; long end; float lr; float weight_decay; float beta1; float beta2; float eps; int flags; } tss_optgroup;
+/* groups: HOST array of ngroups rows, copied into the kernel arguments (no device memory, no synchronisation).  Contract (else
+ * TSS_ERR_SHAPE, nothing launched): 1 <= ngroups <= TSS_OPT_MAX_GROUPS; groups[0].begin == 0, groups[k].begin == groups[k-1].end,
+ * begin <= end, the last end == n.
+ * state == NULL: the rows' lr and step_host (1-based; the bias corrections are computed from it here) are used and the step is ONE
+ * launch.  state != NULL: [ngroups][3] floats {step, 1 - beta1^step, sqrt(1 - beta2^step)} and the learning rates lr[ngroups] live on
+ * the device; a tick kernel advances every row first, so the step can be replayed from a captured graph.
+ * scale != NULL: the gradient factor is read from the device (the second float tss_grad_sqnorm writes) instead of grad_scale.
+ * The per-element arithmetic is tss_adamw_step's, which is the one-row call of the same kernel. */
+int tss_adamw_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n,
+                          const tss_optgroup* groups, int ngroups, const float* lr, float* state, const float* scale,
+                          float grad_scale, long step_host, void* stream);
+/* torch.optim.SGD.step(): g' = g*scale (+ weight_decay*p when weight_decay != 0); momentum != 0: buf = g' on the first step, else
+ * buf = momentum*buf + (1 - dampening)*g', and g' = nesterov ? g' + momentum*buf : buf; p -= lr*g'.  First step: step_host == 1, or
+ * the state row's counter after the tick.  Elements of a group with momentum == 0 never touch momentum_buf, which may be NULL when
+ * no group has momentum (a group with momentum and a NULL buffer: TSS_ERR_SHAPE).  state / lr / scale as tss_adamw_step_groups
+ * (columns 1, 2 of a state row are not used). */
+int tss_sgd_step_groups(float* params, const float* grads, float* momentum_buf, long n, const tss_optgroup* groups, int ngroups,
+                        const float* lr, float* state, const float* scale, float grad_scale, long step_host, void* stream);
+/* Global gradient norm and clip factor of the flat gradient buffer, deterministic and without atomics: every block widens its f32
+ * elements to f64 (the squares are exact), sums in f64 and writes one row of `workspace` (tss_grad_sqnorm_workspace_bytes(n) bytes,
+ * need not be initialised; the block count depends on n only); a one-block pass adds the rows in a fixed order and writes
+ *   out[0] = grad_scale * sqrt(sum)                                  (the norm torch.nn.utils.clip_grad_norm_ returns)
+ *   out[1] = grad_scale * min(1, max_norm / (out[0] + 1e-6))         (the factor it multiplies the gradients by, times grad_scale)
+ * computed in f64 and rounded once each; out[1] == grad_scale bit for bit when the clip does not engage.  grads is not written.
+ * grads must be 16-byte aligned (TSS_ERR_ALIGN).  n == 0: norm 0. */
+long tss_grad_sqnorm_workspace_bytes(long n);
+int tss_grad_sqnorm(const float* grads, long n, double* workspace, float grad_scale, float max_norm, float* out, void* stream);
 
 /* ---- resampling -------------------------------------------------------------------------------------
  * replaces: F.interpolate(mode='bilinear', align_corners=True) TSS/models/fastscnn.py:63-64,119-120,

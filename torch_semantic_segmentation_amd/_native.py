@@ -107,7 +107,7 @@ def dtype_code(dtype):
 
 # ----------------------------------------------------------------------------- profiler helpers
 
-K_COUNT = 35
+K_COUNT = 37
 
 
 def prof_enable(on=True):

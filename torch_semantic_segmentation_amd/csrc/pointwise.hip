@@ -3,7 +3,7 @@
 //   * join: out = relu?(affA(a) + affB(b))   -- the only place a normalised activation is written
 //   * join backward: e = dout * relu'(out) plus the per-channel sums the two BN-backwards need
 //   * dropout (counter-based Philox, mask recomputed in backward), bias gradient, 3x3 weight
-//     re-layout, fused flat AdamW
+//     re-layout (the flat optimizers live in optim.hip)
 #include <cstdlib>
 #include "common.h"
 #include "bnfin.h"
@@ -482,37 +482,6 @@ __global__ __launch_bounds__(NT) void channel_shuffle_kernel(const T* x, long ld
   }
 }
 
-// ------------------------------------------------------------------------------------------ AdamW
-// state = {step, bias_correction1, bias_correction2_sqrt}; torch.optim.AdamW arithmetic, single tensor.
-__global__ void adamw_tick_kernel(float* state, float beta1, float beta2) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    const float step = state[0] + 1.f;
-    state[0] = step;
-    state[1] = 1.f - powf(beta1, step);
-    state[2] = sqrtf(1.f - powf(beta2, step));
-  }
-}
-
-__global__ __launch_bounds__(NT) void adamw_kernel(float* p, const float* g, float* m, float* v, long n,
-                                                   const float* lr_ptr, float beta1, float beta2, float eps,
-                                                   float weight_decay, const float* state, float grad_scale,
-                                                   float lr_host, float bc1_host, float bc2s_host) {
-  // device-side step counter / learning rate (state, lr_ptr: the step can be replayed from a captured graph), or both as
-  // kernel arguments computed on the host (one launch instead of three when the optimizer step is launched eagerly)
-  const float lr = state ? *lr_ptr : lr_host;
-  const float bc1 = state ? state[1] : bc1_host, bc2s = state ? state[2] : bc2s_host;
-  const float step_size = lr / bc1;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float gi = g[i] * grad_scale;
-    float pi = p[i] * (1.f - lr * weight_decay);
-    const float mi = m[i] + (gi - m[i]) * (1.f - beta1);
-    const float vi = v[i] * beta2 + (1.f - beta2) * gi * gi;
-    const float denom = sqrtf(vi) / bc2s + eps;
-    pi -= step_size * (mi / denom);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-  }
-}
-
 // bf16 shadows of the 1x1 convolution weights, all layers in one launch: job j = (f32 source [N][K], bf16 copy [N][K],
 // bf16 transpose [K][N]).  The pointwise kernels stage their weight tiles from these with plain 16-byte copies
 // (forward reads the copy, backward-data the transpose) instead of converting f32 per block.
@@ -735,22 +704,6 @@ int tss_cast_weights(const long long* table, int njobs, int blocks_per_job, floa
   hipLaunchKernelGGL(cast_weights_kernel, dim3(blocks_per_job, njobs + (zero_n > 0 ? 1 : 0)), dim3(256), 0, (hipStream_t)stream, table,
                      njobs, zero, zero_n);
   return tss::check_last("cast_weights");
-}
-
-int tss_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n,
-                   const float* lr, float beta1, float beta2, float eps, float weight_decay,
-                   float* state /*[3]: step, bc1, sqrt(bc2)*/, float grad_scale, float lr_host, long step_host, void* stream) {
-  TSS_REQUIRE(n >= 0 && (state ? lr != nullptr : step_host >= 1), TSS_ERR_SHAPE);
-  float bc1 = 1.f, bc2s = 1.f;
-  if (state) hipLaunchKernelGGL(adamw_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, beta1, beta2);
-  else { bc1 = 1.f - powf(beta1, (float)step_host); bc2s = sqrtf(1.f - powf(beta2, (float)step_host)); }   // as adamw_tick_kernel
-  if (n == 0) return tss::check_last("adamw_tick");
-  long grid = (n + NT - 1) / NT;
-  if (grid > 2048) grid = 2048;
-  tss::ProfScope prof(TSS_K_ADAMW, (hipStream_t)stream, 28.0 * n, 12.0 * n);
-  hipLaunchKernelGGL(adamw_kernel, dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, params, grads, exp_avg,
-                     exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, state, grad_scale, lr_host, bc1, bc2s);
-  return tss::check_last("adamw");
 }
 
 }  // extern "C"

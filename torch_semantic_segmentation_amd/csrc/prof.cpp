@@ -34,6 +34,7 @@ const KernelInfo kInfo[TSS_K_COUNT] = {
     {"cross_entropy_fwd", "ce_fwd_kernel"}, {"cross_entropy_bwd", "ce_bwd_kernel"}, {"argmax_confusion", "argmax_confusion_kernel"},
     {"upsample_ce_fwd", "upsample_ce_onepass_kernel"}, {"upsample_ce_bwd", "upsample_ce_gather_kernel"},
     {"resize_flip_planar", "resize_flip_planar_kernel"}, {"multiscale_argmax_confusion", "multiscale_argmax_kernel"},
+    {"sgd", "sgd_kernel"}, {"grad_norm", "grad_sqnorm_kernel|grad_sqnorm_final_kernel"},
 };
 
 struct Rec { int kid; hipEvent_t a, b; double bytes, flops; };

@@ -5,8 +5,8 @@ train mode, zero_grad, forward, loss, backward, optimizer step, loss value.  ign
 dependencies: the returned :class:`Trainer` is a plain object with `update(batch)` and `run(loader, epochs)`.
 
 MI355X specifics
-  * parameters and gradients of the model live in two flat f32 buffers (`FlatAdamW`), so the optimizer is one
-    fused kernel (tss_adamw_step) and data-parallel training needs ONE RCCL all-reduce per step;
+  * parameters and gradients of the model live in two flat f32 buffers (`FlatAdamW`, `FlatSGD`), so the optimizer is one
+    fused kernel (tss_adamw_step_groups / tss_sgd_step_groups) and data-parallel training needs ONE RCCL all-reduce per step;
   * weight-gradient kernels accumulate straight into the flat gradient buffer (ops.direct_grads), so there is
     no per-parameter `.grad +=` launch;
   * zero_grad + forward + loss + backward can be captured once into a HIP graph (`use_graph=True`) and
@@ -15,6 +15,7 @@ MI355X specifics
     xGMI on GPUs, "gloo" on CPU for tests).  BatchNorm statistics stay per replica unless the model
     went through `convert_syncbn_model` (ops.SyncBatchNorm: one small all-reduce per BatchNorm layer and direction).
 """
+import ctypes
 import os
 from functools import partial
 
@@ -26,44 +27,110 @@ from . import _native as N
 from . import ops
 
 
-# ----------------------------------------------------------------------------- flat parameters + fused AdamW
+# ----------------------------------------------------------------------------- flat parameters + fused optimizers
 
-class FlatAdamW(torch.optim.Optimizer):
-    """torch.optim.AdamW semantics (decoupled weight decay, bias correction) on ONE flat f32 buffer.
+MAX_PARAM_GROUPS = 8            # TSS_OPT_MAX_GROUPS of include/tss_hip.h: the group table travels in the kernel arguments
+_UNSUPPORTED_FLAGS = ('amsgrad', 'maximize', 'foreach', 'fused')
 
-    `param_groups[0]['lr']` stays a Python float so LR schedulers work; it is mirrored into a device scalar
-    before every step (outside any captured graph).
+
+class _OptGroup(ctypes.Structure):
+    """tss_optgroup of include/tss_hip.h."""
+    _fields_ = [('begin', ctypes.c_long), ('end', ctypes.c_long), ('lr', ctypes.c_float), ('weight_decay', ctypes.c_float),
+                ('beta1', ctypes.c_float), ('beta2', ctypes.c_float), ('eps', ctypes.c_float), ('flags', ctypes.c_int)]
+
+
+class FlatOptimizer(torch.optim.Optimizer):
+    """What FlatAdamW and FlatSGD share: the parameters of all groups packed into ONE flat f32 buffer (groups in order, parameters in
+    order within a group), their gradients aliased into a second one, and the step as one fused kernel over both.
+
+    `params` is an iterable of tensors or of group dicts, with torch.optim's defaulting rules; at most MAX_PARAM_GROUPS groups.
+    Each `param_groups[i]['lr']` stays a Python float so LR schedulers work; the rates are kernel arguments of the step, or (with
+    `device_state = True`) mirrored into device memory before every step() that is not being captured -- call sync_lr() between the
+    replays of a captured step().
+
+    `max_grad_norm`: torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm) over ALL groups as part of step(): one
+    deterministic reduction over the flat gradient buffer (after the all-reduce, `grad_scale` applied), whose clip factor the
+    step kernel reads from the device.  The gradients themselves (`p.grad`) are NOT rescaled in place.  `last_grad_norm` is the
+    pre-clip norm of the latest step as a 0-dim device tensor (a view: no synchronisation, overwritten by the next step); a
+    non-finite norm propagates into the parameters as it does in torch.
     """
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
-        params = [p for p in params]
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        if len(self.param_groups) != 1:
-            raise NotImplementedError('FlatAdamW: a single parameter group')
-        ps = self.param_groups[0]['params']
+    def __init__(self, params, defaults, max_grad_norm=None, **flags):
+        name = type(self).__name__
+        self._reject_flags(flags)
+        params = list(params)
+        if params and isinstance(params[0], dict):
+            if len(params) > MAX_PARAM_GROUPS:
+                raise ValueError('%s: at most %d parameter groups, got %d' % (name, MAX_PARAM_GROUPS, len(params)))
+            groups = []
+            for g in params:
+                g = dict(g)
+                ps = g['params']
+                g['params'] = [ps] if isinstance(ps, torch.Tensor) else list(ps)
+                if not g['params']:
+                    raise ValueError('%s: an empty parameter group' % name)
+                self._reject_flags(g)
+                groups.append(g)
+            params = groups
+        self._laid_out = False
+        super().__init__(params, defaults)
+        for g in self.param_groups:
+            self._check_group(g)
+        ps = [p for g in self.param_groups for p in g['params']]
         dev = ps[0].device
         if any(p.dtype != torch.float32 or p.device != dev for p in ps):
-            raise TypeError('FlatAdamW: float32 parameters on one device')
+            raise TypeError('%s: float32 parameters on one device' % name)
         n = sum(p.numel() for p in ps)
         self.flat_param = torch.empty(n, dtype=torch.float32, device=dev)
         self.flat_grad = torch.zeros(n, dtype=torch.float32, device=dev)
         off = 0
+        self.group_ranges = []           # [begin, end) of every group in the flat buffers
         with torch.no_grad():
-            for p in ps:
-                k = p.numel()
-                self.flat_param[off:off + k].copy_(p.reshape(-1))
-                p.data = self.flat_param[off:off + k].view_as(p)
-                p.grad = self.flat_grad[off:off + k].view_as(p)
-                off += k
-        self.exp_avg = torch.zeros_like(self.flat_param)
-        self.exp_avg_sq = torch.zeros_like(self.flat_param)
-        # step counter and learning rate: on the host (kernel arguments of ONE launch per step) unless device_state=True, which
+            for g in self.param_groups:
+                begin = off
+                for p in g['params']:
+                    k = p.numel()
+                    self.flat_param[off:off + k].copy_(p.reshape(-1))
+                    p.data = self.flat_param[off:off + k].view_as(p)
+                    p.grad = self.flat_grad[off:off + k].view_as(p)
+                    off += k
+                self.group_ranges.append((begin, off))
+        self._laid_out = True
+        G = len(self.param_groups)
+        # step counter and learning rates: on the host (kernel arguments of ONE launch per step) unless device_state=True, which
         # keeps them in device memory behind a tick kernel so that step() itself can be captured in a HIP graph
         self.device_state = False
         self.step_count = 0
-        self.state_vec = torch.zeros(3, dtype=torch.float32, device=dev)  # device_state: step, bias corrections
-        self.lr_dev = torch.full((1,), float(lr), dtype=torch.float32, device=dev)
+        self.state_vec = torch.zeros(3 * G, dtype=torch.float32, device=dev)  # device_state: per group step, bias corrections
+        self.lr_dev = torch.tensor([float(g['lr']) for g in self.param_groups], dtype=torch.float32).to(dev)
         self.grad_scale = 1.0
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.last_grad_norm = None
+        if self.max_grad_norm is not None:
+            self._clip_out = torch.zeros(2, dtype=torch.float32, device=dev)     # tss_grad_sqnorm: norm, gradient factor
+            self._clip_ws = None                               # its partial rows (on the device: the library is there to ask)
+            if dev.type == 'cuda':
+                self._clip_ws = torch.empty(N.lib().tss_grad_sqnorm_workspace_bytes(n) // 8, dtype=torch.float64, device=dev)
+            self.last_grad_norm = self._clip_out[0]
+
+    @staticmethod
+    def _reject_flags(mapping):
+        for flag in _UNSUPPORTED_FLAGS:
+            if mapping.get(flag):
+                raise ValueError('the flat optimizers have one fused kernel per step: %s=%r is not supported' % (flag, mapping[flag]))
+
+    def _check_group(self, group):
+        """Subclass hook: validate one parameter group (after torch filled in its defaults)."""
+
+    def add_param_group(self, param_group):
+        if getattr(self, '_laid_out', False):
+            raise NotImplementedError('%s.add_param_group: the flat parameter, gradient and state buffers are laid out once, at '
+                                      'construction, and every parameter is a view into them; build a new optimizer with all '
+                                      'groups instead' % type(self).__name__)
+        super().add_param_group(param_group)
+
+    def _params(self):
+        return (p for g in self.param_groups for p in g['params'])
 
     def zero_grad(self, set_to_none=False):
         self.flat_grad.zero_()
@@ -74,64 +141,160 @@ class FlatAdamW(torch.optim.Optimizer):
         off = 0
         base = self.flat_grad.data_ptr()
         esz = self.flat_grad.element_size()
-        for p in self.param_groups[0]['params']:
+        for p in self._params():
             g = p.grad
             if g is None or g.data_ptr() != base + esz * off:
-                raise RuntimeError('FlatAdamW: a parameter gradient no longer aliases the flat gradient buffer (was '
-                                   'model.zero_grad(set_to_none=True) called?); use optimizer.zero_grad() or reattach()')
+                raise RuntimeError('%s: a parameter gradient no longer aliases the flat gradient buffer (was '
+                                   'model.zero_grad(set_to_none=True) called?); use optimizer.zero_grad() or reattach()'
+                                   % type(self).__name__)
             off += p.numel()
 
     def reattach(self):
         """Point every p.grad back at its slice of the flat gradient buffer."""
         off = 0
-        for p in self.param_groups[0]['params']:
+        for p in self._params():
             k = p.numel()
             p.grad = self.flat_grad[off:off + k].view_as(p)
             off += k
 
+    def sync_lr(self):
+        """device_state: mirror every group's learning rate into device memory (one small fill per group, outside any capture)."""
+        for i, g in enumerate(self.param_groups):
+            self.lr_dev[i:i + 1].fill_(float(g['lr']))
+
+    # -- what a subclass supplies
+    _state_names = ()                    # its flat state buffers, as named in state_dict()['flat']
+
+    def _state_rows(self, k):
+        """[3 * groups] floats of the device-side state after k steps (what the tick kernel would have written)."""
+        raise NotImplementedError
+
+    def _group_row(self, group, begin, end):
+        raise NotImplementedError
+
+    def _launch(self, rows, scale):
+        raise NotImplementedError
+
     def state_dict(self):
-        """torch.optim state_dict plus the flat moments and the device-side step counter (checkpoint / resume)."""
+        """torch.optim state_dict plus the flat state buffers, the group ranges and the step counter (checkpoint / resume)."""
         sd = super().state_dict()
         sv = self.state_vec.clone()
         if not self.device_state:
-            b1, b2 = self.param_groups[0]['betas']
-            k = float(self.step_count)
-            sv = torch.tensor([k, 1.0 - b1 ** k, (1.0 - b2 ** k) ** 0.5], dtype=torch.float32, device=sv.device)
-        sd['flat'] = {'exp_avg': self.exp_avg.clone(), 'exp_avg_sq': self.exp_avg_sq.clone(), 'state_vec': sv}
+            sv = torch.tensor(self._state_rows(float(self.step_count)), dtype=torch.float32, device=sv.device)
+        flat = {name: (None if getattr(self, name) is None else getattr(self, name).clone()) for name in self._state_names}
+        flat['state_vec'] = sv
+        flat['group_ranges'] = [list(r) for r in self.group_ranges]
+        sd['flat'] = flat
         return sd
 
     def load_state_dict(self, state_dict):
+        name = type(self).__name__
         state_dict = dict(state_dict)
         flat = state_dict.pop('flat', None)
         if flat is None and state_dict.get('state'):
-            # a torch.optim.AdamW checkpoint (per-parameter exp_avg / exp_avg_sq / step): its moments would land in self.state and
-            # never be read -- a resume would silently restart the bias correction
-            raise ValueError('FlatAdamW.load_state_dict: this state_dict has per-parameter state but no flat moments (it was not '
-                             'written by FlatAdamW.state_dict()); pack it into the flat buffers before loading')
+            # a torch.optim checkpoint (per-parameter exp_avg / exp_avg_sq / step / momentum_buffer): its state would land in
+            # self.state and never be read -- a resume would silently restart the bias correction
+            raise ValueError('%s.load_state_dict: this state_dict has per-parameter state but no flat moments (it was not '
+                             'written by %s.state_dict()); pack it into the flat buffers before loading' % (name, name))
+        if flat is not None:
+            ranges = flat.get('group_ranges')
+            mine = [list(r) for r in self.group_ranges]
+            if ranges is None:           # written before parameter groups existed: one group over the whole buffer
+                whole = flat.get(self._state_names[0])
+                ranges = [[0, int(whole.numel())]] if whole is not None else None
+            if ranges is None or [list(map(int, r)) for r in ranges] != mine:
+                raise ValueError('%s.load_state_dict: the checkpoint lays its parameter groups out as %s, this optimizer as %s'
+                                 % (name, ranges, mine))
+            missing = [k for k in self._state_names if k not in flat]
+            if missing:
+                raise ValueError('%s.load_state_dict: the checkpoint has no flat %s' % (name, ', '.join(missing)))
         super().load_state_dict(state_dict)
         if flat is not None:
             with torch.no_grad():
-                self.exp_avg.copy_(flat['exp_avg'])
-                self.exp_avg_sq.copy_(flat['exp_avg_sq'])
+                for k in self._state_names:
+                    if flat[k] is not None and getattr(self, k) is not None:
+                        getattr(self, k).copy_(flat[k])
                 self.state_vec.copy_(flat['state_vec'])
             self.step_count = int(round(float(flat['state_vec'][0])))
 
     @torch.no_grad()
     def step(self, closure=None):
-        g = self.param_groups[0]
         if not self.flat_param.is_cuda:
-            raise RuntimeError('FlatAdamW runs on the HIP path only (no CPU fallback)')
+            raise RuntimeError('%s runs on the HIP path only (no CPU fallback)' % type(self).__name__)
         self._check_aliases()
-        b1, b2 = g['betas']
         self.step_count += 1
-        if self.device_state:
-            self.lr_dev.fill_(float(g['lr']))
-        N.call('tss_adamw_step', N.ptr(self.flat_param), N.ptr(self.flat_grad), N.ptr(self.exp_avg),
-               N.ptr(self.exp_avg_sq), self.flat_param.numel(), N.ptr(self.lr_dev) if self.device_state else None,
-               float(b1), float(b2), float(g['eps']), float(g['weight_decay']),
-               N.ptr(self.state_vec) if self.device_state else None, float(self.grad_scale), float(g['lr']),
-               int(self.step_count), N.stream())
+        if self.device_state and not torch.cuda.is_current_stream_capturing():
+            self.sync_lr()
+        rows = (_OptGroup * len(self.param_groups))(*[self._group_row(g, b, e)
+                                                      for g, (b, e) in zip(self.param_groups, self.group_ranges)])
+        scale = None
+        if self.max_grad_norm is not None:
+            N.call('tss_grad_sqnorm', N.ptr(self.flat_grad), self.flat_grad.numel(), N.ptr(self._clip_ws), float(self.grad_scale),
+                   self.max_grad_norm, N.ptr(self._clip_out), N.stream())
+            scale = self._clip_out.data_ptr() + self._clip_out.element_size()
+        self._launch(rows, scale)
 
+
+class FlatAdamW(FlatOptimizer):
+    """torch.optim.AdamW semantics (decoupled weight decay, bias correction) on ONE flat f32 buffer, with parameter groups (a group
+    may override lr, betas, eps, weight_decay) and optional global-norm clipping: see FlatOptimizer."""
+    _state_names = ('exp_avg', 'exp_avg_sq')
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, amsgrad=False,
+                 maximize=False, foreach=None, fused=None):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), max_grad_norm=max_grad_norm,
+                         amsgrad=amsgrad, maximize=maximize, foreach=foreach, fused=fused)
+        self.exp_avg = torch.zeros_like(self.flat_param)
+        self.exp_avg_sq = torch.zeros_like(self.flat_param)
+
+    def _state_rows(self, k):
+        rows = []
+        for g in self.param_groups:
+            b1, b2 = g['betas']
+            rows += [k, 1.0 - b1 ** k, (1.0 - b2 ** k) ** 0.5]
+        return rows
+
+    def _group_row(self, g, begin, end):
+        b1, b2 = g['betas']
+        return _OptGroup(begin, end, float(g['lr']), float(g['weight_decay']), float(b1), float(b2), float(g['eps']), 0)
+
+    def _launch(self, rows, scale):
+        dev = self.device_state
+        N.call('tss_adamw_step_groups', N.ptr(self.flat_param), N.ptr(self.flat_grad), N.ptr(self.exp_avg), N.ptr(self.exp_avg_sq),
+               self.flat_param.numel(), rows, len(rows), N.ptr(self.lr_dev) if dev else None, N.ptr(self.state_vec) if dev else None,
+               scale, float(self.grad_scale), int(self.step_count), N.stream())
+
+
+class FlatSGD(FlatOptimizer):
+    """torch.optim.SGD semantics (weight decay added to the gradient, momentum with dampening, Nesterov) on ONE flat f32 buffer, with
+    parameter groups (a group may override lr, momentum, dampening, weight_decay, nesterov) and optional global-norm clipping: see
+    FlatOptimizer.  The momentum buffer exists only when some group has momentum; a group without never touches it."""
+    _state_names = ('momentum_buffer',)
+
+    def __init__(self, params, lr, momentum=0, dampening=0, weight_decay=0, nesterov=False, max_grad_norm=None, maximize=False,
+                 foreach=None, fused=None):
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov),
+                         max_grad_norm=max_grad_norm, maximize=maximize, foreach=foreach, fused=fused)
+        self.momentum_buffer = None
+        if any(g['momentum'] != 0 for g in self.param_groups):
+            self.momentum_buffer = torch.zeros_like(self.flat_param)
+
+    def _check_group(self, g):
+        if g['nesterov'] and (g['momentum'] <= 0 or g['dampening'] != 0):
+            raise ValueError('Nesterov momentum requires a momentum and zero dampening')
+
+    def _state_rows(self, k):
+        return [k, 0.0, 0.0] * len(self.param_groups)
+
+    def _group_row(self, g, begin, end):
+        return _OptGroup(begin, end, float(g['lr']), float(g['weight_decay']), float(g['momentum']), float(g['dampening']), 0.0,
+                         1 if g['nesterov'] else 0)
+
+    def _launch(self, rows, scale):
+        dev = self.device_state
+        N.call('tss_sgd_step_groups', N.ptr(self.flat_param), N.ptr(self.flat_grad), N.ptr(self.momentum_buffer),
+               self.flat_param.numel(), rows, len(rows), N.ptr(self.lr_dev) if dev else None, N.ptr(self.state_vec) if dev else None,
+               scale, float(self.grad_scale), int(self.step_count), N.stream())
 
 # ----------------------------------------------------------------------------- distributed helpers
 
@@ -158,7 +321,8 @@ def shard_batch(n_items, world_size, rank):
 
 
 def allreduce_mean_(flat, world_size, group=None):
-    """ONE collective per step over the flat gradient buffer: sum here, the 1/world factor is folded into AdamW."""
+    """ONE collective per step over the flat gradient buffer: sum here, the 1/world factor is folded into the optimizer
+    step (FlatOptimizer.grad_scale)."""
     if world_size > 1 or (dist.is_available() and dist.is_initialized()):
         dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
     return flat
@@ -182,7 +346,7 @@ class Trainer:
                              % (world_size, live))
         self.world_size = world_size
         self.use_graph = use_graph
-        self.flat = isinstance(optimizer, FlatAdamW)
+        self.flat = isinstance(optimizer, FlatOptimizer)
         # model(x) followed by CrossEntropyLoss == the fused head+loss operator on model.forward_lowres(x): same
         # value and gradients, but the full-resolution logits never exist (-1.3 GB and ~0.8 ms at 8x1024x2048:
         # one 0.26 ms kernel instead of five that move 3.8 GB).  Only taken when nothing can observe the difference
