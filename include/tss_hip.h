@@ -709,6 +709,27 @@ int tss_dice_fwd(const void* logits, const long long* target, float* lse, void* 
                  int ignore_index, int has_ignore, float smooth, int max_blocks, int dtype, void* stream);
 int tss_dice_bwd(const void* logits, const long long* target, const float* lse, const void* workspace, const float* grad_out,
                  void* dlogits, long B, int C, long HW, int ignore_index, int has_ignore, int max_blocks, int dtype, void* stream);
+/* Logit distillation (csrc/distill.hip) on low-resolution NHWC logits: student and teacher are [B][HW][ld] rows of one dtype,
+ * pitches lds, ldt >= C, multiples of 8, bases 16-byte aligned; 1 <= C <= 256, any HW >= 1, tau > 0.  Pad channels [C, ld) of
+ * the inputs may hold anything (NaN) and reach no result.  With x = logit / tau, p = softmax(x_T), q = softmax(x_S):
+ *   pixel kind   (kind 0): softmax over the C classes of a pixel,       *loss = tau^2 / (B HW) * sum_pixels KL(p || q)
+ *   channel kind (kind 1): softmax over the HW positions of a (b, c) plane, *loss = tau^2 / (B C) * sum_planes KL(p || q)
+ * and d loss / d student = tau / #units * (q - p) * *grad_out (grad_out NULL: 1); the teacher is a constant.
+ * stats: f32 [units][4] = (max x_S, log Z_S, max x_T, log Z_T) per unit, units = B HW (pixel) or B C (channel), 16-byte aligned,
+ * written by the forward and read by the backward.  dstudent: [B][HW][ldd] rows, ldd >= C a multiple of 8; its pad channels are
+ * written as zeros.  No atomics: per-block partial rows go to `workspace` (tss_distill_workspace_bytes bytes, 16-byte aligned, NOT
+ * initialised by the caller), a one-block kernel combines them in a fixed order, so two runs give the same bits; no host read-back.
+ * max_blocks caps the grid, 0 = the default; the workspace size and the forward take the same value.  Anything outside this
+ * contract: TSS_ERR_SHAPE (tss_distill_workspace_bytes: 0). */
+long tss_distill_workspace_bytes(int kind, long B, int C, long HW, int max_blocks);
+int tss_distill_pixel_fwd(const void* student, long lds, const void* teacher, long ldt, float* stats, void* workspace, float* loss,
+                          long B, int C, long HW, float tau, int max_blocks, int dtype, void* stream);
+int tss_distill_pixel_bwd(const void* student, long lds, const void* teacher, long ldt, const float* stats, const float* grad_out,
+                          void* dstudent, long ldd, long B, int C, long HW, float tau, int max_blocks, int dtype, void* stream);
+int tss_distill_channel_fwd(const void* student, long lds, const void* teacher, long ldt, float* stats, void* workspace, float* loss,
+                            long B, int C, long HW, float tau, int max_blocks, int dtype, void* stream);
+int tss_distill_channel_bwd(const void* student, long lds, const void* teacher, long ldt, const float* stats, const float* grad_out,
+                            void* dstudent, long ldd, long B, int C, long HW, float tau, int max_blocks, int dtype, void* stream);
 /* counts[c] += the number of labels equal to c among the n int64 labels of `target`, c in [0, C), the labels equal to
  * ignore_index left out (has_ignore = 0: none are).  Integer arithmetic only: exact, and `counts` (int64 [C], owned and
  * initialised by the caller) accumulates over calls.  C <= tss_label_histogram_max_classes() (per-block LDS counters). */

@@ -332,8 +332,22 @@ def allreduce_mean_(flat, world_size, group=None):
 
 class Trainer:
     def __init__(self, model, optimizer, loss_fn, device=None, use_graph=False, world_size=None,
-                 non_blocking=True, fuse_head_loss=True, graph_allreduce=None):
+                 non_blocking=True, fuse_head_loss=True, graph_allreduce=None, teacher=None, distill_loss=None, distill_weight=1.0):
         self.model, self.optimizer, self.loss_fn = model, optimizer, loss_fn
+        # Logit distillation: `distill_weight * distill_loss(low, teacher_low)` on the low-resolution logits is added to the loss.  The
+        # teacher is frozen: eval() once and for all, forward under no_grad inside an EvalPrep(frozen=True) whose preparation launches
+        # run once (its weights never change), on the step's stream and, with use_graph, inside the captured step.
+        if (teacher is None) != (distill_loss is None):
+            raise ValueError('Trainer: teacher and distill_loss come together (got teacher=%s, distill_loss=%s)'
+                             % (type(teacher).__name__, type(distill_loss).__name__))
+        if teacher is not None:
+            for m, who in ((teacher, 'teacher'), (model, 'model')):
+                if not hasattr(m, 'forward_lowres'):
+                    raise NotImplementedError('Trainer: distillation compares low-resolution logits, but the %s (%s) has no '
+                                              'forward_lowres()' % (who, type(m).__name__))
+            teacher.eval()
+        self.teacher, self.distill_loss, self.distill_weight = teacher, distill_loss, distill_weight
+        self._teacher_prep = None
         self.device = device
         self.non_blocking = non_blocking
         # gradients are SUMMED over the ranks and scaled by 1/world_size: the factor must be the size of the group the
@@ -403,17 +417,56 @@ class Trainer:
         with ops.direct_grads(self.flat), self.shadows:
             if self.fuse_head_loss and not (self.model._forward_hooks or self.model._forward_pre_hooks):
                 low = self.model.forward_lowres(x)
+                if self.teacher is not None:     # two consumers: the head loss and the distillation term
+                    low, low_kd = ops.two_consumers(ops.to_nhwc(ops.materialize(low)))
                 if type(self.loss_fn) is ops.OHEMLoss:
                     loss = ops.upsample_ohem_loss(low, y, scale_factor=self.model.logit_scale, ignore_index=self.loss_fn.ignore_index,
                                                   thresh_loss=self.loss_fn.thresh_loss, numel_frac=self.loss_fn.numel_frac)
                 else:
                     loss = ops.upsample_cross_entropy(low, y, scale_factor=self.model.logit_scale,
                                                       ignore_index=self.loss_fn.ignore_index)
+            elif self.teacher is not None:
+                low_kd, y_pred = self._forward_with_lowres(x)
+                loss = self.loss_fn(y_pred, y)
             else:
                 y_pred = self.model(x)
                 loss = self.loss_fn(y_pred, y)
+            if self.teacher is not None:
+                loss = loss + self.distill_weight * self._distill_term(x, low_kd)
             loss.backward(self._one if (loss.dtype == torch.float32 and loss.dim() == 0 and loss.device == self._one.device) else None)
         return loss
+
+    def _forward_with_lowres(self, x):
+        """(low-resolution logits, model(x)) of ONE student forward: the map that model.forward hands to its head is picked up on
+        its way out of forward_lowres (a second forward would advance the BatchNorm statistics twice and draw other dropout masks)."""
+        seen = []
+        inner = self.model.forward_lowres
+
+        def tap(*args, **kwargs):
+            low, low_kd = ops.two_consumers(ops.to_nhwc(ops.materialize(inner(*args, **kwargs))))
+            seen.append(low_kd)
+            return low
+
+        self.model.forward_lowres = tap         # an instance attribute in front of the method, for this call only
+        try:
+            y_pred = self.model(x)
+        finally:
+            del self.model.forward_lowres
+        if len(seen) != 1:
+            raise NotImplementedError('Trainer: distillation needs a model whose forward() goes through forward_lowres() once; %s '
+                                      'called it %d times' % (type(self.model).__name__, len(seen)))
+        return seen[0], y_pred
+
+    def _distill_term(self, x, low):
+        if self._teacher_prep is None:
+            self._teacher_prep = EvalPrep(self.teacher, frozen=True)
+        with torch.no_grad(), self._teacher_prep:
+            t_low = ops.materialize(self.teacher.forward_lowres(x))
+        if tuple(t_low.shape) != tuple(low.shape):
+            raise NotImplementedError('Trainer: the teacher\'s low-resolution logits are %s, the student\'s %s; distillation of maps of '
+                                      'different shapes is not supported (resize the teacher\'s, e.g. with ops.bilinear, in a wrapper)'
+                                      % (tuple(t_low.shape), tuple(low.shape)))
+        return self.distill_loss(low, t_low)
 
     def _reduce_and_step(self, captured_reduce=False):
         if captured_reduce:
@@ -733,15 +786,19 @@ class HostBatchPipeline:
 
 
 def create_segmentation_trainer(model, optimizer, loss_fn, device, use_f16=False, logging=True,
-                                non_blocking=True, use_graph=False, world_size=None, fuse_head_loss=True):
-    """Same arguments as TSS/engine.py:22.  `use_f16` selects bf16 activations (f32 master parameters), the
+                                non_blocking=True, use_graph=False, world_size=None, fuse_head_loss=True,
+                                teacher=None, distill_loss=None, distill_weight=1.0):
+    """Same arguments as TSS/engine.py:22; `teacher`, `distill_loss` and `distill_weight` add a logit-distillation term (Trainer).  `use_f16` selects bf16 activations (f32 master parameters), the
     MI355X counterpart of the reference's apex amp O2 branch (TSS/engine.py:32-34); no loss scaling is needed."""
     from .models import set_compute_dtype
     set_compute_dtype(model, torch.bfloat16 if use_f16 else torch.float32)
+    if teacher is not None:         # the distillation kernels read student and teacher logits of one dtype
+        set_compute_dtype(teacher, torch.bfloat16 if use_f16 else torch.float32)
     if world_size is None:
         world_size = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     return Trainer(model, optimizer, loss_fn, device=device, use_graph=use_graph, world_size=world_size,
-                   non_blocking=non_blocking, fuse_head_loss=fuse_head_loss)
+                   non_blocking=non_blocking, fuse_head_loss=fuse_head_loss, teacher=teacher, distill_loss=distill_loss,
+                   distill_weight=distill_weight)
 
 
 # ----------------------------------------------------------------------------- evaluator

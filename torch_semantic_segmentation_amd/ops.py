@@ -3469,6 +3469,124 @@ class DiceLoss(torch.nn.Module):
         return dice_loss(input, target, self.num_classes, self.smooth, self.ignore_index)
 
 
+DISTILL_KINDS = {'pixel': 0, 'channel': 1}
+DISTILL_MAX_CLASSES = 256
+distill_max_blocks = 0       # block cap of the distillation kernels; 0: their default (csrc/distill.hip)
+
+
+def _check_distill(temperature, kind):
+    if kind not in DISTILL_KINDS:
+        raise ValueError("kind must be 'pixel' or 'channel', got %r" % (kind,))
+    if not float(temperature) > 0.0:
+        raise ValueError('temperature must be > 0, got %r' % (temperature,))
+
+
+class DistillFn(Function):
+    """distillation_loss on csrc/distill.hip, student and teacher as NHWC low-resolution logits of one dtype: the forward (two
+    launches for the pixel kind, three for the channel kind) leaves the loss and four floats per pixel / per plane, the backward is
+    one elementwise sweep from them.  Per-block partial rows and a fixed-order finalize (no atomics, no host read-back):
+    graph-capturable and bit-reproducible.  The teacher gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, student, teacher, temperature, kind):
+        B, C, h, w = student.shape
+        dev = student.device
+        cap, code, tau = int(distill_max_blocks), N.dtype_code(student.dtype), float(temperature)
+        units = B * h * w if kind == 'pixel' else B * C
+        stats = torch.empty((units, 4), dtype=torch.float32, device=dev)
+        ws = torch.empty(N.lib().tss_distill_workspace_bytes(DISTILL_KINDS[kind], B, C, h * w, cap), dtype=torch.uint8, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        call('tss_distill_%s_fwd' % kind, ptr(student), ld(student), ptr(teacher), ld(teacher), ptr(stats), ptr(ws), ptr(loss),
+             B, C, h * w, tau, cap, code, stream())
+        ctx.args = (kind, B, C, h, w, tau, cap, code)
+        ctx.save_for_backward(student, teacher, stats)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        student, teacher, stats = ctx.saved_tensors
+        kind, B, C, h, w, tau, cap, code = ctx.args
+        gout = gout.to(torch.float32).contiguous()
+        ldd = ld(student)
+        base = torch.empty((B, h, w, ldd), dtype=student.dtype, device=student.device)   # pad channels are written as zeros
+        call('tss_distill_%s_bwd' % kind, ptr(student), ldd, ptr(teacher), ld(teacher), ptr(stats), ptr(gout), ptr(base), ldd,
+             B, C, h * w, tau, cap, code, stream())
+        return base.permute(0, 3, 1, 2)[:, :C], None, None, None
+
+
+def distillation_loss(student, teacher, temperature=1.0, kind='pixel'):
+    """Logit distillation of (B,C,h,w) student logits against teacher logits of the same shape and dtype (float32 or bfloat16),
+    at the resolution of the logits (for the models here: the 1/8-resolution map of forward_lowres).  With x = logits /
+    temperature, p = softmax(x_teacher) and q = softmax(x_student):
+
+    kind='pixel'   (Hinton et al.): softmax over the classes of a pixel, loss = T^2 / (B h w) * sum over pixels of KL(p || q),
+                   which is F.kl_div(F.log_softmax(s / T, 1), F.softmax(t / T, 1), reduction='sum') * T^2 / (B h w);
+    kind='channel' (Shu et al., ICCV 2021): softmax over the h w positions of a (sample, class) plane,
+                   loss = T^2 / (B C) * sum over planes of KL(p || q).
+
+    Every pixel counts (no target, no ignore mask).  The teacher is a constant: it receives no gradient, whatever its
+    requires_grad.  NHWC tensors (what forward_lowres returns) are read in place; a contiguous NCHW tensor is copied to NHWC first
+    (boundary plumbing).  Returns a 0-dim float32 device tensor.  At most 256 classes."""
+    _check_distill(temperature, kind)
+    student, teacher = materialize(student), materialize(teacher)
+    if student.dim() != 4 or tuple(student.shape) != tuple(teacher.shape):
+        raise ValueError('student and teacher logits must have one (B,C,h,w) shape, got %s and %s'
+                         % (tuple(student.shape), tuple(teacher.shape)))
+    if student.shape[1] > DISTILL_MAX_CLASSES:
+        raise ValueError('HIP path: distillation_loss supports at most %d classes, got %d' % (DISTILL_MAX_CLASSES, student.shape[1]))
+    if min(student.shape) < 1:
+        raise ValueError('student and teacher logits must not be empty, got %s' % (tuple(student.shape),))
+    if student.dtype != teacher.dtype:
+        raise TypeError('student and teacher logits must share one dtype, got %s and %s' % (student.dtype, teacher.dtype))
+    N.dtype_code(student.dtype)               # TypeError for anything but float32 / bfloat16
+    _check_device(student)
+    _check_device(teacher)
+    return DistillFn.apply(to_nhwc(student), to_nhwc(teacher.detach()), temperature, kind)
+
+
+class TwoConsumersFn(Function):
+    """x -> (x, x) for low-resolution logits that two losses read (the head loss and the distillation term).  Both hand back an NHWC
+    gradient whose pad channels are zeros; the backward adds them over the whole padded rows (one ATen add), so the sum is again
+    an NHWC tensor with zero pads, the layout the classifier's backward gets from the head loss alone.  Autograd's own add would
+    return a dense C-channel tensor, and its NHWC copy has uninitialised pad channels."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x.view_as(x), x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, ga, gb):
+        if ga is None or gb is None:
+            return gb if ga is None else ga
+        B, C, h, w = ga.shape
+        pitch = ld(ga)
+
+        def whole_rows(g):      # an NHWC view whose storage holds every row up to the pitch
+            return is_nhwc(g) and ld(g) == pitch and (g.storage_offset() + B * h * w * pitch) * g.element_size() <= g.untyped_storage().nbytes()
+
+        if ga.dtype == gb.dtype and whole_rows(ga) and whole_rows(gb):
+            size, stride = (B, h, w, pitch), (h * w * pitch, w * pitch, pitch, 1)
+            return (torch.as_strided(ga, size, stride) + torch.as_strided(gb, size, stride)).permute(0, 3, 1, 2)[:, :C]
+        return ga + gb
+
+
+def two_consumers(x):
+    return TwoConsumersFn.apply(x)
+
+
+class DistillationLoss(torch.nn.Module):
+    """forward(student, teacher) = distillation_loss(student, teacher, temperature, kind); engine.Trainer(teacher=...,
+    distill_loss=DistillationLoss(...)) adds it to the head loss on the low-resolution logits."""
+
+    def __init__(self, temperature=1.0, kind='pixel'):
+        super().__init__()
+        _check_distill(temperature, kind)
+        self.temperature, self.kind = temperature, kind
+
+    def forward(self, student, teacher):
+        return distillation_loss(student, teacher, self.temperature, self.kind)
+
+
 class UpsampleCrossEntropyFn(Function):
     """cross_entropy(F.interpolate(low, scale, bilinear, align_corners=True), target) without the full-res logits:
     one pass yields the loss and the unscaled low-res gradient (per-block tiles in a workspace, no atomics, nothing to
