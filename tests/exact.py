@@ -1,5 +1,5 @@
 """Exact-operand f64 references for the bf16 convolution kernels (tests/test_exact_bounds.py, tests/test_gpu_zoo_exact.py,
-tests/test_gpu_dw_exact.py).
+tests/test_gpu_dw_exact.py, tests/test_gpu_pw_exact.py).
 
 Every operand is a DYADIC bf16 value, +-(1 + k/128) * 2^e with e in [-4, 2): 8 significant bits.  BatchNorm scales are powers of two in
 [1/2, 4], the backward pair (ga, gb) powers of two in [1/4, 2] and [2^-6, 2^-3].  Then the on-load transforms of the kernels
@@ -170,9 +170,12 @@ def stats_excess(slab_sum, terms, chain):
     """statistics slabs from the STORED output bits: each term (a bf16 value, or a product of one with an exact f32 difference: at most
     16 + 8 significant bits) is exact in f32; a lane adds its terms in f32 (chain: the longest such chain plus the in-wave tree), the
     block and slab sums are f64 (2^-50 covers them).  |sum - f64 sum of the terms| <= (2^-23 chain + 2^-50) sum|terms|"""
-    ref = terms.sum(0)
-    bound = (2.0 ** -23 * chain + 2.0 ** -50) * terms.abs().sum(0)
-    return ((slab_sum - ref).abs() - bound).max().item()
+    return stats_excess_sums(slab_sum, terms.sum(0), terms.abs().sum(0), chain)
+
+
+def stats_excess_sums(slab_sum, tsum, tabs, chain):
+    """stats_excess from the column sums of the terms and of their magnitudes (accumulated over row blocks of a large tensor)"""
+    return ((slab_sum - tsum).abs() - (2.0 ** -23 * chain + 2.0 ** -50) * tabs).max().item()
 
 
 def cdiv(a, b):
@@ -197,13 +200,14 @@ def generic_stats_chain(P, ND):
     return 4 * cdiv(per, gs) + 4
 
 
-def generic_wgrad_chain(P, K, N, ntaps):
+def generic_wgrad_chain(P, K, N, ntaps, pt=64):
     """wgrad_kernel (the generic bf16 weight gradient): 64-pixel stages, ns = clamp(1024 / tiles, <= ceil(nstage / 8), >= 1) blocks per
-    output tile, each owning ceil(nstage / ns) stages; a product per pixel, the block's 4 waves combined, ns f32 atomics onto dw"""
+    output tile, each owning ceil(nstage / ns) stages; a product per pixel, the block's 4 waves combined, ns f32 atomics onto dw.
+    pt = 32: the f32 instance's stages (its products of two f32 operands round too: the caller doubles the chain)"""
     tiles = cdiv(N, 128) * cdiv(K, 128) * ntaps
-    nstage = cdiv(P, 64)
+    nstage = cdiv(P, pt)
     ns = max(1, min(max(1, 1024 // tiles), cdiv(nstage, 8)))
-    return cdiv(nstage, ns) * 64 + 4 + ns
+    return cdiv(nstage, ns) * pt + 4 + ns
 
 
 # ---------------------------------------------------------------------------------------------------------- references
@@ -429,3 +433,141 @@ def bilinear_f32_slack(x, Ho, Wo):
                    FMA fewer) plus the weight's: <= gamma_6 sum of |weight products| M <= 2^-21 M (the weights sum to <= 1 + 2 u).
     Together <= 2^-21 M (Hs + Ws)"""
     return 2.0 ** -21 * float(x.abs().max()) * (x.shape[2] + x.shape[3])
+
+
+# ---------------------------------------------------------------------------------------------------------- pointwise (1x1) family
+# csrc/pwfast.hip, wgrad.hip (wgfast_kernel) + wgreduce.h, pwbwd.hip, pwsweep.hip; tests/test_gpu_pw_exact.py.  These kernels feed the
+# matrix unit: a and g are rounded to bf16 (act / gcomb) and the weights are bf16-exact, so every product is exact and conv_excess holds
+# with K the contraction length.  Each helper below restates a launch planner of the C source; the GPU test asserts its rows / workspace
+# count against the library's own entry, so a planner that moves makes the test fail instead of the bound drift.
+PW_SINGLE_THR = 4200      # block-tiles below which the single-chunk kernels take the small tile (TSS_PW_FWD_SMALL / TSS_PW_BWD_SMALL)
+
+
+def pwfast_plan(P, K, N, bwd=False):
+    """tss_pwfast_fwd / tss_pwconv_fwd_joined / tss_pwfast_bwd_data (csrc/pwfast.hip): (multi-chunk kernel, pixels per tile TM) of a
+    GEMM with contraction K and N output columns (backward-data: K = the convolution's Cout, N = its Cin).  K <= 128:
+    pwfast_kernel, forward TM 64 below 4200 block-tiles of 128 pixels else 128, backward 32 below 4200 block-tiles of 64 else 64;
+    K > 128: pwfast_mc_kernel, TM 32 / 64 / 128 at t < 192 / t < 256 / otherwise, t = ceil(P / 128) ceil(N / 128)"""
+    nch = cdiv(N, 128)
+    if K <= 128:
+        if bwd:
+            return False, (32 if cdiv(P, 64) * nch < PW_SINGLE_THR else 64)
+        return False, (64 if cdiv(P, 128) * nch < PW_SINGLE_THR else 128)
+    t = cdiv(P, 128) * nch
+    return True, (32 if t < 192 else 64 if t < 256 else 128)
+
+
+def pwfast_stats_chain(P, K, N, bwd=False):
+    """(f32 chain of one lane's statistics, slab rows in use) of launch_fast / launch_fast_mc_tm: the tiles are dealt to 8 XCD ranges of
+    per = ceil(ntiles / 8), each shared by gs = min(per, cap) blocks, cap = (96 for the small single-chunk tile, else 64) / column
+    chunks, at most 64, at least 1; a block owns ceil(per / gs) tiles, a lane adds TM / 32 pixels per tile (two waves split the tile's
+    pixels, 16 per MFMA fragment), then row16_sum's 4 levels; the two pixel halves and the slab rows meet in f64"""
+    mc, TM = pwfast_plan(P, K, N, bwd)
+    nch = cdiv(N, 128)
+    small = not mc and TM == (32 if bwd else 64)
+    cap = max(1, min(64, (96 if small else 64) // nch))
+    per = cdiv(cdiv(P, TM), 8)
+    gs = min(per, cap)
+    return TM // 32 * cdiv(per, gs) + 4, 8 * gs
+
+
+def pw_ws_dim(d):
+    """tss_wg::ws_dim: a workspace slot's extent along one axis"""
+    return (min(d, 128) + 15) & ~15
+
+
+def pw_wgrad_split(P, K, N):
+    """tss_wg::split_for (csrc/wgreduce.h): (stage length, blocks per output tile, output tiles).  128-pixel stages when both chunk
+    widths are <= 64 channels; a block owns >= 512 pixels, or >= 256 when tiles ceil(P / 512) < 256 (the small-layer rule)"""
+    pt = 128 if max(min(N, 128), min(K, 128)) <= 64 else 64
+    tiles = cdiv(N, 128) * cdiv(K, 128)
+    nstage = cdiv(P, pt)
+    min_px = 256 if tiles * cdiv(P, 512) < 256 else 512
+    ns = max(1, min(max(1, 1024 // tiles), cdiv(nstage, cdiv(min_px, pt))))
+    return pt, ns, tiles
+
+
+def pw_wgrad_chain(P, K, N):
+    """(f32 chain, workspace floats) of wgfast_kernel + tss_wg::reduce_block: a block owns ceil(nstage / nsplit) stages of pt pixels,
+    one exact product per pixel into an accumulator (waves that split a stage's k-steps meet in one LDS addition); reduce_block: a wave
+    adds slots w, w + 4, ... (ceil(nsplit / 4)), one thread adds the 4 waves' sums, and the total is added to dW"""
+    pt, ns, tiles = pw_wgrad_split(P, K, N)
+    return cdiv(cdiv(P, pt), ns) * pt + 1 + cdiv(ns, 4) + 4 + 1, tiles * ns * pw_ws_dim(N) * pw_ws_dim(K)
+
+
+def pwbwd_rows(P, Cin, Cout, big_tr=False, drop=False):
+    """tss_pwconv_bwd_fused_rows / _drop_rows + launch() of csrc/pwbwd.hip: (instance, TM, pixels a lane adds per tile MFX, workspace =
+    slab rows 8 gs, tiles per block).  MFX = TM / (waves / NSPLIT) / 16"""
+    if drop:
+        name, TM, MFX, cap = 'drop', 64, 2, 64
+    elif Cin <= 64 and Cout <= 64:
+        name, TM, MFX, cap = 'small', 128, 2, 64
+    elif Cin <= 64:
+        name, TM, MFX, cap = 'mid', 64, 1, 64
+    elif Cout <= 64:
+        name, TM, MFX, cap = 'tall', 64, 1, 64
+    elif big_tr:
+        name, TM, MFX, cap = 'big_tr', 64, 2, 64
+    else:
+        name, TM, MFX, cap = 'big', 128, 2, 32
+    per = cdiv(cdiv(P, TM), 8)
+    gs = max(1, min(per, cap))
+    return name, TM, MFX, 8 * gs, cdiv(per, gs)
+
+
+def pwbwd_stats_chain(plan):
+    """pwbwd_kernel / pwsweep_kernel: a lane adds MFX pixels per tile it owns, then row16_sum's 4 levels (the waves meet in f64)"""
+    return plan[2] * plan[4] + 4
+
+
+def pwbwd_wgrad_chain(plan):
+    """pwbwd_kernel / pwsweep_kernel + tss_dw_reduce_many: the block keeps its [Cout][Cin] tile in accumulators over every tile it owns
+    (TM exact products each), writes one workspace row, and the rows are added by dw_reduce_block (reduce_chain)"""
+    return plan[4] * plan[1] + reduce_chain(plan[3])
+
+
+def pwbwd_bias_chain(plan):
+    """the bias-gradient row of pwbwd_kernel: a thread adds (v0 + v1) + (v2 + v3) of its 4 pixels to its sum per tile (3 roundings a
+    term goes through), then one thread adds the TM / 4 pixel groups"""
+    return 3 * plan[4] + plan[1] // 4
+
+
+PWSWEEP_KINDS = {(128, 128): (64, 2), (64, 384): (32, 1), (384, 64): (32, 2), (32, 192): (64, 1), (192, 32): (32, 1)}     # (TM, DXM)
+
+
+def pwsweep_rows(P, Cin, Cout):
+    """slots_for + Cfg of csrc/pwsweep.hip in pwbwd_rows' form: one 512-thread block per CU (gs <= 32), P / TM whole tiles"""
+    TM, DXM = PWSWEEP_KINDS[(Cin, Cout)]
+    assert P % TM == 0
+    per = cdiv(P // TM, 8)
+    gs = max(1, min(per, 32))
+    return 'sweep', TM, DXM, 8 * gs, cdiv(per, gs)
+
+
+def joined_fwd_ref(conv, S, cbias, omean, oscale, obeta, res=None, relu=False):
+    """tss_pwconv_fwd_joined: y = relu?((v - out_mean) out_scale + out_beta + residual), v = conv + bias.  Returns (ref, M) for
+    conv_excess(out, ref, M, K + 2).  The kernel computes shift = out_beta + (bias - out_mean) out_scale once per channel: exact in
+    f32 for dyadic vectors and a power-of-two out_scale (checked here), whatever the contraction of the compiler.  Then per element
+        acc  = f32 sum of the K exact products             |acc - conv| <= gamma_K S
+        t1   = fl(acc out_scale + shift)                   the product is a shift: ONE rounding, of a value <= out_scale S' + |shift|
+        t2   = fl(t1 + residual)                           one more, of a value <= |t1| + |residual|
+    so |t2 - r| <= out_scale gamma_K S + u (1 + u) (|t1| + |t2|) <= gamma_(K + 2) M with M = out_scale S + |shift| + |residual| (the
+    accumulation term is multiplied by out_scale, as are S and hence M).  ReLU is 1-Lipschitz, and the bf16 rounding adds
+    2^-8 (|ref| + gamma_(K + 2) M): |y - ref| <= 2^-8 |ref| + 2^-23 (K + 2) (1 + 2^-8) M <= 2^-8 |ref| + 2^-22 (K + 2) M"""
+    shift = exact_f32(obeta + ((cbias if cbias is not None else 0.0) - omean) * oscale)
+    r, M = conv * oscale + shift, S * oscale + shift.abs()
+    if res is not None:
+        r, M = r + res, M + res.abs()
+    return (r.clamp_min(0.0) if relu else r), M
+
+
+def joined_bwd_ref(rin, Sin, radd, jout):
+    """tss_pwconv_bwd_data_joined: e_in = (g W + radd) where join_out > 0, else 0.  Returns (ref, M) for conv_excess(out, ref, M, K + 1):
+    the f32 sum of the K exact products takes radd (a bf16 value, exact) in one more addition -- K + 1 terms, gamma_(K + 1) M with
+    M = S + |radd| -- the mask selects the value or an exact 0 (join_out is given, so the mask is the reference's own), and the result is
+    rounded to bf16 once.  join_bstats then holds sum e_in and sum e_in (join_y - join_mean) of the STORED bits: stats_excess with the
+    launch's pwfast_stats_chain (the difference is exact in f32 for dyadic operands, the product has <= 8 + 16 bits)"""
+    keep = (jout > 0).double()
+    if radd is not None:
+        rin, Sin = rin + radd, Sin + radd.abs()
+    return rin * keep, Sin * keep

@@ -1,5 +1,10 @@
-"""GPU harness of the exact-operand tests (tests/test_gpu_zoo_exact.py, tests/test_gpu_dw_exact.py): sentinel-padded device buffers with
-spare rows, NaN statistics slabs, the dyadic operands of a layer with planted exact zeros, and the checks against tests/exact.py's bounds."""
+"""GPU harness of the exact-operand tests (tests/test_gpu_zoo_exact.py, tests/test_gpu_dw_exact.py, tests/test_gpu_pw_exact.py):
+sentinel-padded device buffers with spare rows, NaN statistics slabs, the dyadic operands of a layer with planted exact zeros, and the
+checks against tests/exact.py's bounds."""
+import contextlib
+import ctypes
+import os
+
 import torch
 
 from tests import exact as X
@@ -37,6 +42,31 @@ class Buf:
         b = X.bits(self.t.cpu()).clone()
         b[:self.P, self.off:self.off + self.C] = self.sbits
         return bool((b == self.sbits).all())
+
+
+@contextlib.contextmanager
+def env(**kw):
+    """environment switches of the kernels (read per call by getenv), restored whatever happens"""
+    old = {k: os.environ.get(k) for k in kw}
+    try:
+        for k, v in kw.items():
+            os.environ[k] = str(v)
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def reduce_many(jobs):
+    """tss_dw_reduce_many over [(ws tensor or pointer, dw tensor or pointer, n, rows)]"""
+    N = N_()
+    n = len(jobs)
+    p = lambda t: t if isinstance(t, int) else t.data_ptr()
+    N.call('tss_dw_reduce_many', n, (ctypes.c_void_p * n)(*[p(j[0]) for j in jobs]), (ctypes.c_void_p * n)(*[p(j[1]) for j in jobs]),
+           (ctypes.c_int * n)(*[j[2] for j in jobs]), (ctypes.c_int * n)(*[j[3] for j in jobs]), N.stream())
 
 
 def nan_slabs(C):
@@ -109,3 +139,38 @@ def check_stats(slabs, terms, chain, what):
     assert not torch.isnan(s).any(), (what, 'a slab row neither written nor zeroed')
     ex = X.stats_excess(s.sum(0), terms, chain)
     assert ex <= 0, (what, 'statistics excess', ex)
+
+
+BLOCK_ROWS = 16384   # rows of a large tensor evaluated and checked at a time (the f64 reference of 90 k x 768 outputs stays ~100 MB)
+
+
+def check_blocked(buf, ref_fn, K, what, second=None, excess=X.conv_excess):
+    """check_out in row blocks: ref_fn(r0, r1) -> (ref, S) rows of [r0, r1).  With second(out, r0, r1) (the second statistics factor per
+    element), returns the column sums (terms, |terms|) of [out, out * second] over all rows for check_stats_sums"""
+    tsum = tabs = 0.0
+    for r0 in range(0, buf.P, BLOCK_ROWS):
+        r1 = min(r0 + BLOCK_ROWS, buf.P)
+        out = buf.t[r0:r1, buf.off:buf.off + buf.C].double().cpu()
+        ref, S = ref_fn(r0, r1)
+        ex = excess(out, ref, S, K)
+        assert ex <= 0, (what, 'rows', r0, r1, 'excess over the bound', ex)
+        if second is not None:
+            t = torch.cat([out, out * second(out, r0, r1)], 1)
+            tsum, tabs = tsum + t.sum(0), tabs + t.abs().sum(0)
+    assert buf.untouched(), (what, 'sentinel overwritten')
+    return tsum, tabs
+
+
+def check_stats_sums(slabs, sums, chain, what, rows_used=None, f64=False):
+    """check_stats from check_blocked's column sums.  rows_used: rows beyond it must hold exact zeros and the launch's last owner row
+    a value (the planner's restatement and the kernel agree on the grid).  f64: an f32 instance, whose sums are f64 throughout (terms
+    exact in f64, within 2^-40 sum|terms|)"""
+    s = slabs.double().cpu()
+    assert not torch.isnan(s).any(), (what, 'a slab row neither written nor zeroed')
+    if rows_used is not None:
+        assert (s[rows_used:] == 0).all() and (s[rows_used - 8] != 0).any(), (what, 'slab rows in use', rows_used)
+    if f64:
+        assert ((s.sum(0) - sums[0]).abs() <= 2.0 ** -40 * sums[1]).all(), what
+        return
+    ex = X.stats_excess_sums(s.sum(0), sums[0], sums[1], chain)
+    assert ex <= 0, (what, 'statistics excess', ex, 'chain', chain)

@@ -372,3 +372,248 @@ def test_dyadic_transforms_are_exact_in_f32_in_the_depthwise_kernels_orders():
             a, b_, c_, d = (f(xs[:, :, r, q]) for r, q in ((i0, j0), (i0, j1), (i1, j0), (i1, j1)))
             o = l0y * (l0x * a + l1x * b_) + l1y * (l0x * c_ + l1x * d)
             assert torch.equal(o.double(), v[:, :, oy, ox])
+
+
+# ---------------------------------------------------------------------------------------------------------- pointwise (1x1) family
+# f32 emulation of csrc/pwfast.hip, wgrad.hip (wgfast_kernel + wgreduce.h), pwbwd.hip and pwsweep.hip in their planners' order: rows are
+# pixels, operands a / g already rounded to bf16, every product exact, the f32 sum walked in 8-channel steps of 128-channel chunks
+# (forward, backward-data) or stage by stage (weight gradient); statistics per block and lane as the epilogues add them
+def _pw_case(seed, P, K, N, zero_frac=0.05):
+    g = _gen(seed)
+    a = X.rne_bf16(X.dyadic((P, K), g, zero_frac=zero_frac))
+    w = X.dyadic((N, K), g, emin=-6, emax=-2)
+    gr = X.rne_bf16(X.dyadic((P, N), g))
+    return a, w, gr
+
+
+def _as_map(rows):
+    """[P][C] rows as the [1][C][P][1] map the f64 references take"""
+    return rows.t().reshape(1, rows.shape[1], rows.shape[0], 1)
+
+
+def _pw_ref(a, w):
+    ref, S = X.conv_ref(_as_map(a), w.reshape(*w.shape, 1, 1))
+    return X.nchw_to_rows(ref), X.nchw_to_rows(S)
+
+
+def _pw_wref(a, gr):
+    ref, S = X.conv_weight_ref(_as_map(a), (gr.shape[1], a.shape[1], 1, 1), _as_map(gr))
+    return ref.reshape(gr.shape[1], a.shape[1]), S.reshape(gr.shape[1], a.shape[1])
+
+
+def _pw_gemm32(a, w, drop=None):
+    """f32 a W^T, 8 channels at a time; drop = (pixel, first channel): that 8-channel step never reaches the accumulator of that pixel"""
+    a32, w32 = a.float(), w.float()
+    acc = torch.zeros(a.shape[0], w.shape[0])
+    for k0 in range(0, a.shape[1], 8):
+        step = a32[:, k0:k0 + 8] @ w32[:, k0:k0 + 8].t()
+        if drop is not None and drop[1] == k0:
+            step[drop[0]] = 0.0
+        acc = acc + step
+    return acc
+
+
+def _pw_slabs(out, fac, TM, rows):
+    """slab rows of pwfast_kernel / pwfast_mc_kernel from the stored outputs: the tiles dealt to 8 XCD ranges shared by rows / 8 blocks; a
+    lane (pixel half, fragment row) adds its TM / 32 pixels per tile in f32, 16 lanes meet in a 4-level tree, the rest is f64"""
+    P, C = out.shape
+    gs, ntiles = rows // 8, X.cdiv(P, TM)
+    per = X.cdiv(ntiles, 8)
+    terms = torch.zeros(ntiles * TM, 2 * C)
+    terms[:P] = torch.cat([out.float(), out.float() * fac.float()], 1)
+    terms = terms.reshape(ntiles, 2, TM // 32, 16, 2 * C)
+    slabs = torch.zeros(512, 2 * C, dtype=torch.float64)
+    for xcd in range(8):
+        for gslot in range(gs):
+            lanes = torch.zeros(2, 16, 2 * C)
+            for t in range(xcd * per + gslot, min(xcd * per + per, ntiles), gs):
+                for m in range(TM // 32):
+                    lanes = lanes + terms[t, :, m]
+            for half in (8, 4, 2, 1):
+                lanes = lanes[:, :half] + lanes[:, half:2 * half]
+            slabs[xcd + 8 * gslot] = lanes.double().sum((0, 1))
+    return slabs
+
+
+# (P, K, N, backward-data, statistics chain): one tile per block (multi-chunk TM 32, two column chunks); 625 tiles of 64: 79 per range
+# over 64 blocks, 2 per block; 1 032 tiles of 32: 3 per block, the last ragged
+@pytest.mark.parametrize('P,K,N,bwd,chain', [(1000, 264, 40, False, 5), (3075, 136, 256, False, 5), (40000, 8, 8, False, 2 * 2 + 4),
+                                             (33013, 8, 8, True, 1 * 3 + 4)])
+def test_f32_emulation_of_the_pointwise_layer_meets_the_bounds_in_the_planners_order(P, K, N, bwd, chain):
+    a, w, _ = _pw_case(P + K, P, K, N)
+    ref, S = _pw_ref(a, w)
+    out = X.rne_bf16(_pw_gemm32(a, w).double())
+    assert X.conv_excess(out, ref, S, K) <= 0
+    _, TM = X.pwfast_plan(P, K, N, bwd)
+    assert X.pwfast_stats_chain(P, K, N, bwd)[0] == chain
+    rows = X.pwfast_stats_chain(P, K, N, bwd)[1]
+    fac = out if not bwd else X.dyadic((P, N), _gen(1)) - X.dyadic((1, N), _gen(2))
+    slabs = _pw_slabs(out, fac, TM, rows)
+    assert (slabs[rows:] == 0).all() and (slabs[rows - 8] != 0).any()
+    assert X.stats_excess(slabs.sum(0), torch.cat([out, out * fac], 1), chain) <= 0
+
+
+def test_a_dropped_k_step_of_the_second_contraction_chunk_at_one_pixel_fails():
+    P, K, N = 300, 264, 40
+    a, w, _ = _pw_case(3, P, K, N, zero_frac=0.0)
+    ref, S = _pw_ref(a, w)
+    out = X.rne_bf16(_pw_gemm32(a, w, drop=(217, 128 + 40)).double())
+    assert X.conv_excess(out, ref, S, K) > 0
+    assert X.conv_excess(torch.cat([out[:217], out[218:]]), torch.cat([ref[:217], ref[218:]]), torch.cat([S[:217], S[218:]]), K) <= 0
+
+
+def test_a_ragged_last_tile_that_repeats_the_previous_tile_fails():
+    P, K, N, TM = 200, 48, 96, 64
+    a, w, _ = _pw_case(4, P, K, N)
+    ref, S = _pw_ref(a, w)
+    out = X.rne_bf16(_pw_gemm32(a, w).double())
+    p0 = P // TM * TM
+    out[p0:] = out[p0 - TM:p0 - TM + (P - p0)]                      # the prefetched tile consumed one iteration late
+    assert X.conv_excess(out, ref, S, K) > 0
+
+
+def _wgfast_slots(a, gr, P, K, N):
+    """per-block f32 partial tiles of wgfast_kernel (one output tile: K, N <= 128): split s owns ceil(nstage / nsplit) stages of pt
+    pixels, added 32 pixels (one MFMA k-step) at a time"""
+    pt, ns, tiles = X.pw_wgrad_split(P, K, N)
+    assert tiles == 1
+    per = X.cdiv(X.cdiv(P, pt), ns)
+    slots = []
+    for s in range(ns):
+        acc = torch.zeros(N, K)
+        for p0 in range(s * per * pt, min((s + 1) * per * pt, P), 32):
+            p1 = min(p0 + 32, P, (s + 1) * per * pt)
+            acc = acc + gr[p0:p1].float().t() @ a[p0:p1].float()
+        slots.append(acc)
+    return slots
+
+
+def _wg_reduce(slots, leave_out=None):
+    """tss_wg::reduce_block: wave w adds slots w, w + 4, ..., one thread adds the four waves, the total goes onto dW"""
+    waves = []
+    for wv in range(4):
+        acc = torch.zeros_like(slots[0])
+        for q in range(wv, len(slots), 4):
+            if q != leave_out:
+                acc = acc + slots[q]
+        waves.append(acc)
+    t = torch.zeros_like(slots[0])
+    for acc in waves:
+        t = t + acc
+    return torch.zeros_like(t) + t
+
+
+@pytest.mark.parametrize('P,K,N', [(3000, 64, 64), (5000, 128, 128), (517, 48, 8)])
+def test_weight_gradient_slots_meet_the_bound_and_a_slot_left_out_fails(P, K, N):
+    a, _, gr = _pw_case(5 + P, P, K, N)
+    ref, S = _pw_wref(a, gr)
+    chain, nws = X.pw_wgrad_chain(P, K, N)
+    slots = _wgfast_slots(a, gr, P, K, N)
+    assert nws == len(slots) * X.pw_ws_dim(N) * X.pw_ws_dim(K) and len(slots) >= 2
+    assert X.wgrad_excess(_wg_reduce(slots).double(), ref, S, chain) <= 0
+    assert X.wgrad_excess(_wg_reduce(slots, leave_out=len(slots) - 1).double(), ref, S, chain) > 0
+
+
+@pytest.mark.parametrize('Cin,Cout,P,sweep', [(8, 8, 512 * 128 + 300, False), (64, 128, 700, False), (32, 192, 64 * 40, True), (192, 32, 32 * 776, True)])
+def test_one_sweep_backward_rows_meet_the_bounds_in_the_planners_order(Cin, Cout, P, sweep):
+    """pwbwd_kernel / pwsweep_kernel: a block keeps its [Cout][Cin] tile over every tile it owns and writes one row; dw_reduce_block adds
+    rows w, w + 16, ... per wave, then the 16 waves, then onto dW"""
+    a, _, gr = _pw_case(Cin + P, P, Cin, Cout)
+    ref, S = _pw_wref(a, gr)
+    plan = X.pwsweep_rows(P, Cin, Cout) if sweep else X.pwbwd_rows(P, Cin, Cout)
+    _, TM, _, rows, tpb = plan
+    gs, ntiles = rows // 8, X.cdiv(P, TM)
+    per = X.cdiv(ntiles, 8)
+    ws = torch.zeros(rows, Cout, Cin)
+    most = 0
+    for xcd in range(8):
+        for gslot in range(gs):
+            mine = range(xcd * per + gslot, min(xcd * per + per, ntiles), gs)
+            most = max(most, len(mine))
+            for t in mine:
+                for p0 in range(t * TM, min((t + 1) * TM, P), 32):
+                    p1 = min(p0 + 32, P)
+                    ws[xcd + 8 * gslot] = ws[xcd + 8 * gslot] + gr[p0:p1].float().t() @ a[p0:p1].float()
+    assert most == tpb
+    waves = []
+    for wv in range(X.RED_WAVES):
+        acc = torch.zeros(Cout, Cin)
+        for r in range(wv, rows, X.RED_WAVES):
+            acc = acc + ws[r]
+        waves.append(acc)
+    dw = torch.zeros(Cout, Cin)
+    for acc in waves:
+        dw = dw + acc
+    assert X.wgrad_excess(dw.double(), ref, S, X.pwbwd_wgrad_chain(plan)) <= 0
+
+
+def _joined_fwd_case(K, res, relu, seed=0):
+    P, N = 300, 24
+    a, w, _ = _pw_case(seed + K, P, K, N)
+    g = _gen(seed + 9)
+    cb, omean, obeta, oscale = X.dyadic((N,), g), X.dyadic((N,), g), X.dyadic((N,), g), X.pow2((N,), g, 0.5, 4)
+    resid = X.dyadic((P, N), g, zero_frac=0.05) if res else None
+    conv, S = _pw_ref(a, w)
+    ref, M = X.joined_fwd_ref(conv, S, cb, omean, oscale, obeta, resid, relu)
+    f = lambda t: t.float()
+    shift = f(obeta) + (f(cb) - f(omean)) * f(oscale)
+    v = _pw_gemm32(a, w) * f(oscale) + shift                       # the epilogue's order: one rounding here ...
+    return v, f(resid) if res else None, ref, M
+
+
+@pytest.mark.parametrize('K', [64, 264])
+@pytest.mark.parametrize('res,relu', [(False, False), (False, True), (True, False), (True, True)])
+def test_f32_emulation_of_the_joined_forward_epilogue_meets_its_bound(K, res, relu):
+    v, resid, ref, M = _joined_fwd_case(K, res, relu)
+    if res:
+        v = v + resid                                               # ... one here
+    if relu:
+        v = v.clamp_min(0.0)
+    assert X.conv_excess(X.rne_bf16(v.double()), ref, M, K + 2) <= 0
+
+
+def test_a_joined_forward_epilogue_that_applies_the_relu_before_the_residual_fails():
+    v, resid, ref, M = _joined_fwd_case(64, True, True, seed=1)
+    assert X.conv_excess(X.rne_bf16((v.clamp_min(0.0) + resid).double()), ref, M, 64 + 2) > 0
+
+
+def _joined_bwd_case(seed=0):
+    P, K, N = 300, 48, 24                                           # contraction K = the convolution's Cout, N = its Cin
+    gr, w, _ = _pw_case(seed + 21, P, K, N)
+    g = _gen(seed + 22)
+    radd, jout = X.dyadic((P, N), g, zero_frac=0.05), X.dyadic((P, N), g, zero_frac=0.1)
+    jy, jmean = X.dyadic((P, N), g), X.dyadic((1, N), g)
+    rin, Sin = _pw_ref(gr, w)
+    return gr, w, radd, jout, jy - jmean, X.joined_bwd_ref(rin, Sin, radd, jout), K
+
+
+def test_f32_emulation_of_the_joined_backward_epilogue_meets_its_bounds():
+    gr, w, radd, jout, fac, (ref, M), K = _joined_bwd_case()
+    v = _pw_gemm32(gr, w) + radd.float()
+    out = X.rne_bf16(torch.where(jout > 0, v, torch.zeros_like(v)).double())
+    assert X.conv_excess(out, ref, M, K + 1) <= 0
+    assert (jout <= 0).any() and (out[jout <= 0] == 0).all()
+    chain, rows = X.pwfast_stats_chain(300, K, 24, bwd=True)
+    slabs = _pw_slabs(out, fac, 32, rows)
+    assert X.stats_excess(slabs.sum(0), torch.cat([out, out * fac], 1), chain) <= 0
+
+
+def test_a_residual_added_behind_the_join_mask_fails():
+    gr, w, radd, jout, fac, (ref, M), K = _joined_bwd_case(seed=1)
+    v = _pw_gemm32(gr, w)
+    out = X.rne_bf16((torch.where(jout > 0, v, torch.zeros_like(v)) + radd.float()).double())
+    assert X.conv_excess(out, ref, M, K + 1) > 0
+
+
+def test_a_dropout_keep_byte_of_the_neighbouring_channel_group_fails():
+    """tss_pwconv_fwd_drop with p = 0.75: the reference applies the mask bytes as read back; a kernel that takes byte v + 1 for the 8-channel
+    vector v keeps other channels"""
+    P, K, N, dinv = 200, 48, 24, 4.0
+    a, w, _ = _pw_case(31, P, K, N, zero_frac=0.0)
+    mbytes = torch.randint(0, 256, (P, 16), generator=_gen(32)) & torch.randint(0, 256, (P, 16), generator=_gen(33))       # ~1/4 kept
+    keep = lambda shift: torch.stack([(mbytes[:, (k // 8 + shift) % (K // 8)] >> (k % 8)) & 1 for k in range(K)], 1).double()
+    ref, S = _pw_ref(a * keep(0), w)
+    ok = X.rne_bf16((_pw_gemm32(a * keep(0), w) * dinv).double())
+    assert X.conv_excess(ok, ref * dinv, S * dinv, K) <= 0
+    bad = X.rne_bf16((_pw_gemm32(a * keep(1), w) * dinv).double())
+    assert X.conv_excess(bad, ref * dinv, S * dinv, K) > 0

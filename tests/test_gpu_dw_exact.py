@@ -17,35 +17,17 @@ reference is the convolution of v and the bound grows by that amount times the a
 
 Template instances the C entry points cannot reach: dw_bwd_data_strip_kernel<float, S, D, true> is never instantiated
 (launch_strip_fused is bf16 only: the f32 path keeps the two separate kernels)."""
-import contextlib
 import ctypes
-import os
 
 import pytest
 import torch
 
 from tests import exact as X
-from tests.exact_gpu import DEV, Buf, Layer, N_, check_out, check_stats, dev, nan_slabs, to_rows, vecs
+from tests.exact_gpu import DEV, Buf, Layer, N_, check_out, check_stats, dev, env, nan_slabs, reduce_many, to_rows, vecs
 
 pytestmark = pytest.mark.gpu
 BF, F32 = torch.bfloat16, torch.float32
 VARIANTS = {'bnrelu': (True, True), 'bn': (True, False), 'mat': (False, False)}       # (pending BatchNorm, ReLU)
-
-
-@contextlib.contextmanager
-def env(**kw):
-    """environment switches of the kernels (read per call by getenv), restored whatever happens"""
-    old = {k: os.environ.get(k) for k in kw}
-    try:
-        for k, v in kw.items():
-            os.environ[k] = str(v)
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 class DwLayer(Layer):
@@ -131,15 +113,6 @@ def check_rows(ws, rows, what):
     w = ws.cpu()
     assert not torch.isnan(w[:rows]).any(), (what, 'a workspace row not written')
     assert torch.isnan(w[rows:]).all(), (what, 'a workspace row beyond the grid written')
-
-
-def reduce_many(jobs):
-    """tss_dw_reduce_many over [(ws tensor or pointer, dw tensor or pointer, n, rows)]"""
-    N = N_()
-    n = len(jobs)
-    p = lambda t: t if isinstance(t, int) else t.data_ptr()
-    N.call('tss_dw_reduce_many', n, (ctypes.c_void_p * n)(*[p(j[0]) for j in jobs]), (ctypes.c_void_p * n)(*[p(j[1]) for j in jobs]),
-           (ctypes.c_int * n)(*[j[2] for j in jobs]), (ctypes.c_int * n)(*[j[3] for j in jobs]), N.stream())
 
 
 def path_of(C, stride, dil, dtype, roll_on=True):

@@ -305,7 +305,8 @@ def setup_distributed(enable=True, local_rank=None, backend=None):
         return 1, 0, 0
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0')) if local_rank is None else local_rank
-    if torch.cuda.is_available():
+    # (gloo ranks hold CPU tensors: more of them than visible devices is fine; any other backend needs its own device and raises here)
+    if torch.cuda.is_available() and (backend != 'gloo' or local_rank < torch.cuda.device_count()):
         torch.cuda.set_device(local_rank)
     launched = 'RANK' in os.environ and 'MASTER_ADDR' in os.environ     # under torch.distributed.run, even with 1 rank
     if (world > 1 or launched) and not dist.is_initialized():
