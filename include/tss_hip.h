@@ -656,6 +656,22 @@ int tss_cross_entropy_fwd(const void* logits, const long long* target, float* ls
 int tss_cross_entropy_bwd(const void* logits, const long long* target, const float* lse, const float* inv_count,
                           const float* grad_out, void* dlogits, long B, int C, long HW, int ignore_index,
                           int dtype, void* stream);
+/* Cross-entropy with class weights and label smoothing, torch's semantics (nn.CrossEntropyLoss(weight=, label_smoothing=), the
+ * alternative loss of scripts/contextnet/train_contextnet.py:123-125).  weight: [C] f32 on the device, or NULL for all ones; it
+ * is read by the kernels, so an in-place update takes effect on the next launch (or graph replay).  0 <= label_smoothing <= 1.
+ * With W = sum_c w_c, s = (1 - eps) w_t + eps W / C per valid pixel and den = the sum of w_t over the valid pixels:
+ *   loss = [(1 - eps) sum w_t (lse - x_t) + eps / C sum sum_c w_c (lse - x_c)] / den
+ *   dlogits_c = (s p_c - (1 - eps) w_t [c == t] - eps w_c / C) * grad_out / den,   0 at a pixel that is not valid
+ * *inv_count = 1 / den; den == 0 gives loss = nan, *inv_count = 0 and a zero gradient.  The block partial sums go to `rows`
+ * ([tss_cross_entropy_ex_rows(B, HW)][2] f64, NOT initialised by the caller) and are added in a fixed order: no atomics, the
+ * same bits on every run.  tss_cross_entropy_fwd / _bwd stay the entries of the plain loss. */
+long tss_cross_entropy_ex_rows(long B, long HW);
+int tss_cross_entropy_fwd_ex(const void* logits, const long long* target, const float* weight, float label_smoothing,
+                             float* lse, double* rows, float* loss, float* inv_count, long B, int C, long HW, int ignore_index,
+                             int dtype, void* stream);
+int tss_cross_entropy_bwd_ex(const void* logits, const long long* target, const float* weight, float label_smoothing,
+                             const float* lse, const float* inv_count, const float* grad_out, void* dlogits, long B, int C, long HW,
+                             int ignore_index, int dtype, void* stream);
 /* Online hard example mining cross-entropy: OHEMLoss(ignore_index, thresh_loss = -log 0.7, numel_frac = 0.01) of the
  * reference's training recipe (TSS/losses/ohem_loss.py:10-21, scripts/train_fastscnn.py:133-137).  n_top = int(B*HW *
  * numel_frac).  The (n_top+1)-th largest per-pixel loss is found by a device-side radix select (no sort, no host read-back);
@@ -748,6 +764,11 @@ int tss_upsample_ce_fwd(const void* low, long ldl, const long long* target, floa
                         int B, int C, int h, int w, int H, int W, int ignore_index, int dtype, void* stream);
 int tss_upsample_ce_bwd(const float* ws, const float* inv_count, const float* grad_out, void* dlow, long ldl,
                         int B, int C, int h, int w, int H, int W, int dtype, void* stream);
+/* tss_upsample_ce_fwd with class weights (NULL: all ones) and label smoothing, the semantics of tss_cross_entropy_fwd_ex on the
+ * upsampled logits: same workspace layout, same gather (tss_upsample_ce_bwd), *inv_count = 1 / sum of the valid pixels' weights. */
+int tss_upsample_ce_fwd_ex(const void* low, long ldl, const long long* target, const float* weight, float label_smoothing,
+                           float* ws, float* loss, float* inv_count, int B, int C, int h, int w, int H, int W, int ignore_index,
+                           int dtype, void* stream);
 /* OHEM on the fused head (TSS/losses/ohem_loss.py:10-21 on F.interpolate(low, x8) without the full-resolution logits): per-pixel
  * cross-entropy from the low-res logits -> tss_ohem_select on that array -> gradient tiles of the selected pixels
  * (tss_upsample_ohem_grad; ws as for tss_upsample_ce_fwd) -> tss_upsample_ce_bwd with *inv_count = 1 gathers them. */

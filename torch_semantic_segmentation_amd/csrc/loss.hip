@@ -3,6 +3,7 @@
 // The planar kernels are instances of the class-plane sweep of losssweep.h (lane layout, labels, validity rule, reductions).
 // forward: online log-sum-exp over the C planes -> per-pixel lse (saved), sum of losses + valid count (f64 atomics)
 // backward: dlogits[c] = (exp(l_c - lse) - [c == t]) * grad_out / count, recomputed from the saved lse
+// ce_fwd_ex / ce_bwd_ex: the same with class weights and label smoothing, per-block partial rows instead of the atomics
 #include "losssweep.h"
 
 namespace {
@@ -56,6 +57,71 @@ __global__ __launch_bounds__(NT) void ce_bwd_kernel(const T* logits, const long 
   }
 }
 
+// Class weights w[C] (nullptr: all ones) and label smoothing eps, torch's semantics; the kernels above stay as they are for the
+// plain loss.  With W = sum_c w_c and, per valid pixel, s = (1 - eps) w_t + eps W / C:
+//   loss = [ (1 - eps) sum w_t (lse - x_t) + eps / C sum sum_c w_c (lse - x_c) ] / den,  den = sum w_t  (sums over the valid pixels)
+//   dx_c = ( s p_c - (1 - eps) w_t [c == t] - eps w_c / C ) / den
+// The block sums go to a row of the block's own ([grid][2] f64, ce_finalize_rows_ex_kernel adds them in a fixed order): no atomics.
+__device__ __forceinline__ float class_weight_sum(const float* cw, int C) {
+  if (!cw) return (float)C;
+  float W = 0.f;
+  for (int c = 0; c < C; ++c) W += cw[c];
+  return W;
+}
+
+template <typename T, bool SMOOTH>
+__global__ __launch_bounds__(NT) void ce_fwd_ex_kernel(const T* logits, const long long* target, const float* cw, float eps,
+                                                       float* lse_out, double* rows /*[grid][2]: loss sum, weight sum*/, long B,
+                                                       int C, long HW, int ignore_index) {
+  const float W = SMOOTH ? class_weight_sum(cw, C) : 0.f, eC = eps / (float)C, om = 1.f - eps;
+  double lsum = 0.0, lcnt = 0.0;
+  for (lsw::Groups g(B, HW); g.more(); g.next()) {
+    const long b = g.b(), off = g.off();
+    int tv[8];
+    float l[8], lt[8], xw[8];
+    lsw::load_labels(target + b * HW + off, C, ignore_index, 1, tv);
+    lsw::lse8_weighted<SMOOTH>(logits + b * C * HW + off, C, HW, cw, tv, l, lt, xw);
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (tv[j] >= 0) {
+        const float wt = cw ? cw[tv[j]] : 1.f;
+        float term = wt * (l[j] - lt[j]);
+        if (SMOOTH) term = om * term + eC * (W * l[j] - xw[j]);
+        lsum += (double)term;
+        lcnt += (double)wt;
+      }
+    V8<float>::store(lse_out + b * HW + off, l);
+  }
+  if (lsw::block_sum2(lsum, lcnt)) {
+    rows[2 * (long)blockIdx.x] = lsum;
+    rows[2 * (long)blockIdx.x + 1] = lcnt;
+  }
+}
+
+template <typename T, bool SMOOTH>
+__global__ __launch_bounds__(NT) void ce_bwd_ex_kernel(const T* logits, const long long* target, const float* cw, float eps,
+                                                       const float* lse, const float* inv_count, const float* grad_out, T* dlogits,
+                                                       long B, int C, long HW, int ignore_index) {
+  const float gs = (*inv_count) * (grad_out ? *grad_out : 1.f);
+  const float om = (1.f - eps) * gs, uW = SMOOTH ? eps / (float)C * gs : 0.f, sW = SMOOTH ? uW * class_weight_sum(cw, C) : 0.f;
+  for (lsw::Groups g(B, HW); g.more(); g.next()) {
+    const long b = g.b(), off = g.off();
+    int tv[8];
+    float l[8], s[8], a[8], u[8];
+    lsw::load_labels(target + b * HW + off, C, 0, 0, tv);
+    V8<float>::load(lse + b * HW + off, l);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const bool ok = lsw::counts(tv[j], ignore_index);
+      const float wt = ok ? (cw ? cw[tv[j]] : 1.f) : 0.f;
+      a[j] = om * wt;
+      u[j] = ok ? uW : 0.f;
+      s[j] = ok ? a[j] + sW : 0.f;
+    }
+    lsw::grad8_weighted<SMOOTH>(logits + b * C * HW + off, dlogits + b * C * HW + off, C, HW, cw, tv, l, s, a, u);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // Fused decoder head + loss: cross-entropy of the x`scale` bilinearly upsampled logits
 // computed straight from the LOW-RES NHWC logits, loss AND gradient in ONE pass.  The (B, C, H, W) full-resolution
@@ -85,11 +151,15 @@ struct CeGeom { int nstrip, nband, band_rows, tile_rows, tile_cells; };
 // ([B][H][W] f32, 0 for ignored pixels) -- the input of the OHEM selection (TSS/losses/ohem_loss.py:11-12 without the 318.8 M-element
 // logits).  MODE 2: gradient tiles of a WEIGHTED sum of per-pixel losses, the weight of a pixel derived from its stored loss and
 // the selection parameters `sel` = [mode, cut, weight of l > cut, weight of l == cut] (tss_ohem_select): OHEM's backward.
+// MODE 3: MODE 0 with class weights `cw` ([C] f32, nullptr: all ones): the pixel weight is w_t, the count row holds sum w_t.
+// MODE 4: MODE 3 with label smoothing `eps`: the softmax half carries s = (1 - eps) w_t + eps W / C, the one-hot half (1 - eps) w_t,
+// and the uniform part eps w_c / C of the target distribution enters Hh at flush time, once per low-res row, scaled by the sum
+// of the row weights of the valid pixels seen (nA, nB: one scalar per row buffer).  MODE 0 / 1 / 2 do not read cw and eps.
 template <typename T, int CP, int MODE>
 __global__ __launch_bounds__(NT, (CP <= 20 ? 3 : 2)) void upsample_ce_onepass_kernel(const T* low, long ldl, const long long* target,
                                                                  float* tiles, double* lossrows, int B, int C, int h, int w,
                                                                  int H, int W, int ignore_index, const CeGeom geo,
-                                                                 float* pix, const float* sel) {
+                                                                 float* pix, const float* sel, const float* cw, float eps) {
   const int band_rows = geo.band_rows;
   constexpr int MAXCELL = NT + 2, WTAB = 1024;
   constexpr float LOG2E = 1.44269504088896340736f;
@@ -103,7 +173,11 @@ __global__ __launch_bounds__(NT, (CP <= 20 ? 3 : 2)) void upsample_ce_onepass_ke
   __shared__ float Ll1[NT];
   __shared__ float Wt[WTAB];                          // gather weights [cell][lane - Wlo[cell]] (fixed for the block)
   __shared__ double red[2][NT / 64];
+  __shared__ __align__(16) float Cw[CP];              // MODE 3 / 4: the class weights, 0 for the padding classes
+  __shared__ float Nn[2][NT];                         // MODE 4: per row buffer and lane, the sum of the row weights of the valid pixels
   const int tid = threadIdx.x;
+  if (MODE >= 3 && tid < CP) Cw[tid] = tid < C ? (cw ? cw[tid] : 1.f) : 0.f;
+  if (MODE == 4) { Nn[0][tid] = 0.f; Nn[1][tid] = 0.f; }
   const int nstrip = geo.nstrip, nband = geo.nband;
   float* const tile = tiles + (long)blockIdx.x * geo.tile_rows * geo.tile_cells * CP;
   int bid = blockIdx.x;
@@ -167,6 +241,7 @@ __global__ __launch_bounds__(NT, (CP <= 20 ? 3 : 2)) void upsample_ce_onepass_ke
       for (int q = 0; q < 4; ++q) a[c4 + q] = (c4 + q < C) ? (tx.l0 * u[q] + tx.l1 * v[q]) * LOG2E : -TSS_INF;
     }
   };
+  const float eC = MODE == 4 ? eps / (float)C : 0.f;
   float lsum = 0.f, lcnt = 0.f;     // loss sum in base-2 units (the rows carry logits * log2(e): one v_exp per class, no multiply)
   // finished low-res row r (buffer k): the lane's gradient g[] - Hh[k][] is parked in Hh[k] (plain stores), then one thread
   // per (cell, class) gathers the <= ~2*scale+4 lanes whose column taps include that cell and adds the sum to dlow; the
@@ -174,11 +249,16 @@ __global__ __launch_bounds__(NT, (CP <= 20 ? 3 : 2)) void upsample_ce_onepass_ke
   // per wave instruction: 550 us of a 790 us kernel.)
   auto flush_row = [&](int r, int k, const float* g, const float* a) {
     float* G = Hh[k];
-    float zt = 0.f;
+    float zt = 0.f, nk = 0.f;
+    if (MODE == 4) { nk = Nn[k][tid] * eC; Nn[k][tid] = 0.f; }      // eps / C * the buffer's row-weight sum
 #pragma unroll
     for (int c4 = 0; c4 < CP; c4 += 4) {
       const float4 hv = *reinterpret_cast<const float4*>(G + tid * CP + c4);
-      const float hq[4] = {hv.x, hv.y, hv.z, hv.w};
+      float hq[4] = {hv.x, hv.y, hv.z, hv.w};
+      if (MODE == 4) {                                 // the uniform part of the smoothed target; Cw = 0 keeps the padding classes out
+        const float4 wv = *reinterpret_cast<const float4*>(Cw + c4);
+        hq[0] += nk * wv.x; hq[1] += nk * wv.y; hq[2] += nk * wv.z; hq[3] += nk * wv.w;
+      }
 #pragma unroll
       for (int q = 0; q < 4; ++q) if (c4 + q < C) zt += a[c4 + q] * hq[q];     // padding classes: a = -inf, Hh = 0
       *reinterpret_cast<float4*>(G + tid * CP + c4) = make_float4(g[c4] - hq[0], g[c4 + 1] - hq[1], g[c4 + 2] - hq[2], g[c4 + 3] - hq[3]);
@@ -218,6 +298,11 @@ __global__ __launch_bounds__(NT, (CP <= 20 ? 3 : 2)) void upsample_ce_onepass_ke
   long long tnext = *trow;
   float sel_cut = 0.f, sel_gt = 0.f, sel_eq = 0.f;
   if (MODE == 2) { sel_cut = sel[1]; sel_gt = sel[2]; sel_eq = sel[0] != 0.f ? 0.f : sel[3]; }
+  float om = 1.f, sW = 0.f;                                     // MODE 4: 1 - eps, eps W / C
+  if (MODE == 4) {                                              // uniform: scalar loads, scalar registers
+    om = 1.f - eps;
+    sW = eC * class_weight_sum(cw, C);
+  }
   float* prow = (MODE != 0) ? pix + (b * H + ya) * (long)W + (xin ? x : 0) : nullptr;
   for (int y = ya; y < yb; ++y) {
     const long long t = tnext;
@@ -257,7 +342,19 @@ __global__ __launch_bounds__(NT, (CP <= 20 ? 3 : 2)) void upsample_ce_onepass_ke
       const float pl = xin ? prow[(long)(y - ya) * W] : 0.f;
       wpx = pl > sel_cut ? sel_gt : (pl == sel_cut ? sel_eq : 0.f);
     }
-    if (valid) {
+    if (MODE >= 3) {      // class weights (and smoothing): wsm scales the softmax half and the lse, wpx the one-hot half
+      if (valid) {
+        const float wt = Cw[(int)t];
+        float wsm = wt;
+        wpx = wt;
+        if (MODE == 4) { wpx = om * wt; wsm = wpx + sW; Nn[kA][tid] += ty.l0; Nn[kA ^ 1][tid] += ty.l1; }
+        lsum += wsm * (m + __builtin_amdgcn_logf(ssum));      // log2
+        lcnt += wt;
+        Hh[kA][tid * CP + (int)t] += ty.l0 * wpx;
+        Hh[kA ^ 1][tid * CP + (int)t] += ty.l1 * wpx;
+        wpx = wsm;
+      }
+    } else if (valid) {
       lsum += m + __builtin_amdgcn_logf(ssum);      // log2
       lcnt += 1.f;
       float* ha = &Hh[kA][tid * CP + (int)t];                 // this lane's own row of the table: no race
@@ -297,6 +394,16 @@ __global__ __launch_bounds__(NT) void ce_finalize_rows_kernel(const double* rows
   double sum, n;
   if (lsw::row_sum2(rows, nrows, sum, n)) {
     *loss = (float)(sum / n);          // n == 0 -> nan, like torch
+    *inv_count = n > 0.0 ? (float)(1.0 / n) : 0.f;
+  }
+}
+
+// The same sum for the weighted / smoothed entries: there the numerator of an empty denominator need not be 0 (valid pixels whose
+// class weight is 0 still carry the smoothing term), and torch's (1 - eps) * (0 / 0) + ... is nan, not inf.
+__global__ __launch_bounds__(NT) void ce_finalize_rows_ex_kernel(const double* rows, int nrows, float* loss, float* inv_count) {
+  double sum, n;
+  if (lsw::row_sum2(rows, nrows, sum, n)) {
+    *loss = n > 0.0 ? (float)(sum / n) : __builtin_nanf("");
     *inv_count = n > 0.0 ? (float)(1.0 / n) : 0.f;
   }
 }
@@ -503,6 +610,51 @@ int tss_cross_entropy_bwd(const void* logits, const long long* target, const flo
   return tss::check_last("cross_entropy_bwd");
 }
 
+// Rows of the [rows][2] f64 workspace that tss_cross_entropy_fwd_ex writes (one per block of its grid); 0 for shapes it refuses.
+long tss_cross_entropy_ex_rows(long B, long HW) {
+  if (B <= 0 || HW <= 0 || (HW % 8) != 0) return 0;
+  return tss::grid_for(B * (HW / 8), NT);
+}
+
+int tss_cross_entropy_fwd_ex(const void* logits, const long long* target, const float* weight /*[C] or null*/, float label_smoothing,
+                             float* lse, double* rows /*[tss_cross_entropy_ex_rows][2], not initialised*/, float* loss,
+                             float* inv_count, long B, int C, long HW, int ignore_index, int dtype, void* stream) {
+  TSS_CHECK_DTYPE(dtype);
+  TSS_REQUIRE(tss::planar_shape_ok(B, C, HW) && label_smoothing >= 0.f && label_smoothing <= 1.f && rows, TSS_ERR_SHAPE);
+  TSS_REQUIRE(tss::aligned16(logits) && tss::aligned16(lse), TSS_ERR_ALIGN);
+  const long groups = B * (HW / 8);
+  const int grid = tss::grid_for(groups, NT);
+  {
+    tss::ProfScope prof(TSS_K_CE_FWD, (hipStream_t)stream, (double)B * HW * (C * tss::esz(dtype) + 12.0), 0);
+    if (label_smoothing > 0.f)
+      TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL((ce_fwd_ex_kernel<TT, true>), dim3(grid), dim3(NT), 0, (hipStream_t)stream, (const TT*)logits,
+                                               target, weight, label_smoothing, lse, rows, B, C, HW, ignore_index));
+    else
+      TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL((ce_fwd_ex_kernel<TT, false>), dim3(grid), dim3(NT), 0, (hipStream_t)stream, (const TT*)logits,
+                                               target, weight, 0.f, lse, rows, B, C, HW, ignore_index));
+  }
+  hipLaunchKernelGGL(ce_finalize_rows_ex_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, rows, grid, loss, inv_count);
+  return tss::check_last("cross_entropy_fwd_ex");
+}
+
+int tss_cross_entropy_bwd_ex(const void* logits, const long long* target, const float* weight, float label_smoothing, const float* lse,
+                             const float* inv_count, const float* grad_out, void* dlogits, long B, int C, long HW, int ignore_index,
+                             int dtype, void* stream) {
+  TSS_CHECK_DTYPE(dtype);
+  TSS_REQUIRE(tss::planar_shape_ok(B, C, HW) && label_smoothing >= 0.f && label_smoothing <= 1.f, TSS_ERR_SHAPE);
+  TSS_REQUIRE(tss::aligned16(logits) && tss::aligned16(dlogits) && tss::aligned16(lse), TSS_ERR_ALIGN);
+  const long groups = B * (HW / 8);
+  const int grid = tss::grid_for(groups, NT);
+  tss::ProfScope prof(TSS_K_CE_BWD, (hipStream_t)stream, (double)B * HW * (2.0 * C * tss::esz(dtype) + 12.0), 0);
+  if (label_smoothing > 0.f)
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL((ce_bwd_ex_kernel<TT, true>), dim3(grid), dim3(NT), 0, (hipStream_t)stream, (const TT*)logits,
+                                             target, weight, label_smoothing, lse, inv_count, grad_out, (TT*)dlogits, B, C, HW, ignore_index));
+  else
+    TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL((ce_bwd_ex_kernel<TT, false>), dim3(grid), dim3(NT), 0, (hipStream_t)stream, (const TT*)logits,
+                                             target, weight, 0.f, lse, inv_count, grad_out, (TT*)dlogits, B, C, HW, ignore_index));
+  return tss::check_last("cross_entropy_bwd_ex");
+}
+
 int tss_argmax_confusion(const void* logits, const long long* target, unsigned char* pred,
                          unsigned long long* confusion /*[C*C] accumulated*/, long B, int C, long HW,
                          int ignore_index, int dtype, void* stream) {
@@ -582,10 +734,39 @@ int tss_upsample_ce_fwd(const void* low, long ldl, const long long* target, floa
                         (double)B * h * w * C * (tss::esz(dtype) + 8.0) + (double)B * H * W * 8.0, 0);
     TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
       hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 0>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,
-                         (const TT*)low, ldl, target, tiles, lossrows, B, C, h, w, H, W, ignore_index, geo, nullptr, nullptr)));
+                         (const TT*)low, ldl, target, tiles, lossrows, B, C, h, w, H, W, ignore_index, geo, nullptr, nullptr, nullptr, 0.f)));
   }
   hipLaunchKernelGGL(ce_finalize_rows_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, lossrows, (int)grid, loss, inv_count);
   return tss::check_last("upsample_ce_fwd");
+}
+
+// tss_upsample_ce_fwd with class weights (nullptr: all ones) and label smoothing: the MODE 3 (weights) or MODE 4 (smoothing)
+// instance of the pass; same workspace, same gather (tss_upsample_ce_bwd), *inv_count = 1 / sum of the valid pixels' weights.
+int tss_upsample_ce_fwd_ex(const void* low, long ldl, const long long* target, const float* weight, float label_smoothing, float* ws,
+                           float* loss, float* inv_count, int B, int C, int h, int w, int H, int W, int ignore_index, int dtype,
+                           void* stream) {
+  TSS_CHECK_DTYPE(dtype);
+  TSS_REQUIRE(upsample_ce_shape_ok(C, ldl, h, w, H, W) && label_smoothing >= 0.f && label_smoothing <= 1.f, TSS_ERR_SHAPE);
+  TSS_REQUIRE(tss::aligned16(low) && tss::aligned16(ws), TSS_ERR_ALIGN);
+  if ((long)B * H * W == 0) return TSS_OK;
+  const CeGeom geo = ce_geom(B, h, w, H, W);
+  const long grid = (long)B * geo.nstrip * geo.nband;
+  double* lossrows = reinterpret_cast<double*>(ws);
+  float* tiles = ws + grid * 4;
+  {
+    tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream,
+                        (double)B * h * w * C * (tss::esz(dtype) + 8.0) + (double)B * H * W * 8.0, 0);
+    if (label_smoothing > 0.f)
+      TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
+        hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 4>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const TT*)low, ldl,
+                           target, tiles, lossrows, B, C, h, w, H, W, ignore_index, geo, nullptr, nullptr, weight, label_smoothing)));
+    else
+      TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
+        hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 3>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const TT*)low, ldl,
+                           target, tiles, lossrows, B, C, h, w, H, W, ignore_index, geo, nullptr, nullptr, weight, 0.f)));
+  }
+  hipLaunchKernelGGL(ce_finalize_rows_ex_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, lossrows, (int)grid, loss, inv_count);
+  return tss::check_last("upsample_ce_fwd_ex");
 }
 
 // Per-pixel cross-entropy of the upsampled logits ([B][H][W] f32, 0 for ignored pixels), straight from the low-res logits.
@@ -600,7 +781,7 @@ int tss_upsample_pixel_ce(const void* low, long ldl, const long long* target, fl
   tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream, (double)B * h * w * C * tss::esz(dtype) + (double)B * H * W * 12.0, 0);
   TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
     hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 1>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,
-                       (const TT*)low, ldl, target, nullptr, nullptr, B, C, h, w, H, W, ignore_index, geo, pix, nullptr)));
+                       (const TT*)low, ldl, target, nullptr, nullptr, B, C, h, w, H, W, ignore_index, geo, pix, nullptr, nullptr, 0.f)));
   return tss::check_last("upsample_pixel_ce");
 }
 
@@ -618,7 +799,7 @@ int tss_upsample_ohem_grad(const void* low, long ldl, const long long* target, c
   tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream, (double)B * h * w * C * (tss::esz(dtype) + 8.0) + (double)B * H * W * 12.0, 0);
   TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
     hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 2>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,
-                       (const TT*)low, ldl, target, tiles, nullptr, B, C, h, w, H, W, ignore_index, geo, const_cast<float*>(pix), sel)));
+                       (const TT*)low, ldl, target, tiles, nullptr, B, C, h, w, H, W, ignore_index, geo, const_cast<float*>(pix), sel, nullptr, 0.f)));
   return tss::check_last("upsample_ohem_grad");
 }
 

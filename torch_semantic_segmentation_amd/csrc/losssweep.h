@@ -11,6 +11,7 @@
 //   (e - 1) * 0 = -0 as the formula has it, not +0.
 //   lse8       : online log-sum-exp over the C planes, optionally with the pick of the label's logit -> per-pixel lse in f32
 //   grad8      : dlogits[c] = (exp(x_c - lse) - [c == label]) * w for all C planes, softmax recomputed from the saved lse
+//   lse8_weighted, grad8_weighted : the same two sweeps for the class-weighted, label-smoothed cross-entropy (loss.hip: ce_fwd_ex, ce_bwd_ex)
 //   block_sum2 : two f64 sums over the block (wave_sum, LDS, thread 0)
 //   row_sum2   : the two columns of [nrows][2] per-block rows summed by one block in a fixed order (the finalize kernels)
 //
@@ -84,6 +85,50 @@ __device__ __forceinline__ void grad8(const T* x, T* dx, int C, long HW, const i
     for (int j = 0; j < 8; ++j) {
       const float e = __expf(v[j] - l[j]), h = tv[j] == c ? 1.f : 0.f;
       d[j] = (NEGATED ? h - e : e - h) * w[j];
+    }
+    V8<T>::store(dx + (long)c * HW, d);
+  }
+}
+
+// lse8 with the label's logit picked and, SMOOTH only, xw[j] = sum_c cw[c] * x[c][j] (cw == nullptr: all ones): the extra term of
+// the class-weighted, label-smoothed cross-entropy.  cw[c] is the same address in every lane.
+template <bool SMOOTH, typename T>
+__device__ __forceinline__ void lse8_weighted(const T* x, int C, long HW, const float* cw, const int* tv, float l[8], float* xt,
+                                              float* xw) {
+  float m[8], s[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { m[j] = -INFINITY; s[j] = 0.f; xt[j] = 0.f; if (SMOOTH) xw[j] = 0.f; }
+  for (int c = 0; c < C; ++c) {
+    float v[8];
+    V8<T>::load(x + (long)c * HW, v);
+    const float wc = (SMOOTH && cw) ? cw[c] : 1.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float mn = fmaxf(m[j], v[j]);
+      s[j] = s[j] * __expf(m[j] - mn) + __expf(v[j] - mn);
+      m[j] = mn;
+      if (tv[j] == c) xt[j] = v[j];
+      if (SMOOTH) xw[j] = fmaf(wc, v[j], xw[j]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) l[j] = m[j] + __logf(s[j]);
+}
+
+// dx[c][j] = exp(x[c][j] - l[j]) * s[j] - [c == tv[j]] * a[j] - cw[c] * u[j] for all C planes (cw == nullptr: all ones): the
+// gradient of the class-weighted, label-smoothed cross-entropy, s = the pixel's total weight, a = its one-hot part, u = its
+// uniform part per unit class weight; all three are 0 for a pixel that does not count.  SMOOTH == false: u is not read.
+template <bool SMOOTH, typename T>
+__device__ __forceinline__ void grad8_weighted(const T* x, T* dx, int C, long HW, const float* cw, const int tv[8], const float l[8],
+                                               const float s[8], const float a[8], const float u[8]) {
+  for (int c = 0; c < C; ++c) {
+    float v[8], d[8];
+    V8<T>::load(x + (long)c * HW, v);
+    const float wc = (SMOOTH && cw) ? cw[c] : 1.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      d[j] = __expf(v[j] - l[j]) * s[j] - (tv[j] == c ? a[j] : 0.f);
+      if (SMOOTH) d[j] -= wc * u[j];
     }
     V8<T>::store(dx + (long)c * HW, d);
   }

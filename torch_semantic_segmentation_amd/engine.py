@@ -425,7 +425,8 @@ class Trainer:
                                                   thresh_loss=self.loss_fn.thresh_loss, numel_frac=self.loss_fn.numel_frac)
                 else:
                     loss = ops.upsample_cross_entropy(low, y, scale_factor=self.model.logit_scale,
-                                                      ignore_index=self.loss_fn.ignore_index)
+                                                      ignore_index=self.loss_fn.ignore_index, weight=self.loss_fn.weight,
+                                                      label_smoothing=self.loss_fn.label_smoothing)
             elif self.teacher is not None:
                 low_kd, y_pred = self._forward_with_lowres(x)
                 loss = self.loss_fn(y_pred, y)

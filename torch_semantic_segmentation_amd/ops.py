@@ -2940,20 +2940,83 @@ class CrossEntropyFn(Function):
         return d, None, None
 
 
-def cross_entropy(logits, target, ignore_index=-100):
-    """F.cross_entropy(logits, target, ignore_index=..., reduction='mean') for (B,C,H,W) logits."""
-    return CrossEntropyFn.apply(logits, target, ignore_index)
+def _check_smoothing(label_smoothing):
+    eps = float(label_smoothing)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError('label_smoothing must be in [0, 1], got %r' % (label_smoothing,))
+    return eps
+
+
+def _class_weight(weight, num_classes, dev=None):
+    """The class weights as the kernels read them: contiguous float32 of shape (C,); None stays None (all ones).  Weights that
+    already have that form are returned as they are, so an in-place update of the caller's tensor reaches a captured step."""
+    if weight is None:
+        return None
+    if not torch.is_tensor(weight) or not weight.is_floating_point():
+        raise ValueError('weight must be a floating-point tensor')
+    if weight.dim() != 1 or (num_classes is not None and weight.shape[0] != num_classes):
+        raise ValueError('weight must have shape (C,) = (%s,), got %s' % (num_classes, tuple(weight.shape)))
+    if dev is not None and weight.device != dev:
+        raise ValueError('weight lives on %s but the logits on %s' % (weight.device, dev))
+    if weight.dtype != torch.float32 or not weight.is_contiguous():
+        weight = weight.detach().to(torch.float32).contiguous()
+    return weight.detach()
+
+
+class WeightedCrossEntropyFn(Function):
+    """cross_entropy with class weights and / or label smoothing (tss_cross_entropy_{fwd,bwd}_ex): per-block partial rows summed in
+    a fixed order, no atomics, so two evaluations give the same bits.  The weights are constants: no gradient flows to them."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, weight, eps):
+        logits, target = _check_logits_target(logits, target)
+        B, C, H, W = logits.shape
+        dev = logits.device
+        lse = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+        rows = torch.empty((max(N.lib().tss_cross_entropy_ex_rows(B, H * W), 1), 2), dtype=torch.float64, device=dev)
+        scal = torch.empty(2, dtype=torch.float32, device=dev)
+        call('tss_cross_entropy_fwd_ex', ptr(logits), ptr(target), ptr(weight), eps, ptr(lse), ptr(rows), ptr(scal[0:1]), ptr(scal[1:2]),
+             B, C, H * W, int(ignore_index), N.dtype_code(logits.dtype), stream())
+        ctx.ignore_index, ctx.eps = int(ignore_index), eps
+        ctx.has_weight = weight is not None
+        ctx.save_for_backward(logits, target, lse, scal, *([weight] if weight is not None else []))
+        return scal[0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        logits, target, lse, scal = ctx.saved_tensors[:4]
+        weight = ctx.saved_tensors[4] if ctx.has_weight else None
+        gout, d, dims = _open_backward(logits, gout)
+        call('tss_cross_entropy_bwd_ex', ptr(logits), ptr(target), ptr(weight), ctx.eps, ptr(lse), ptr(scal[1:2]), ptr(gout), ptr(d),
+             *dims, ctx.ignore_index, N.dtype_code(logits.dtype), stream())
+        return d, None, None, None, None
+
+
+def cross_entropy(logits, target, ignore_index=-100, weight=None, label_smoothing=0.0):
+    """F.cross_entropy(logits, target, weight=..., ignore_index=..., reduction='mean', label_smoothing=...) for (B,C,H,W) logits.
+    weight: floating (C,) tensor on the logits' device or None; the mean is over the sum of the valid pixels' weights, as in torch."""
+    eps = _check_smoothing(label_smoothing)
+    if weight is None and eps == 0.0:
+        return CrossEntropyFn.apply(logits, target, ignore_index)
+    weight = _class_weight(weight, logits.shape[1] if logits.dim() == 4 else None, logits.device)
+    return WeightedCrossEntropyFn.apply(logits, target, ignore_index, weight, eps)
 
 
 class CrossEntropyLoss(torch.nn.Module):
-    """Drop-in for nn.CrossEntropyLoss(ignore_index=...) as scripts/train_fastscnn.py:132 builds it."""
+    """Drop-in for nn.CrossEntropyLoss(ignore_index=...) as scripts/train_fastscnn.py:132 builds it, and for
+    nn.CrossEntropyLoss(ignore_index=255, weight=...) of scripts/contextnet/train_contextnet.py:123-125.  `weight` is a registered
+    buffer (contiguous float32 (C,), or None): .cuda() / .to() move it, and the kernels read it from device memory, so an in-place
+    update between replays of a captured step takes effect without a re-capture."""
 
-    def __init__(self, ignore_index=-100):
+    def __init__(self, ignore_index=-100, weight=None, label_smoothing=0.0):
         super().__init__()
         self.ignore_index = ignore_index
+        self.label_smoothing = _check_smoothing(label_smoothing)
+        weight = _class_weight(weight, None)
+        self.register_buffer('weight', None if weight is None else weight.clone())
 
     def forward(self, input, target):
-        return cross_entropy(input, target, self.ignore_index)
+        return cross_entropy(input, target, self.ignore_index, self.weight, self.label_smoothing)
 
 
 def label_histogram(target, num_classes, ignore_index=255, out=None):
@@ -3593,7 +3656,7 @@ class UpsampleCrossEntropyFn(Function):
     zero-fill), backward gathers the tiles in a fixed order and scales by grad_out / #valid: bit-identical from run to run."""
 
     @staticmethod
-    def forward(ctx, low, target, ho, wo, ignore_index):
+    def forward(ctx, low, target, ho, wo, ignore_index, weight=None, eps=0.0):
         B, C, h, w = low.shape
         dev = low.device
         target = target.contiguous()
@@ -3601,8 +3664,12 @@ class UpsampleCrossEntropyFn(Function):
         ws = torch.empty(nws, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)        # written by the kernel: no copy launch for the return value
         inv = torch.empty(1, dtype=torch.float32, device=dev)
-        call('tss_upsample_ce_fwd', ptr(low), ld(low), ptr(target), ptr(ws), ptr(loss),
-             ptr(inv), B, C, h, w, ho, wo, int(ignore_index), N.dtype_code(low.dtype), stream())
+        if weight is None and eps == 0.0:
+            call('tss_upsample_ce_fwd', ptr(low), ld(low), ptr(target), ptr(ws), ptr(loss),
+                 ptr(inv), B, C, h, w, ho, wo, int(ignore_index), N.dtype_code(low.dtype), stream())
+        else:       # class weights / label smoothing: other instances of the same pass, same workspace, same gather
+            call('tss_upsample_ce_fwd_ex', ptr(low), ld(low), ptr(target), ptr(weight), eps, ptr(ws), ptr(loss),
+                 ptr(inv), B, C, h, w, ho, wo, int(ignore_index), N.dtype_code(low.dtype), stream())
         ctx.geom = (B, C, h, w, ho, wo, ld(low), low.dtype)
         ctx.save_for_backward(ws, inv)
         return loss
@@ -3615,22 +3682,24 @@ class UpsampleCrossEntropyFn(Function):
         base = torch.empty((B, h, w, ldl), dtype=dtype, device=ws.device)   # pad channels are written as zeros
         call('tss_upsample_ce_bwd', ptr(ws), ptr(inv), ptr(gout), ptr(base), ldl, B, C, h, w, ho, wo,
              N.dtype_code(dtype), stream())
-        return base.permute(0, 3, 1, 2)[:, :C], None, None, None, None
+        return base.permute(0, 3, 1, 2)[:, :C], None, None, None, None, None, None
 
 
-def upsample_cross_entropy(low, target, scale_factor=None, size=None, ignore_index=-100):
+def upsample_cross_entropy(low, target, scale_factor=None, size=None, ignore_index=-100, weight=None, label_smoothing=0.0):
     """Fused decoder head + loss:
-    F.cross_entropy(F.interpolate(low, scale_factor, mode='bilinear', align_corners=True), target, ignore_index)
+    F.cross_entropy(F.interpolate(low, scale_factor, mode='bilinear', align_corners=True), target, weight=weight,
+    ignore_index=ignore_index, label_smoothing=label_smoothing)
     computed from the low-resolution logits; the full-resolution logits are never materialised."""
+    eps = _check_smoothing(label_smoothing)
     low = to_nhwc(materialize(low))
     ho, wo = _out_size(low, size, scale_factor)
     if low.shape[1] > 24 or ho < low.shape[2] or wo < low.shape[3]:
         # outside the one-pass kernel's envelope (class registers, upsampling only): same result, unfused
-        return cross_entropy(upsample_logits(low, size=(ho, wo)), target, ignore_index=ignore_index)
+        return cross_entropy(upsample_logits(low, size=(ho, wo)), target, ignore_index=ignore_index, weight=weight, label_smoothing=eps)
     if target.dtype != torch.int64 or tuple(target.shape) != (low.shape[0], ho, wo):
         raise RuntimeError('target must be int64 of shape (B,H,W) = %s' % ((low.shape[0], ho, wo),))
     _check_device(target)
-    return UpsampleCrossEntropyFn.apply(low, target, ho, wo, ignore_index)
+    return UpsampleCrossEntropyFn.apply(low, target, ho, wo, ignore_index, _class_weight(weight, low.shape[1], low.device), eps)
 
 
 class UpsampleOHEMFn(Function):
