@@ -63,6 +63,7 @@ enum {
   TSS_K_CE_FWD, TSS_K_CE_BWD, TSS_K_ARGMAX, TSS_K_UPSAMPLE_CE_FWD, TSS_K_UPSAMPLE_CE_BWD,
   TSS_K_RESIZE_FLIP_PLANAR, TSS_K_MULTISCALE_ARGMAX,
   TSS_K_SGD, TSS_K_GRAD_NORM,
+  TSS_K_WIDE_CE_FWD, TSS_K_WIDE_CE_BWD, TSS_K_WIDE_ARGMAX, TSS_K_WIDE_MULTISCALE_ARGMAX,
   TSS_K_COUNT
 };
 
@@ -855,6 +856,40 @@ typedef struct tss_msmap { const void* low; long ldl; int h; int w; int flip; in
 int tss_multiscale_argmax_confusion(const tss_msmap* maps, int K, const long long* target, unsigned char* pred,
                                     unsigned long long* confusion, int B, int C, int H, int W,
                                     int ignore_index, int mode, int dtype, void* stream);
+
+/* ---- the fused head, its losses and the evaluators for up to 256 classes (csrc/widehead.hip) ---------------------------
+ * The entries above keep one pixel's class scores in registers and stop at 24 classes (the planar arg-max at 64: LDS
+ * counters).  These are their class-chunked counterparts: the same arguments in the same order, the same results, the same
+ * error rules, for 1 <= C <= tss_widehead_max_classes() (= 256).  A block walks its band of output rows once per chunk of 16
+ * classes with the two interpolated low-res rows of that chunk in registers; what a pixel carries from chunk to chunk (running
+ * maximum and sum, best score and index) lives in LDS, so no tensor of B*C*H*W elements exists in any form.
+ *   tss_upsample_ce_wide_fwd : tss_upsample_ce_fwd (weight == NULL and label_smoothing == 0) or tss_upsample_ce_fwd_ex.
+ *     ws = tss_upsample_ce_wide_ws(...) floats (0 for a refused shape), not initialised by the caller; tiles are
+ *     [rows][cells][round_up(C, 4)].  tss_upsample_ce_wide_bwd gathers them (pitch padding written as zeros).
+ *   tss_upsample_pixel_ce_wide / tss_upsample_ohem_grad_wide : the OHEM pair, as tss_upsample_pixel_ce / tss_upsample_ohem_grad.
+ *   tss_upsample_argmax_confusion_wide, tss_multiscale_argmax_confusion_wide, tss_argmax_confusion_wide : lowest index wins
+ *     ties, across chunks too; the C x C counts sit in LDS up to 96 classes and go to `confusion` with 64-bit integer
+ *     atomics past that (integer adds commute: exact and bit-reproducible either way). */
+int tss_widehead_max_classes(void);
+long tss_upsample_ce_wide_ws(int B, int C, int h, int w, int H, int W);
+int tss_upsample_ce_wide_fwd(const void* low, long ldl, const long long* target, const float* weight, float label_smoothing,
+                             float* ws, float* loss, float* inv_count, int B, int C, int h, int w, int H, int W, int ignore_index,
+                             int dtype, void* stream);
+int tss_upsample_pixel_ce_wide(const void* low, long ldl, const long long* target, float* pix, int B, int C, int h, int w, int H,
+                               int W, int ignore_index, int dtype, void* stream);
+int tss_upsample_ohem_grad_wide(const void* low, long ldl, const long long* target, const float* pix, const float* sel, float* ws,
+                                int B, int C, int h, int w, int H, int W, int ignore_index, int dtype, void* stream);
+int tss_upsample_ce_wide_bwd(const float* ws, const float* inv_count, const float* grad_out, void* dlow, long ldl,
+                             int B, int C, int h, int w, int H, int W, int dtype, void* stream);
+int tss_upsample_argmax_confusion_wide(const void* low, long ldl, const long long* target, unsigned char* pred,
+                                       unsigned long long* confusion, int B, int C, int h, int w, int H, int W,
+                                       int ignore_index, int dtype, void* stream);
+int tss_multiscale_argmax_confusion_wide(const tss_msmap* maps, int K, const long long* target, unsigned char* pred,
+                                         unsigned long long* confusion, int B, int C, int H, int W,
+                                         int ignore_index, int mode, int dtype, void* stream);
+int tss_argmax_confusion_wide(const void* logits, const long long* target, unsigned char* pred,
+                              unsigned long long* confusion, long B, int C, long HW, int ignore_index,
+                              int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,9 @@ const KernelInfo kInfo[TSS_K_COUNT] = {
     {"upsample_ce_fwd", "upsample_ce_onepass_kernel"}, {"upsample_ce_bwd", "upsample_ce_gather_kernel"},
     {"resize_flip_planar", "resize_flip_planar_kernel"}, {"multiscale_argmax_confusion", "multiscale_argmax_kernel"},
     {"sgd", "sgd_kernel"}, {"grad_norm", "grad_sqnorm_kernel|grad_sqnorm_final_kernel"},
+    {"upsample_ce_wide_fwd", "wide_ce_kernel"}, {"upsample_ce_wide_bwd", "wide_ce_gather_kernel"},
+    {"argmax_confusion_wide", "wide_upsample_argmax_kernel|wide_planar_argmax_kernel"},
+    {"multiscale_argmax_confusion_wide", "wide_multiscale_argmax_kernel"},
 };
 
 struct Rec { int kid; hipEvent_t a, b; double bytes, flops; };

@@ -3650,21 +3650,34 @@ class DistillationLoss(torch.nn.Module):
         return distillation_loss(student, teacher, self.temperature, self.kind)
 
 
+HEAD_REGISTER_CLASSES = 24        # the fused head's kernels that keep every class of a pixel in registers (csrc/loss.hip, msflip.hip)
+WIDEHEAD_MAX_CLASSES = 256        # their class-chunked counterparts (csrc/widehead.hip, tss_widehead_max_classes())
+
+
+def _wide(C):
+    """The suffix of the fused head's entry points for C classes: '' up to 24 (the register kernels), '_wide' up to 256."""
+    return '_wide' if C > HEAD_REGISTER_CLASSES else ''
+
+
 class UpsampleCrossEntropyFn(Function):
     """cross_entropy(F.interpolate(low, scale, bilinear, align_corners=True), target) without the full-res logits:
     one pass yields the loss and the unscaled low-res gradient (per-block tiles in a workspace, no atomics, nothing to
-    zero-fill), backward gathers the tiles in a fixed order and scales by grad_out / #valid: bit-identical from run to run."""
+    zero-fill), backward gathers the tiles in a fixed order and scales by grad_out / #valid: bit-identical from run to run.
+    More than 24 classes: the class-chunked entries (tss_upsample_ce_wide_*), same workspace convention, same returns."""
 
     @staticmethod
     def forward(ctx, low, target, ho, wo, ignore_index, weight=None, eps=0.0):
         B, C, h, w = low.shape
         dev = low.device
         target = target.contiguous()
-        nws = N.lib().tss_upsample_ce_ws(B, C, h, w, ho, wo)
+        nws = getattr(N.lib(), 'tss_upsample_ce%s_ws' % _wide(C))(B, C, h, w, ho, wo)
         ws = torch.empty(nws, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)        # written by the kernel: no copy launch for the return value
         inv = torch.empty(1, dtype=torch.float32, device=dev)
-        if weight is None and eps == 0.0:
+        if _wide(C):    # one entry for the plain, the weighted and the smoothed loss
+            call('tss_upsample_ce_wide_fwd', ptr(low), ld(low), ptr(target), ptr(weight), eps, ptr(ws), ptr(loss),
+                 ptr(inv), B, C, h, w, ho, wo, int(ignore_index), N.dtype_code(low.dtype), stream())
+        elif weight is None and eps == 0.0:
             call('tss_upsample_ce_fwd', ptr(low), ld(low), ptr(target), ptr(ws), ptr(loss),
                  ptr(inv), B, C, h, w, ho, wo, int(ignore_index), N.dtype_code(low.dtype), stream())
         else:       # class weights / label smoothing: other instances of the same pass, same workspace, same gather
@@ -3680,7 +3693,7 @@ class UpsampleCrossEntropyFn(Function):
         B, C, h, w, ho, wo, ldl, dtype = ctx.geom
         gout = gout.to(torch.float32).contiguous()
         base = torch.empty((B, h, w, ldl), dtype=dtype, device=ws.device)   # pad channels are written as zeros
-        call('tss_upsample_ce_bwd', ptr(ws), ptr(inv), ptr(gout), ptr(base), ldl, B, C, h, w, ho, wo,
+        call('tss_upsample_ce%s_bwd' % _wide(C), ptr(ws), ptr(inv), ptr(gout), ptr(base), ldl, B, C, h, w, ho, wo,
              N.dtype_code(dtype), stream())
         return base.permute(0, 3, 1, 2)[:, :C], None, None, None, None, None, None
 
@@ -3693,8 +3706,8 @@ def upsample_cross_entropy(low, target, scale_factor=None, size=None, ignore_ind
     eps = _check_smoothing(label_smoothing)
     low = to_nhwc(materialize(low))
     ho, wo = _out_size(low, size, scale_factor)
-    if low.shape[1] > 24 or ho < low.shape[2] or wo < low.shape[3]:
-        # outside the one-pass kernel's envelope (class registers, upsampling only): same result, unfused
+    if low.shape[1] > WIDEHEAD_MAX_CLASSES or ho < low.shape[2] or wo < low.shape[3]:
+        # outside the fused kernels' envelope (at most 256 classes, upsampling only): same result, unfused
         return cross_entropy(upsample_logits(low, size=(ho, wo)), target, ignore_index=ignore_index, weight=weight, label_smoothing=eps)
     if target.dtype != torch.int64 or tuple(target.shape) != (low.shape[0], ho, wo):
         raise RuntimeError('target must be int64 of shape (B,H,W) = %s' % ((low.shape[0], ho, wo),))
@@ -3716,7 +3729,8 @@ class UpsampleOHEMFn(Function):
         pix = torch.empty((B, ho, wo), dtype=torch.float32, device=dev)
         out = torch.empty(8, dtype=torch.float32, device=dev)              # loss, 3 pad, the 4 selection parameters (16 B aligned)
         code = N.dtype_code(low.dtype)
-        call('tss_upsample_pixel_ce', ptr(low), ld(low), ptr(target), ptr(pix), B, C, h, w, ho, wo, int(ignore_index), code, stream())
+        call('tss_upsample_pixel_ce' + _wide(C), ptr(low), ld(low), ptr(target), ptr(pix), B, C, h, w, ho, wo, int(ignore_index), code,
+             stream())
         call('tss_ohem_select', ptr(pix), ptr(OHEMFn.workspace(dev)), ptr(out[0:1]), ptr(out[4:8]), B * ho * wo, float(thresh_loss),
              int(B * ho * wo * float(numel_frac)), stream())
         ctx.geom = (B, C, h, w, ho, wo, ld(low), low.dtype, int(ignore_index))
@@ -3729,12 +3743,12 @@ class UpsampleOHEMFn(Function):
         B, C, h, w, ho, wo, ldl, dtype, ignore_index = ctx.geom
         dev = low.device
         gout = gout.to(torch.float32).contiguous()
-        ws = torch.empty(N.lib().tss_upsample_ce_ws(B, C, h, w, ho, wo), dtype=torch.float32, device=dev)
+        ws = torch.empty(getattr(N.lib(), 'tss_upsample_ce%s_ws' % _wide(C))(B, C, h, w, ho, wo), dtype=torch.float32, device=dev)
         code = N.dtype_code(dtype)
-        call('tss_upsample_ohem_grad', ptr(low), ldl, ptr(target), ptr(pix), ptr(out[4:8]), ptr(ws), B, C, h, w, ho, wo,
+        call('tss_upsample_ohem_grad' + _wide(C), ptr(low), ldl, ptr(target), ptr(pix), ptr(out[4:8]), ptr(ws), B, C, h, w, ho, wo,
              ignore_index, code, stream())
         base = torch.empty((B, h, w, ldl), dtype=dtype, device=dev)
-        call('tss_upsample_ce_bwd', ptr(ws), ptr(_unit(dev)), ptr(gout), ptr(base), ldl, B, C, h, w, ho, wo, code, stream())
+        call('tss_upsample_ce%s_bwd' % _wide(C), ptr(ws), ptr(_unit(dev)), ptr(gout), ptr(base), ldl, B, C, h, w, ho, wo, code, stream())
         return base.permute(0, 3, 1, 2)[:, :C], None, None, None, None, None, None
 
 
@@ -3752,7 +3766,7 @@ def upsample_ohem_loss(low, target, scale_factor=None, size=None, ignore_index=-
     low = to_nhwc(materialize(low))
     ho, wo = _out_size(low, size, scale_factor)
     B = low.shape[0]
-    if low.shape[1] > 24 or ho < low.shape[2] or wo < low.shape[3] or (B * ho * wo) % 4:
+    if low.shape[1] > WIDEHEAD_MAX_CLASSES or ho < low.shape[2] or wo < low.shape[3] or (B * ho * wo) % 4:
         return ohem_loss(upsample_logits(low, size=(ho, wo)), target, ignore_index, thresh_loss, numel_frac)
     if target.dtype != torch.int64 or tuple(target.shape) != (B, ho, wo):
         raise RuntimeError('target must be int64 of shape (B,H,W) = %s' % ((B, ho, wo),))
@@ -3768,7 +3782,9 @@ def upsample_argmax_confusion(low, target=None, scale_factor=None, size=None, ig
     _check_device(low)
     ho, wo = _out_size(low, size, scale_factor)
     B, C, h, w = low.shape
-    if C > 24 or ho < h or wo < w:
+    if C > WIDEHEAD_MAX_CLASSES:
+        raise ValueError('upsample_argmax_confusion supports at most %d classes, got %d' % (WIDEHEAD_MAX_CLASSES, C))
+    if ho < h or wo < w:
         return argmax_confusion(upsample_logits(low, size=(ho, wo)), target, ignore_index=ignore_index,
                                 confusion=confusion, want_pred=want_pred)
     pred = torch.empty((B, ho, wo), dtype=torch.uint8, device=low.device) if want_pred else None
@@ -3778,7 +3794,7 @@ def upsample_argmax_confusion(low, target=None, scale_factor=None, size=None, ig
         _check_device(target)
         if confusion is None:
             confusion = torch.zeros((C, C), dtype=torch.int64, device=low.device)
-    call('tss_upsample_argmax_confusion', ptr(low), ld(low), ptr(target.contiguous()) if target is not None else None,
+    call('tss_upsample_argmax_confusion' + _wide(C), ptr(low), ld(low), ptr(target.contiguous()) if target is not None else None,
          ptr(pred), ptr(confusion), B, C, h, w, ho, wo, int(ignore_index), N.dtype_code(low.dtype), stream())
     return pred, confusion
 
@@ -3816,7 +3832,9 @@ def multiscale_argmax_confusion(lows, flips, target=None, size=None, ignore_inde
     AFTER the upsample: F.interpolate(...).flip(-1)), the per-map softmax (average='softmax') or the raw logits ('logits') are summed
     in list order, and the arg-max of the sum is scored against `target`.  No full-resolution float tensor exists.
     lows[i]: logits [B,C,h,w] with flips[i] a bool, or [2B,C,h,w] with flips[i] == (False, True): the plain and the mirrored half of
-    one forward (two maps).  At most 16 maps, C <= 24, no map larger than `size`.  Returns (pred uint8 or None, confusion)."""
+    one forward (two maps).  At most 16 maps, at most 256 classes (up to 24 the scores of a pixel live in registers, past that the
+    class-chunked kernel of csrc/widehead.hip runs: same arithmetic per score, same results), no map larger than `size`.
+    Returns (pred uint8 or None, confusion)."""
     if average not in _MS_AVERAGE:
         raise ValueError("average must be 'softmax' or 'logits', got %r" % (average,))
     lows, flips = list(lows), list(flips)
@@ -3854,8 +3872,8 @@ def multiscale_argmax_confusion(lows, flips, target=None, size=None, ignore_inde
         descs += [_MsMap(low.data_ptr(), ld(low), h, w, int(fl), i * B) for i, fl in enumerate(halves)]
     if len(descs) > MULTISCALE_MAX_MAPS:
         raise ValueError('at most %d maps per call, got %d' % (MULTISCALE_MAX_MAPS, len(descs)))
-    if C > 24:
-        raise ValueError('at most 24 classes (the scores live in registers), got %d' % C)
+    if C > WIDEHEAD_MAX_CLASSES:
+        raise ValueError('multiscale_argmax_confusion supports at most %d classes, got %d' % (WIDEHEAD_MAX_CLASSES, C))
     pred = torch.empty((B, ho, wo), dtype=torch.uint8, device=first.device) if want_pred else None
     if target is not None:
         if target.dtype != torch.int64 or tuple(target.shape) != (B, ho, wo):
@@ -3864,20 +3882,23 @@ def multiscale_argmax_confusion(lows, flips, target=None, size=None, ignore_inde
         target = target.contiguous()
         if confusion is None:
             confusion = torch.zeros((C, C), dtype=torch.int64, device=first.device)
-    call('tss_multiscale_argmax_confusion', (_MsMap * len(descs))(*descs), len(descs), ptr(target), ptr(pred), ptr(confusion),
+    call('tss_multiscale_argmax_confusion' + _wide(C), (_MsMap * len(descs))(*descs), len(descs), ptr(target), ptr(pred), ptr(confusion),
          B, C, ho, wo, int(ignore_index), _MS_AVERAGE[average], N.dtype_code(first.dtype), stream())
     return pred, confusion
 
 
 def argmax_confusion(logits, target=None, num_classes=None, ignore_index=255, confusion=None, want_pred=True):
     """argmax over dim 1 (lowest index wins ties) and, with a target, the confusion-matrix update
-    (rows = truth, cols = prediction) that create_segmentation_evaluator's metrics need (TSS/engine.py:65-72)."""
+    (rows = truth, cols = prediction) that create_segmentation_evaluator's metrics need (TSS/engine.py:65-72).  At most 256 classes
+    (past 64 the counters of the first kernel no longer fit LDS: tss_argmax_confusion_wide)."""
     _check_device(logits)
     logits = logits.contiguous()
     B, C, H, W = logits.shape
+    if C > WIDEHEAD_MAX_CLASSES:
+        raise ValueError('argmax_confusion supports at most %d classes, got %d' % (WIDEHEAD_MAX_CLASSES, C))
     pred = torch.empty((B, H, W), dtype=torch.uint8, device=logits.device) if want_pred else None
     if target is not None and confusion is None:
         confusion = torch.zeros((C, C), dtype=torch.int64, device=logits.device)
-    call('tss_argmax_confusion', ptr(logits), ptr(target.contiguous()) if target is not None else None, ptr(pred),
+    call('tss_argmax_confusion' + ('_wide' if C > 64 else ''), ptr(logits), ptr(target.contiguous()) if target is not None else None, ptr(pred),
          ptr(confusion), B, C, H * W, int(ignore_index), N.dtype_code(logits.dtype), stream())
     return pred, confusion
