@@ -881,6 +881,11 @@ int tss_upsample_ohem_grad_wide(const void* low, long ldl, const long long* targ
                                 int B, int C, int h, int w, int H, int W, int ignore_index, int dtype, void* stream);
 int tss_upsample_ce_wide_bwd(const float* ws, const float* inv_count, const float* grad_out, void* dlow, long ldl,
                              int B, int C, int h, int w, int H, int W, int dtype, void* stream);
+/* tss_upsample_ohem_grad_wide with the weight of a pixel read from `coef` ([B][H][W] f32, 0 for every pixel that does not count)
+ * instead of derived from a stored loss and the selection parameters: tiles of sum_p coef[p] * CE_p.  The second half of the focal
+ * loss past 24 classes (below); ws as for tss_upsample_ce_wide_fwd, tss_upsample_ce_wide_bwd gathers. */
+int tss_upsample_coef_grad_wide(const void* low, long ldl, const long long* target, const float* coef, float* ws, int B, int C, int h,
+                                int w, int H, int W, int ignore_index, int dtype, void* stream);
 int tss_upsample_argmax_confusion_wide(const void* low, long ldl, const long long* target, unsigned char* pred,
                                        unsigned long long* confusion, int B, int C, int h, int w, int H, int W,
                                        int ignore_index, int dtype, void* stream);
@@ -890,6 +895,39 @@ int tss_multiscale_argmax_confusion_wide(const tss_msmap* maps, int K, const lon
 int tss_argmax_confusion_wide(const void* logits, const long long* target, unsigned char* pred,
                               unsigned long long* confusion, long B, int C, long HW, int ignore_index,
                               int dtype, void* stream);
+
+/* ---- focal and soft Dice loss on the fused head (csrc/softhead.hip) -----------------------------------------------------
+ * tss_focal_fwd / tss_dice_fwd of the bilinearly (align_corners=True) upsampled logits, straight from the low-res NHWC logits
+ * [B][h][w][ldl] (ldl % 8 == 0, ldl >= round_up(C, 4), pad channels ignored, 16-byte aligned): the semantics, the validity rule
+ * (has_ignore = 0: no ignore index), the variants and the empty-set rule (*loss = 0, zero gradient) of those entries; the
+ * full-resolution logits and their gradient never exist.  No atomics, no host read-back: capturable, the same bits on every run.
+ * Workspaces are NOT initialised by the caller: every element that a later call reads was written.  Anything outside the contract
+ * (C, H < h, W < w, gamma < 0, smooth < 0, variant not 0 / 1, a NULL pointer): TSS_ERR_SHAPE, nothing launched.
+ *   focal, 1 <= C <= 24: tss_upsample_focal_fwd, one pass, built like tss_upsample_ce_fwd_ex: ws = tss_upsample_ce_ws(...) floats in
+ *     that layout (per-block loss rows, then per-block gradient tiles of sum coef (p_k - [k == t]), unscaled);
+ *     *loss = -alpha sum w log p_t / #valid, *scale = alpha / #valid.  Backward: tss_upsample_ce_bwd with inv_count := scale.
+ *   focal, 24 < C <= 256: tss_upsample_pixel_ce_wide writes ce = -log p_t per pixel; tss_focal_coef_from_ce turns that array (n = B H W
+ *     floats, 16-byte aligned like target) IN PLACE into the per-pixel gradient coefficient (0 for a pixel that does not count) and
+ *     leaves *loss and *scale as above, rows = [tss_focal_coef_rows(n)][2] f64; backward: tss_upsample_coef_grad_wide fills the tiles,
+ *     tss_upsample_ce_wide_bwd gathers with inv_count := scale.  On this route q = 1 - p_t is formed from the STORED cross-entropy as
+ *     -expm1(-ce), without cancellation, and not as the sum of the other classes' probabilities.
+ *   dice, 1 <= C <= 24: tss_upsample_dice_fwd = a statistics pass (per-block f64 rows of sum p_c, sum p_c [t == c], sum [t == c]) and a
+ *     one-block finalize that leaves *loss and, at the head of dice_ws (tss_upsample_dice_ws(...) floats), the coefficients
+ *     a_c = -2 / (C (U_c + smooth)) at [0, 24) and b_c = (2 I_c + smooth) / (C (U_c + smooth)^2) at [24, 48) (zero past C, and all
+ *     zero when no pixel is valid).  Backward: tss_upsample_dice_grad recomputes the softmax from the low-res rows and fills
+ *     ws = tss_upsample_ce_ws(...) floats with tiles of dz_k = p_k (b_k - S) + [k == t] a_t p_t, S = sum_c b_c p_c + a_t p_t;
+ *     tss_upsample_ce_bwd gathers with *inv_count = 1. */
+int tss_upsample_focal_fwd(const void* low, long ldl, const long long* target, float* ws, float* loss, float* scale, int B, int C, int h,
+                           int w, int H, int W, int ignore_index, int has_ignore, float alpha, float gamma, int variant, int dtype,
+                           void* stream);
+long tss_focal_coef_rows(long n);
+int tss_focal_coef_from_ce(float* pix, const long long* target, double* rows, float* loss, float* scale, long n, int C, int ignore_index,
+                           int has_ignore, float alpha, float gamma, int variant, void* stream);
+long tss_upsample_dice_ws(int B, int C, int h, int w, int H, int W);
+int tss_upsample_dice_fwd(const void* low, long ldl, const long long* target, float* dice_ws, float* loss, int B, int C, int h, int w,
+                          int H, int W, int ignore_index, int has_ignore, float smooth, int dtype, void* stream);
+int tss_upsample_dice_grad(const void* low, long ldl, const long long* target, const float* dice_ws, float* ws, int B, int C, int h,
+                           int w, int H, int W, int ignore_index, int has_ignore, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

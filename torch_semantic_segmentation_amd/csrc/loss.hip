@@ -4,7 +4,7 @@
 // forward: online log-sum-exp over the C planes -> per-pixel lse (saved), sum of losses + valid count (f64 atomics)
 // backward: dlogits[c] = (exp(l_c - lse) - [c == t]) * grad_out / count, recomputed from the saved lse
 // ce_fwd_ex / ce_bwd_ex: the same with class weights and label smoothing, per-block partial rows instead of the atomics
-#include "losssweep.h"
+#include "headgeom.h"
 
 namespace {
 
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(NT) void ce_bwd_ex_kernel(const T* logits, const lo
 // of its own, and the backward kernel gathers the <= 4 tiles of a cell in a fixed order.  (Round 2 added them with f32
 // global atomics into a zero-filled buffer: last-bit differences from run to run that a train step amplifies.)
 //   ws = [nblocks][2] f64 loss rows, then [nblocks][tile_rows][tile_cells][CP] f32 tiles; block = (b * nband + band) * nstrip + strip
-struct CeGeom { int nstrip, nband, band_rows, tile_rows, tile_cells; };
+// (CeGeom, ce_geom and the shape rule: headgeom.h, shared with softhead.hip)
 
 // MODE 0: mean cross-entropy (loss rows + unscaled gradient tiles).  MODE 1: the per-pixel cross-entropy only, written to `pix`
 // ([B][H][W] f32, 0 for ignored pixels) -- the input of the OHEM selection (TSS/losses/ohem_loss.py:11-12 without the 318.8 M-element
@@ -570,11 +570,6 @@ __global__ __launch_bounds__(NT, 3) void upsample_argmax_kernel(const T* low, lo
       if (scm[i]) atomicAdd(cm + i, (unsigned long long)scm[i]);
 }
 
-// What every entry point of the upsampled-CE family asks of its shapes: classes in registers (at most 24), whole class groups per pixel.
-inline bool upsample_ce_shape_ok(int C, long ldl, int h, int w, int H, int W) {
-  return C > 0 && C <= 24 && (ldl % 8) == 0 && ldl >= (C + 3) / 4 * 4 && h > 0 && w > 0 && H >= h && W >= w;
-}
-
 }  // namespace
 
 extern "C" {
@@ -689,24 +684,6 @@ int tss_upsample_argmax_confusion(const void* low, long ldl, const long long* ta
     hipLaunchKernelGGL((upsample_argmax_kernel<TT, CPV>), dim3((int)grid), dim3(NT), sh, (hipStream_t)stream,
                        (const TT*)low, ldl, target, pred, confusion, B, C, h, w, H, W, ignore_index, band_rows)));
   return tss::check_last("upsample_argmax_confusion");
-}
-
-// Geometry of the pass (the same on the host, in the pass and in the gather): bands / strips and the tile every block owns.
-static CeGeom ce_geom(int B, int h, int w, int H, int W) {
-  CeGeom g;
-  g.nstrip = (W + NT - 1) / NT;
-  // bands: enough blocks to fill the chip, but every band pays two extra row flushes
-  g.band_rows = 64;
-  while (g.band_rows > 16 && (long)B * g.nstrip * ((H + g.band_rows - 1) / g.band_rows) < 2048) g.band_rows /= 2;
-  g.nband = (H + g.band_rows - 1) / g.band_rows;
-  // conservative tile extent: a band of R output rows touches at most floor((R - 1) * (h - 1) / (H - 1)) + 3 low-res rows
-  // (the pass and the gather index the tile by the rows / cells actually touched, which they both compute exactly)
-  const double sy = H > 1 ? (double)(h - 1) / (double)(H - 1) : 0.0, sx = W > 1 ? (double)(w - 1) / (double)(W - 1) : 0.0;
-  g.tile_rows = (int)((g.band_rows - 1) * sy) + 3;
-  g.tile_cells = (int)((NT - 1) * sx) + 3;
-  if (g.tile_rows > h) g.tile_rows = h;
-  if (g.tile_cells > w) g.tile_cells = w;
-  return g;
 }
 
 long tss_upsample_ce_ws(int B, int C, int h, int w, int H, int W) {

@@ -61,10 +61,14 @@ constexpr size_t wide_ce_lds_bytes() {
 
 // MODE as in upsample_ce_onepass_kernel (loss.hip): 0 mean CE, 1 per-pixel CE -> pix, 2 OHEM gradient tiles from pix and sel,
 // 3 class weights, 4 class weights + label smoothing.  ws layout as there, tiles [tile_rows][tile_cells][cpw].
+// MODE 5: MODE 2 with the weight of a pixel READ from `pix` (0 for a pixel that does not count) instead of derived from a stored
+// loss and `sel`: gradient tiles of sum_p pix[p] * CE_p, the second half of the focal loss past 24 classes (softhead.hip).
 template <typename T, int MODE>
 __global__ __launch_bounds__(NT, 2) void wide_ce_kernel(const T* low, long ldl, const long long* target, float* tiles, double* lossrows,
                                                         int C, int h, int w, int H, int W, int ignore_index, const WGeom geo,
                                                         float* pix, const float* sel, const float* cw, float eps) {
+  constexpr bool WEIGHTED = MODE == 3 || MODE == 4;             // class weights in play
+  constexpr bool TILES_ONLY = MODE == 2 || MODE == 5;           // no loss terms, no loss rows
   extern __shared__ __align__(16) unsigned char wlds[];
   double* const red = reinterpret_cast<double*>(wlds);          // [2][NT / 64]
   float* const Pm = reinterpret_cast<float*>(wlds + 64);        // [WROWS][NT] running maximum, then the log-sum-exp (log2 units)
@@ -84,7 +88,7 @@ __global__ __launch_bounds__(NT, 2) void wide_ce_kernel(const T* low, long ldl, 
 
   const int tid = threadIdx.x;
   const int cpw = geo.cpw;
-  Cw[tid] = (MODE >= 3 && tid < C) ? (cw ? cw[tid] : 1.f) : 0.f;
+  Cw[tid] = (WEIGHTED && tid < C) ? (cw ? cw[tid] : 1.f) : 0.f;
   Nn[tid] = 0.f; Nn[NT + tid] = 0.f;
   const int nstrip = geo.nstrip, nband = geo.nband;
   float* const tile = tiles + (long)blockIdx.x * geo.tile_rows * geo.tile_cells * cpw;
@@ -186,7 +190,7 @@ __global__ __launch_bounds__(NT, 2) void wide_ce_kernel(const T* low, long ldl, 
       for (int c = 0; c < WK; ++c) s += (c0 + c < C) ? __builtin_amdgcn_exp2f(z[c] - mn) : 0.f;
       Pm[j * NT + tid] = mn;
       Ps[j * NT + tid] = s;
-      if (MODE != 2) {
+      if (!TILES_ONLY) {
         const int t = Tt[j * NT + tid];
         const int tc = t - c0;
         if (tc >= 0 && tc < WK) {                  // the one chunk that holds the pixel's class: its logit, by compare
@@ -194,7 +198,7 @@ __global__ __launch_bounds__(NT, 2) void wide_ce_kernel(const T* low, long ldl, 
 #pragma unroll
           for (int c = 0; c < WK; ++c) zt = (tc == c) ? z[c] : zt;
           if (MODE == 1) Pz[j * NT + tid] = zt;
-          else lsum -= (double)((MODE >= 3 ? om * Cw[t] : 1.f) * zt);
+          else lsum -= (double)((WEIGHTED ? om * Cw[t] : 1.f) * zt);
         }
         if (MODE == 4 && t >= 0) {                 // the uniform part of the smoothed target: eps / C * sum_c w_c z_c
           float zs = 0.f;
@@ -212,8 +216,8 @@ __global__ __launch_bounds__(NT, 2) void wide_ce_kernel(const T* low, long ldl, 
     const int t = Tt[j * NT + tid];
     if (MODE == 1) {      // per-pixel loss in nats, >= 0 (rounding may give -1e-7), 0 for ignored pixels
       if (xin) pix[(b * H + y) * (long)W + x] = t >= 0 ? fmaxf((lse - Pz[j * NT + tid]) * (float)LN2, 0.f) : 0.f;
-    } else if (MODE != 2 && t >= 0) {
-      const float wt = MODE >= 3 ? Cw[t] : 1.f;
+    } else if (!TILES_ONLY && t >= 0) {
+      const float wt = WEIGHTED ? Cw[t] : 1.f;
       lsum += (double)((om * wt + sW) * lse);
       lcnt += wt;
     }
@@ -297,13 +301,13 @@ __global__ __launch_bounds__(NT, 2) void wide_ce_kernel(const T* low, long ldl, 
       const int t = Tt[j * NT + tid];
       const bool valid = t >= 0;
       float wpx = 1.f, wsm = 1.f;                  // weights of the one-hot and of the softmax half
-      if (MODE == 2) {
+      if (TILES_ONLY) {
         const float pl = xin ? pix[(b * H + y) * (long)W + x] : 0.f;
-        wpx = pl > sel_cut ? sel_gt : (pl == sel_cut ? sel_eq : 0.f);
+        wpx = MODE == 5 ? pl : (pl > sel_cut ? sel_gt : (pl == sel_cut ? sel_eq : 0.f));
         wsm = wpx;
       }
       if (valid) {
-        if (MODE >= 3) { wpx = om * Cw[t]; wsm = wpx + sW; }
+        if (WEIGHTED) { wpx = om * Cw[t]; wsm = wpx + sW; }
         if (MODE == 4) { Nn[kA * NT + tid] += ty.l0; Nn[(kA ^ 1) * NT + tid] += ty.l1; }
         const int tc = t - c0;
         if (tc >= 0 && tc < WK) {                  // this lane's own rows of the table: no race
@@ -329,7 +333,7 @@ __global__ __launch_bounds__(NT, 2) void wide_ce_kernel(const T* low, long ldl, 
       Nn[(kA ^ 1) * NT + tid] = 0.f;
     }
   }
-  if (MODE == 2) return;
+  if (TILES_ONLY) return;
 
   double ds = wave_sum(lsum * LN2), dc = wave_sum((double)lcnt);   // back to nats
   const int wave = tid >> 6;
@@ -776,6 +780,24 @@ int tss_upsample_ohem_grad_wide(const void* low, long ldl, const long long* targ
   TSS_WITH_DTYPE(dtype, (launch_wide_ce<TT, 2>(grid, (hipStream_t)stream, low, ldl, target, tiles, nullptr, C, h, w, H, W, ignore_index, geo,
                                                const_cast<float*>(pix), sel, nullptr, 0.f)));
   return tss::check_last("upsample_ohem_grad_wide");
+}
+
+// Gradient tiles of sum_p coef[p] * CE_p, coef ([B][H][W] f32) 0 for every pixel that does not count (tss_focal_coef_from_ce writes it
+// that way): the MODE 5 instance.  ws as for tss_upsample_ce_wide_fwd; tss_upsample_ce_wide_bwd gathers.
+int tss_upsample_coef_grad_wide(const void* low, long ldl, const long long* target, const float* coef, float* ws, int B, int C, int h,
+                                int w, int H, int W, int ignore_index, int dtype, void* stream) {
+  TSS_CHECK_DTYPE(dtype);
+  TSS_REQUIRE(wide_shape_ok(C, ldl, h, w, H, W) && coef && ws && B >= 0, TSS_ERR_SHAPE);
+  TSS_REQUIRE(tss::aligned16(low) && tss::aligned16(ws), TSS_ERR_ALIGN);
+  if ((long)B * H * W == 0) return TSS_OK;
+  const WGeom geo = wide_geom(C, h, w, H, W);
+  const long grid = (long)B * geo.nstrip * geo.nband;
+  TSS_REQUIRE(grid <= 0x7fffffffL, TSS_ERR_SHAPE);
+  float* tiles = ws + grid * 4;
+  tss::ProfScope prof(TSS_K_WIDE_CE_FWD, (hipStream_t)stream, (double)B * h * w * C * (tss::esz(dtype) + 8.0) + (double)B * H * W * 12.0, 0);
+  TSS_WITH_DTYPE(dtype, (launch_wide_ce<TT, 5>(grid, (hipStream_t)stream, low, ldl, target, tiles, nullptr, C, h, w, H, W, ignore_index, geo,
+                                               const_cast<float*>(coef), nullptr, nullptr, 0.f)));
+  return tss::check_last("upsample_coef_grad_wide");
 }
 
 int tss_upsample_ce_wide_bwd(const float* ws, const float* inv_count, const float* grad_out, void* dlow, long ldl,

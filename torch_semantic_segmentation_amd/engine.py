@@ -365,9 +365,12 @@ class Trainer:
         # model(x) followed by CrossEntropyLoss == the fused head+loss operator on model.forward_lowres(x): same
         # value and gradients, but the full-resolution logits never exist (-1.3 GB and ~0.8 ms at 8x1024x2048:
         # one 0.26 ms kernel instead of five that move 3.8 GB).  Only taken when nothing can observe the difference
-        # (our loss class, a model that offers forward_lowres, no hooks on the model itself).
-        self.fuse_head_loss = bool(fuse_head_loss) and type(loss_fn) in (ops.CrossEntropyLoss, ops.OHEMLoss) \
-            and hasattr(model, 'forward_lowres') and hasattr(model, 'logit_scale')
+        # (our loss class, a model that offers forward_lowres, no hooks on the model itself).  FocalLoss and DiceLoss have a fused
+        # operator too (ops.upsample_focal_loss / upsample_dice_loss), but its result differs from the unfused one in the last bits,
+        # so they take it only when the module was built with fused_head=True.
+        fusable = type(loss_fn) in (ops.CrossEntropyLoss, ops.OHEMLoss) \
+            or (type(loss_fn) in (ops.FocalLoss, ops.DiceLoss) and loss_fn.fused_head)
+        self.fuse_head_loss = bool(fuse_head_loss) and fusable and hasattr(model, 'forward_lowres') and hasattr(model, 'logit_scale')
         if self.flat:
             optimizer.grad_scale = 1.0 / world_size
         self.shadows = None
@@ -423,6 +426,13 @@ class Trainer:
                 if type(self.loss_fn) is ops.OHEMLoss:
                     loss = ops.upsample_ohem_loss(low, y, scale_factor=self.model.logit_scale, ignore_index=self.loss_fn.ignore_index,
                                                   thresh_loss=self.loss_fn.thresh_loss, numel_frac=self.loss_fn.numel_frac)
+                elif type(self.loss_fn) is ops.FocalLoss:
+                    loss = ops.upsample_focal_loss(low, y, scale_factor=self.model.logit_scale, alpha=self.loss_fn.alpha,
+                                                   gamma=self.loss_fn.gamma, ignore_index=self.loss_fn.ignore_index,
+                                                   variant=self.loss_fn.variant)
+                elif type(self.loss_fn) is ops.DiceLoss:
+                    loss = ops.upsample_dice_loss(low, y, self.loss_fn.num_classes, scale_factor=self.model.logit_scale,
+                                                  smooth=self.loss_fn.smooth, ignore_index=self.loss_fn.ignore_index)
                 else:
                     loss = ops.upsample_cross_entropy(low, y, scale_factor=self.model.logit_scale,
                                                       ignore_index=self.loss_fn.ignore_index, weight=self.loss_fn.weight,

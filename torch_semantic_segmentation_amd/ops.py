@@ -3459,12 +3459,15 @@ def focal_loss(input, target, alpha=0.25, gamma=2.0, ignore_index=-100, variant=
 
 class FocalLoss(torch.nn.Module):
     """Drop-in for TSS.losses.FocalLoss (TSS/losses/focal_loss.py:18-32), constructor defaults included; the default
-    ignore_index=None keeps every in-range pixel (the reference raises there).  See focal_loss."""
+    ignore_index=None keeps every in-range pixel (the reference raises there).  See focal_loss.
+    fused_head=True lets engine.Trainer take upsample_focal_loss on the model's low-resolution logits; the module itself, called on
+    full-resolution logits, computes the same either way."""
 
-    def __init__(self, alpha=0.25, gamma=2.0, ignore_index=None, variant='reference'):
+    def __init__(self, alpha=0.25, gamma=2.0, ignore_index=None, variant='reference', fused_head=False):
         super().__init__()
         _check_variant(variant, FOCAL_VARIANTS)
         self.alpha, self.gamma, self.ignore_index, self.variant = alpha, gamma, ignore_index, variant
+        self.fused_head = bool(fused_head)
 
     def forward(self, input, target):
         return focal_loss(input, target, self.alpha, self.gamma, self.ignore_index, self.variant)
@@ -3522,11 +3525,14 @@ def dice_loss(input, target, num_classes, smooth=1.0, ignore_index=-100):
 
 
 class DiceLoss(torch.nn.Module):
-    """Drop-in for TSS.losses.DiceLoss (TSS/losses/dice_loss.py:29-42), which cannot run upstream; see dice_loss."""
+    """Drop-in for TSS.losses.DiceLoss (TSS/losses/dice_loss.py:29-42), which cannot run upstream; see dice_loss.
+    fused_head=True lets engine.Trainer take upsample_dice_loss on the model's low-resolution logits; the module itself, called on
+    full-resolution logits, computes the same either way."""
 
-    def __init__(self, num_classes, smooth=1.0, ignore_index=-100):
+    def __init__(self, num_classes, smooth=1.0, ignore_index=-100, fused_head=False):
         super().__init__()
         self.num_classes, self.smooth, self.ignore_index = num_classes, smooth, ignore_index
+        self.fused_head = bool(fused_head)
 
     def forward(self, input, target):
         return dice_loss(input, target, self.num_classes, self.smooth, self.ignore_index)
@@ -3772,6 +3778,128 @@ def upsample_ohem_loss(low, target, scale_factor=None, size=None, ignore_index=-
         raise RuntimeError('target must be int64 of shape (B,H,W) = %s' % ((B, ho, wo),))
     _check_device(target)
     return UpsampleOHEMFn.apply(low, target, ho, wo, ignore_index, thresh_loss, numel_frac)
+
+
+def _head_gather(ws, scale, gout, geom):
+    """The backward every fused head loss ends in: the gradient tiles of `ws` gathered in a fixed order and scaled by scale * gout;
+    returns the NCHW view of the NHWC gradient (pad channels written as zeros)."""
+    B, C, h, w, ho, wo, ldl, dtype = geom
+    gout = gout.to(torch.float32).contiguous()
+    base = torch.empty((B, h, w, ldl), dtype=dtype, device=ws.device)
+    call('tss_upsample_ce%s_bwd' % _wide(C), ptr(ws), ptr(scale), ptr(gout), ptr(base), ldl, B, C, h, w, ho, wo, N.dtype_code(dtype), stream())
+    return base.permute(0, 3, 1, 2)[:, :C]
+
+
+class UpsampleFocalFn(Function):
+    """focal_loss(F.interpolate(low, bilinear, align_corners=True), target) without the full-resolution logits (csrc/softhead.hip).
+    Up to 24 classes: one pass leaves the loss rows and the unscaled gradient tiles, as UpsampleCrossEntropyFn does.  Up to 256: the
+    OHEM route -- the per-pixel cross-entropy of the wide head, turned in place into the per-pixel gradient coefficient (and the loss),
+    and in backward the wide gradient-tile pass weighted by that array.  No atomics, no host read-back, the same bits on every run."""
+
+    @staticmethod
+    def forward(ctx, low, target, ho, wo, alpha, gamma, ignore_index, variant):
+        B, C, h, w = low.shape
+        dev = low.device
+        target = target.contiguous()
+        ign, code = _ignore_pair(ignore_index), N.dtype_code(low.dtype)
+        out = torch.empty(2, dtype=torch.float32, device=dev)              # loss, alpha / number of valid pixels
+        ctx.geom = (B, C, h, w, ho, wo, ld(low), low.dtype)
+        if not _wide(C):
+            ws = torch.empty(N.lib().tss_upsample_ce_ws(B, C, h, w, ho, wo), dtype=torch.float32, device=dev)
+            call('tss_upsample_focal_fwd', ptr(low), ld(low), ptr(target), ptr(ws), ptr(out[0:1]), ptr(out[1:2]), B, C, h, w, ho, wo,
+                 *ign, float(alpha), float(gamma), FOCAL_VARIANTS[variant], code, stream())
+            ctx.save_for_backward(ws, out)
+        else:
+            # the wide pixel pass has no has_ignore flag: -1 is out of range, hence ignored anyway
+            ctx.wide_ignore = ign[0] if ign[1] else -1
+            pix = torch.empty((B, ho, wo), dtype=torch.float32, device=dev)
+            rows = torch.empty((N.lib().tss_focal_coef_rows(B * ho * wo), 2), dtype=torch.float64, device=dev)
+            call('tss_upsample_pixel_ce_wide', ptr(low), ld(low), ptr(target), ptr(pix), B, C, h, w, ho, wo, ctx.wide_ignore, code, stream())
+            call('tss_focal_coef_from_ce', ptr(pix), ptr(target), ptr(rows), ptr(out[0:1]), ptr(out[1:2]), B * ho * wo, C, *ign,
+                 float(alpha), float(gamma), FOCAL_VARIANTS[variant], stream())
+            ctx.save_for_backward(low, target, pix, out)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        B, C, h, w, ho, wo, ldl, dtype = ctx.geom
+        if not _wide(C):
+            ws, out = ctx.saved_tensors
+        else:
+            low, target, pix, out = ctx.saved_tensors
+            ws = torch.empty(N.lib().tss_upsample_ce_wide_ws(B, C, h, w, ho, wo), dtype=torch.float32, device=low.device)
+            call('tss_upsample_coef_grad_wide', ptr(low), ldl, ptr(target), ptr(pix), ptr(ws), B, C, h, w, ho, wo, ctx.wide_ignore,
+                 N.dtype_code(dtype), stream())
+        return _head_gather(ws, out[1:2], gout, ctx.geom), None, None, None, None, None, None, None
+
+
+def _check_head_target(low, target, ho, wo):
+    if target.dtype != torch.int64 or tuple(target.shape) != (low.shape[0], ho, wo):
+        raise RuntimeError('target must be int64 of shape (B,H,W) = %s' % ((low.shape[0], ho, wo),))
+    _check_device(target)
+
+
+def upsample_focal_loss(low, target, scale_factor=None, size=None, alpha=0.25, gamma=2.0, ignore_index=-100, variant='reference'):
+    """Fused decoder head + focal loss: focal_loss(F.interpolate(low, scale_factor, mode='bilinear', align_corners=True), target, alpha,
+    gamma, ignore_index, variant) from the low-resolution logits (the NHWC map of forward_lowres, read in place, or an NCHW tensor);
+    the full-resolution logits and their gradient are never materialised.  Every rule of focal_loss holds (validity, both variants,
+    ignore_index=None, 0.0 and a zero gradient for an empty valid set).  More than 256 classes, or an output smaller than the map:
+    the unfused composition."""
+    _check_variant(variant, FOCAL_VARIANTS)
+    if not float(gamma) >= 0.0:
+        raise ValueError('gamma must be >= 0, got %r' % (gamma,))
+    low = to_nhwc(materialize(low))
+    ho, wo = _out_size(low, size, scale_factor)
+    if low.shape[1] > WIDEHEAD_MAX_CLASSES or ho < low.shape[2] or wo < low.shape[3]:
+        return focal_loss(upsample_logits(low, size=(ho, wo)), target, alpha, gamma, ignore_index, variant)
+    _check_head_target(low, target, ho, wo)
+    return UpsampleFocalFn.apply(low, target, ho, wo, alpha, gamma, ignore_index, variant)
+
+
+class UpsampleDiceFn(Function):
+    """dice_loss(F.interpolate(low, bilinear, align_corners=True), target) without the full-resolution logits (csrc/softhead.hip), up to
+    24 classes: a statistics pass and a one-block finalize (loss and the 2C backward coefficients) forward; backward recomputes the
+    softmax from the low-resolution rows into gradient tiles, gathered in a fixed order.  No atomics, no host read-back."""
+
+    @staticmethod
+    def forward(ctx, low, target, ho, wo, smooth, ignore_index):
+        B, C, h, w = low.shape
+        dev = low.device
+        target = target.contiguous()
+        ign = _ignore_pair(ignore_index)
+        dws = torch.empty(N.lib().tss_upsample_dice_ws(B, C, h, w, ho, wo), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        call('tss_upsample_dice_fwd', ptr(low), ld(low), ptr(target), ptr(dws), ptr(loss), B, C, h, w, ho, wo, *ign, float(smooth),
+             N.dtype_code(low.dtype), stream())
+        ctx.geom, ctx.ign = (B, C, h, w, ho, wo, ld(low), low.dtype), ign
+        ctx.save_for_backward(low, target, dws)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        low, target, dws = ctx.saved_tensors
+        B, C, h, w, ho, wo, ldl, dtype = ctx.geom
+        ws = torch.empty(N.lib().tss_upsample_ce_ws(B, C, h, w, ho, wo), dtype=torch.float32, device=low.device)
+        call('tss_upsample_dice_grad', ptr(low), ldl, ptr(target), ptr(dws), ptr(ws), B, C, h, w, ho, wo, *ctx.ign, N.dtype_code(dtype),
+             stream())
+        return _head_gather(ws, _unit(low.device), gout, ctx.geom), None, None, None, None, None
+
+
+def upsample_dice_loss(low, target, num_classes, scale_factor=None, size=None, smooth=1.0, ignore_index=-100):
+    """Fused decoder head + soft Dice loss: dice_loss(F.interpolate(low, scale_factor, mode='bilinear', align_corners=True), target,
+    num_classes, smooth, ignore_index) from the low-resolution logits; the full-resolution logits and their gradient are never
+    materialised.  Every rule of dice_loss holds.  More than 24 classes (HEAD_REGISTER_CLASSES), or an output smaller than the map:
+    the unfused composition."""
+    low = materialize(low)
+    _check_num_classes(low, num_classes)
+    if not float(smooth) >= 0.0:
+        raise ValueError('smooth must be >= 0, got %r' % (smooth,))
+    low = to_nhwc(low)
+    ho, wo = _out_size(low, size, scale_factor)
+    if low.shape[1] > HEAD_REGISTER_CLASSES or ho < low.shape[2] or wo < low.shape[3]:
+        return dice_loss(upsample_logits(low, size=(ho, wo)), target, num_classes, smooth, ignore_index)
+    _check_head_target(low, target, ho, wo)
+    return UpsampleDiceFn.apply(low, target, ho, wo, smooth, ignore_index)
 
 
 def upsample_argmax_confusion(low, target=None, scale_factor=None, size=None, ignore_index=255, confusion=None,
