@@ -1,5 +1,5 @@
 """Exact-operand f64 references for the bf16 convolution kernels (tests/test_exact_bounds.py, tests/test_gpu_zoo_exact.py,
-tests/test_gpu_dw_exact.py, tests/test_gpu_pw_exact.py).
+tests/test_gpu_dw_exact.py, tests/test_gpu_pw_exact.py, tests/test_gpu_dense_exact.py).
 
 Every operand is a DYADIC bf16 value, +-(1 + k/128) * 2^e with e in [-4, 2): 8 significant bits.  BatchNorm scales are powers of two in
 [1/2, 4], the backward pair (ga, gb) powers of two in [1/4, 2] and [2^-6, 2^-3].  Then the on-load transforms of the kernels
@@ -571,3 +571,168 @@ def joined_bwd_ref(rin, Sin, radd, jout):
     if radd is not None:
         rin, Sin = rin + radd, Sin + radd.abs()
     return rin * keep, Sin * keep
+
+
+# ---------------------------------------------------------------------------------------------------------- dense 3x3 family and stem
+# csrc/wstat.hip, atrous.hip, conv3x3.hip, the 9-tap A_TAPS path of convgemm.hip / wgrad.hip and csrc/stem.hip; tests/test_gpu_dense_exact.py.
+# These kernels feed the matrix unit from bf16 operands (act / gcomb; the weights are bf16-exact), so conv_excess holds with K = 9 x the
+# contraction.  Each helper restates a dispatch rule or a launch planner of the C source; the GPU test checks the slab / workspace rows a
+# launch leaves in use against the restated grid.
+WSTAT_TP, WSTAT_GRID, WSTAT_MAXD = 64, 256, 18      # TP, the launch's block count, MAXD of csrc/wstat.hip
+LEAN_MAXDIL = 18                                      # MAXDIL of csrc/conv3x3.hip
+
+
+def conv3x3_fwd_route(H, Cin, N, stride, dil, pending, relu, ldx, ldy, shadow=True, bf16=True):
+    """which kernel tss_conv3x3_fwd (csrc/convgemm.hip) launches, in the order it asks: tss_conv3x3_wstat_fwd, tss_conv3x3_stream_fwd,
+    tss_conv3x3_lean_fwd (all three need the bf16 weight copy), tss_sconv_fwd, convgemm_kernel.  pending: in_scale given"""
+    if bf16 and shadow:
+        mat = not pending and not relu and stride == 1
+        if mat and dil <= WSTAT_MAXD and Cin == 128 and N == 128 and ldx % 8 == 0 and ldy % 8 == 0 and H >= dil:
+            return 'wstat'
+        if mat and 32 <= Cin <= 128 and Cin % 32 == 0 and 16 <= N <= 128 and N % 16 == 0 and ldx % 8 == 0 and ldy % 4 == 0:
+            return 'stream<4, true>' if (Cin, N) == (128, 128) else 'stream<0, false>'
+        if stride == 1 and dil <= LEAN_MAXDIL and Cin in (32, 64, 128) and 16 <= N <= 128 and N % 16 == 0 and ldx % 8 == 0 and ldy % 4 == 0:
+            return 'lean<false, 2>' if dil == 1 else 'lean<false, 3>'
+    if bf16 and stride == 2 and dil == 1 and Cin <= 64 and N <= 128:
+        return 'sconv or generic'
+    return 'generic'
+
+
+def conv3x3_bwd_route(Cin, N, dil, with_y, shadow=True, bf16=True):
+    """tss_conv3x3_bwd_data: conv3x3_lean_kernel<true, 2 | 3> (contraction N in {32, 64, 128}, outputs Cin % 16 == 0 <= 128, yraw and
+    the bf16 weight copy given, dilation <= 18), else convgemm_kernel with two sources (yraw) or one"""
+    if bf16 and shadow and with_y and dil <= LEAN_MAXDIL and N in (32, 64, 128) and 16 <= Cin <= 128 and Cin % 16 == 0:
+        return 'lean<true, 2>' if dil == 1 else 'lean<true, 3>'
+    return 'generic'
+
+
+def wstat_decode(u, H, W, D):
+    """decode() of conv3x3_wstat_kernel: unit u of the walk order -- (image, strip) major, then residue class r = y mod D, then j
+    (y = r + j D) -- as (b, strip, r, j, rows of the class)"""
+    nstrip = cdiv(W, WSTAT_TP)
+    qd = H // D
+    rem = H - qd * D                          # classes r < rem have qd + 1 rows, the others qd
+    bs, pp = divmod(u, H)
+    b, sx = divmod(bs, nstrip)
+    if pp < rem * (qd + 1):
+        r, j = divmod(pp, qd + 1)
+        return b, sx, r, j, qd + 1
+    pp -= rem * (qd + 1)
+    r = rem + pp // qd
+    return b, sx, r, pp - (r - rem) * qd, qd
+
+
+def wstat_ranges(B, H, W):
+    """the launch of tss_conv3x3_wstat_fwd: nrows = B ceil(W / 64) H units, grid = min(nrows, 256), block i owns
+    [i nrows / grid, (i + 1) nrows / grid)"""
+    nrows = B * cdiv(W, WSTAT_TP) * H
+    grid = min(nrows, WSTAT_GRID)
+    return [(i * nrows // grid, (i + 1) * nrows // grid) for i in range(grid)]
+
+
+def wstat_segments(lo, hi, H, W, D):
+    """the while loop of conv3x3_wstat_kernel over one block's range: [(b, strip, r, j0, j1)], rows j0 .. j1 - 1 of one walk each"""
+    segs, u = [], lo
+    while u < hi:
+        b, sx, r, j0, nj = wstat_decode(u, H, W, D)
+        j1 = nj if nj - j0 < hi - u else j0 + (hi - u)
+        segs.append((b, sx, r, j0, j1))
+        u += j1 - j0
+    return segs
+
+
+def wstat_plan(B, H, W, D):
+    """rows per block, the statistics chain (a lane adds 4 pixel fragments per owned row, then row16_sum's 4 levels; waves own their
+    channels alone and blocks meet in f64), the slab rows in use, and what the ranges exercise: the longest run of consecutive rows of
+    one walk (> 4: the four ring slots wrap) and whether some range crosses a class, a strip and an image boundary"""
+    ranges = wstat_ranges(B, H, W)
+    run, cross = 0, set()
+    for lo, hi in ranges:
+        segs = wstat_segments(lo, hi, H, W, D)
+        run = max([run] + [s[4] - s[3] for s in segs])
+        for p, q in zip(segs, segs[1:]):
+            cross.add('image' if p[0] != q[0] else 'strip' if p[1] != q[1] else 'class')
+    rows = max(hi - lo for lo, hi in ranges)
+    return dict(grid=len(ranges), rows=rows, chain=4 * rows + 4, run=run, cross=cross)
+
+
+def stream_plan(P):
+    """tss_conv3x3_stream_fwd + xcd_tiles (csrc/atrous.hip, common.h): 256-pixel tiles dealt to 8 XCD ranges of per = ceil(ntiles / 8),
+    each shared by grid / 8 blocks, grid = persistent_blocks(ntiles, 512).  (statistics chain: a lane adds 4 pixels per tile it owns, then
+    row16_sum's 4 levels, the waves meet in f64; slab rows that own a tile; grid)"""
+    ntiles = cdiv(P, 256)
+    grid = cdiv(min(max(ntiles, 1), STAT_SLABS), 8) * 8
+    slots, per = grid // 8, cdiv(ntiles, 8)
+    owners = [r for r in range(grid) if (r & 7) * per + (r >> 3) < min((r & 7) * per + per, ntiles)]
+    return 4 * cdiv(per, slots) + 4, owners, grid
+
+
+def stream_tiles(row, P):
+    """the tiles block `row` of the stream kernel's grid owns, in its order"""
+    ntiles = cdiv(P, 256)
+    grid = cdiv(min(max(ntiles, 1), STAT_SLABS), 8) * 8
+    per = cdiv(ntiles, 8)
+    return list(range((row & 7) * per + (row >> 3), min((row & 7) * per + per, ntiles), grid // 8))
+
+
+def lean3x3_plan(B, H, W):
+    """launch_lean_nb + the grid-stride tile loop of conv3x3_lean_kernel (csrc/conv3x3.hip): tiles of 64 pixels of one image row,
+    grid = min(ntiles, 512), block i owns tiles i, i + grid, ...; a lane adds 2 pixels per tile, then row16_sum's 4 levels, and the two
+    wm halves meet in f64.  (statistics chain, slab rows that own a tile, grid)"""
+    ntiles = B * H * cdiv(W, 64)
+    grid = min(ntiles, STAT_SLABS)
+    return 2 * cdiv(ntiles, grid) + 4, list(range(grid)), grid
+
+
+def stem_fwd_plan(P):
+    """tss_stem_direct_fwd + stem_fwd_mfma_kernel (csrc/stem.hip): 256-pixel tiles, grid = persistent_blocks(ceil(P / 256), 512), block
+    i owns tiles i, i + grid, ...; a lane adds 4 pixels per tile, then row16_sum's 4 levels, the waves meet in f64"""
+    ntiles = cdiv(P, 256)
+    grid = cdiv(min(max(ntiles, 1), STAT_SLABS), 8) * 8
+    return 4 * cdiv(ntiles, grid) + 4, list(range(min(ntiles, grid))), grid
+
+
+def stem_wgrad_plan(P, mfma):
+    """tss_stem_direct_wgrad: grid = min(ceil(P / 256), 512) blocks = workspace rows, block i owns tiles i, i + grid, ...
+    MFMA form: a wave adds its 64 pixels of every tile to its accumulators (exact products), the 4 waves meet in 3 additions.
+    VALU form (yraw == NULL): a lane adds the 256 pixels of every tile, each product of an f32 g and an f32 tap rounded first (2
+    roundings per pixel).  stem_wgrad_reduce_kernel: a lane adds rows rg, rg + 16, ..., one thread the 16 groups, the total onto dW.
+    (chain, workspace rows)"""
+    ntiles = cdiv(P, 256)
+    grid = min(ntiles, STAT_SLABS)
+    tpb = cdiv(ntiles, grid)
+    return (64 * tpb + 3 if mfma else 2 * 256 * tpb) + cdiv(grid, 16) + 16 + 1, grid
+
+
+def stem_tap_columns(ox, Win, stride, window):
+    """the image column each of the three kx taps of output column ox reads (None: the tap is a 0), as stem_taps (csrc/stem.hip) picks
+    it.  window: the f32 stride-2 path at Win >= 4 -- ONE 4-float load at base = clamp(2 ox - 1, 0, Win - 4), tap kx at position
+    kx + (2 ox - 1 - base) of it (positions <= 0 read element 0, >= 3 element 3), masked where that position is left of the window or the
+    tap's column is >= Win; else one load per tap at the column clamped into [0, Win - 1], masked outside the image"""
+    cols = []
+    if window:
+        assert stride == 2 and Win >= 4
+        ix0 = 2 * ox - 1
+        base = 0 if ix0 < 0 else (Win - 4 if ix0 > Win - 4 else ix0)
+        sh = ix0 - base
+        for kx in range(3):
+            idx = kx + sh
+            pos = 0 if idx <= 0 else min(idx, 3)
+            cols.append(base + pos if (idx >= 0 and ix0 + kx < Win) else None)
+        return cols
+    for kx in range(3):
+        ix = ox * stride + kx - 1
+        cols.append(min(max(ix, 0), Win - 1) if 0 <= ix < Win else None)
+    return cols
+
+
+def full_f32(shape, gen):
+    """f32 values with all 24 bits of the significand in use: the sum of two dyadic values whose exponents differ by 16 (bits e .. e - 7
+    and e - 16 .. e - 23: exact in f32, checked), so rounding one to bf16 moves it"""
+    e = torch.randint(-4, 2, shape, generator=gen).double()
+    parts = []
+    for shift in (0.0, 16.0):
+        k = torch.randint(0, 128, shape, generator=gen).double()
+        s = torch.randint(0, 2, shape, generator=gen).double() * 2 - 1
+        parts.append(s * (1 + k / 128) * torch.pow(2.0, e - shift))
+    return exact_f32(parts[0] + parts[1])

@@ -1,4 +1,5 @@
-"""GPU harness of the exact-operand tests (tests/test_gpu_zoo_exact.py, tests/test_gpu_dw_exact.py, tests/test_gpu_pw_exact.py):
+"""GPU harness of the exact-operand tests (tests/test_gpu_zoo_exact.py, tests/test_gpu_dw_exact.py, tests/test_gpu_pw_exact.py,
+tests/test_gpu_dense_exact.py):
 sentinel-padded device buffers with spare rows, NaN statistics slabs, the dyadic operands of a layer with planted exact zeros, and the
 checks against tests/exact.py's bounds."""
 import contextlib
@@ -67,6 +68,28 @@ def reduce_many(jobs):
     p = lambda t: t if isinstance(t, int) else t.data_ptr()
     N.call('tss_dw_reduce_many', n, (ctypes.c_void_p * n)(*[p(j[0]) for j in jobs]), (ctypes.c_void_p * n)(*[p(j[1]) for j in jobs]),
            (ctypes.c_int * n)(*[j[2] for j in jobs]), (ctypes.c_int * n)(*[j[3] for j in jobs]), N.stream())
+
+
+class GuardedImage:
+    """an NCHW image (f64 values exact in `dtype`) inside a larger device allocation with NaN in front of it and behind it: a tap taken
+    from outside the image poisons the result.  The image starts `front` elements into the allocation (odd: element-aligned only)"""
+    def __init__(self, x, dtype, front=37, back=64):
+        flat = torch.full((front + x.numel() + back,), float('nan'), dtype=dtype)
+        flat[front:front + x.numel()] = x.reshape(-1).to(dtype)
+        assert torch.equal(flat[front:front + x.numel()].double(), x.reshape(-1)), 'image not exact in its dtype'
+        self.t = flat.to(DEV)
+        self.ptr = self.t.data_ptr() + flat.element_size() * front
+
+
+def check_slab_rows(slabs, owners, what):
+    """the slab rows a launch leaves in use against the restated grid: every row written or zeroed, the rows of blocks that own work
+    hold a value and all others exact zeros"""
+    s = slabs.double().cpu()
+    assert not torch.isnan(s).any(), (what, 'a slab row neither written nor zeroed')
+    used = (s != 0).any(1)
+    want = torch.zeros(s.shape[0], dtype=torch.bool)
+    want[list(owners)] = True
+    assert torch.equal(used, want), (what, 'slab rows in use', used.nonzero().flatten().tolist()[-3:], 'restated', len(owners))
 
 
 def nan_slabs(C):

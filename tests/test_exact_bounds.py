@@ -617,3 +617,298 @@ def test_a_dropout_keep_byte_of_the_neighbouring_channel_group_fails():
     assert X.conv_excess(ok, ref * dinv, S * dinv, K) <= 0
     bad = X.rne_bf16((_pw_gemm32(a * keep(1), w) * dinv).double())
     assert X.conv_excess(bad, ref * dinv, S * dinv, K) > 0
+
+
+# ---------------------------------------------------------------------------------------------------------- dense 3x3 family and stem
+# f32 emulation of csrc/wstat.hip, atrous.hip, conv3x3.hip, the 9-tap paths of convgemm.hip / wgrad.hip and csrc/stem.hip in their planners'
+# order: operands a / g already rounded to bf16, every product exact, one f32 addition per 32-channel MFMA k-step and tap; statistics per
+# block, wave and lane as the epilogues add them; the weight gradient stage by stage and split by split.  Defects go into the emulation.
+@pytest.mark.parametrize('B,H,W,D', [(1, 7, 5, 1), (2, 11, 70, 3), (3, 20, 129, 18), (2, 19, 64, 18), (1, 6, 65, 6), (2, 7, 200, 6), (3, 100, 321, 7)])
+def test_weight_stationary_walk_visits_every_row_once_and_its_ranges_partition_it(B, H, W, D):
+    nstrip = X.cdiv(W, 64)
+    nrows = B * nstrip * H
+    seen = []
+    for u in range(nrows):
+        b, sx, r, j, nj = X.wstat_decode(u, H, W, D)
+        assert 0 <= r < D and 0 <= j < nj and nj == len(range(r, H, D))
+        seen.append((b, sx, r + j * D))
+    assert sorted(seen) == [(b, sx, y) for b in range(B) for sx in range(nstrip) for y in range(H)]
+    ranges = X.wstat_ranges(B, H, W)
+    assert ranges[0][0] == 0 and ranges[-1][1] == nrows and all(p[1] == q[0] for p, q in zip(ranges, ranges[1:]))
+    assert len(ranges) == min(nrows, 256) and max(hi - lo for lo, hi in ranges) == X.cdiv(nrows, len(ranges)) == X.wstat_plan(B, H, W, D)['rows']
+    walked = []
+    for lo, hi in ranges:                                          # the kernel's while loop walks exactly its range, row by row
+        for b, sx, r, j0, j1 in X.wstat_segments(lo, hi, H, W, D):
+            assert 0 <= j0 < j1
+            walked += [(b, sx, r + j * D) for j in range(j0, j1)]
+    assert walked == seen
+
+
+def _dense_case(seed, B=2, C=64, N=16, H=9, W=70, Ho=None, Wo=None):
+    g = _gen(seed)
+    a = X.rne_bf16(X.dyadic((B, C, H, W), g, zero_frac=0.05))
+    w = X.dyadic((N, C, 3, 3), g, emin=-6, emax=-2)
+    gr = X.rne_bf16(X.dyadic((B, N, Ho or H, Wo or W), g))
+    return a, w, gr
+
+
+def _dense_fwd32(a, w, D, defect=None):
+    """f32 sum over the nine taps and the 32-channel k-steps of each.  Defects, each at ONE pixel: 'ring' -- the ring slot of row y + D
+    still holds row y - 2 D (refilled one row late); 'wrap' -- the left tap at x = 0 reads D pixels back in the flat row-major image, i.e.
+    the end of the previous image row"""
+    B, C, H, W = a.shape
+    a32, w32 = a.float(), w.float()
+    out = torch.zeros(B, w.shape[0], H, W)
+    b, y = B - 1, 2 * D
+    for ky in range(3):
+        for kx in range(3):
+            src = _dw_tap(a32, ky, kx, 1, D, H, W).clone()
+            if defect == 'ring' and ky == 2:
+                x = W // 2
+                xs = x + (kx - 1) * D
+                src[b, :, y, x] = a32[b, :, y - 2 * D, xs] if 0 <= xs < W else 0.0
+            if defect == 'wrap' and kx == 0:
+                yy = y + (ky - 1) * D
+                if 0 < yy < H:
+                    src[b, :, y, 0] = a32[b, :, yy - 1, W - D]
+            for k0 in range(0, C, 32):
+                out = out + torch.einsum('bchw,nc->bnhw', src[:, k0:k0 + 32], w32[:, k0:k0 + 32, ky, kx])
+    return out
+
+
+def _frag(p0, n, limit):
+    """pixel indices of a 16-lane fragment starting at p0 (lanes past `limit` or past n lanes: -1)"""
+    i = torch.arange(16) + p0
+    return torch.where((torch.arange(16) < n) & (i < limit), i, torch.full_like(i, -1))
+
+
+def _dense_blocks(kind, B, H, W, D=1):
+    """[(slab row, [per f64-meeting wave group: [16-lane fragments in the order a lane adds them]])] of a launch over the [B][H][W] outputs"""
+    P = B * H * W
+    blocks = []
+    if kind == 'wstat':
+        for i, (lo, hi) in enumerate(X.wstat_ranges(B, H, W)):
+            frags = []
+            for b, sx, r, j0, j1 in X.wstat_segments(lo, hi, H, W, D):
+                for j in range(j0, j1):
+                    row0 = (b * H + r + j * D) * W
+                    frags += [_frag(row0 + sx * 64 + m * 16, W - sx * 64 - m * 16, P) for m in range(4)]
+            blocks.append((i, [frags]))
+    elif kind in ('stream', 'stem'):
+        ntiles = X.cdiv(P, 256)
+        plan = X.stream_plan(P) if kind == 'stream' else X.stem_fwd_plan(P)
+        for i in range(plan[2]):
+            tiles = X.stream_tiles(i, P) if kind == 'stream' else list(range(i, ntiles, plan[2]))
+            blocks.append((i, [[_frag(t * 256 + wv * 64 + m * 16, 16, P) for t in tiles for m in range(4)] for wv in range(4)]))
+    else:
+        tpr = X.cdiv(W, 64)
+        ntiles, grid = B * H * tpr, X.lean3x3_plan(B, H, W)[2]
+        for i in range(grid):
+            groups = []
+            for wm in range(2):
+                frags = []
+                for t in range(i, ntiles, grid):
+                    by, tx = divmod(t, tpr)
+                    x0 = tx * 64 + wm * 32
+                    frags += [_frag(by * W + x0 + m * 16, W - x0 - m * 16, P) for m in range(2)]
+                groups.append(frags)
+            blocks.append((i, groups))
+    return blocks
+
+
+def _slabs_from_blocks(out_rows, fac_rows, blocks, stale=None):
+    """slab rows of the launch: a lane adds its fragments' values in f32, 16 lanes meet in row16_sum's 4-level tree, the groups of a block
+    and the rows meet in f64; rows no block owns are zeroed -- but `stale`, a row beyond the grid a defective kernel leaves as it was"""
+    P, C = out_rows.shape
+    terms = torch.zeros(P + 1, 2 * C)
+    terms[:P] = torch.cat([out_rows.float(), out_rows.float() * fac_rows.float()], 1)
+    slabs = torch.zeros(512, 2 * C, dtype=torch.float64)
+    longest = 0
+    for row, groups in blocks:
+        for frags in groups:
+            lanes = torch.zeros(16, 2 * C)
+            longest = max(longest, len(frags))
+            for f in frags:
+                lanes = lanes + terms[f]                        # (index -1 is the zero row P)
+            for half in (8, 4, 2, 1):
+                lanes = lanes[:half] + lanes[half:2 * half]
+            slabs[row] += lanes[0].double()
+    if stale is not None:
+        slabs[stale] = slabs[0] + 1.0
+    return slabs, longest + 4
+
+
+@pytest.mark.parametrize('kind,B,H,W,D,C', [('wstat', 2, 40, 130, 3, 32), ('wstat', 2, 9, 70, 1, 32), ('stream', 3, 11, 37, 2, 32), ('stream', 2, 257, 257, 1, 32),
+                                            ('lean', 2, 3, 65, 1, 64), ('lean', 2, 130, 65, 2, 32)])
+def test_f32_emulation_of_the_dense_3x3_layer_meets_the_bounds_in_each_planners_order(kind, B, H, W, D, C):
+    N = 16 if H * W > 9000 else 48
+    a, w, _ = _dense_case(B + H + W, B=B, C=C, N=N, H=H, W=W)
+    ref, S = X.conv_ref(a, w, padding=D, dilation=D)
+    out = X.rne_bf16(_dense_fwd32(a, w, D).double())
+    assert X.conv_excess(out, ref, S, 9 * C) <= 0
+    rows = X.nchw_to_rows(out)
+    blocks = _dense_blocks(kind, B, H, W, D)
+    slabs, chain = _slabs_from_blocks(rows, rows, blocks)
+    want, owners = {'wstat': lambda: (X.wstat_plan(B, H, W, D)['chain'], range(X.wstat_plan(B, H, W, D)['grid'])),
+                    'stream': lambda: X.stream_plan(B * H * W)[:2], 'lean': lambda: X.lean3x3_plan(B, H, W)[:2]}[kind]()
+    assert chain == want and [r for r, _ in blocks if (slabs[r] != 0).any()] == list(owners)
+    assert X.stats_excess(slabs.sum(0), torch.cat([rows, rows * rows], 1), chain) <= 0
+
+
+@pytest.mark.parametrize('defect', ['ring', 'wrap'])
+def test_one_wrong_input_row_or_column_at_one_pixel_of_the_dense_layer_fails(defect):
+    D = 2
+    a, w, _ = _dense_case(50, H=9, W=70)
+    ref, S = X.conv_ref(a, w, padding=D, dilation=D)
+    out = X.rne_bf16(_dense_fwd32(a, w, D, defect=defect).double())
+    ex = X.conv_excess(out, ref, S, 9 * a.shape[1])
+    print(defect, 'excess over the bound', ex)
+    assert ex > 0
+    good = X.rne_bf16(_dense_fwd32(a, w, D).double())
+    assert (out != good).any((1,)).sum() == 1                       # one pixel
+
+
+def test_a_statistics_row_of_a_block_beyond_the_grid_not_zeroed_fails():
+    B, H, W, D = 2, 9, 70, 1
+    a, w, _ = _dense_case(51, H=H, W=W)
+    rows = X.nchw_to_rows(X.rne_bf16(_dense_fwd32(a, w, D).double()))
+    blocks = _dense_blocks('wstat', B, H, W, D)
+    assert len(blocks) == 36
+    slabs, chain = _slabs_from_blocks(rows, rows, blocks, stale=36 + 3 * 36)      # a row the block-0 loop `rr += gridDim.x` must clear
+    assert X.stats_excess(slabs.sum(0), torch.cat([rows, rows * rows], 1), chain) > 0
+
+
+def _dense_wgrad32(a, gr, stride, D, mirror=False):
+    """wgrad_kernel + its atomics (csrc/wgrad.hip): per tap and split, stages of 64 pixels in two 32-pixel k-steps, then one f32 addition
+    per split onto dW [N][C][3][3]; mirror: the tap's result lands at the mirrored kx"""
+    B, C, H, W = a.shape
+    N, Ho, Wo = gr.shape[1:]
+    P = B * Ho * Wo
+    tiles = X.cdiv(N, 128) * X.cdiv(C, 128) * 9
+    nstage = X.cdiv(P, 64)
+    ns = max(1, min(max(1, 1024 // tiles), X.cdiv(nstage, 8)))
+    per = X.cdiv(nstage, ns)
+    gp = X.nchw_to_rows(gr).float()
+    dw = torch.zeros(N, C, 3, 3)
+    for ky in range(3):
+        for kx in range(3):
+            src = X.nchw_to_rows(_dw_tap(a.float(), ky, kx, stride, D, Ho, Wo)).float()
+            for s in range(ns):
+                acc = torch.zeros(N, C)
+                for p0 in range(s * per * 64, min((s + 1) * per * 64, P), 32):
+                    p1 = min(p0 + 32, P)
+                    acc = acc + gp[p0:p1].t() @ src[p0:p1]
+                dw[:, :, ky, 2 - kx if mirror else kx] += acc
+    return dw
+
+
+@pytest.mark.parametrize('stride,D', [(1, 1), (2, 3)])
+def test_nine_tap_weight_gradient_meets_the_bound_and_a_mirrored_tap_fails(stride, D):
+    B, C, N, H, W = 2, 40, 24, 33, 41
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    a, _, gr = _dense_case(60 + D, B=B, C=C, N=N, H=H, W=W, Ho=Ho, Wo=Wo)
+    ref, S = X.conv_weight_ref(a, (N, C, 3, 3), gr, stride=stride, padding=D, dilation=D)
+    chain = X.generic_wgrad_chain(B * Ho * Wo, C, N, 9)
+    assert X.wgrad_excess(_dense_wgrad32(a, gr, stride, D).double(), ref, S, chain) <= 0
+    assert X.wgrad_excess(_dense_wgrad32(a, gr, stride, D, mirror=True).double(), ref, S, chain) > 0
+
+
+def test_dyadic_transforms_are_exact_in_f32_in_the_dense_kernels_orders():
+    """the kadd folds of conv3x3_lean_kernel (forward: x k0 + (c2 - c1 c0); backward: (e k0 + kadd) + y k1, kadd = -(c0 c2) - c1 c3),
+    wgrad_kernel (x cs + (cb - cm cs); ca e + (cb y + cc)), stem_wgrad_mfma_kernel (the same), im2col3x3_kernel ((x - mu) sc + be) and
+    the masks' (x - mean) scale + bias > 0, with ReLU alone (no scale) as the identity transform"""
+    g = _gen(12)
+    n = 1 << 18
+    f = lambda t: t.float()
+    x, mean, bias, scale = X.dyadic((n,), g), X.dyadic((n,), g), X.dyadic((n,), g), X.pow2((n,), g, 0.5, 4)
+    ref = (x - mean) * scale + bias
+    for got in (f(x) * f(scale) + (f(bias) - f(mean) * f(scale)), (f(x) - f(mean)) * f(scale) + f(bias)):
+        assert torch.equal(got.double(), ref)
+    assert torch.equal((f(x) * 1.0 + (0.0 - 0.0 * 1.0)).double(), x)
+    e, y, gce, gmu = X.dyadic((n,), g), X.dyadic((n,), g), X.dyadic((n,), g), X.dyadic((n,), g)
+    ga, gb = X.pow2((n,), g, 0.25, 2), X.pow2((n,), g, 2.0 ** -6, 2.0 ** -3)
+    ref = ga * (e - gce) + gb * (y - gmu)
+    kadd = -(f(ga) * f(gce)) - f(gb) * f(gmu)
+    for got in ((f(e) * f(ga) + kadd) + f(y) * f(gb), f(ga) * f(e) + (f(gb) * f(y) + kadd), f(ga) * (f(e) - f(gce)) + f(gb) * (f(y) - f(gmu))):
+        assert torch.equal(got.double(), ref)
+    # the 24-bit stem image is exact in f32 and its bf16 rounding moves it
+    v = X.full_f32((4096,), g)
+    assert (X.rne_bf16(v) != v).float().mean() > 0.9
+
+
+def _stem_patches(x, stride, window, defect=False):
+    """[P][Cin 9] taps of every output pixel as stem_taps picks them (X.stem_tap_columns); defect: the right-edge tap at ix == Win is not
+    masked and reads the clamped element"""
+    B, Cin, Hin, Win = x.shape
+    Ho, Wo = (Hin - 1) // stride + 1, (Win - 1) // stride + 1
+    out = torch.zeros(B, Ho, Wo, Cin, 3, 3, dtype=x.dtype)
+    for ox in range(Wo):
+        cols = X.stem_tap_columns(ox, Win, stride, window)
+        for kx, col in enumerate(cols):
+            if col is None and defect and ox * stride + kx - 1 == Win:
+                col = Win - 1
+            if col is None:
+                continue
+            for oy in range(Ho):
+                for ky in range(3):
+                    iy = oy * stride + ky - 1
+                    if 0 <= iy < Hin:
+                        out[:, oy, ox, :, ky, kx] = x[:, :, iy, col]
+    return out.reshape(B * Ho * Wo, Cin * 9)
+
+
+@pytest.mark.parametrize('stride', [2, 1])
+def test_stem_window_arithmetic_picks_the_padded_taps_at_every_width(stride):
+    for Win in range(1, 10):
+        x = X.dyadic((2, 3, 4, Win), _gen(Win))
+        want = torch.nn.functional.unfold(x, 3, padding=1, stride=stride).permute(0, 2, 1).reshape(-1, 27)
+        for window in ([False, True] if (stride == 2 and Win >= 4) else [False]):
+            assert torch.equal(_stem_patches(x, stride, window), want), (Win, stride, window)
+
+
+def test_f32_emulation_of_the_stem_meets_the_bounds_and_an_unmasked_right_edge_tap_fails():
+    B, Hin, Win, N = 2, 9, 35, 32                                   # odd width: the last output column's right tap is at ix == Win
+    g = _gen(70)
+    x = X.full_f32((B, 3, Hin, Win), g)
+    xb = X.rne_bf16(x)                                              # the MFMA forms pack the taps as bf16
+    w = X.dyadic((N, 3, 3, 3), g, emin=-6, emax=-2)
+    ref, S = X.conv_ref(xb, w, stride=2, padding=1)
+    P = ref.numel() // N
+    for defect in (False, True):
+        pt = _stem_patches(xb, 2, True, defect=defect).float()
+        out = X.rne_bf16((pt @ w.reshape(N, 27).float().t()).double())
+        ex = X.conv_excess(out, X.nchw_to_rows(ref), X.nchw_to_rows(S), 27)
+        assert (ex > 0) == defect, (defect, ex)
+    # statistics and weight gradient in the planners' order (stem_fwd_plan / stem_wgrad_plan: one tile per block here, 360 pixels = 2 tiles)
+    Ho, Wo = ref.shape[2:]
+    slabs, chain = _slabs_from_blocks(out, out, _dense_blocks('stem', 1, 1, P))
+    assert chain == X.stem_fwd_plan(P)[0] and X.stats_excess(slabs.sum(0), torch.cat([out, out * out], 1), chain) <= 0
+    gr = X.rne_bf16(X.dyadic((B, N, Ho, Wo), g))
+    rw, Sw = X.conv_weight_ref(xb, (N, 3, 3, 3), gr, stride=2, padding=1)
+    pt, gp = _stem_patches(xb, 2, True).float(), X.nchw_to_rows(gr).float()
+    chain_w, rows = X.stem_wgrad_plan(P, True)
+    ws = []
+    for i in range(rows):
+        waves = [torch.zeros(N, 27) for _ in range(4)]
+        for t in range(i, X.cdiv(P, 256), rows):
+            for wv in range(4):
+                for p0 in range(t * 256 + wv * 64, min(t * 256 + wv * 64 + 64, P), 32):
+                    p1 = min(p0 + 32, P)
+                    waves[wv] = waves[wv] + gp[p0:p1].t() @ pt[p0:p1]
+        ws.append(((waves[0] + waves[1]) + waves[2]) + waves[3])
+    groups = [torch.zeros(N, 27) for _ in range(16)]
+    for r, part in enumerate(ws):
+        groups[r % 16] = groups[r % 16] + part
+    tot = torch.zeros(N, 27)
+    for gsum in groups:
+        tot = tot + gsum
+    dw = torch.zeros(N, 27) + tot
+    assert X.wgrad_excess(dw.double().reshape(rw.shape), rw, Sw, chain_w) <= 0
+    # the VALU form keeps the f32 image: unrounded reference, every product a rounding, 256 pixels per lane and tile
+    rwf, Swf = X.conv_weight_ref(x, (N, 3, 3, 3), gr, stride=2, padding=1)
+    ptf = _stem_patches(x, 2, True).float()
+    acc = torch.zeros(N, 27)
+    for p in range(P):
+        acc = acc + gp[p].unsqueeze(1) * ptf[p].unsqueeze(0)
+    chain_v, _ = X.stem_wgrad_plan(512, False)                      # one lane's chain over two tiles, as this single accumulator adds them
+    assert X.wgrad_excess(acc.double().reshape(rwf.shape), rwf, Swf, chain_v) <= 0
