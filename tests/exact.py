@@ -1,5 +1,6 @@
 """Exact-operand f64 references for the bf16 convolution kernels (tests/test_exact_bounds.py, tests/test_gpu_zoo_exact.py,
-tests/test_gpu_dw_exact.py, tests/test_gpu_pw_exact.py, tests/test_gpu_dense_exact.py).
+tests/test_gpu_dw_exact.py, tests/test_gpu_pw_exact.py, tests/test_gpu_dense_exact.py) and for the resample, pyramid and gate kernels
+(tests/test_gpu_resample_exact.py: the last section of this file, with its own tiers).
 
 Every operand is a DYADIC bf16 value, +-(1 + k/128) * 2^e with e in [-4, 2): 8 significant bits.  BatchNorm scales are powers of two in
 [1/2, 4], the backward pair (ga, gb) powers of two in [1/4, 2] and [2^-6, 2^-3].  Then the on-load transforms of the kernels
@@ -24,6 +25,7 @@ the chain helpers at the end of this file restate each kernel's planner.  tss_up
 materialised upsampled tensor would have been: bilinear_ref / upsampled_operand."""
 import math
 
+import numpy as np
 import torch
 
 U32 = 2.0 ** -24
@@ -736,3 +738,611 @@ def full_f32(shape, gen):
         s = torch.randint(0, 2, shape, generator=gen).double() * 2 - 1
         parts.append(s * (1 + k / 128) * torch.pow(2.0, e - shift))
     return exact_f32(parts[0] + parts[1])
+
+
+# ---------------------------------------------------------------------------------------------------------- resample, pyramid, gate
+# csrc/resample.hip and gate.hip; tests/test_gpu_resample_exact.py.  None of these kernels feeds the matrix unit: operands are loaded
+# into f32, blended / gathered / averaged in f32 and rounded once to the output dtype.  Three tiers (the GPU file names the tier of a case):
+#   1  bit for bit.  The size pair is exact_resize on both axes: every tap weight is a multiple of 2^-k.  With operands that are
+#      multiples of 2^lsb, every product and every partial sum of a blend or a gather is a multiple of 2^(lsb - ky - kx) and, in ANY
+#      order and with or without FMA contraction, at most sum|terms| in magnitude: if max sum|terms| < 2^(24 + lsb - ky - kx) all of
+#      them are f32 numbers and nothing rounds (exact_budget).  The f32 output equals the f64 reference, the bf16 output its rne_bf16.
+#   2  derived bound on the restated taps.  Indices and f32 weights from ac_taps_f32 (tap_matrix_f32), blended / gathered in f64;
+#      the kernel's roundings are counted in u = 2^-24 against sum|terms|, + 2^-8 |ref| for a bf16 output (resample_excess).  The same
+#      outputs are also held to bilinear_matrix within bilinear_f32_slack (+ the same bound): the only check that would catch the
+#      restated taps and the kernel being wrong together.
+#   3  near-tie allowance, tss_ppm_arms_bwd in training mode only: arms_bwd_ref at the end of this file.
+F32 = np.float32
+
+
+def dyadic_q(shape, gen, bits, emin, emax, zero_frac=0.0):
+    """dyadic with `bits` significant bits: +-(1 + k / 2^(bits-1)) 2^e, k in [0, 2^(bits-1)), e in [emin, emax): multiples of
+    2^(emin - bits + 1), below 2^emax in magnitude.  The narrow operands of the tier-1 gathers, whose window sums have to fit 24 bits"""
+    m = 1 << (bits - 1)
+    k = torch.randint(0, m, shape, generator=gen).double()
+    e = torch.randint(emin, emax, shape, generator=gen).double()
+    s = torch.randint(0, 2, shape, generator=gen).double() * 2 - 1
+    v = s * (1 + k / m) * torch.pow(2.0, e)
+    if zero_frac > 0:
+        v = torch.where(torch.rand(shape, generator=gen, dtype=torch.float64) < zero_frac, torch.zeros_like(v), v)
+    return v
+
+
+def lsb_exp(v):
+    """largest e such that every element of v (f64) is a multiple of 2^e"""
+    nz = v[v != 0]
+    e = 0
+    while not torch.equal(torch.round(nz * 2.0 ** -e), nz * 2.0 ** -e):
+        e -= 1
+    return e
+
+
+def ac_scale_f32(n_in, n_out):
+    return F32(n_in - 1) / F32(n_out - 1) if n_out > 1 else F32(0.0)
+
+
+def exact_resize(n_in, n_out):
+    """tier-1 premise of one axis: n_out - 1 = 2^k >= n_in - 1 (or one of the extents is 1).  Then ac_scale = (n_in - 1) 2^-k is exact
+    in f32, src = scale dst = (n_in - 1) dst 2^-k has < 24 bits, i0 = (int)src = floor of the exact coordinate, l1 = src - i0 is a
+    multiple of 2^-k in [0, 1) and l0 = 1 - l1 is exact.  Wider than dyadic_resize (which asks for a power-of-two RATIO): 6 -> 17,
+    4 -> 33 and 7 -> 33 are exact although 16 / 5, 32 / 3 and 32 / 6 are not integers.  Returns k or None;
+    ac_taps_f32 is compared with bilinear_matrix on every such pair in tests/test_exact_bounds.py"""
+    if n_in == 1 or n_out == 1 or n_in == n_out:      # scale 0 (every weight 1 at index 0) or exactly 1 (l1 = 0)
+        return 0
+    m = n_out - 1
+    if m & (m - 1) == 0 and n_in - 1 <= m:
+        return m.bit_length() - 1
+    if dyadic_resize(n_in, n_out):                      # the ratio itself is 2^k: scale = 2^-k whatever n_out - 1 is
+        return (m // (n_in - 1)).bit_length() - 1
+    return None
+
+
+def tap_matrix_f32(n_in, n_out, clamp=True, fused=True):
+    """[n_out][n_in] f64 matrix of the restated f32 taps (ac_taps_f32): row d holds l0 at i0 and l1 at i1, as f32 values.
+    clamp=False is the injected defect of tests/test_exact_bounds.py: i1 = i0 + 1 unclamped (reads the next row / image)"""
+    i0, i1, l0, l1 = ac_taps_np(n_in, n_out, fused)
+    M = np.zeros((n_out, n_in + (0 if clamp else 1)))
+    d = np.arange(n_out)
+    np.add.at(M, (d, i0), l0.astype(np.float64))
+    np.add.at(M, (d, i1 if clamp else i0 + 1), l1.astype(np.float64))
+    return torch.from_numpy(M)
+
+
+def ac_taps_np(n_in, n_out, fused=True):
+    """ac_tap of csrc/common.h for all destinations at once (numpy f32 arrays i0, i1, l0, l1).  fused: l1 = fl(scale dst - i0) in ONE
+    rounding, which is what hipcc's default -ffp-contract=fast makes of `src - (float)i0` with src = scale * dst (a v_fma_f32 in the
+    disassembly of every kernel of resample.hip; i0 = (int)src still comes from the ROUNDED product).  The f64 product of a 24-bit
+    scale and an integer below 2^29 is exact, so rounding it once to f32 restates the FMA bit for bit.  fused=False is ac_taps_f32,
+    l1 = fl(fl(scale dst) - i0); the two differ by the rounding of src, <= u src <= u (n_in - 1) (tap_slack), and not at all on an
+    exact_resize pair, where src is exact.  Both are compared with ac_taps_f32 / bilinear_matrix in tests/test_exact_bounds.py"""
+    scale = ac_scale_f32(n_in, n_out)
+    dst = np.arange(n_out)
+    src = scale * dst.astype(F32)
+    i0 = np.minimum(src.astype(np.int64), n_in - 1)
+    i1 = i0 + (i0 < n_in - 1)
+    l1 = (np.float64(scale) * dst - i0).astype(F32) if fused else src - i0.astype(F32)
+    return i0, i1, F32(1.0) - l1, l1
+
+
+def tap_support(n_in, n_out):
+    """[n_out][n_in] 0/1: the source indices an output reads (i0 and i1, whatever their weights)"""
+    i0, i1, _, _ = ac_taps_np(n_in, n_out)
+    M = np.zeros((n_out, n_in))
+    M[np.arange(n_out), i0] = 1.0
+    M[np.arange(n_out), i1] = 1.0
+    return torch.from_numpy(M)
+
+
+def tap_slack(x, Ho, Wo):
+    """what a forward blend of x [B][C][H][W] may differ by when the compiler does NOT contract l1 (or contracts where the restated taps do
+    not): each weight of an axis moves by <= u (n_in - 1), and the blend by that times the sum of the |values| it reads (the other
+    axis' weights sum to <= 1 + 2 u, covered by the factor 1.001)"""
+    T = torch.einsum('oh,bchw,pw->bcop', tap_support(x.shape[2], Ho), x.abs(), tap_support(x.shape[3], Wo))
+    return 1.001 * U32 * (x.shape[2] - 1 + x.shape[3] - 1) * T
+
+
+def tap_slack_bwd(g, Hin, Win=None):
+    """the same for the transposed gather of g [B][C][Ho][Wo] onto [Hin][Win]; Win=None: the row pass alone, onto [Hin][Wo]"""
+    sy = tap_support(Hin, g.shape[2])
+    if Win is None:
+        return 1.001 * U32 * (Hin - 1) * torch.einsum('oh,bcop->bchp', sy, g.abs())
+    T = torch.einsum('oh,bcop,pw->bchw', sy, g.abs(), tap_support(Win, g.shape[3]))
+    return 1.001 * U32 * (Hin - 1 + Win - 1) * T
+
+
+def ac_windows_np(n_in, n_out):
+    """ac_window of csrc/common.h in f32 for every source index at once: the conservative ranges [lo, hi] of outputs whose taps can
+    include source index i"""
+    scale = ac_scale_f32(n_in, n_out)
+    if scale <= 0:
+        return np.zeros(n_in, dtype=np.int64), np.full(n_in, n_out - 1, dtype=np.int64)
+    i = np.arange(n_in)
+    lo = np.floor((i - 1).astype(F32) / scale).astype(np.int64) - 1
+    hi = np.ceil((i + 1).astype(F32) / scale).astype(np.int64) + 1
+    return np.maximum(lo, 0), np.minimum(hi, n_out - 1)
+
+
+def ac_window_f32(n_in, n_out, i):
+    lo, hi = ac_windows_np(n_in, n_out)
+    return int(lo[i]), int(hi[i])
+
+
+def window_len(n_in, n_out):
+    """longest restated window over the source indices: the n of gamma_n of a backward gather along this axis"""
+    lo, hi = ac_windows_np(n_in, n_out)
+    return int((hi - lo).max()) + 1
+
+
+def window_misses(n_in, n_out, short=0):
+    """taps with a nonzero f32 weight whose output lies outside the restated window of their source index (hi - short: the defect)"""
+    i0, i1, l0, l1 = ac_taps_np(n_in, n_out)
+    lo, hi = ac_windows_np(n_in, n_out)
+    hi = hi - short
+    d = np.arange(n_out)
+    return int(((l0 != 0) & ((d < lo[i0]) | (d > hi[i0]))).sum() + ((l1 != 0) & ((d < lo[i1]) | (d > hi[i1]))).sum())
+
+
+def windowed(M, n_in, n_out, short=0):
+    """the tap matrix with everything outside the restated windows zeroed: what a gather over ac_window_f32 sums"""
+    Mw = torch.zeros_like(M)
+    for i in range(n_in):
+        lo, hi = ac_window_f32(n_in, n_out, i)
+        Mw[lo:hi + 1 - short, i] = M[lo:hi + 1 - short, i]
+    return Mw
+
+
+def resize_ref(x, Ho, Wo, My=None, Mx=None):
+    """(reference, sum|terms|) of the align_corners=True resize of x [B][C][H][W] on the restated f32 taps, in f64"""
+    My = tap_matrix_f32(x.shape[2], Ho) if My is None else My
+    Mx = tap_matrix_f32(x.shape[3], Wo) if Mx is None else Mx
+    return torch.einsum('oh,bchw,pw->bcop', My, x, Mx), torch.einsum('oh,bchw,pw->bcop', My, x.abs(), Mx)
+
+
+def resize_bwd_ref(g, Hin, Win):
+    """(tmp reference, its sum|terms|, dx reference, its sum|terms|) of the two-pass backward of a resize to g's [B][C][Ho][Wo]: the
+    row pass tmp [B][C][Hin][Wo] = My^T g, then dx [B][C][Hin][Win] = tmp Mx.  The restated windows hold every nonzero weight
+    (window_misses == 0, asserted on the CPU), so the windowed gather equals the full transposed product"""
+    My, Mx = tap_matrix_f32(Hin, g.shape[2]), tap_matrix_f32(Win, g.shape[3])
+    t, ta = torch.einsum('oh,bcop->bchp', My, g), torch.einsum('oh,bcop->bchp', My, g.abs())
+    return t, ta, torch.einsum('bchp,pw->bchw', t, Mx), torch.einsum('bchp,pw->bchw', ta, Mx)
+
+
+def resize_matrix_excess(out, x, Ho, Wo, bf16):
+    """the forward outputs against bilinear_matrix (f64 coordinates) within bilinear_f32_slack, which already holds the blend's own
+    roundings; a bf16 output adds 2^-8 (|ref| + slack)"""
+    My, Mx = bilinear_matrix(x.shape[2], Ho), bilinear_matrix(x.shape[3], Wo)
+    ref = torch.einsum('oh,bchw,pw->bcop', My, x, Mx)
+    slack = bilinear_f32_slack(x, Ho, Wo)
+    bound = slack + (2.0 ** -8 * (ref.abs() + slack) if bf16 else 0.0)
+    return ((out - ref).abs() - bound).max().item()
+
+
+def resize_bwd_matrix_excess(out, g, Hin, Win, n, bf16, gs=1.0):
+    """the backward outputs dx [B][C][Hin][Win] against the transposed bilinear_matrix.  The weight with which output o reads source i
+    is the hat function max(0, 1 - |src_o - i|) of the coordinate: 1-Lipschitz, so the f32 weight is within |d src| + u of the f64
+    one, |d src| <= 2^-22 (n_in - 1) as in bilinear_f32_slack, and a product of two weights (each <= 1) within the sum of the two
+    (+ their product, covered by the factor 2 already in 2^-22).  Summed over the outputs where either weight is nonzero; plus the
+    gather's own bound resample_excess(n) on the f64 weights' sum|terms|"""
+    My, Mx = bilinear_matrix(Hin, g.shape[2]), bilinear_matrix(Win, g.shape[3])
+    sy = ((My != 0) | (tap_matrix_f32(Hin, g.shape[2]) != 0)).double()
+    sx = ((Mx != 0) | (tap_matrix_f32(Win, g.shape[3]) != 0)).double()
+    ref = gs * torch.einsum('oh,bcop,pw->bchw', My, g, Mx)
+    S = gs * torch.einsum('oh,bcop,pw->bchw', My, g.abs(), Mx)
+    slack = gs * (2.0 ** -22 * (Hin - 1 + Win - 1) + 4 * U32) * torch.einsum('oh,bcop,pw->bchw', sy, g.abs(), sx)
+    bound = slack + 2.0 ** -23 * (n + (1 if bf16 else 0)) * (S + slack) + (2.0 ** -8 * (ref.abs() + slack) if bf16 else 0.0)
+    return ((out - ref).abs() - bound).max().item()
+
+
+BLEND_N = 6     # roundings a value goes through in a 2 x 2 blend: two products and two sums (an FMA fewer) + the weight's l0 = fl(1 - l1)
+
+
+def resample_excess(out, ref, S, n, bf16, slack=0.0):
+    """|out - ref| <= gamma_n S (<= 2^-23 n S) + slack + 2^-8 (|ref| + gamma_n S + slack) for a bf16 output.  n = BLEND_N for a forward
+    blend; a gather over a window of L outputs rounds each product once and each partial sum once: n = L + 1 per pass, and the column
+    pass of a two-pass backward inherits the row pass's: n = Ly + Lx + 2.  2^-8 gamma_n S is covered by counting one more rounding
+    (n + 1).  slack: tap_slack / tap_slack_bwd, the contraction of l1 the compiler is free to make or not.
+    Returns max(|out - ref| - bound)"""
+    bound = 2.0 ** -23 * (n + (1 if bf16 else 0)) * S + slack * (1 + 2.0 ** -8) + (2.0 ** -8 * ref.abs() if bf16 else 0.0)
+    return ((out - ref).abs() - bound).max().item()
+
+
+def exact_budget(S, lsb, ky=0, kx=0):
+    """tier-1 premise: every partial sum (<= max S = sum|terms|) of multiples of 2^(lsb - ky - kx) stays below 2^24 of them"""
+    return float(S.max()) < 2.0 ** (24 + lsb - ky - kx)
+
+
+def out_bits_ref(ref, bf16):
+    """the bits a tier-1 kernel must store: the exact value (checked to be an f32 number), rounded to bf16 once for a bf16 output"""
+    return rne_bf16(ref) if bf16 else exact_f32(ref)
+
+
+# --- logits head (upsample_head_fwd_kernel<T, 3 | 4>, upsample_head_fwd_generic_kernel)
+def head_instance(w, W, ldl, N, aligned=True):
+    """the dispatch of tss_upsample_head_fwd: 'three' / 'four' source columns per lane of 8 outputs, or 'generic'"""
+    sx = F32(w - 1) / F32(W - 1) if W > 1 else F32(0.0)
+    fast = F32(7.0) * sx < F32(1.99) and ldl % 8 == 0 and ldl >= cdiv(N, 8) * 8 and aligned
+    if not fast:
+        return 'generic'
+    return 'three' if F32(7.0) * sx < F32(0.99) else 'four'
+
+
+def head_columns_hold(w, W, ncols):
+    """every lane's 8 outputs read source columns c0 .. c0 + ncols - 1 only, c0 = i0 of the lane's first output (an i1 beyond them
+    with the weight l1 == 0 multiplies a finite column by 0: harmless)"""
+    i0, i1, _, l1 = (v.reshape(W // 8, 8) for v in ac_taps_np(w, W))
+    c0 = i0[:, :1]
+    return bool(((i0 - c0 >= 0) & (i0 - c0 < ncols) & ((i1 - c0 < ncols) | (l1 == 0))).all())
+
+
+# --- adaptive average pooling (adaptive_pool_*_kernel, ppm_pool_*_kernel)
+def pool_windows(n, bins):
+    """pool_start / pool_end: [(start, end)] of the bins windows along an extent of n (overlapping when bins does not divide n,
+    one-pixel windows that repeat when bins > n)"""
+    return [(i * n // bins, ((i + 1) * n + bins - 1) // bins) for i in range(bins)]
+
+
+def pool_matrix(n, bins, inverse=False, drop_last=False):
+    """[bins][n] 0/1 membership; inverse: 1 / window length instead (the f64 reciprocal).  drop_last: the defect of a window one short"""
+    M = torch.zeros(bins, n, dtype=torch.float64)
+    for i, (a, b) in enumerate(pool_windows(n, bins)):
+        b2 = b - 1 if drop_last and b - a > 1 else b
+        M[i, a:b2] = 1.0 / (b - a) if inverse else 1.0
+    return M
+
+
+def pool_ref(x, bins):
+    """(window sums, sum|terms|, window sizes [bins][bins]) of x [B][C][H][W] in f64"""
+    Py, Px = pool_matrix(x.shape[2], bins), pool_matrix(x.shape[3], bins)
+    n = Py.sum(1)[:, None] * Px.sum(1)[None, :]
+    return torch.einsum('ih,bchw,jw->bcij', Py, x, Px), torch.einsum('ih,bchw,jw->bcij', Py, x.abs(), Px), n
+
+
+def pool_fwd_excess(out, sums, n, bf16):
+    """forward: the window sum is EXACT in f32 (operands multiples of 2^-11 below 4, at most 2^11 of them: exact_budget, asserted by the
+    caller), then ONE f32 division s / (float)n.  hipcc's default (-O3, no fast-math; -fhip-fp32-correctly-rounded-divide-sqrt is on
+    by default, clang's HIP options reference) lowers `/` to the v_div_scale / v_div_fmas / v_div_fixup sequence: correctly rounded,
+    |fl(q) - q| <= u |q|.  A bf16 output rounds fl(q) once more: <= 2^-8 |fl(q)| <= 2^-8 (1 + u) |q|"""
+    ref = sums / n
+    bound = ref.abs() * (U32 + (2.0 ** -8 * (1 + U32) if bf16 else 0.0))
+    return ((out - ref).abs() - bound).max().item()
+
+
+def pool_bwd_ref(gs, H, W, binss, radd=None):
+    """(reference, sum|terms|, longest chain) of dx = sum over arms of P_y^T (dy / n) P_x (+ radd): every pixel adds v * fl(1 / n) per
+    window that holds it.  A term is rounded in fl(1 / n) (correctly rounded), in the product and in each addition that follows it:
+    chain = 2 + the number of terms a pixel can add (overlaps per arm, + 1 for radd)"""
+    ref = torch.zeros(gs[0].shape[0], gs[0].shape[1], H, W, dtype=torch.float64)
+    S, terms = torch.zeros_like(ref), 0
+    for g, bins in zip(gs, binss):
+        Py, Px = pool_matrix(H, bins), pool_matrix(W, bins)
+        n = Py.sum(1)[:, None] * Px.sum(1)[None, :]
+        ref += torch.einsum('ih,bcij,jw->bchw', Py, g / n, Px)
+        S += torch.einsum('ih,bcij,jw->bchw', Py, g.abs() / n, Px)
+        terms += int(Py.sum(0).max()) * int(Px.sum(0).max())
+    if radd is not None:
+        ref, S, terms = ref + radd, S + radd.abs(), terms + 1
+    return ref, S, 2 + terms
+
+
+def ppm_pool_slices(B, ncells):
+    """tss_ppm_pool_slices: row slices per window"""
+    w = B * ncells
+    if w <= 0 or w > 128:
+        return 1
+    return min(cdiv(1024, w), 256)
+
+
+def ppm_slice_rows(y0, y1, S):
+    """the rows [a, b) of slice sl = 0 .. S - 1 of a window [y0, y1) in ppm_pool_fwd_kernel (empty where S exceeds the rows)"""
+    return [(y0 + (y1 - y0) * sl // S, y0 + (y1 - y0) * (sl + 1) // S) for sl in range(S)]
+
+
+# --- attention gates (csrc/gate.hip)
+def gate_slices(B, HW):
+    """tss_gate_slices: min(ceil(1024 / B), ceil(HW / 64)), at least 1"""
+    if B <= 0 or HW <= 0:
+        return 1
+    return max(1, min(cdiv(1024, B), cdiv(HW, 64)))
+
+
+def gate_slice_walk(HW, S):
+    """[q0, q1) of every slice of gate_bwd_kernel: per = ceil(HW / S) pixels, the last ones ragged or empty"""
+    per = cdiv(HW, S)
+    return [(min(sl * per, HW), min(sl * per + per, HW)) for sl in range(S)]
+
+
+def gate_chain(HW, S, C):
+    """f32 chain of da's sum: a lane adds the products (EXACT: two 8-bit significands) of ceil(per / NPL) pixels, one thread adds the
+    NPL lanes, gate_bwd_reduce_kernel the S slices"""
+    NPL = 256 // (C // 8)
+    return cdiv(cdiv(HW, S), NPL) + NPL + S
+
+
+def sigmoid_rel_err(a):
+    """relative error bound of sigm(a) = 1.f / (1.f + __expf(-a)) in units of u = 2^-24, elementwise.
+    __expf(x) is __builtin_amdgcn_exp2f(0x1.715476p+0f * x) (clang's __clang_hip_math.h, which the HIP math API reference lists under
+    the fast intrinsics): the constant is log2(e) within u, the product rounds once, so the argument of exp2 is off by <= 2 u (1 + u)
+    |x| log2(e) and the value by the factor exp2 of that: <= 2 u (1 + u) |x| log2(e) ln(2) (1 + ..) <= 2.01 u |x|; V_EXP_F32 itself is
+    accurate to 1 ulp <= 2 u (CDNA4 ISA guide).  Together E = __expf(-a) has relative error <= (2 + 2.01 |a|) u (1 + 2^-20).
+    1 + E rounds once (u), the division is correctly rounded (u); d s / s = -E / (1 + E) dE / E, and E / (1 + E) < 1:
+        rel(s) <= (2 + 2.01 |a| + 2) u (1 + 2^-20) <= (4.01 + 2.02 |a|) u.
+    a == 0: exp2(0) = 1, s = 0.5: no error at all"""
+    r = 4.01 + 2.02 * a.abs()
+    return torch.where(a == 0, torch.zeros_like(r), r)
+
+
+def gate_fwd_bound(x, a, add_one, bf16):
+    """out = x * (s + add_one): |out - ref| <= |x| s rel(s) u  [the sigmoid]  + (add_one: u (s + 1) |x|: the sum rounds)
+    + u |out| (the product) + 2^-8 (1 + 2^-20) |out| for bf16.  Where a == 0 the factor is 0.5 or 1.5 and the product of an 8-bit x with
+    it is exact: the bound is the bf16 rounding alone (f32: 0, bit for bit)"""
+    s = torch.sigmoid(a)
+    ref = x * (s + add_one)
+    b = x.abs() * s * sigmoid_rel_err(a) * U32 + torch.where(a == 0, torch.zeros_like(ref), ((s + 1) * x.abs() * add_one + ref.abs()) * U32 * 1.001)
+    if bf16:
+        b = b + 2.0 ** -8 * (ref.abs() + b)
+    return ref, b
+
+
+def gate_da_bound(t, tabs, a, chain, bf16):
+    """da = fl(fl(t sg) fl(1 - sg)), t the f32 slice sum (gamma_chain on sum|g x|): sg has rel(s) u, 1 - sg the absolute error
+    sg rel(s) u + u (1 - sg), i.e. relative (e^a rel(s) + 1) u, and the two products round once each.  a == 0: sg = 1 - sg = 0.5, the
+    products are shifts: only the sum's error"""
+    s = torch.sigmoid(a)
+    ref = t * s * (1 - s)
+    rel = sigmoid_rel_err(a)
+    relp = torch.where(a == 0, torch.zeros_like(rel), rel + rel * torch.exp(a) + 1 + 2)
+    b = (2.0 ** -23 * chain * tabs * s * (1 - s) + ref.abs() * relp * U32) * 1.001
+    if bf16:
+        b = b + 2.0 ** -8 * (ref.abs() + b)
+    return ref, b
+
+
+# --- the cases of tests/test_gpu_resample_exact.py and their operands, shared with the f32 emulations of tests/test_exact_bounds.py
+#               Hin Win Hout Wout C  tier
+RS_BILINEAR = [(5, 9, 17, 33, 8, 1), (2, 3, 17, 33, 24, 1), (13, 21, 32, 50, 8, 2), (17, 33, 6, 11, 24, 2), (7, 9, 7, 9, 8, 1),
+               (1, 9, 17, 33, 8, 1), (5, 1, 17, 33, 24, 1), (5, 9, 1, 33, 8, 1), (5, 9, 17, 1, 8, 1), (1, 1, 12, 20, 24, 1), (3, 4, 12, 20, 8, 2)]
+#           w   W  instance       7 sx
+RS_HEAD = [(11, 72, 'three'),     # 0.986
+           (3, 16, 'three'),      # 0.933
+           (2, 8, 'four'),        # exactly 1.0
+           (10, 64, 'four'),      # 1.0
+           (5, 16, 'four'),       # 1.867
+           (3, 8, 'generic'),     # 2.0
+           (10, 32, 'generic'),   # 2.03
+           (6, 24, 'four')]       # 1.52: the smallest pair whose lanes READ the fourth column (none of the seven above does:
+#                                   at 5 -> 16 the clamp at the last source column keeps the second lane within three)
+#           H   W   C   bins
+RS_POOL = [(13, 21, 24, 1), (13, 21, 24, 2), (13, 21, 24, 3), (13, 21, 24, 6),     # NPL = 85 with idle lanes; overlapping windows
+           (4, 5, 8, 6),                                                           # bins > H: one-pixel windows repeat
+           (13, 21, 8, 2),                                                         # NPL = 256 > the 77 pixels of a window
+           (3, 4, 2048, 2)]                                                        # NPL = 1
+#               B  bins          H   W   C   workspace  S
+RS_PPM_POOL = [(2, (1, 2, 3, 6), 13, 21, 24, False, 1),
+               (1, (1, 2, 3, 6), 13, 21, 24, True, 21),       # the 6-bin windows are 3 rows high: most of their slices are empty
+               (1, (1,), 13, 21, 8, True, 256),               # S > H
+               (3, (2, 3), 13, 21, 16, True, 27)]
+#           B  HW   C   slices
+RS_GATE = [(2, 35, 8, 1), (3, 200, 24, 4), (2, 130, 8, 3), (1, 130, 24, 3)]      # 130 / 3: slices of 44, 44 and a ragged 42
+
+
+def case_gen(*key):
+    """the generator of a case, seeded by its parameters"""
+    s = 17
+    for k in key:
+        s = (s * 1000003 + int(k)) % (2 ** 31 - 1)
+    return torch.Generator().manual_seed(s)
+
+
+def narrow(shape, g, zero_frac=0.0):
+    """4 significant bits, multiples of 2^-4 below 2: the operands of the tier-1 gathers"""
+    return dyadic_q(shape, g, 4, -1, 1, zero_frac)
+
+
+def resize_tier1(x, S, pairs):
+    """the tier of a case from its own operands: every (n_in, n_out) pair exact_resize and the budget of sum|terms| S"""
+    ks = [exact_resize(a, b) for a, b in pairs]
+    return all(k is not None for k in ks) and exact_budget(S, lsb_exp(x), sum(ks))
+
+
+def bilinear_fwd_operand(Hi, Wi, Ho, Wo, C, B=2):
+    return dyadic((B, C, Hi, Wi), case_gen(1, Hi, Wi, Ho, Wo), zero_frac=0.03)
+
+
+def bilinear_bwd_operand(Hi, Wi, Ho, Wo, C, tier, B=2):
+    g = case_gen(2, Hi, Wi, Ho, Wo)
+    return narrow((B, C, Ho, Wo), g, 0.03) if tier == 1 else dyadic((B, C, Ho, Wo), g, zero_frac=0.03)
+
+
+def concat_slab_faults(s, e, xc, rows):
+    """what is wrong with the statistics slab an arm of tss_ppm_concat_bwd leaves, [] if nothing: s [512][2 ca] f64, e the STORED
+    gradient rows [rows][ca], xc = raw - mean"""
+    faults = []
+    if torch.isnan(s).any():
+        faults.append('a slab row neither written nor zeroed')
+    if not bool((s[rows:] == 0).all()):
+        faults.append('a slab row beyond B bins^2 holds a value')
+    if not torch.equal(s[:rows], torch.cat([e, e * xc], 1)):
+        faults.append('slab rows differ from (t, t (raw - mean))')
+    return faults
+
+
+RS_BINS = (1, 2, 3, 6)
+RS_LINK = (False, True, False, True)       # the arm has a BatchNorm link (mean, scale, beta) or none (the null-pointer path, also on
+RS_RELU = (1, 1, 0, 0)                     # the one-bin arm): unlinked + ReLU, linked + ReLU on 2 bins, unlinked, linked without ReLU
+
+
+class ArmOperands:
+    """the arms' raw tensors [B][ca][bins][bins] of tss_ppm_concat_* with their links (mean, scale, beta or None), the pre-activation
+    (exact zeros planted), the activation as the kernel rounds it (bf16: rne_bf16; f32: not at all) and xc = raw - mean.  Tier 1: narrow
+    operands and scales 1 or 2: the pre-activations are multiples of 2^-4 below 10, which bf16 holds, so nothing is rounded in either
+    dtype and exact_budget holds with lsb = -4"""
+    def __init__(self, g, B, ca, tier, bf16, binss=RS_BINS, link=RS_LINK, relu=RS_RELU):
+        draw = (lambda s: narrow(s, g)) if tier == 1 else (lambda s: dyadic(s, g))
+        self.binss, self.link, self.relu, self.ca, self.B = binss, link, relu, ca, B
+        self.raw, self.links, self.pre, self.act, self.xc = [], [], [], [], []
+        for bins, lk, rl in zip(binss, link, relu):
+            raw = draw((B, ca, bins, bins))
+            if lk:
+                mean, beta = draw((1, ca, 1, 1)), draw((1, ca, 1, 1))
+                scale = pow2((1, ca, 1, 1), g, 1, 2) if tier == 1 else pow2((1, ca, 1, 1), g, 0.5, 4)
+                raw = plant_zeros(raw, mean, scale, beta, g, 0.1)
+                pre = pre_act(raw, mean, scale, beta)
+                self.links.append([mean, scale, beta])
+                self.xc.append(raw - mean)
+            else:
+                raw = torch.where(torch.rand(raw.shape, generator=g, dtype=torch.float64) < 0.1, torch.zeros_like(raw), raw)
+                pre = raw
+                self.links.append([None, None, None])
+                self.xc.append(raw)
+            a = exact_f32(pre.clamp_min(0.0) if rl else pre)
+            self.raw.append(raw)
+            self.pre.append(pre)
+            self.act.append(rne_bf16(a) if bf16 else a)
+        assert sum(int((p == 0).sum()) for p in self.pre) > 0, 'no exact zero of a pre-activation planted'
+
+
+def concat_gather_chain(bins, H, W, ca):
+    """ppm_concat_bwd_kernel: the weight product and the term round once each, a lane adds ceil(n / NPL) terms of the window's n, one
+    thread the min(n, NPL) lanes that hold one (the others add an exact 0)"""
+    n = window_len(bins, H) * window_len(bins, W)
+    NPL = 256 // (ca // 8)
+    return 2 + cdiv(n, NPL) + min(n, NPL)
+
+
+# --- the arms of the pyramid (csrc/ppm.hip, forward): one block per arm, 1x1 convolution on the matrix unit + batch statistics
+#           C    Ca  P per arm          training
+RS_ARMS = [(32, 16, (3, 12, 27, 108), 1), (128, 32, (3, 12, 27, 108), 1), (128, 16, (512, 1), 1), (32, 32, (512, 1, 130), 1),
+           (32, 16, (3, 12, 27, 108), 0), (128, 32, (512, 1), 0)]
+ARMS_EPS, ARMS_MOMENTUM = float(np.float32(1e-5)), 0.1          # eps as the f32 the entry receives
+
+
+def arms_operands(C, Ca, Ps, seed=0):
+    """per arm: x [P][C] and w [Ca][C] (bf16-exact, so every product is exact), gamma, running mean / variance (f32-exact)"""
+    g = case_gen(15, C, Ca, len(Ps), seed)
+    return [dict(x=dyadic((P, C), g, zero_frac=0.03), w=dyadic((Ca, C), g, emin=-6, emax=-2), gamma=dyadic((Ca,), g),
+                 rmean=dyadic((Ca,), g), rvar=dyadic((Ca,), g).abs(), P=P) for P in Ps]
+
+
+def arms_stats_chain(P):
+    """ppm_arms_fwd_kernel: lane (wave, fr) adds its pixel of every 64-pixel tile in f32 (ceil(P / 64) additions), row16_sum adds the
+    16 lanes of a row in 4 levels; the 4 waves meet in f64"""
+    return cdiv(P, 64) + 4
+
+
+def arms_vec_ref(yq, gamma, rmean, rvar, eps=ARMS_EPS, momentum=ARMS_MOMENTUM):
+    """(reference, bound) per output of the training-mode finalize, from the STORED y (yq [P][Ca], f64 of the bf16 bits): mean, invstd,
+    gamma invstd, running mean, running variance.  With g = gamma_chain (<= 2^-23 chain), the f32 sums obey |s - sum y| <= g sum|y| and
+    |ss - sum y^2| <= g sum y^2 (y y is exact: 16 bits).  Everything after is f64 (2^-48 relative covers it) until the f32 stores:
+      mean    Em = g sum|y| / P                                        stored: + u |mean|
+      var     Ev = g sum y^2 / P + 2 |mean| Em + Em^2                  (clamped at 0: 1-Lipschitz)
+      invstd  f(v) = (v + eps)^-1/2, |f'| <= (vmin + eps)^-3/2 / 2 on [vmin, ..], vmin = max(var - Ev, 0):  Ei = that times Ev; + u f
+      scale   gamma * invstd_f32 rounds once:  |gamma| (Ei + u f) + u |gamma f|
+      running (1.f - m) r + m v in f32: 1.f - m rounds, two products, one sum (or an FMA): <= 3 u (|(1 - m) r| + |m v|), + m times v's
+              own error; the variance enters unbiased, var P / (P - 1) (P = 1: var), rounded to f32 first"""
+    P = yq.shape[0]
+    g = 2.0 ** -23 * arms_stats_chain(P)
+    tiny = 1 + 2.0 ** -40
+    mean, sa, sq = yq.sum(0) / P, yq.abs().sum(0) / P, (yq * yq).sum(0) / P
+    Em = g * sa * tiny
+    var = (sq - mean * mean).clamp_min(0.0)
+    Ev = (g * sq + 2 * mean.abs() * Em + Em * Em) * tiny + 2.0 ** -48 * (sq + mean * mean)
+    inv = (var + eps) ** -0.5
+    Ei = 0.5 * ((var - Ev).clamp_min(0.0) + eps) ** -1.5 * Ev * tiny
+    bm, bi = Em + U32 * mean.abs() * tiny, Ei + U32 * inv * tiny
+    m32 = float(np.float32(momentum))
+    keep = float(np.float32(1.0) - np.float32(momentum))           # fl(1.f - momentum), as the kernel forms it
+    unb = var * (P / (P - 1.0) if P > 1 else 1.0)
+    bu = Ev * (P / (P - 1.0) if P > 1 else 1.0) + U32 * unb * tiny
+    run = lambda r, v, bv: (keep * r + m32 * v, 3.01 * U32 * ((keep * r).abs() + (m32 * v).abs() + m32 * bv) + m32 * bv)
+    return dict(mean=(mean, bm), invstd=(inv, bi), scale=(gamma * inv, gamma.abs() * bi + U32 * (gamma * inv).abs() * tiny),
+                rmean=run(rmean, mean, bm), rvar=run(rvar, unb, bu))
+
+
+# --- the arms of the pyramid, backward (ppm_arms_bwd_kernel): tier 3
+#               C    Ca  P per arm          training  accumulate
+RS_ARMS_BWD = [(32, 32, (130, 3), 1, 0),                 # a second pixel chunk with 2 live pixels
+               (128, 16, (512, 1), 1, 1),                # the MAXU edge; Ca = 16: the zeroed upper half of the k-step; count = 1
+               (32, 16, (3, 12, 27, 108), 1, 1),
+               (128, 32, (130,), 1, 0),
+               (32, 32, (130, 512), 0, 1),               # eval: gamma invstd a power of two, g = ga e exact
+               (128, 16, (3, 12, 27, 108), 0, 0)]
+NEAR_TIE_CAP = 0.01
+
+
+def arms_bwd_operands(C, Ca, Ps, training, accumulate):
+    """per arm: e, y [P][Ca], x [P][C], w [Ca][C] (bf16-exact), mean (dyadic: y - mean is exact in f32), gamma and invstd -- dyadic in
+    training mode, powers of two in eval mode (g = gamma invstd e is then a shift of e: exact) -- and the dyadic prior contents of dw,
+    dgamma, dbeta the launch adds onto when `accumulate`"""
+    g = case_gen(16, C, Ca, len(Ps), training, accumulate)
+    ops = []
+    for P in Ps:
+        o = dict(P=P, e=dyadic((P, Ca), g, zero_frac=0.03), y=dyadic((P, Ca), g), x=dyadic((P, C), g, zero_frac=0.03),
+                 w=dyadic((Ca, C), g, emin=-6, emax=-2), mean=dyadic((Ca,), g))
+        if training:
+            o.update(gamma=dyadic((Ca,), g), invstd=dyadic((Ca,), g).abs())
+        else:
+            o.update(gamma=pow2((Ca,), g, 0.5, 2), invstd=pow2((Ca,), g, 0.25, 4))
+        o.update(dw0=dyadic((Ca, C), g), dgamma0=dyadic((Ca,), g), dbeta0=dyadic((Ca,), g))
+        ops.append(o)
+    return ops
+
+
+def bf16_of_f64(v):
+    """(v rounded ONCE to bf16, nearest even; the bf16 ulp at v; the distance of v to the nearest rounding tie), all f64.  frexp gives
+    |v| = m 2^e with m in [1/2, 1): 8 significant bits are multiples of 2^(e - 8), ties sit half way between them"""
+    m, e = torch.frexp(v.abs())
+    ulp = torch.ldexp(torch.full_like(v, 2.0 ** -8), e)
+    t = m * 256
+    q = torch.sign(v) * torch.round(t) * ulp
+    return q, ulp, ((t - torch.floor(t)) - 0.5).abs() * ulp
+
+
+def arms_bwd_ref(o, training, accumulate):
+    """references and bounds of one arm of tss_ppm_arms_bwd, {name: (reference, bound)} + 'near' (the near-tie mask of g).
+    se = sum e and sey = sum e (y - mean) are f64 sums of exact terms (y - mean is exact in f32, the product of two f32 numbers exact in
+    f64): 2^-40 sum|terms| covers any order.  dg = invstd sey, db = se, k = gamma invstd (exact in f64).
+      dgamma, dbeta   (float) of the f64 value (u), added onto the prior in f32 when accumulate (u of the sum)
+      vec[3..5]       ga = fl(k); training: gb = fl(-k (dg / P) invstd), gce = fl(db / P); eval: 0, 0.  u each + the sums' 2^-40
+      g               line 293 of ppm.hip: ga (e - gce) + gb (y - mean) in f32, then ONE bf16 rounding.  Against the f64 g of the f64
+                      coefficients the f32 value is off by at most Eg: with A = |ga (e - gce)|, B = |gb (y - mean)|
+                        e - gce rounds (u A), gce is off by u |gce| (u |ga gce|), ga by u |ga| (u A), the product rounds (u A),
+                        gb is off by u |gb| (u B), its product rounds (u B), the sum (or FMA) rounds (u (A + B))
+                      Eg = 1.01 u (4 A + 3 B + |ga gce|).  Eval mode: ga is a power of two and gb = gce = 0: g = ga e, Eg = 0.
+      tier 3          an element whose f64 g lies closer than Eg to a bf16 rounding tie may round either way: it contributes ONE bf16 ulp
+                      of itself times |w| (e_in) or |x| (dw) to the bound of every sum it enters; every other element rounds as the
+                      reference does and contributes nothing.  At most NEAR_TIE_CAP of the elements may be near a tie (asserted from
+                      the reference alone in tests/test_exact_bounds.py): a cap on the allowance, not a tolerance
+      e_in            conv_excess with K = Ca on the rounded g (exact products), + the allowance (1 + 2^-8)
+      dw              wgrad_excess with chain = ceil(P / 32) MFMA steps + 1 (the addition onto the prior / the zero), + the allowance"""
+    P, Ca = o['e'].shape
+    e, x, w, r = o['e'], o['x'], o['w'], o['invstd']
+    xc = exact_f32(o['y'] - o['mean'])
+    noise = 2.0 ** -40
+    se, sea, sey, seya = e.sum(0), e.abs().sum(0), (e * xc).sum(0), (e * xc).abs().sum(0)
+    dg, db, k = r * sey, se, o['gamma'] * r
+    if training:
+        ga, gb, gce = k, -k * (dg / P) * r, db / P
+    else:
+        ga, gb, gce = k, torch.zeros_like(k), torch.zeros_like(k)
+    u = 1.001 * U32
+    out = dict(ga=(ga, u * ga.abs()), gb=(gb, u * gb.abs() + noise * (k * r * r).abs() * seya / P), gce=(gce, u * gce.abs() + noise * sea / P))
+    for name, v, va, prior in (('dgamma', dg, r * seya, o['dgamma0']), ('dbeta', db, sea, o['dbeta0'])):
+        ref = v + prior if accumulate else v
+        out[name] = (ref, noise * va + u * v.abs() + (u * ref.abs() if accumulate else 0.0))
+    g64 = ga * (e - gce) + gb * xc
+    A, B = (ga * (e - gce)).abs(), (gb * xc).abs()
+    Eg = 1.01 * U32 * (4 * A + 3 * B + (ga * gce).abs()) if training else torch.zeros_like(g64)
+    gq, ulp, dist = bf16_of_f64(g64)
+    if not training:
+        assert torch.equal(gq, g64), 'eval mode: g = ga e is not a bf16 number'
+    near = dist < Eg
+    allow = near.double() * ulp
+    ref, S = gq @ w, gq.abs() @ w.abs()
+    out['e_in'] = (ref, 2.0 ** -8 * ref.abs() + 2.0 ** -22 * Ca * S + (1 + 2.0 ** -8) * (allow @ w.abs()))
+    ref, S = gq.T @ x, gq.abs().T @ x.abs()
+    if accumulate:
+        ref, S = ref + o['dw0'], S + o['dw0'].abs()
+    out['dw'] = (ref, 2.0 ** -23 * (cdiv(P, 32) + 1) * S + allow.T @ x.abs())
+    out['near'] = near
+    out['gq'] = gq
+    return out

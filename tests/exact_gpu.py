@@ -1,5 +1,5 @@
 """GPU harness of the exact-operand tests (tests/test_gpu_zoo_exact.py, tests/test_gpu_dw_exact.py, tests/test_gpu_pw_exact.py,
-tests/test_gpu_dense_exact.py):
+tests/test_gpu_dense_exact.py, tests/test_gpu_resample_exact.py):
 sentinel-padded device buffers with spare rows, NaN statistics slabs, the dyadic operands of a layer with planted exact zeros, and the
 checks against tests/exact.py's bounds."""
 import contextlib
@@ -26,11 +26,13 @@ def dev(v):
 class Buf:
     """a [P + SPARE][ld] bf16 device buffer, sentinel everywhere, the tensor's rows (f64 [P][C], exact bf16 values) at columns
     [off, off + C); .ptr points at column off"""
-    def __init__(self, P, C, ld, off=0, rows=None, dtype=torch.bfloat16):
+    def __init__(self, P, C, ld, off=0, rows=None, dtype=torch.bfloat16, nan_spare=False):
         self.P, self.C, self.ld, self.off = P, C, ld, off
         t = X.sentinel((P + SPARE, ld), dtype=dtype)
         if rows is not None:
             t[:P, off:off + C] = rows.to(dtype)
+        if nan_spare:        # an INPUT whose spare rows poison whatever reads them, even with the weight 0 (an unclamped i1 tap)
+            t[P:] = float('nan')
         self.t = t.to(DEV)
         self.ptr = self.t.data_ptr() + t.element_size() * off
         self.sbits = X.SENTINEL_BITS32 if dtype == torch.float32 else X.SENTINEL_BITS
@@ -68,6 +70,34 @@ def reduce_many(jobs):
     p = lambda t: t if isinstance(t, int) else t.data_ptr()
     N.call('tss_dw_reduce_many', n, (ctypes.c_void_p * n)(*[p(j[0]) for j in jobs]), (ctypes.c_void_p * n)(*[p(j[1]) for j in jobs]),
            (ctypes.c_int * n)(*[j[2] for j in jobs]), (ctypes.c_int * n)(*[j[3] for j in jobs]), N.stream())
+
+
+def ptr_table(items):
+    """a host array of pointers for the all-arms entries (tss_ppm_*): Buf / tensor / int / None -> NULL, reduce_many's idiom"""
+    p = lambda t: None if t is None else t if isinstance(t, int) else t.ptr if isinstance(t, Buf) else t.data_ptr()
+    return (ctypes.c_void_p * len(items))(*[p(t) for t in items])
+
+
+def long_table(items):
+    return (ctypes.c_long * len(items))(*[t.ld if isinstance(t, Buf) else int(t) for t in items])
+
+
+def int_table(items):
+    return (ctypes.c_int * len(items))(*[int(t) for t in items])
+
+
+def check_resample(buf, ref, S, n, what, tier1=False, slack=0.0):
+    """tier 1: the stored bits are the exact value's (rounded once to bf16); tier 2: X.resample_excess.  Always: sentinel intact"""
+    out, bf = buf.rows(), buf.t.dtype == torch.bfloat16
+    if tier1:
+        want = X.out_bits_ref(ref, bf)
+        bad = (out != want).nonzero()
+        assert bad.numel() == 0, (what, 'not bit for bit at', bad[:3].tolist(), len(bad), 'elements')
+    else:
+        ex = X.resample_excess(out, ref, S, n, bf, slack)
+        assert ex <= 0, (what, 'excess over the bound', ex, 'at', ((out - ref).abs().argmax().item()))
+    assert buf.untouched(), (what, 'sentinel overwritten')
+    return out
 
 
 class GuardedImage:

@@ -1,6 +1,7 @@
 """The exact-operand method of tests/exact.py checked on the CPU (no GPU): its premise (the on-load transforms are exact in f32), the
 soundness of its bounds (an f32 emulation of each convolution from the same bf16 operands passes) and their sharpness (the same emulation
 with one realistic kernel defect fails)."""
+import numpy as np
 import pytest
 import torch
 
@@ -912,3 +913,409 @@ def test_f32_emulation_of_the_stem_meets_the_bounds_and_an_unmasked_right_edge_t
         acc = acc + gp[p].unsqueeze(1) * ptf[p].unsqueeze(0)
     chain_v, _ = X.stem_wgrad_plan(512, False)                      # one lane's chain over two tiles, as this single accumulator adds them
     assert X.wgrad_excess(acc.double().reshape(rwf.shape), rwf, Swf, chain_v) <= 0
+
+
+# ---------------------------------------------------------------------------------------------------------- resample, pyramid, gate
+# the restated planners and f32 emulations behind tests/test_gpu_resample_exact.py (csrc/resample.hip, gate.hip)
+NAN = float('nan')
+
+
+def _T(a):
+    return torch.from_numpy(np.ascontiguousarray(a))
+
+
+def _blend32(x, Ho, Wo, order=0, clamp=True, fused=True):
+    """bilinear_nhwc_fwd_kernel / planar_bilinear in f32: rows of columns (order 0, the kernels') or columns of rows (order 1: the head's
+    fast kernel blends vertically first).  clamp=False: i1 = i0 + 1 behind the last source row, where the harness keeps NaN"""
+    B, C, H, W = x.shape
+    y0, y1, ly0, ly1 = X.ac_taps_np(H, Ho, fused)
+    x0, x1, lx0, lx1 = X.ac_taps_np(W, Wo, fused)
+    xf = x.float()
+    if not clamp:
+        xf, y1 = torch.cat([xf, torch.full((B, C, 1, W), NAN)], 2), y0 + 1
+    ly0, ly1, lx0, lx1 = _T(ly0)[:, None], _T(ly1)[:, None], _T(lx0)[None, :], _T(lx1)[None, :]
+    v = lambda iy, ix: xf[:, :, _T(iy)][:, :, :, _T(ix)]
+    if order == 0:
+        return ly0 * (lx0 * v(y0, x0) + lx1 * v(y0, x1)) + ly1 * (lx0 * v(y1, x0) + lx1 * v(y1, x1))
+    return lx0 * (ly0 * v(y0, x0) + ly1 * v(y1, x0)) + lx1 * (ly0 * v(y0, x1) + ly1 * v(y1, x1))
+
+
+def _gather32(g, n_in, axis, reverse=False, short=0, fused=True):
+    """one pass of a two-pass backward in f32: out[.., i, ..] = the window's weighted sum along `axis` (2 or 3) in window order (or
+    reversed), weight 0 skipped as the kernels do.  short: ac_window's hi one short"""
+    n_out = g.shape[axis]
+    M = X.tap_matrix_f32(n_in, n_out, fused=fused).float()
+    lo, hi = X.ac_windows_np(n_in, n_out)
+    gf = g.float().movedim(axis, 0)
+    out = torch.zeros((n_in,) + tuple(gf.shape[1:]))
+    for i in range(n_in):
+        idx = list(range(int(lo[i]), int(hi[i]) + 1 - short))
+        for o in (reversed(idx) if reverse else idx):
+            if M[o, i] != 0:
+                out[i] = out[i] + M[o, i] * gf[o]
+    return out.movedim(0, axis)
+
+
+def _as_dtype(v, bf16):
+    return v.bfloat16().double() if bf16 else v.double()
+
+
+def test_exact_resize_pairs_have_exact_taps_and_contain_the_dyadic_ones():
+    exact = 0
+    for n_in in range(1, 41):
+        for n_out in range(1, 200):
+            k = X.exact_resize(n_in, n_out)
+            assert k is not None or not X.dyadic_resize(n_in, n_out)
+            if k is not None:
+                exact += 1
+                M = X.tap_matrix_f32(n_in, n_out)
+                assert torch.equal(M, X.bilinear_matrix(n_in, n_out)), (n_in, n_out)
+                assert torch.equal(torch.round(M * 2 ** k), M * 2 ** k)
+    assert exact > 300 and X.exact_resize(6, 17) == 4 and not X.dyadic_resize(6, 17) and X.exact_resize(13, 32) is None
+    for n_in, n_out in ((13, 50), (17, 6), (1, 12), (5, 1), (6, 17)):      # the vectorised taps are ac_taps_f32's
+        i0, i1, l0, l1 = X.ac_taps_np(n_in, n_out, fused=False)
+        fz = X.ac_taps_np(n_in, n_out)
+        assert (i0 == fz[0]).all() and np.abs(l1 - fz[3]).max() <= X.U32 * (n_in - 1)
+        for d, t in enumerate(X.ac_taps_f32(n_in, n_out)):
+            assert (int(i0[d]), int(i1[d]), float(l0[d]), float(l1[d])) == (t[0], t[1], float(t[2]), float(t[3]))
+
+
+def test_restated_windows_hold_every_tap_and_one_short_does_not():
+    taps = 0
+    for n_in in range(1, 41):
+        for n_out in range(1, 200):
+            assert X.window_misses(n_in, n_out) == 0, (n_in, n_out)
+            taps += n_out
+    assert taps == 40 * 199 * 100
+    for Hi, Wi, Ho, Wo, _, _ in X.RS_BILINEAR:
+        assert X.window_misses(Hi, Ho, 1) > 0 and X.window_misses(Wi, Wo, 1) > 0
+
+
+def test_head_dispatch_keeps_every_lane_within_the_columns_of_its_instance():
+    count = {'three': 0, 'four': 0, 'generic': 0}
+    for w in range(1, 70):
+        for W in range(8, 1097, 8):
+            inst = X.head_instance(w, W, 24, 19)
+            count[inst] += 1
+            assert inst == 'generic' or X.head_columns_hold(w, W, 3 if inst == 'three' else 4), (w, W, inst)
+    assert min(count.values()) > 900
+    for w, W, inst in X.RS_HEAD:
+        assert X.head_instance(w, W, 24, 19) == X.head_instance(w, W, 8, 8) == inst
+        assert X.head_instance(w, W, 5, 5) == X.head_instance(w, W, 24, 19, aligned=False) == 'generic'
+    # which of the chosen pairs READ the fourth column: only 6 -> 24; at 5 -> 16 the last-column clamp keeps the lanes within three
+    assert [p[:2] for p in X.RS_HEAD if not X.head_columns_hold(p[0], p[1], 3) and p[2] != 'generic'] == [(6, 24)]
+
+
+def test_pool_windows_slices_and_gate_walks_partition_what_they_cover():
+    F = torch.nn.functional
+    g = _gen(5)
+    for H, W, bins in ((13, 21, 1), (13, 21, 2), (13, 21, 3), (13, 21, 6), (4, 5, 6), (3, 4, 2), (17, 33, 6), (9, 9, 8)):
+        x = X.dyadic((2, 3, H, W), g)
+        sums, _, n = X.pool_ref(x, bins)
+        assert torch.allclose(sums / n, F.adaptive_avg_pool2d(x, bins), rtol=1e-14, atol=0)
+        for y0, y1 in X.pool_windows(H, bins):
+            assert y1 > y0
+            for S in (1, 2, 21, 27, 256):
+                sl = X.ppm_slice_rows(y0, y1, S)
+                assert sl[0][0] == y0 and sl[-1][1] == y1 and all(a[1] == b[0] for a, b in zip(sl, sl[1:])) and all(b >= a for a, b in sl)
+    assert [X.ppm_pool_slices(*a) for a in ((1, 50), (1, 1), (3, 13), (2, 50), (3, 50), (0, 5))] == [21, 256, 27, 11, 1, 1]
+    for B in (1, 2, 3, 64, 2000):
+        for HW in (1, 35, 64, 65, 130, 200, 4096, 70000):
+            S = X.gate_slices(B, HW)
+            walk = X.gate_slice_walk(HW, S)
+            assert 1 <= S <= max(1, X.cdiv(HW, 64)) and walk[0][0] == 0 and walk[-1][1] == HW
+            assert all(a[1] == b[0] for a, b in zip(walk, walk[1:])) and all(b >= a for a, b in walk)
+    assert [X.gate_slices(B, HW) for B, HW, _, _ in X.RS_GATE] == [s for _, _, _, s in X.RS_GATE]
+
+
+@pytest.mark.parametrize('bf16', [True, False])
+@pytest.mark.parametrize('Hi,Wi,Ho,Wo,C,tier', X.RS_BILINEAR)
+def test_f32_emulation_of_the_bilinear_forward_meets_its_tier(Hi, Wi, Ho, Wo, C, tier, bf16):
+    x = X.bilinear_fwd_operand(Hi, Wi, Ho, Wo, C)
+    ref, S = X.resize_ref(x, Ho, Wo)
+    assert X.resize_tier1(x, S, [(Hi, Ho), (Wi, Wo)]) == (tier == 1)
+    a, b, c = _blend32(x, Ho, Wo, 0), _blend32(x, Ho, Wo, 1), _blend32(x, Ho, Wo, 0, fused=False)
+    if tier == 1:       # the budget: two orders, contracted or not, the same bits, the exact value's
+        assert torch.equal(a, b) and torch.equal(a, c) and torch.equal(_as_dtype(a, bf16), X.out_bits_ref(ref, bf16))
+    else:
+        for out in (a, b, c):
+            assert X.resample_excess(_as_dtype(out, bf16), ref, S, X.BLEND_N, bf16, X.tap_slack(x, Ho, Wo)) <= 0
+            assert X.resize_matrix_excess(_as_dtype(out, bf16), x, Ho, Wo, bf16) <= 0
+    if Ho > 1 or Hi == 1:       # (a single output row reads source rows 0 and 1 only)
+        bad = _as_dtype(_blend32(x, Ho, Wo, 0, clamp=False), bf16)         # defect: i1 not clamped at the last source index
+        assert not X.resample_excess(bad, ref, S, X.BLEND_N, bf16, X.tap_slack(x, Ho, Wo)) <= 0
+
+
+@pytest.mark.parametrize('bf16', [True, False])
+@pytest.mark.parametrize('Hi,Wi,Ho,Wo,C,tier', X.RS_BILINEAR)
+def test_f32_emulation_of_the_two_pass_backward_meets_its_tier(Hi, Wi, Ho, Wo, C, tier, bf16):
+    dy = X.bilinear_bwd_operand(Hi, Wi, Ho, Wo, C, tier)
+    t, ta, ref, S = X.resize_bwd_ref(dy, Hi, Wi)
+    assert (X.resize_tier1(dy, S, [(Hi, Ho), (Wi, Wo)]) and X.resize_tier1(dy, ta, [(Hi, Ho)])) == (tier == 1)
+    ny = X.window_len(Hi, Ho) + 1
+    nx = ny + X.window_len(Wi, Wo) + 1
+    tmp = _gather32(dy, Hi, 2)
+    dx = _gather32(tmp.double(), Wi, 3)
+    rev = _gather32(_gather32(dy, Hi, 2, reverse=True, fused=False).double(), Wi, 3, reverse=True, fused=False)
+    if tier == 1:
+        assert torch.equal(tmp.double(), t) and torch.equal(dx, rev) and torch.equal(_as_dtype(dx, bf16), X.out_bits_ref(ref, bf16))
+    else:
+        assert X.resample_excess(tmp.double(), t, ta, ny, False, X.tap_slack_bwd(dy, Hi)) <= 0
+        for out in (dx, rev):
+            assert X.resample_excess(_as_dtype(out, bf16), ref, S, nx, bf16, X.tap_slack_bwd(dy, Hi, Wi)) <= 0
+            assert X.resize_bwd_matrix_excess(_as_dtype(out, bf16), dy, Hi, Wi, nx, bf16) <= 0
+    bad = _gather32(_gather32(dy, Hi, 2, short=1).double(), Wi, 3, short=1)       # defect: ac_window's hi one short
+    assert X.resample_excess(_as_dtype(bad, bf16), ref, S, nx, bf16, X.tap_slack_bwd(dy, Hi, Wi)) > 0
+
+
+def _head32(low, H, W, ncols):
+    """upsample_head_fwd_kernel<T, ncols> in f32: the vertical blend of source columns c0 .. c0 + ncols - 1 first, then per output the
+    two columns picked by d = i - c0 (d >= ncols - 1 picks the last one)"""
+    B, N, h, w = low.shape
+    y0, y1, ly0, ly1 = X.ac_taps_np(h, H)
+    x0, x1, lx0, lx1 = X.ac_taps_np(w, W)
+    lf = low.float()
+    rows = _T(ly0)[:, None] * lf[:, :, _T(y0)] + _T(ly1)[:, None] * lf[:, :, _T(y1)]          # [B][N][H][w]
+    c0 = np.repeat(x0.reshape(-1, 8)[:, :1], 8, 1).reshape(-1)
+    pick = lambda i: _T(np.minimum(c0 + np.minimum(i - c0, ncols - 1), w - 1))
+    return _T(lx0) * rows[..., pick(x0)] + _T(lx1) * rows[..., pick(x1)]
+
+
+@pytest.mark.parametrize('bf16', [True, False])
+@pytest.mark.parametrize('w,W,inst', X.RS_HEAD)
+def test_f32_emulation_of_the_head_meets_the_bound_and_three_columns_where_four_are_read_fail(w, W, inst, bf16):
+    low = X.dyadic((2, 19, 6, w), X.case_gen(4, w, W, 19), zero_frac=0.03)
+    ref, S = X.resize_ref(low, 14, W)
+    ncols = {'three': 3, 'four': 4, 'generic': 8}[inst]
+    out = _as_dtype(_head32(low, 14, W, ncols), bf16)
+    slack = X.tap_slack(low, 14, W)
+    assert X.resample_excess(out, ref, S, X.BLEND_N, bf16, slack) <= 0 and X.resize_matrix_excess(out, low, 14, W, bf16) <= 0
+    if (w, W) == (6, 24):       # defect: the 3-column selection on a pair that reads the fourth
+        assert X.resample_excess(_as_dtype(_head32(low, 14, W, 3), bf16), ref, S, X.BLEND_N, bf16, slack) > 0
+    if (w, W) == (5, 16):       # ... which 5 -> 16 does not: three columns are enough there
+        assert torch.equal(_head32(low, 14, W, 3), _head32(low, 14, W, 4))
+
+
+def _pool32(x, bins, chunk=None, drop_last=False):
+    """f32 window sums in pixel order, or as partial sums of `chunk` pixels added afterwards (the lanes of a block)"""
+    out = torch.zeros(x.shape[0], x.shape[1], bins, bins)
+    for i, (y0, y1) in enumerate(X.pool_windows(x.shape[2], bins)):
+        y1 = y1 - 1 if drop_last and y1 - y0 > 1 else y1
+        for j, (x0, x1) in enumerate(X.pool_windows(x.shape[3], bins)):
+            px = x[:, :, y0:y1, x0:x1].float().reshape(x.shape[0], x.shape[1], -1)
+            parts = [px] if chunk is None else list(px.split(chunk, 2))
+            tot = torch.zeros(px.shape[:2])
+            for p in parts:
+                s = torch.zeros(px.shape[:2])
+                for k in range(p.shape[2]):
+                    s = s + p[:, :, k]
+                tot = tot + s
+            out[:, :, i, j] = tot
+    return out
+
+
+@pytest.mark.parametrize('bf16', [True, False])
+@pytest.mark.parametrize('H,W,C,bins', X.RS_POOL)
+def test_f32_emulation_of_the_pools_meets_the_bounds_and_a_dropped_row_or_a_slice_count_fails(H, W, C, bins, bf16):
+    x = X.dyadic((2, C, H, W), X.case_gen(6, H, W, C, bins), zero_frac=0.03)
+    sums, sabs, n = X.pool_ref(x, bins)
+    assert X.exact_budget(sabs, X.lsb_exp(x))
+    a, b = _pool32(x, bins), _pool32(x, bins, chunk=7)
+    assert torch.equal(a, b) and torch.equal(a.double(), sums)            # the budget: exact whatever the order
+    out = _as_dtype(a / n.float(), bf16)
+    assert X.pool_fwd_excess(out, sums, n, bf16) <= 0
+    if H > bins:
+        assert X.pool_fwd_excess(_as_dtype(_pool32(x, bins, drop_last=True) / n.float(), bf16), sums, n, bf16) > 0      # defect: a dropped row
+        rows = torch.tensor([float(y1 - y0) for y0, y1 in X.pool_windows(H, bins)])[:, None]
+        sliced = a / (n.float() / rows * (rows - 1).clamp_min(1))          # defect: divided by the pixels of a slice one row short
+        assert X.pool_fwd_excess(_as_dtype(sliced, bf16), sums, n, bf16) > 0
+    # backward: every pixel adds v * fl(1 / n) per window that holds it
+    dy = X.dyadic((2, C, bins, bins), X.case_gen(7, H, W, C, bins), zero_frac=0.03)
+    ref, S, chain = X.pool_bwd_ref([dy], H, W, [bins])
+    dx = torch.zeros(2, C, H, W)
+    for i, (y0, y1) in enumerate(X.pool_windows(H, bins)):
+        for j, (x0, x1) in enumerate(X.pool_windows(W, bins)):
+            inv = torch.tensor(1.0) / torch.tensor(float((y1 - y0) * (x1 - x0)))
+            dx[:, :, y0:y1, x0:x1] = dx[:, :, y0:y1, x0:x1] + (dy[:, :, i, j].float() * inv)[:, :, None, None]
+    assert X.resample_excess(_as_dtype(dx, bf16), ref, S, chain, bf16) <= 0
+
+
+@pytest.mark.parametrize('bf16', [True, False])
+@pytest.mark.parametrize('H,W,tier', [(17, 33, 1), (12, 20, 2)])
+def test_f32_emulation_of_the_concat_meets_its_tier_and_its_defects_fail(H, W, tier, bf16):
+    B, C, ca = 2, 8, 8
+    g = X.case_gen(10, H, W, C, ca)
+    A = X.ArmOperands(g, B, ca, tier, bf16)
+    taken = {'late': 0, 'mask': 0}
+    for k, bins in enumerate(A.binss):
+        ref, S = X.resize_ref(A.act[k], H, W)
+        t1 = X.resize_tier1(A.act[k], S, [(bins, H), (bins, W)])
+        assert t1 == (tier == 1 or bins == 1)
+        a, b = _blend32(A.act[k], H, W, 0), _blend32(A.act[k], H, W, 1)
+        if t1:
+            assert torch.equal(a, b) and torch.equal(_as_dtype(a, bf16), X.out_bits_ref(ref, bf16))
+        else:
+            assert X.resample_excess(_as_dtype(a, bf16), ref, S, X.BLEND_N, bf16, X.tap_slack(A.act[k], H, W)) <= 0
+    # defect: BatchNorm + ReLU applied after the blend instead of per tap (linked ReLU arms with more than one bin)
+    D = X.ArmOperands(X.case_gen(10, H, W, C, ca, 1), B, ca, tier, bf16, binss=(3, 6), link=(True, True), relu=(1, 1))
+    for k in range(2):
+        ref, S = X.resize_ref(D.act[k], H, W)
+        mean, scale, beta = D.links[k]
+        late = (_blend32(D.raw[k], H, W, 0).double() - mean) * scale + beta
+        assert X.resample_excess(_as_dtype(late.clamp_min(0).float(), bf16), ref, S, X.BLEND_N, bf16, X.tap_slack(D.act[k], H, W)) > 0
+        taken['late'] += 1
+    # backward on the GPU file's operands: the gather, the mask act > 0, the slab rows
+    g = X.case_gen(11, B, H, W, C, ca)
+    A = X.ArmOperands(g, B, ca, tier, bf16)
+    Ct = C + 4 * ca
+    dout = X.narrow((B, Ct, H, W), g, 0.03) if tier == 1 else X.dyadic((B, Ct, H, W), g, zero_frac=0.03)
+    for k, bins in enumerate(A.binss):
+        gk = dout[:, C + k * ca:C + (k + 1) * ca]
+        _, _, ref, S = X.resize_bwd_ref(gk, bins, bins)
+        keep = (A.pre[k] > 0).double() if A.relu[k] else torch.ones_like(ref)
+        n = X.concat_gather_chain(bins, H, W, ca)
+        raw = _gather32(_gather32(gk, bins, 2).double(), bins, 3)
+        rev = _gather32(_gather32(gk, bins, 3, reverse=True).double(), bins, 2, reverse=True)
+        t1 = X.resize_tier1(gk, S, [(bins, H), (bins, W)])
+        assert t1 == (tier == 1 or bins == 1)
+        for out in (raw, rev):
+            e = _as_dtype(out * keep.float(), bf16)
+            if t1:
+                assert torch.equal(e, X.out_bits_ref(ref * keep, bf16))
+            else:
+                assert X.resample_excess(e, ref * keep, S * keep, n, bf16, X.tap_slack_bwd(gk, bins, bins) * keep) <= 0
+        if A.relu[k] and bool(((A.pre[k] == 0) & (ref != 0)).any()):          # defect: the ReLU mask taken on >= 0
+            loose = _as_dtype(raw * (A.pre[k] >= 0).float(), bf16)
+            assert X.resample_excess(loose, ref * keep, S * keep, n, bf16, X.tap_slack_bwd(gk, bins, bins) * keep) > 0
+            taken['mask'] += 1
+        rows, er, xc = B * bins * bins, X.nchw_to_rows(e), X.nchw_to_rows(A.xc[k])
+        slab = torch.zeros(X.STAT_SLABS, 2 * ca, dtype=torch.float64)
+        slab[:rows] = torch.cat([er, er * xc], 1)
+        assert X.concat_slab_faults(slab, er, xc, rows) == []
+        slab[rows + 3, 1] = NAN                                                # defect: a slab row beyond rows_used left stale
+        assert X.concat_slab_faults(slab, er, xc, rows) == ['a slab row neither written nor zeroed', 'a slab row beyond B bins^2 holds a value']
+    assert taken['late'] > 0 and taken['mask'] > 0, ('a defect branch was never taken', taken)
+
+
+@pytest.mark.parametrize('bf16', [True, False])
+@pytest.mark.parametrize('add_one', [0.0, 1.0])
+@pytest.mark.parametrize('B,HW,C,S', X.RS_GATE)
+def test_f32_emulation_of_the_gates_meets_the_bounds(B, HW, C, S, add_one, bf16):
+    g = X.case_gen(14, B, HW, C)
+    x = X.dyadic((B, HW, C), g, zero_frac=0.03)
+    a = X.dyadic((B, 1, C), g, zero_frac=0.25)
+    gr = X.dyadic((B, HW, C), g, zero_frac=0.03)
+    # sigm() with exp2 of the f32 product as __expf forms it (the host's exp2f stands in for V_EXP_F32: both within 1 ulp)
+    sg = 1.0 / (1.0 + torch.exp2(torch.tensor(1.4426950408889634).float() * -a.float()))
+    assert bool((sg[a == 0] == 0.5).all())
+    out = _as_dtype(gr.float() * (sg + add_one), bf16)
+    ref, bound = X.gate_fwd_bound(gr, a.expand_as(gr), add_one, bf16)
+    assert ((out - ref).abs() - bound).max() <= 0
+    z = (a == 0).expand_as(gr)
+    assert torch.equal(out[z], X.out_bits_ref(ref[z], bf16))
+    wrong = _as_dtype(gr.float() * (sg * (1 + 2.0 ** -18) + add_one), bf16)          # a sigmoid 64 ulp off fails in f32, and at a == 0
+    assert bf16 or ((wrong - ref).abs() - bound).max() > 0
+    # da: the slice walk in f32 (lanes, then slices), times s (1 - s)
+    prod = (gr * x).float()
+    NPL = 256 // (C // 8)
+    t = torch.zeros(B, C)
+    for q0, q1 in X.gate_slice_walk(HW, S):
+        lanes = torch.zeros(B, NPL, C)
+        for q in range(q0, q1):
+            lanes[:, (q - q0) % NPL] = lanes[:, (q - q0) % NPL] + prod[:, q]
+        sl = torch.zeros(B, C)
+        for r in range(NPL):
+            sl = sl + lanes[:, r]
+        t = t + sl
+    s1 = sg.reshape(B, C)
+    da = _as_dtype(t * s1 * (1 - s1), bf16)
+    p64 = gr * x
+    ref, bound = X.gate_da_bound(p64.sum(1), p64.abs().sum(1), a.reshape(B, C), X.gate_chain(HW, S, C), bf16)
+    assert ((da - ref).abs() - bound).max() <= 0
+    short = _as_dtype((t - prod[:, HW - 1]) * s1 * (1 - s1), bf16)          # defect: the ragged last slice one pixel short
+    assert ((short - ref).abs() - bound).max() > 0
+
+
+def _arms_finalize32(yq, gamma, rmean, rvar, biased=False):
+    """the statistics of ppm_arms_fwd_kernel in its order: f32 lane sums over the 64-pixel tiles, row16_sum's four rotations, the four
+    waves in f64, the finalize in f64 and its f32 stores; the running statistics in f32"""
+    P, Ca = yq.shape
+    y = torch.zeros(X.cdiv(P, 64) * 64, Ca)
+    y[:P] = yq.float()
+    s1, s2 = torch.zeros(64, Ca), torch.zeros(64, Ca)
+    for t in y.split(64):
+        s1, s2 = s1 + t, s2 + t * t
+    tot = []
+    for v in (s1, s2):
+        v = v.reshape(4, 16, Ca)
+        for r in (8, 4, 2, 1):
+            v = v + torch.roll(v, -r, 1)
+        tot.append(v[:, 0].double().sum(0))
+    mean = tot[0] / P
+    var = (tot[1] / P - mean * mean).clamp_min(0.0)
+    inv = ((var + X.ARMS_EPS) ** -0.5).float()
+    m, mom = mean.float(), torch.tensor(X.ARMS_MOMENTUM).float()
+    unb = (var if biased or P == 1 else var * P / (P - 1.0)).float()
+    return dict(mean=m, invstd=inv, scale=gamma.float() * inv, rmean=(1 - mom) * rmean.float() + mom * m,
+                rvar=(1 - mom) * rvar.float() + mom * unb)
+
+
+@pytest.mark.parametrize('C,Ca,Ps,training', X.RS_ARMS)
+def test_f32_emulation_of_the_arms_finalize_meets_its_bounds_and_a_biased_running_variance_fails(C, Ca, Ps, training):
+    for o in X.arms_operands(C, Ca, Ps):
+        ref, S = o['x'] @ o['w'].T, o['x'].abs() @ o['w'].abs().T
+        yq = (o['x'].float() @ o['w'].float().T).bfloat16().double()          # an f32 GEMM in the host's order, rounded once
+        assert X.conv_excess(yq, ref, S, C) <= 0
+        want = X.arms_vec_ref(yq, o['gamma'], o['rmean'], o['rvar'])
+        got = _arms_finalize32(yq, o['gamma'], o['rmean'], o['rvar'])
+        for name, (r, b) in want.items():
+            assert ((got[name].double() - r).abs() - b).max() <= 0, (name, o['P'])
+        if o['P'] == 1:
+            assert bool((got['invstd'] == torch.tensor(X.ARMS_EPS ** -0.5).float()).all())       # count = 1: the variance is an exact 0
+        elif o['P'] <= 130:
+            bad = _arms_finalize32(yq, o['gamma'], o['rmean'], o['rvar'], biased=True)
+            r, b = want['rvar']
+            assert ((bad['rvar'].double() - r).abs() - b).max() > 0
+
+
+def _arms_bwd32(o, R, training, accumulate, mirror=False):
+    """ppm_arms_bwd_kernel from its staging on, in f32: g by line 293 with the f32 coefficients, rounded to bf16; e_in as one k-step
+    per output (the f64 sum of the exact products rounded once); dw as ceil(P / 32) k-steps of 32 pixels, each an f64 sum rounded once
+    and added in f32, then onto the prior.  mirror: the channel vector cv of the transposed store written to rows of nvg - 1 - cv"""
+    P, Ca = o['e'].shape
+    ga, gb, gce = (R[k][0].float() for k in ('ga', 'gb', 'gce'))
+    g = (ga * (o['e'].float() - gce) + gb * (o['y'].float() - o['mean'].float())).bfloat16().double()
+    e_in = (g @ o['w']).float().bfloat16().double()
+    gt = g.reshape(P, Ca // 8, 8).flip(1).reshape(P, Ca) if mirror else g
+    dw = torch.zeros(Ca, o['x'].shape[1])
+    for p0 in range(0, P, 32):
+        dw = dw + (gt[p0:p0 + 32].T @ o['x'][p0:p0 + 32]).float()
+    dw = (o['dw0'].float() if accumulate else 0.0) + dw
+    return g, e_in, dw.double()
+
+
+@pytest.mark.parametrize('C,Ca,Ps,training,accumulate', X.RS_ARMS_BWD)
+def test_f32_emulation_of_the_arms_backward_meets_tier_3_and_a_mirrored_channel_vector_fails(C, Ca, Ps, training, accumulate):
+    for o in X.arms_bwd_operands(C, Ca, Ps, training, accumulate):
+        R = X.arms_bwd_ref(o, training, accumulate)
+        near = R['near']
+        assert float(near.double().mean()) <= X.NEAR_TIE_CAP                    # the cap, from the reference alone
+        g, e_in, dw = _arms_bwd32(o, R, training, accumulate)
+        # the premise of tier 3: away from a tie the f32 chain rounds as the reference does; near one it is at most one ulp off
+        _, ulp, _ = X.bf16_of_f64(R['gq'])
+        assert torch.equal(g[~near], R['gq'][~near]) and bool(((g - R['gq']).abs() <= ulp)[near].all())
+        assert training or not bool(near.any())
+        for name, out in (('e_in', e_in), ('dw', dw)):
+            ref, bound = R[name]
+            assert ((out - ref).abs() - bound).max() <= 0, (name, o['P'])
+        # dgamma / dbeta: f64 sums in another order (per-thread partials of 8 pixels, then the partials), stored as the kernel stores
+        xc = o['y'] - o['mean']
+        for name, terms, scale, prior in (('dgamma', o['e'] * xc, o['invstd'], o['dgamma0']), ('dbeta', o['e'], 1.0, o['dbeta0'])):
+            part = torch.stack([t.flip(0).sum(0) for t in terms.split(8)]).sum(0)
+            out = (scale * part).float()
+            out = (prior.float() + out) if accumulate else out
+            ref, bound = R[name]
+            assert ((out.double() - ref).abs() - bound).max() <= 0, name
+        _, _, bad = _arms_bwd32(o, R, training, accumulate, mirror=True)          # defect: a mirrored cv in the transposed store
+        ref, bound = R['dw']
+        assert ((bad - ref).abs() - bound).max() > 0

@@ -4,8 +4,9 @@ on the same inputs, so a wrong template instance or pointer cast in either branc
 
 Bounds.  float32: the bound of the operator's existing test (cited per case).  bfloat16: the bound of the operator's
 existing bf16 test where there is one (the upsampled cross-entropy / OHEM / argmax family).  bilinear, upsample_logits,
-adaptive_avg_pool, resize_image and gate have NO existing bf16 test, so no existing bf16 bound was available for them;
-theirs is derived from the number format: the kernels compute in f32 from the bf16 inputs and round every output element
+adaptive_avg_pool, resize_image and gate are held elementwise, in both dtypes and at the C ABI, by
+tests/test_gpu_resample_exact.py (bit for bit or to a derived bound on dyadic operands); the norm-wise bf16 bound used for them
+here is derived from the number format: the kernels compute in f32 from the bf16 inputs and round every output element
 once, so an element is off by at most half a bf16 ulp, which is 2**-8 relative (8 significand bits), and so is the
 relative L2 error (one rounding typically gives about 1.1e-3; a wrong instance or cast gives O(1)).  BF16 below adds the
 operator's f32 bound to that.  The reference of a bf16 case is the f32 formula on the same bf16 values.  (The upsampled

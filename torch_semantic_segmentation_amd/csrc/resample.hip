@@ -500,6 +500,10 @@ __global__ __launch_bounds__(NT) void ppm_pool_bwd_kernel(const PpmArgs g) {
   }
 }
 
+// where an arm has no BatchNorm link its three vector loads still issue and are discarded: they read these 32 bytes (the arm tensor's
+// own last channel group can be shorter than that in bf16)
+[[maybe_unused]] __device__ __attribute__((aligned(16))) const float ppm_unlinked[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+
 template <typename T>
 __global__ __launch_bounds__(NT) void ppm_concat_fwd_kernel(const PpmArgs g) {
   const int CVx = g.C / 8, CVa = g.ca / 8, CVt = CVx + g.narms * CVa;
@@ -531,7 +535,7 @@ __global__ __launch_bounds__(NT) void ppm_concat_fwd_kernel(const PpmArgs g) {
       V8<T>::load(base + ((long)ty.i1 * bins + tx.i1) * ld, v11);
       const bool aff = g.scale[arm] != nullptr;
       {   // six 16-byte loads through null-safe pointers (24 scalar loads behind a branch otherwise)
-        const float* safe = reinterpret_cast<const float*>(base);
+        const float* safe = ppm_unlinked;
         const float* pm = aff ? g.mean[arm] + c0 : safe; const float* ps = aff ? g.scale[arm] + c0 : safe;
         const float* pb = aff ? g.beta[arm] + c0 : safe;
 #pragma unroll
