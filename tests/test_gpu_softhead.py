@@ -8,7 +8,8 @@ cases.rel_err <= max(2e-5, 3 d_ref), the floor alone where the f32 restatement i
 
 Geometries of the register kernels: the FUSED table of tests/test_gpu_wce.py with its fused_input (CP 20 and 24 instances, lanes past
 the image edge, two strips, several bands, scale 1 with rB == rA at the end, pad classes), plus EXTRA below: two classes, 99.5 % of
-the labels ignored, one class absent.  Wide route: c25, c33, edge, strips, scale1, c256 of tests/test_gpu_widehead.py's WIDE.
+the labels ignored, one class absent, an output size that is no multiple of the map (15 x 29 -> 16 x 32).
+Wide route: c25, c33, edge, strips, scale1, c256 of tests/test_gpu_widehead.py's WIDE.
 Labels as there: about 10 % of 255, three -1, two 300.  Every call is made twice and must give the same bits.
 """
 import functools
@@ -32,6 +33,8 @@ EXTRA = {
     'tiny':      ((2, 2, 4, 4), 2, 0.10, None),       # the smallest class count
     'few_valid': ((2, 19, 8, 16), 8, 0.995, None),    # almost nothing counts
     'absent':    ((1, 5, 6, 9), 4, 0.10, 3),          # class 3 absent; 36 columns: lanes past the edge
+    # an output SIZE, no multiple of the map and nearly equal to it; the name sorts last, so the seeds of the cases above stay
+    'uneven':    ((1, 19, 15, 29), (16, 32), 0.10, None),
 }
 REGISTER = list(FUSED) + list(EXTRA)
 WIDE_NAMES = ['c25', 'c33', 'edge', 'strips', 'scale1', 'c256']
@@ -48,7 +51,7 @@ def head_input(name, bf16):
     low = 2.0 * torch.randn(B, C, h, w, generator=g)
     if bf16:
         low = low.bfloat16().float()
-    H, W = h * scale, w * scale
+    H, W = scale if isinstance(scale, tuple) else (h * scale, w * scale)
     target = torch.randint(0, C, (B, H, W), generator=g)
     if absent is not None:
         target[target == absent] = (absent + 1) % C
@@ -90,10 +93,15 @@ def nhwc(low, dtype):
     return ops.to_nhwc(low.to(DEV).to(dtype))
 
 
+def out_size(scale):
+    """the operators' size / scale_factor arguments of a case's scale (an output size where it is a tuple)"""
+    return {'size': scale} if isinstance(scale, tuple) else {'scale_factor': scale}
+
+
 def hip_focal(low, target, scale, gamma, variant, dtype=torch.float32, ignore=255, gscale=None, alpha=ALPHA):
     import torch_semantic_segmentation_amd as tssa
     a = nhwc(low, dtype).clone().requires_grad_(True)
-    loss = tssa.upsample_focal_loss(a, target.to(DEV), scale_factor=scale, alpha=alpha, gamma=gamma, ignore_index=ignore, variant=variant)
+    loss = tssa.upsample_focal_loss(a, target.to(DEV), alpha=alpha, gamma=gamma, ignore_index=ignore, variant=variant, **out_size(scale))
     (loss if gscale is None else gscale * loss).backward()
     return loss.detach().cpu(), a.grad.detach().float().cpu()
 
@@ -101,7 +109,7 @@ def hip_focal(low, target, scale, gamma, variant, dtype=torch.float32, ignore=25
 def hip_dice(low, target, scale, smooth, dtype=torch.float32, ignore=255, gscale=None):
     import torch_semantic_segmentation_amd as tssa
     a = nhwc(low, dtype).clone().requires_grad_(True)
-    loss = tssa.upsample_dice_loss(a, target.to(DEV), low.shape[1], scale_factor=scale, smooth=smooth, ignore_index=ignore)
+    loss = tssa.upsample_dice_loss(a, target.to(DEV), low.shape[1], smooth=smooth, ignore_index=ignore, **out_size(scale))
     (loss if gscale is None else gscale * loss).backward()
     return loss.detach().cpu(), a.grad.detach().float().cpu()
 

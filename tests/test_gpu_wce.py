@@ -39,6 +39,10 @@ FUSED = {
 }
 
 
+# an output that is no multiple of the map and nearly equal to it: the row tap moves on almost every output row, 32 of 256 lanes in use
+NEAR = ((1, 19, 15, 29), (16, 32))
+
+
 def drop_last_class(target, C):
     if C > 2:
         target[target == C - 1] = 0
@@ -67,14 +71,14 @@ def planar_input(name, bf16):
     return logits, target, class_weights(target, C)
 
 
-@functools.lru_cache(maxsize=None)
-def fused_input(name, bf16):
-    (B, C, h, w), scale = FUSED[name]
-    g = torch.Generator().manual_seed(sorted(FUSED).index(name) + 900)
+def labelled_input(shape, size, seed, bf16):
+    """(low-resolution logits, labels of `size` with about 10 % of 255, three -1 and two 300, class weights) from one seed."""
+    B, C, h, w = shape
+    H, W = size
+    g = torch.Generator().manual_seed(seed)
     low = 2.0 * torch.randn(B, C, h, w, generator=g)
     if bf16:
         low = low.bfloat16().float()
-    H, W = h * scale, w * scale
     target = torch.randint(0, C, (B, H, W), generator=g)
     target = drop_last_class(target, C)
     target[torch.rand(B, H, W, generator=g) < 0.10] = 255
@@ -82,6 +86,17 @@ def fused_input(name, bf16):
     flat[[3, 17, 40]] = -1
     flat[[5, 29]] = 300
     return low, target, class_weights(target, C)
+
+
+@functools.lru_cache(maxsize=None)
+def fused_input(name, bf16):
+    (B, C, h, w), scale = FUSED[name]
+    return labelled_input((B, C, h, w), (h * scale, w * scale), sorted(FUSED).index(name) + 900, bf16)
+
+
+@functools.lru_cache(maxsize=None)
+def near_input(bf16):
+    return labelled_input(NEAR[0], NEAR[1], 960, bf16)
 
 
 def reference(fn, x, target, w, eps):
@@ -118,11 +133,11 @@ def hip_planar(logits, target, w, eps, dtype=torch.float32, scale=None):
     return loss.detach().cpu(), x.grad.detach().float().cpu()
 
 
-def hip_fused(low, target, w, eps, scale_factor, dtype=torch.float32, scale=None):
+def hip_fused(low, target, w, eps, scale_factor, dtype=torch.float32, scale=None, size=None):
     import torch_semantic_segmentation_amd as tssa
     from torch_semantic_segmentation_amd import ops
     a = ops.to_nhwc(low.to(DEV).to(dtype)).clone().requires_grad_(True)
-    loss = tssa.upsample_cross_entropy(a, target.to(DEV), scale_factor=scale_factor, ignore_index=255,
+    loss = tssa.upsample_cross_entropy(a, target.to(DEV), scale_factor=scale_factor, size=size, ignore_index=255,
                                        weight=None if w is None else w.to(DEV), label_smoothing=eps)
     (loss if scale is None else scale * loss).backward()
     return loss.detach().cpu(), a.grad.detach().float().cpu()
@@ -162,6 +177,17 @@ def test_fused_loss_and_gradient_vs_f64_restatement(name, dtype, weighted, eps):
     low, target, w = fused_input(name, bf16)
     got = hip_fused(low, target, w if weighted else None, eps, FUSED[name][1], dtype)
     check(tag_of('fused ', name, bf16, weighted, eps), got, fused_reference(name, bf16, weighted, eps), bf16)
+
+
+@pytest.mark.parametrize('weighted,eps', [(False, 0.0), (True, 0.0), (False, EPS), (True, EPS)], ids=['plain', 'w', 'eps', 'w_eps'])
+@DTYPES
+def test_fused_output_nearly_the_map_size_vs_f64_restatement(dtype, weighted, eps):
+    bf16 = dtype == torch.bfloat16
+    low, target, w = near_input(bf16)
+    assert (target == 255).sum() > 0 and (target == -1).sum() == 3 and (target == 300).sum() == 2
+    got = hip_fused(low, target, w if weighted else None, eps, None, dtype, size=NEAR[1])
+    want = reference(R.upsampled_wce_loss, low, target, w if weighted else None, eps)
+    check(tag_of('fused ', 'near', bf16, weighted, eps), got, want, bf16)
 
 
 @pytest.mark.parametrize('name', ['sub_wave', 'two_blocks', 'odd_batch'])

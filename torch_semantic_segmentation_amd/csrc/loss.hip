@@ -8,8 +8,6 @@
 
 namespace {
 
-constexpr int NT = lsw::NT;
-
 template <typename T>
 __global__ __launch_bounds__(NT) void ce_fwd_kernel(const T* logits, const long long* target, float* lse_out,
                                                     double* acc /*[2]: loss sum, valid count*/, long B, int C,
@@ -61,7 +59,7 @@ __global__ __launch_bounds__(NT) void ce_bwd_kernel(const T* logits, const long 
 // plain loss.  With W = sum_c w_c and, per valid pixel, s = (1 - eps) w_t + eps W / C:
 //   loss = [ (1 - eps) sum w_t (lse - x_t) + eps / C sum sum_c w_c (lse - x_c) ] / den,  den = sum w_t  (sums over the valid pixels)
 //   dx_c = ( s p_c - (1 - eps) w_t [c == t] - eps w_c / C ) / den
-// The block sums go to a row of the block's own ([grid][2] f64, ce_finalize_rows_ex_kernel adds them in a fixed order): no atomics.
+// The block sums go to a row of the block's own ([grid][2] f64, ce_finalize_rows_kernel<true> adds them in a fixed order): no atomics.
 __device__ __forceinline__ float class_weight_sum(const float* cw, int C) {
   if (!cw) return (float)C;
   float W = 0.f;
@@ -132,20 +130,11 @@ __global__ __launch_bounds__(NT) void ce_bwd_ex_kernel(const T* logits, const lo
 // The mean reduction makes the gradient linear in one unknown scalar (1 / #valid pixels, times grad_out), so the
 // forward pass accumulates the UNSCALED low-res gradient and backward is a scale + cast of 6 M elements.
 //
-//   block  = 256 consecutive output columns x a band of output rows of one image; lane = one output column.
-//   The column taps (i0x, i1x, l0x, l1x) of a lane never change, and the row taps change only every ~scale rows, so
-//   the lane keeps the two horizontally interpolated low-res rows aA[c], aB[c] in registers: a logit is ONE FMA,
-//   z_c = l0y*aA[c] + l1y*aB[c].  Softmax, loss and dz_c = (p_c - [t == c]) stay in registers; dz is accumulated into
-//   gA[c] += l0y*dz_c, gB[c] += l1y*dz_c and only when the row tap advances is a finished low-res row gathered
-//   horizontally through LDS (one thread per low-res cell and class) and added to the f32 gradient (global atomics:
-//   ~650 per 8 output rows of a block, each address touched by <= 4 blocks).
-// Run-to-run determinism: a low-res cell receives contributions from up to four blocks (two bands x two strips).  Each
-// block therefore stores ITS contribution to every (row, cell, class) of its footprint into a tile of its own (plain
-// stores, every element of the footprint written exactly once, nothing zero-filled), its loss / count partial into a row
-// of its own, and the backward kernel gathers the <= 4 tiles of a cell in a fixed order.  (Round 2 added them with f32
-// global atomics into a zero-filled buffer: last-bit differences from run to run that a train step amplifies.)
-//   ws = [nblocks][2] f64 loss rows, then [nblocks][tile_rows][tile_cells][CP] f32 tiles; block = (b * nband + band) * nstrip + strip
-// (CeGeom, ce_geom and the shape rule: headgeom.h, shared with softhead.hip)
+// Block layout, workspace layout and the flush protocol: headgeom.h.  Here: the lane keeps the two horizontally interpolated low-res
+// rows aA[c], aB[c] in registers, a logit is ONE FMA, z_c = l0y*aA[c] + l1y*aB[c]; softmax, loss and dz_c = (p_c - [t == c]) stay in
+// registers; dz is accumulated into gA[c] += l0y*dz_c, gB[c] += l1y*dz_c and a finished low-res row is flushed into the block's own
+// tile.  (Round 2 added the rows with f32 global atomics into a zero-filled buffer: last-bit differences from run to run that a
+// train step amplifies.)
 
 // MODE 0: mean cross-entropy (loss rows + unscaled gradient tiles).  MODE 1: the per-pixel cross-entropy only, written to `pix`
 // ([B][H][W] f32, 0 for ignored pixels) -- the input of the OHEM selection (TSS/losses/ohem_loss.py:11-12 without the 318.8 M-element
@@ -158,11 +147,10 @@ __global__ __launch_bounds__(NT) void ce_bwd_ex_kernel(const T* logits, const lo
 template <typename T, int CP, int MODE>
 __global__ __launch_bounds__(NT, (CP <= 20 ? 3 : 2)) void upsample_ce_onepass_kernel(const T* low, long ldl, const long long* target,
                                                                  float* tiles, double* lossrows, int B, int C, int h, int w,
-                                                                 int H, int W, int ignore_index, const CeGeom geo,
+                                                                 int H, int W, int ignore_index, const HeadGeom geo,
                                                                  float* pix, const float* sel, const float* cw, float eps) {
+  // block set-up, tables and flush of headgeom.h, written out (see "Who uses what" there)
   const int band_rows = geo.band_rows;
-  constexpr int MAXCELL = NT + 2, WTAB = 1024;
-  constexpr float LOG2E = 1.44269504088896340736f;
   // Hh[k][lane][c]: the one-hot half of the gradient, sum over the rows seen so far of (row weight) * [target == c], kept
   // per low-res row (k = buffer of row rA / rB).  The softmax half lives in registers (gA, gB); the two meet at flush time.
   // The kernel is VALU-bound (SQ_ACTIVE_INST_VALU = 89 % of the SIMD cycles): a compare + select per class for the one-hot
@@ -188,6 +176,7 @@ __global__ __launch_bounds__(NT, (CP <= 20 ? 3 : 2)) void upsample_ce_onepass_ke
   const int x = strip * NT + tid;
   const bool xin = x < W;
   const Tap tx = ac_tap(sx, xin ? x : W - 1, w);
+  // the strip's cells and the band's rows: head_strip_cells and head_band, the gather's expressions, written out like the rest
   const int cx0 = ac_tap(sx, strip * NT, w).i0;                     // first low-res column this strip touches
   const int xl = (strip * NT + NT - 1 < W) ? strip * NT + NT - 1 : W - 1;
   const int ncell = ac_tap(sx, xl, w).i1 - cx0 + 1;                 // <= NT + 2 for W >= w (host-checked)
@@ -389,78 +378,11 @@ __global__ __launch_bounds__(NT, (CP <= 20 ? 3 : 2)) void upsample_ce_onepass_ke
   }
 }
 
-// loss = sum(rows[.][0]) / sum(rows[.][1]) in a fixed order (one block)
-__global__ __launch_bounds__(NT) void ce_finalize_rows_kernel(const double* rows, int nrows, float* loss, float* inv_count) {
-  double sum, n;
-  if (lsw::row_sum2(rows, nrows, sum, n)) {
-    *loss = (float)(sum / n);          // n == 0 -> nan, like torch
-    *inv_count = n > 0.0 ? (float)(1.0 / n) : 0.f;
-  }
-}
-
-// The same sum for the weighted / smoothed entries: there the numerator of an empty denominator need not be 0 (valid pixels whose
-// class weight is 0 still carry the smoothing term), and torch's (1 - eps) * (0 / 0) + ... is nan, not inf.
-__global__ __launch_bounds__(NT) void ce_finalize_rows_ex_kernel(const double* rows, int nrows, float* loss, float* inv_count) {
-  double sum, n;
-  if (lsw::row_sum2(rows, nrows, sum, n)) {
-    *loss = n > 0.0 ? (float)(sum / n) : __builtin_nanf("");
-    *inv_count = n > 0.0 ? (float)(1.0 / n) : 0.f;
-  }
-}
-
-// first / last low-res row a band's block wrote, first cell / cell count of a strip: the same expressions as in the pass
-__device__ __forceinline__ void ce_band_rows(float sy, int band, int band_rows, int H, int h, int* r0, int* r1) {
-  const int ya = band * band_rows;
-  const int yb = ya + band_rows < H ? ya + band_rows : H;
-  *r0 = ac_tap(sy, ya, h).i0;
-  *r1 = ac_tap(sy, yb - 1, h).i1;
-}
-__device__ __forceinline__ void ce_strip_cells(float sx, int strip, int W, int w, int* c0, int* n) {
-  const int xl = (strip * NT + NT - 1 < W) ? strip * NT + NT - 1 : W - 1;
-  *c0 = ac_tap(sx, strip * NT, w).i0;
-  *n = ac_tap(sx, xl, w).i1 - *c0 + 1;
-}
-
-// dlow[b][r][cx][:] = (T)(grad_out / count * sum over the tiles that hold cell (r, cx), in (band, strip) order); thread = one
-// cell x 8 channels.  Channels >= CP (pitch padding) are written as zeros.
 template <typename T, int CP>
 __global__ __launch_bounds__(NT) void upsample_ce_gather_kernel(const float* tiles, const float* inv_count, const float* grad_out,
                                                                 T* dlow, long ldl, int B, int h, int w, int H, int W,
-                                                                const CeGeom geo) {
-  const float gs = (*inv_count) * (grad_out ? *grad_out : 1.f);
-  const float sy = ac_scale(h, H), sx = ac_scale(w, W);
-  const int cv = (int)(ldl / 8);
-  const long total = (long)B * h * w * cv;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int c8 = (int)(i % cv) * 8;
-    long q = i / cv;
-    const int cx = (int)(q % w); q /= w;
-    const int r = (int)(q % h);
-    const long b = q / h;
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = 0.f;
-    int ylo, yhi, xlo, xhi;
-    ac_window(sy, r, H, &ylo, &yhi);
-    ac_window(sx, cx, W, &xlo, &xhi);
-    for (int band = ylo / geo.band_rows; band <= yhi / geo.band_rows; ++band) {
-      int r0, r1;
-      ce_band_rows(sy, band, geo.band_rows, H, h, &r0, &r1);
-      if (r < r0 || r > r1) continue;
-      for (int strip = xlo / NT; strip <= xhi / NT; ++strip) {
-        int c0, n;
-        ce_strip_cells(sx, strip, W, w, &c0, &n);
-        if (cx < c0 || cx >= c0 + n) continue;
-        const float* t = tiles + ((((b * geo.nband + band) * geo.nstrip + strip) * geo.tile_rows + (r - r0)) * (long)geo.tile_cells
-                                  + (cx - c0)) * CP + c8;
-        if (c8 + 4 <= CP) { float u[4]; V4<float>::load(t, u); v[0] += u[0]; v[1] += u[1]; v[2] += u[2]; v[3] += u[3]; }
-        if (c8 + 8 <= CP) { float u[4]; V4<float>::load(t + 4, u); v[4] += u[0]; v[5] += u[1]; v[6] += u[2]; v[7] += u[3]; }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] *= gs;
-    V8<T>::store(dlow + ((b * h + r) * (long)w + cx) * ldl + c8, v);
-  }
+                                                                const HeadGeom geo) {
+  head_gather<T, CP>(tiles, inv_count, grad_out, dlow, ldl, B, h, w, H, W, geo);
 }
 
 // argmax over class planes (lowest index wins ties, like torch.argmax) + confusion matrix [C][C] (rows = truth)
@@ -511,6 +433,8 @@ __global__ __launch_bounds__(NT, 3) void upsample_argmax_kernel(const T* low, lo
   const int tid = threadIdx.x;
   for (int i = tid; i < C * C; i += NT) scm[i] = 0u;
   __syncthreads();
+  // head_block and head_taps written out: through the structs the float32 CP = 20 instance takes 130 registers instead of 128 and
+  // loses a wave per SIMD (0.126 -> 0.142 ms at 8 x 19 x 128 x 256 -> 1024 x 2048)
   const int nstrip = (W + NT - 1) / NT, nband = (H + band_rows - 1) / band_rows;
   int bid = blockIdx.x;
   const int strip = bid % nstrip; bid /= nstrip;
@@ -520,8 +444,8 @@ __global__ __launch_bounds__(NT, 3) void upsample_argmax_kernel(const T* low, lo
   const int x = strip * NT + tid;
   const bool xin = x < W;
   const Tap tx = ac_tap(sx, xin ? x : W - 1, w);
-  const int ya = band * band_rows;
-  const int yb = ya + band_rows < H ? ya + band_rows : H;
+  int ya, yb;
+  head_band(band, band_rows, H, &ya, &yb);
   float aA[CP], aB[CP];
   auto load_row = [&](int r, float* a) {
     const T* p0 = low + ((b * h + r) * (long)w + tx.i0) * ldl;
@@ -628,7 +552,7 @@ int tss_cross_entropy_fwd_ex(const void* logits, const long long* target, const 
       TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL((ce_fwd_ex_kernel<TT, false>), dim3(grid), dim3(NT), 0, (hipStream_t)stream, (const TT*)logits,
                                                target, weight, 0.f, lse, rows, B, C, HW, ignore_index));
   }
-  hipLaunchKernelGGL(ce_finalize_rows_ex_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, rows, grid, loss, inv_count);
+  hipLaunchKernelGGL(ce_finalize_rows_kernel<true>, dim3(1), dim3(NT), 0, (hipStream_t)stream, rows, grid, loss, inv_count);
   return tss::check_last("cross_entropy_fwd_ex");
 }
 
@@ -671,39 +595,30 @@ int tss_upsample_argmax_confusion(const void* low, long ldl, const long long* ta
                                   unsigned long long* confusion /*[C*C] accumulated*/, int B, int C, int h, int w,
                                   int H, int W, int ignore_index, int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(upsample_ce_shape_ok(C, ldl, h, w, H, W), TSS_ERR_SHAPE);
+  TSS_REQUIRE(head_shape_ok(C, 24, ldl, h, w, H, W), TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(low), TSS_ERR_ALIGN);
   if ((long)B * H * W == 0) return TSS_OK;
-  const int nstrip = (W + NT - 1) / NT;
-  int band_rows = 64;
-  while (band_rows > 16 && (long)B * nstrip * ((H + band_rows - 1) / band_rows) < 2048) band_rows /= 2;
-  const long grid = (long)B * nstrip * ((H + band_rows - 1) / band_rows);
+  const HeadGeom geo = head_geom(B, C, h, w, H, W, false);     // the bands of the loss pass; no tiles here
+  const long grid = head_blocks(B, geo);
   tss::ProfScope prof(TSS_K_ARGMAX, (hipStream_t)stream, (double)B * h * w * C * tss::esz(dtype) + (double)B * H * W * 9.0, 0);
   const size_t sh = (size_t)C * C * sizeof(unsigned int);
   TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
     hipLaunchKernelGGL((upsample_argmax_kernel<TT, CPV>), dim3((int)grid), dim3(NT), sh, (hipStream_t)stream,
-                       (const TT*)low, ldl, target, pred, confusion, B, C, h, w, H, W, ignore_index, band_rows)));
+                       (const TT*)low, ldl, target, pred, confusion, B, C, h, w, H, W, ignore_index, geo.band_rows)));
   return tss::check_last("upsample_argmax_confusion");
 }
 
-long tss_upsample_ce_ws(int B, int C, int h, int w, int H, int W) {
-  if (B <= 0 || C <= 0 || C > 24 || h <= 0 || w <= 0 || H < h || W < w) return 0;
-  const CeGeom g = ce_geom(B, h, w, H, W);
-  const long nblocks = (long)B * g.nband * g.nstrip;
-  int CP = 0;
-  TSS_WITH_CLASS_REGS(C, CP = CPV);   // the tiles are CPV floats per cell: the same choice as the kernels that fill them
-  return nblocks * 4 /* 2 doubles */ + nblocks * g.tile_rows * g.tile_cells * CP;
-}
+long tss_upsample_ce_ws(int B, int C, int h, int w, int H, int W) { return head_ws_floats(B, C, 24, h, w, H, W, false); }
 
 int tss_upsample_ce_fwd(const void* low, long ldl, const long long* target, float* ws /* tss_upsample_ce_ws floats, not initialised */,
                         float* loss, float* inv_count,
                         int B, int C, int h, int w, int H, int W, int ignore_index, int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(upsample_ce_shape_ok(C, ldl, h, w, H, W), TSS_ERR_SHAPE);
+  TSS_REQUIRE(head_shape_ok(C, 24, ldl, h, w, H, W), TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(low) && tss::aligned16(ws), TSS_ERR_ALIGN);
   if ((long)B * H * W == 0) return TSS_OK;
-  const CeGeom geo = ce_geom(B, h, w, H, W);
-  const long grid = (long)B * geo.nstrip * geo.nband;
+  const HeadGeom geo = head_geom(B, C, h, w, H, W, false);
+  const long grid = head_blocks(B, geo);
   double* lossrows = reinterpret_cast<double*>(ws);
   float* tiles = ws + grid * 4;
   {
@@ -713,7 +628,7 @@ int tss_upsample_ce_fwd(const void* low, long ldl, const long long* target, floa
       hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 0>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,
                          (const TT*)low, ldl, target, tiles, lossrows, B, C, h, w, H, W, ignore_index, geo, nullptr, nullptr, nullptr, 0.f)));
   }
-  hipLaunchKernelGGL(ce_finalize_rows_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, lossrows, (int)grid, loss, inv_count);
+  hipLaunchKernelGGL(ce_finalize_rows_kernel<false>, dim3(1), dim3(NT), 0, (hipStream_t)stream, lossrows, (int)grid, loss, inv_count);
   return tss::check_last("upsample_ce_fwd");
 }
 
@@ -723,11 +638,11 @@ int tss_upsample_ce_fwd_ex(const void* low, long ldl, const long long* target, c
                            float* loss, float* inv_count, int B, int C, int h, int w, int H, int W, int ignore_index, int dtype,
                            void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(upsample_ce_shape_ok(C, ldl, h, w, H, W) && label_smoothing >= 0.f && label_smoothing <= 1.f, TSS_ERR_SHAPE);
+  TSS_REQUIRE(head_shape_ok(C, 24, ldl, h, w, H, W) && label_smoothing >= 0.f && label_smoothing <= 1.f, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(low) && tss::aligned16(ws), TSS_ERR_ALIGN);
   if ((long)B * H * W == 0) return TSS_OK;
-  const CeGeom geo = ce_geom(B, h, w, H, W);
-  const long grid = (long)B * geo.nstrip * geo.nband;
+  const HeadGeom geo = head_geom(B, C, h, w, H, W, false);
+  const long grid = head_blocks(B, geo);
   double* lossrows = reinterpret_cast<double*>(ws);
   float* tiles = ws + grid * 4;
   {
@@ -742,7 +657,7 @@ int tss_upsample_ce_fwd_ex(const void* low, long ldl, const long long* target, c
         hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 3>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const TT*)low, ldl,
                            target, tiles, lossrows, B, C, h, w, H, W, ignore_index, geo, nullptr, nullptr, weight, 0.f)));
   }
-  hipLaunchKernelGGL(ce_finalize_rows_ex_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, lossrows, (int)grid, loss, inv_count);
+  hipLaunchKernelGGL(ce_finalize_rows_kernel<true>, dim3(1), dim3(NT), 0, (hipStream_t)stream, lossrows, (int)grid, loss, inv_count);
   return tss::check_last("upsample_ce_fwd_ex");
 }
 
@@ -750,11 +665,11 @@ int tss_upsample_ce_fwd_ex(const void* low, long ldl, const long long* target, c
 int tss_upsample_pixel_ce(const void* low, long ldl, const long long* target, float* pix, int B, int C, int h, int w, int H, int W,
                           int ignore_index, int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(upsample_ce_shape_ok(C, ldl, h, w, H, W) && pix, TSS_ERR_SHAPE);
+  TSS_REQUIRE(head_shape_ok(C, 24, ldl, h, w, H, W) && pix, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(low), TSS_ERR_ALIGN);
   if ((long)B * H * W == 0) return TSS_OK;
-  const CeGeom geo = ce_geom(B, h, w, H, W);
-  const long grid = (long)B * geo.nstrip * geo.nband;
+  const HeadGeom geo = head_geom(B, C, h, w, H, W, false);
+  const long grid = head_blocks(B, geo);
   tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream, (double)B * h * w * C * tss::esz(dtype) + (double)B * H * W * 12.0, 0);
   TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
     hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 1>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,
@@ -767,11 +682,11 @@ int tss_upsample_pixel_ce(const void* low, long ldl, const long long* target, fl
 int tss_upsample_ohem_grad(const void* low, long ldl, const long long* target, const float* pix, const float* sel, float* ws,
                            int B, int C, int h, int w, int H, int W, int ignore_index, int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(upsample_ce_shape_ok(C, ldl, h, w, H, W) && pix && sel && ws, TSS_ERR_SHAPE);
+  TSS_REQUIRE(head_shape_ok(C, 24, ldl, h, w, H, W) && pix && sel && ws, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(low) && tss::aligned16(ws), TSS_ERR_ALIGN);
   if ((long)B * H * W == 0) return TSS_OK;
-  const CeGeom geo = ce_geom(B, h, w, H, W);
-  const long grid = (long)B * geo.nstrip * geo.nband;
+  const HeadGeom geo = head_geom(B, C, h, w, H, W, false);
+  const long grid = head_blocks(B, geo);
   float* tiles = ws + grid * 4;
   tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream, (double)B * h * w * C * (tss::esz(dtype) + 8.0) + (double)B * H * W * 12.0, 0);
   TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
@@ -783,12 +698,12 @@ int tss_upsample_ohem_grad(const void* low, long ldl, const long long* target, c
 int tss_upsample_ce_bwd(const float* ws, const float* inv_count, const float* grad_out, void* dlow, long ldl,
                         int B, int C, int h, int w, int H, int W, int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(upsample_ce_shape_ok(C, ldl, h, w, H, W), TSS_ERR_SHAPE);
+  TSS_REQUIRE(head_shape_ok(C, 24, ldl, h, w, H, W), TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(ws) && tss::aligned16(dlow), TSS_ERR_ALIGN);
   const long n = (long)B * h * w * ldl;
   if (n == 0) return TSS_OK;
-  const CeGeom geo = ce_geom(B, h, w, H, W);
-  const float* tiles = ws + (long)B * geo.nstrip * geo.nband * 4;
+  const HeadGeom geo = head_geom(B, C, h, w, H, W, false);
+  const float* tiles = ws + head_blocks(B, geo) * 4;
   tss::ProfScope prof(TSS_K_UPSAMPLE_CE_BWD, (hipStream_t)stream, (double)n * (4.0 + tss::esz(dtype)), 0);
   TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
     hipLaunchKernelGGL((upsample_ce_gather_kernel<TT, CPV>), dim3(tss::grid_for(n / 8, NT)), dim3(NT), 0, (hipStream_t)stream,

@@ -14,14 +14,12 @@
 // rows and keeps their MS_ROWS x CP scores in registers; maps are the outer loop, so a map's rows are fetched once per
 // band.  The low-res maps total a few MB (L2 / Infinity Cache); only the prediction and the C x C counts reach HBM.
 // Counts go through LDS and one integer atomic per non-zero cell: exact and order-independent, so bit-reproducible.
-#include "common.h"
+#include "headgeom.h"
 
 namespace {
 
-constexpr int NT = 256;
 constexpr int MS_ROWS = 4;     // band height: MS_ROWS x CP score registers per lane; with the two rows and the logits that is past the 168
                                // registers of 3 waves per SIMD (it spilled 59..131 of them there), so the kernel asks for 2
-constexpr int MS_MAXK = 16;
 
 template <typename TO>
 __global__ __launch_bounds__(NT) void resize_flip_planar_kernel(const float* x, TO* y, long planes /* B*C */, int Hin, int Win,
@@ -40,10 +38,6 @@ __global__ __launch_bounds__(NT) void resize_flip_planar_kernel(const float* x, 
   }
 }
 
-// The descriptors as the kernel takes them: by value, in the kernel argument segment (no device memory, no copy to wait for).
-struct MsMap { const void* low; long first; int ldl, h, w, flip; };
-struct MsArgs { MsMap m[MS_MAXK]; };
-
 template <typename T, int CP, int MODE>
 __global__ __launch_bounds__(NT, 2) void multiscale_argmax_kernel(const MsArgs args, int K, const long long* target,
                                                                   unsigned char* pred_out, unsigned long long* cm, int B, int C,
@@ -52,15 +46,10 @@ __global__ __launch_bounds__(NT, 2) void multiscale_argmax_kernel(const MsArgs a
   const int tid = threadIdx.x;
   for (int i = tid; i < C * C; i += NT) scm[i] = 0u;
   __syncthreads();
-  const int nstrip = (W + NT - 1) / NT, nband = (H + MS_ROWS - 1) / MS_ROWS;
-  int bid = blockIdx.x;
-  const int strip = bid % nstrip; bid /= nstrip;
-  const int band = bid % nband;
-  const long b = bid / nband;
-  const int x = strip * NT + tid;
-  const bool xin = x < W;
-  const int xc = xin ? x : W - 1;              // lanes past the edge compute column W-1 and write nothing
-  const int ya = band * MS_ROWS;
+  const HeadBlock blk = head_block((W + NT - 1) / NT, (H + MS_ROWS - 1) / MS_ROWS, MS_ROWS, H, W);
+  const long b = blk.b;
+  const int x = blk.x, ya = blk.ya;
+  const bool xin = blk.xin;
   float score[MS_ROWS][CP];
 #pragma unroll
   for (int j = 0; j < MS_ROWS; ++j)
@@ -71,28 +60,16 @@ __global__ __launch_bounds__(NT, 2) void multiscale_argmax_kernel(const MsArgs a
     const MsMap mp = args.m[k];                // uniform: scalar loads from the argument segment
     const int h = mp.h, w = mp.w;
     const long ldl = mp.ldl;
-    const float sy = ac_scale(h, H), sx = ac_scale(w, W);
-    const Tap tx = ac_tap(sx, mp.flip ? W - 1 - xc : xc, w);
+    const HeadTaps map = head_taps(blk, h, w, H, W, mp.flip);
+    const float sy = map.sy;
+    const Tap tx = map.tx;
     const T* const img = reinterpret_cast<const T*>(mp.low) + (mp.first + b) * h * (long)w * ldl;
     float aA[CP], aB[CP];
-    auto load_row = [&](int r, float* a) {
-      const T* p0 = img + ((long)r * w + tx.i0) * ldl;
-      const T* p1 = img + ((long)r * w + tx.i1) * ldl;
-#pragma unroll
-      for (int c4 = 0; c4 < CP; c4 += 4) {
-        float u[4] = {0.f, 0.f, 0.f, 0.f}, v[4] = {0.f, 0.f, 0.f, 0.f};
-        if (c4 < C) {                          // uniform; ldl >= round_up(C, 4) (host-checked), nothing past it is read
-          V4<T>::load(p0 + c4, u);
-          V4<T>::load(p1 + c4, v);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) a[c4 + q] = (c4 + q < C) ? tx.l0 * u[q] + tx.l1 * v[q] : 0.f;   // pad channels hold anything
-      }
-    };
+    auto load = [&](int r, float* a) { load_row<CP, false, false>(img, r, w, ldl, tx, C, a); };   // pad channels hold anything
     int rA = ac_tap(sy, ya, h).i0;
     int rB = rA + (rA < h - 1 ? 1 : 0);
-    load_row(rA, aA);
-    load_row(rB, aB);
+    load(rA, aA);
+    load(rB, aB);
 #pragma unroll
     for (int j = 0; j < MS_ROWS; ++j) {
       const int y = ya + j;
@@ -106,7 +83,7 @@ __global__ __launch_bounds__(NT, 2) void multiscale_argmax_kernel(const MsArgs a
           rB = rA + (rA < h - 1 ? 1 : 0);
 #pragma unroll
           for (int c = 0; c < CP; ++c) aA[c] = aB[c];
-          load_row(rB, aB);
+          load(rB, aB);
         }
         float z[CP];
 #pragma unroll
@@ -177,16 +154,9 @@ int tss_multiscale_argmax_confusion(const tss_msmap* maps, int K, const long lon
   TSS_REQUIRE(maps && K >= 1 && K <= MS_MAXK && C >= 1 && C <= 24 && B >= 0 && H >= 0 && W >= 0 && (mode == 0 || mode == 1),
               TSS_ERR_SHAPE);
   MsArgs args = {};
-  double low_bytes = 0.0;
-  for (int k = 0; k < K; ++k) {
-    const tss_msmap& m = maps[k];
-    TSS_REQUIRE(m.low && (m.ldl % 8) == 0 && m.ldl >= (C + 3) / 4 * 4 && m.ldl <= (1L << 30) && m.h >= 1 && m.w >= 1 &&
-                m.h <= H && m.w <= W && m.first >= 0, TSS_ERR_SHAPE);
-    TSS_REQUIRE(tss::aligned16(m.low), TSS_ERR_ALIGN);
-    args.m[k].low = m.low; args.m[k].first = m.first; args.m[k].ldl = (int)m.ldl;
-    args.m[k].h = m.h; args.m[k].w = m.w; args.m[k].flip = m.flip ? 1 : 0;
-    low_bytes += (double)B * m.h * m.w * C * tss::esz(dtype);
-  }
+  double low_bytes;
+  const int err = ms_args(maps, K, B, C, H, W, dtype, &args, &low_bytes);
+  if (err != TSS_OK) return err;
   const bool counts = confusion && target;
   if ((long)B * H * W == 0 || (!pred && !counts)) return TSS_OK;
   const long grid = (long)B * ((W + NT - 1) / NT) * ((H + MS_ROWS - 1) / MS_ROWS);

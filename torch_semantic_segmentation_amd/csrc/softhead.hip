@@ -1,12 +1,9 @@
 // Focal loss and soft Dice loss (softloss.hip's definitions) of the bilinearly upsampled logits, straight from the LOW-RES NHWC logits:
 // the fused decoder head of loss.hip for the other two pixel-wise losses.  The (B, C, H, W) logits and their gradient never exist.
 //
-// The geometry is that of upsample_ce_onepass_kernel (loss.hip; headgeom.h): block = 256 output columns x a band of output rows of
-// one image, lane = one output column, the two horizontally interpolated low-res rows aA, aB in registers (times log2 e), a logit is
-// one FMA; the softmax half of the gradient is accumulated in registers (gA, gB), the one-hot half per lane in LDS (Hh), and a
-// finished low-res row is gathered through LDS into the block's own tile (plain stores, every element of the footprint written once,
-// nothing zero-filled).  tss_upsample_ce_bwd gathers the tiles in a fixed order.  No atomics, no host read-back: capturable, and two
-// runs give the same bits.  A pixel counts iff target != ignore_index (has_ignore = 0: no ignore index) and 0 <= target < C.
+// Block layout, workspace layout and the flush protocol are those of upsample_ce_onepass_kernel: headgeom.h.  tss_upsample_ce_bwd gathers
+// the tiles in a fixed order.  No atomics, no host read-back: capturable, and two runs give the same bits.  A pixel counts iff
+// target != ignore_index (has_ignore = 0: no ignore index) and 0 <= target < C.
 //
 //   focal (C <= 24), one pass: per valid pixel p = p_t, q = sum_{c != t} p_c (summed, not 1 - p), lp = log p_t,
 //       w = exp(q^gamma) (variant 0) or q^gamma (variant 1),  coef = w - w'(q) p lp  (w' = gamma q^(gamma-1) w, variant 1: gamma q^(gamma-1);
@@ -22,18 +19,14 @@
 //       (loss and the 2C coefficients a_c = -2 / (C (U_c + s)), b_c = (2 I_c + s) / (C (U_c + s)^2), U_c = P_c + N_c; all zero when no
 //       pixel is valid), and a gradient pass that recomputes the softmax: dz_k = p_k (b_k - S) + [k == t] a_t p_t,
 //       S = sum_c b_c p_c + a_t p_t (coefficients in LDS).  tss_upsample_ce_bwd gathers with *inv_count = 1.
-// The pass below repeats the block set-up and the row flush of upsample_ce_onepass_kernel instead of adding modes to it: that
-// kernel's instances are the benchmark's hot path and stay byte for byte what they were.
 #include "headgeom.h"
 
 namespace {
 
-constexpr int NT = lsw::NT;
 constexpr int WAVES = NT / 64;
 constexpr int FIN_NT = 1024;                 // the Dice finalize block: 16 waves, one column of the rows per wave at a time
 constexpr int DICE_COEF = 64;                // floats at the head of the Dice workspace: a[24], b[24], padding to 256 bytes
 constexpr int CPMAX = 24;
-constexpr float LOG2E = 1.44269504088896340736f;
 constexpr float LN2F = 0.69314718055994530942f;
 
 enum { SH_FOCAL = 0, SH_DICE_STATS = 1, SH_DICE_GRAD = 2 };
@@ -56,126 +49,45 @@ __device__ __forceinline__ void focal_terms(float p, float q, float lp, float ga
 template <typename T, int CP, int KIND>
 __global__ __launch_bounds__(NT, (CP <= 20 ? 3 : 2)) void softhead_pass_kernel(const T* low, long ldl, const long long* target, float* tiles,
                                                                                 double* rows, int C, int h, int w, int H, int W,
-                                                                                int ignore_index, int has_ignore, const CeGeom geo,
+                                                                                int ignore_index, int has_ignore, const HeadGeom geo,
                                                                                 float gamma, int variant, const float* coef) {
   constexpr bool TILES = KIND != SH_DICE_STATS;
-  constexpr int MAXCELL = NT + 2, WTAB = 1024;
   // Hh[k][lane][c]: SH_FOCAL / SH_DICE_GRAD the one-hot half of the gradient per low-res row buffer; SH_DICE_STATS k = 0: I, k = 1: N per lane
   __shared__ __align__(16) float Hh[2][NT * CP];
-  __shared__ int Li0[NT], Li1[NT], Wlo[MAXCELL], Whi[MAXCELL];
-  __shared__ float Ll1[NT];
-  __shared__ float Wt[WTAB];                          // gather weights [cell][lane - Wlo[cell]] (fixed for the block)
-  __shared__ double red[2][WAVES];
+  __shared__ GatherLds tabs;
   __shared__ __align__(16) float Ca[CP], Cb[CP];      // SH_DICE_GRAD: the coefficients, 0 for the padding classes
   const int tid = threadIdx.x;
   if (KIND == SH_DICE_GRAD && tid < CP) { Ca[tid] = coef[tid]; Cb[tid] = coef[CPMAX + tid]; }
-  const int nstrip = geo.nstrip, nband = geo.nband, band_rows = geo.band_rows;
   float* const tile = TILES ? tiles + (long)blockIdx.x * geo.tile_rows * geo.tile_cells * CP : nullptr;
-  int bid = blockIdx.x;
-  const int strip = bid % nstrip; bid /= nstrip;
-  const int band = bid % nband;
-  const long b = bid / nband;
-  const float sy = ac_scale(h, H), sx = ac_scale(w, W);
-  const int x = strip * NT + tid;
-  const bool xin = x < W;
-  const Tap tx = ac_tap(sx, xin ? x : W - 1, w);
-  const int ya = band * band_rows;
-  const int yb = ya + band_rows < H ? ya + band_rows : H;
-  int ncell = 0, maxwin = 0;
-  bool wtab = false;
-  if (TILES) {
-    const int cx0 = ac_tap(sx, strip * NT, w).i0;                     // first low-res column this strip touches
-    const int xl = (strip * NT + NT - 1 < W) ? strip * NT + NT - 1 : W - 1;
-    ncell = ac_tap(sx, xl, w).i1 - cx0 + 1;                           // <= NT + 2 for W >= w (host-checked)
-    Li0[tid] = xin ? tx.i0 - cx0 : -1;      // lanes past the image edge match no cell
-    Li1[tid] = xin ? tx.i1 - cx0 : -1;
-    Ll1[tid] = tx.l1;
-    maxwin = sx > 0.f ? (int)(2.f / sx) + 6 : NT;                     // widest window of lanes whose taps can include one low-res column
-    wtab = (long)ncell * maxwin <= WTAB;
-    for (int cell = tid; cell < ncell; cell += NT) {
-      int lo, hi;
-      ac_window(sx, cx0 + cell, W, &lo, &hi);
-      lo -= strip * NT; hi -= strip * NT;
-      lo = lo < 0 ? 0 : lo;
-      hi = hi > NT - 1 ? NT - 1 : hi;
-      if (wtab && hi - lo + 1 > maxwin) hi = lo + maxwin - 1;          // cannot happen (conservative bound); keeps the table safe
-      Wlo[cell] = lo;
-      Whi[cell] = hi;
-    }
-  }
+  const HeadBlock blk = head_block(geo.nstrip, geo.nband, geo.band_rows, H, W);
+  const HeadTaps map = head_taps(blk, h, w, H, W);
+  const long b = blk.b;
+  const int x = blk.x, ya = blk.ya, yb = blk.yb;
+  const bool xin = blk.xin;
+  const float sy = map.sy;
+  const Tap tx = map.tx;
+  Gather gt = {};
+  if constexpr (TILES) gt = gather_windows(&tabs, blk, map, h, w, W);
 #pragma unroll
   for (int c4 = 0; c4 < CP; c4 += 4) {
     *reinterpret_cast<float4*>(&Hh[0][tid * CP + c4]) = make_float4(0.f, 0.f, 0.f, 0.f);
     *reinterpret_cast<float4*>(&Hh[1][tid * CP + c4]) = make_float4(0.f, 0.f, 0.f, 0.f);
   }
   __syncthreads();
-  if (TILES && wtab) {
-    for (int i = tid; i < ncell * maxwin; i += NT) {
-      const int cell = i / maxwin, k = i - cell * maxwin;
-      const int l = Wlo[cell] + k;
-      float wgt = 0.f;
-      if (l <= Whi[cell]) { const float l1 = Ll1[l]; wgt = (Li0[l] == cell ? 1.f - l1 : 0.f) + (Li1[l] == cell ? l1 : 0.f); }
-      Wt[i] = wgt;
-    }
-  }
+  if constexpr (TILES) gather_weights(gt);
 
   int rA = ac_tap(sy, ya, h).i0;
   int rB = rA + (rA < h - 1 ? 1 : 0);
-  const int r_first = rA;
   float aA[CP], aB[CP], gA[CP], gB[CP];      // SH_DICE_STATS: gA holds the lane's sum of p_c, gB is not used
-  auto load_row = [&](int r, float* a) {     // a[c] = (l0x * L[r][i0x][c] + l1x * L[r][i1x][c]) * log2(e), -inf for the padding classes
-    const T* p0 = low + ((b * h + r) * (long)w + tx.i0) * ldl;
-    const T* p1 = low + ((b * h + r) * (long)w + tx.i1) * ldl;
-#pragma unroll
-    for (int c4 = 0; c4 < CP; c4 += 4) {
-      float u[4] = {0.f, 0.f, 0.f, 0.f}, v[4] = {0.f, 0.f, 0.f, 0.f};
-      if (c4 < C) {                            // uniform; a group that starts below C ends inside the pitch (ldl >= round_up(C, 4))
-        V4<T>::load(p0 + c4, u);
-        V4<T>::load(p1 + c4, v);
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) a[c4 + q] = (c4 + q < C) ? (tx.l0 * u[q] + tx.l1 * v[q]) * LOG2E : -TSS_INF;
-    }
-  };
-  // finished low-res row r (buffer k): the lane's gradient g[] - Hh[k][] is parked in Hh[k] (plain stores), then one thread per
-  // (cell, class) sums the lanes whose column taps include that cell and stores the sum into the block's tile
+  auto load = [&](int r, float* a) { load_row<CP, true, true>(low, b * h + r, w, ldl, tx, C, a); };
   auto flush_row = [&](int r, int k, const float* g) {
-    float* G = Hh[k];
-#pragma unroll
-    for (int c4 = 0; c4 < CP; c4 += 4) {
-      const float4 hv = *reinterpret_cast<const float4*>(G + tid * CP + c4);
-      *reinterpret_cast<float4*>(G + tid * CP + c4) = make_float4(g[c4] - hv.x, g[c4 + 1] - hv.y, g[c4 + 2] - hv.z, g[c4 + 3] - hv.w);
-    }
-    __syncthreads();
-    const int tr = r - r_first;
-    if (tr >= 0 && tr < geo.tile_rows) {     // always (the host's tile extent is conservative); keeps the stores inside the tile
-      float* drow = tile + (long)tr * geo.tile_cells * CP;
-      for (int i = tid; i < ncell * CP; i += NT) {
-        const int cell = i / CP, c = i - cell * CP;
-        if (cell >= geo.tile_cells) continue;
-        const int llo = Wlo[cell], lhi = Whi[cell];
-        float sum = 0.f;
-        if (wtab) {
-          const float* wt = Wt + cell * maxwin - llo;
-          for (int l = llo; l <= lhi; ++l) sum += wt[l] * G[l * CP + c];
-        } else {
-          for (int l = llo; l <= lhi; ++l) {
-            const float l1 = Ll1[l];
-            const float wgt = (Li0[l] == cell ? 1.f - l1 : 0.f) + (Li1[l] == cell ? l1 : 0.f);
-            sum += wgt * G[l * CP + c];
-          }
-        }
-        drow[i] = sum;                       // [cell][c]: every element of the block's footprint, exactly once
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c4 = 0; c4 < CP; c4 += 4) *reinterpret_cast<float4*>(G + tid * CP + c4) = make_float4(0.f, 0.f, 0.f, 0.f);
+    head_flush_row<CP>(gt, geo, Hh[k], g, r, CP, [](int, float*) {},
+                       [&](int tr, int, int, int i, float sum) { tile[(long)tr * geo.tile_cells * CP + i] = sum; });   // [cell][c]
   };
 
   int kA = 0;                                  // Hh[kA] belongs to row rA, Hh[kA ^ 1] to row rB
-  load_row(rA, aA);
-  load_row(rB, aB);
+  load(rA, aA);
+  load(rB, aB);
 #pragma unroll
   for (int c = 0; c < CP; ++c) { gA[c] = 0.f; gB[c] = 0.f; }
   __syncthreads();
@@ -187,7 +99,7 @@ __global__ __launch_bounds__(NT, (CP <= 20 ? 3 : 2)) void softhead_pass_kernel(c
     const long long t = tnext;
     if (y + 1 < yb) tnext = trow[(long)(y + 1 - ya) * W];      // next row's target under this row's arithmetic
     const Tap ty = ac_tap(sy, y, h);                           // uniform over the block
-    while (rA < ty.i0) {                                       // row tap advanced (uniform; by one: H >= h)
+    while (rA < ty.i0) {                                       // row tap advanced (headgeom.h)
       if (TILES) flush_row(rA, kA, gA);
       kA ^= 1;
       rA = rB;
@@ -197,7 +109,7 @@ __global__ __launch_bounds__(NT, (CP <= 20 ? 3 : 2)) void softhead_pass_kernel(c
         aA[c] = aB[c];
         if (TILES) { gA[c] = gB[c]; gB[c] = 0.f; }
       }
-      load_row(rB, aB);
+      load(rB, aB);
     }
     const bool valid = xin && (!has_ignore || t != (long long)ignore_index) && t >= 0 && t < C;
     const int ti = valid ? (int)t : -1;
@@ -299,14 +211,10 @@ __global__ __launch_bounds__(NT, (CP <= 20 ? 3 : 2)) void softhead_pass_kernel(c
   }
   const int lane = tid & 63, wave = tid >> 6;
   if (KIND == SH_FOCAL) {
-    const double ds = wave_sum((double)lsum), dc = wave_sum((double)lcnt);
-    if (lane == 0) { red[0][wave] = ds; red[1][wave] = dc; }
-    __syncthreads();
-    if (tid == 0) {
-      double a = 0.0, c = 0.0;
-      for (int wv = 0; wv < WAVES; ++wv) { a += red[0][wv]; c += red[1][wv]; }
-      rows[2 * (long)blockIdx.x] = a;
-      rows[2 * (long)blockIdx.x + 1] = c;
+    double ds = (double)lsum, dc = (double)lcnt;
+    if (lsw::block_sum2(ds, dc)) {
+      rows[2 * (long)blockIdx.x] = ds;
+      rows[2 * (long)blockIdx.x + 1] = dc;
     }
   }
   if (KIND == SH_DICE_STATS) {
@@ -420,7 +328,7 @@ __global__ __launch_bounds__(FIN_NT) void softhead_dice_finalize_kernel(const do
   }
 }
 
-inline bool softhead_grid_ok(int B, const CeGeom& geo) { return B >= 0 && (long)B * geo.nstrip * geo.nband <= 0x7fffffffL; }
+inline bool softhead_grid_ok(int B, const HeadGeom& geo) { return B >= 0 && head_blocks(B, geo) <= 0x7fffffffL; }
 
 inline double pass_bytes(int B, int C, int h, int w, int H, int W, int dtype) {
   return (double)B * h * w * C * (tss::esz(dtype) + 8.0) + (double)B * H * W * 8.0;
@@ -434,13 +342,13 @@ int tss_upsample_focal_fwd(const void* low, long ldl, const long long* target, f
                            float* loss, float* scale, int B, int C, int h, int w, int H, int W, int ignore_index, int has_ignore,
                            float alpha, float gamma, int variant, int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(upsample_ce_shape_ok(C, ldl, h, w, H, W) && gamma >= 0.f && (variant == 0 || variant == 1), TSS_ERR_SHAPE);
+  TSS_REQUIRE(head_shape_ok(C, CPMAX, ldl, h, w, H, W) && gamma >= 0.f && (variant == 0 || variant == 1), TSS_ERR_SHAPE);
   TSS_REQUIRE(target && ws && loss && scale, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(low) && tss::aligned16(ws), TSS_ERR_ALIGN);
   if ((long)B * H * W == 0) return TSS_OK;
-  const CeGeom geo = ce_geom(B, h, w, H, W);
+  const HeadGeom geo = head_geom(B, C, h, w, H, W, false);
   TSS_REQUIRE(softhead_grid_ok(B, geo), TSS_ERR_SHAPE);
-  const long grid = (long)B * geo.nstrip * geo.nband;
+  const long grid = head_blocks(B, geo);
   double* rows = reinterpret_cast<double*>(ws);
   float* tiles = ws + grid * 4;
   const hipStream_t st = (hipStream_t)stream;
@@ -475,20 +383,20 @@ int tss_focal_coef_from_ce(float* pix, const long long* target, double* rows /*[
 // floats of the Dice workspace: 64 for the coefficients, then [nblocks][3][C] f64 rows; 0 for a refused shape
 long tss_upsample_dice_ws(int B, int C, int h, int w, int H, int W) {
   if (B <= 0 || C <= 0 || C > CPMAX || h <= 0 || w <= 0 || H < h || W < w) return 0;
-  const CeGeom g = ce_geom(B, h, w, H, W);
-  return DICE_COEF + (long)B * g.nband * g.nstrip * 3 * C * 2;
+  const HeadGeom g = head_geom(B, C, h, w, H, W, false);
+  return DICE_COEF + head_blocks(B, g) * 3 * C * 2;
 }
 
 int tss_upsample_dice_fwd(const void* low, long ldl, const long long* target, float* dice_ws /* tss_upsample_dice_ws floats, not initialised */,
                           float* loss, int B, int C, int h, int w, int H, int W, int ignore_index, int has_ignore, float smooth,
                           int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(upsample_ce_shape_ok(C, ldl, h, w, H, W) && smooth >= 0.f && target && dice_ws && loss, TSS_ERR_SHAPE);
+  TSS_REQUIRE(head_shape_ok(C, CPMAX, ldl, h, w, H, W) && smooth >= 0.f && target && dice_ws && loss, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(low) && tss::aligned16(dice_ws), TSS_ERR_ALIGN);
   if ((long)B * H * W == 0) return TSS_OK;
-  const CeGeom geo = ce_geom(B, h, w, H, W);
+  const HeadGeom geo = head_geom(B, C, h, w, H, W, false);
   TSS_REQUIRE(softhead_grid_ok(B, geo), TSS_ERR_SHAPE);
-  const long grid = (long)B * geo.nstrip * geo.nband;
+  const long grid = head_blocks(B, geo);
   double* rows = reinterpret_cast<double*>(dice_ws + DICE_COEF);
   const hipStream_t st = (hipStream_t)stream;
   {
@@ -504,12 +412,12 @@ int tss_upsample_dice_fwd(const void* low, long ldl, const long long* target, fl
 int tss_upsample_dice_grad(const void* low, long ldl, const long long* target, const float* dice_ws, float* ws /* tss_upsample_ce_ws floats */,
                            int B, int C, int h, int w, int H, int W, int ignore_index, int has_ignore, int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(upsample_ce_shape_ok(C, ldl, h, w, H, W) && target && dice_ws && ws, TSS_ERR_SHAPE);
+  TSS_REQUIRE(head_shape_ok(C, CPMAX, ldl, h, w, H, W) && target && dice_ws && ws, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(low) && tss::aligned16(dice_ws) && tss::aligned16(ws), TSS_ERR_ALIGN);
   if ((long)B * H * W == 0) return TSS_OK;
-  const CeGeom geo = ce_geom(B, h, w, H, W);
+  const HeadGeom geo = head_geom(B, C, h, w, H, W, false);
   TSS_REQUIRE(softhead_grid_ok(B, geo), TSS_ERR_SHAPE);
-  const long grid = (long)B * geo.nstrip * geo.nband;
+  const long grid = head_blocks(B, geo);
   float* tiles = ws + grid * 4;
   tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream, pass_bytes(B, C, h, w, H, W, dtype), 0);
   TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,

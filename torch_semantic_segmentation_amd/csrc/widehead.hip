@@ -15,23 +15,16 @@
 // No tensor of B x C x H x W elements exists; the only per-pixel arrays in memory are the f32 `pix` of the OHEM pair.
 // Counts: C x C u32 counters in LDS up to WCM_LDS classes, 64-bit integer atomics on the matrix past that (integer adds
 // commute: exact and bit-reproducible).  No float atomics.  LDS is dynamic throughout (the CE pass needs 68 KiB).
-#include "losssweep.h"
+#include "headgeom.h"
 
 namespace {
 
-constexpr int NT = lsw::NT;
 constexpr int WK = 16;            // classes per chunk: 5 x 16 floats of class registers per lane
-constexpr int WROWS = 16;         // output rows per band: WROWS x 256 floats of LDS per per-pixel quantity
 constexpr int WMAXC = 256;
 constexpr int WCM_LDS = 96;       // C x C u32 counters in LDS up to here (36 KiB)
-constexpr int WTAB = 1024;
 constexpr int MSW_ROWS = 2;       // band of the multi-scale kernel: MS_MAXK x MSW_ROWS x 256 x (max, 1/sum) = 64 KiB
-constexpr int MS_MAXK = 16;
 constexpr int WIDE_LDS_CAP = 160 * 1024;
-constexpr float LOG2E = 1.44269504088896340736f;
 constexpr double LN2 = 0.69314718055994530942;
-
-struct WGeom { int nstrip, nband, tile_rows, tile_cells, cpw; };
 
 // l0 a + l1 b with ONE spelling of the roundings, fma(l0, a, round(l1 b)).  Left to the compiler's contraction, a + of two products may
 // fuse either of them, and not the same one for every class of an unrolled loop: two equal class planes then differ in the last
@@ -65,10 +58,12 @@ constexpr size_t wide_ce_lds_bytes() {
 // loss and `sel`: gradient tiles of sum_p pix[p] * CE_p, the second half of the focal loss past 24 classes (softhead.hip).
 template <typename T, int MODE>
 __global__ __launch_bounds__(NT, 2) void wide_ce_kernel(const T* low, long ldl, const long long* target, float* tiles, double* lossrows,
-                                                        int C, int h, int w, int H, int W, int ignore_index, const WGeom geo,
+                                                        int C, int h, int w, int H, int W, int ignore_index, const HeadGeom geo,
                                                         float* pix, const float* sel, const float* cw, float eps) {
   constexpr bool WEIGHTED = MODE == 3 || MODE == 4;             // class weights in play
   constexpr bool TILES_ONLY = MODE == 2 || MODE == 5;           // no loss terms, no loss rows
+  // all of this kernel's LDS is dynamic: wide_allow_lds asks for the whole 160 KiB as dynamic LDS, and the request is refused (the
+  // launch then fails) once the kernel also holds static LDS, as a call of lsw::block_sum2 would give it
   extern __shared__ __align__(16) unsigned char wlds[];
   double* const red = reinterpret_cast<double*>(wlds);          // [2][NT / 64]
   float* const Pm = reinterpret_cast<float*>(wlds + 64);        // [WROWS][NT] running maximum, then the log-sum-exp (log2 units)
@@ -87,7 +82,7 @@ __global__ __launch_bounds__(NT, 2) void wide_ce_kernel(const T* low, long ldl, 
   static_assert(WMAXC == NT && WROWS * NT <= NT * WK, "LDS layout");
 
   const int tid = threadIdx.x;
-  const int cpw = geo.cpw;
+  const int cpw = geo.cp;
   Cw[tid] = (WEIGHTED && tid < C) ? (cw ? cw[tid] : 1.f) : 0.f;
   Nn[tid] = 0.f; Nn[NT + tid] = 0.f;
   const int nstrip = geo.nstrip, nband = geo.nband;
@@ -347,57 +342,10 @@ __global__ __launch_bounds__(NT, 2) void wide_ce_kernel(const T* low, long ldl, 
   }
 }
 
-// loss = sum(rows[.][0]) / sum(rows[.][1]) in a fixed order (one block); EX: the weighted / smoothed rule for an empty denominator
-template <bool EX>
-__global__ __launch_bounds__(NT) void wide_ce_finalize_kernel(const double* rows, int nrows, float* loss, float* inv_count) {
-  double sum, n;
-  if (lsw::row_sum2(rows, nrows, sum, n)) {
-    *loss = (EX && !(n > 0.0)) ? __builtin_nanf("") : (float)(sum / n);          // n == 0 -> nan, like torch
-    *inv_count = n > 0.0 ? (float)(1.0 / n) : 0.f;
-  }
-}
-
-// dlow[b][r][cx][:] = (T)(grad_out / count * sum over the tiles that hold cell (r, cx), in (band, strip) order); thread = one
-// cell x 8 channels, the tile pitch cpw at run time.  Channels >= cpw (pitch padding) are written as zeros.
 template <typename T>
 __global__ __launch_bounds__(NT) void wide_ce_gather_kernel(const float* tiles, const float* inv_count, const float* grad_out,
-                                                            T* dlow, long ldl, int B, int h, int w, int H, int W, const WGeom geo) {
-  const float gs = (*inv_count) * (grad_out ? *grad_out : 1.f);
-  const float sy = ac_scale(h, H), sx = ac_scale(w, W);
-  const int cv = (int)(ldl / 8), cpw = geo.cpw;
-  const long total = (long)B * h * w * cv;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int c8 = (int)(i % cv) * 8;
-    long q = i / cv;
-    const int cx = (int)(q % w); q /= w;
-    const int r = (int)(q % h);
-    const long b = q / h;
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = 0.f;
-    int ylo, yhi, xlo, xhi;
-    ac_window(sy, r, H, &ylo, &yhi);
-    ac_window(sx, cx, W, &xlo, &xhi);
-    for (int band = ylo / WROWS; band <= yhi / WROWS && c8 < cpw; ++band) {
-      const int ya = band * WROWS;
-      const int yb = ya + WROWS < H ? ya + WROWS : H;
-      const int r0 = ac_tap(sy, ya, h).i0, r1 = ac_tap(sy, yb - 1, h).i1;
-      if (r < r0 || r > r1 || r - r0 >= geo.tile_rows) continue;
-      for (int strip = xlo / NT; strip <= xhi / NT; ++strip) {
-        const int xl = (strip * NT + NT - 1 < W) ? strip * NT + NT - 1 : W - 1;
-        const int c0 = ac_tap(sx, strip * NT, w).i0;
-        const int n = ac_tap(sx, xl, w).i1 - c0 + 1;
-        if (cx < c0 || cx >= c0 + n || cx - c0 >= geo.tile_cells) continue;
-        const float* t = tiles + ((((b * geo.nband + band) * geo.nstrip + strip) * geo.tile_rows + (r - r0)) * (long)geo.tile_cells
-                                  + (cx - c0)) * cpw + c8;
-        if (c8 + 4 <= cpw) { float u[4]; V4<float>::load(t, u); v[0] += u[0]; v[1] += u[1]; v[2] += u[2]; v[3] += u[3]; }
-        if (c8 + 8 <= cpw) { float u[4]; V4<float>::load(t + 4, u); v[4] += u[0]; v[5] += u[1]; v[6] += u[2]; v[7] += u[3]; }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] *= gs;
-    V8<T>::store(dlow + ((b * h + r) * (long)w + cx) * ldl + c8, v);
-  }
+                                                            T* dlow, long ldl, int B, int h, int w, int H, int W, const HeadGeom geo) {
+  head_gather<T, 0>(tiles, inv_count, grad_out, dlow, ldl, B, h, w, H, W, geo);
 }
 
 // one count of (truth t, prediction arg): LDS counter, or a 64-bit integer atomic on the matrix itself
@@ -433,17 +381,13 @@ __global__ __launch_bounds__(NT, 2) void wide_upsample_argmax_kernel(const T* lo
     for (int i = tid; i < C * C; i += NT) scm[i] = 0u;
     __syncthreads();
   }
-  const int nstrip = (W + NT - 1) / NT, nband = (H + WROWS - 1) / WROWS;
-  int bid = blockIdx.x;
-  const int strip = bid % nstrip; bid /= nstrip;
-  const int band = bid % nband;
-  const long b = bid / nband;
-  const float sy = ac_scale(h, H), sx = ac_scale(w, W);
-  const int x = strip * NT + tid;
-  const bool xin = x < W;
-  const Tap tx = ac_tap(sx, xin ? x : W - 1, w);
-  const int ya = band * WROWS;
-  const int yb = ya + WROWS < H ? ya + WROWS : H;
+  const HeadBlock blk = head_block((W + NT - 1) / NT, (H + WROWS - 1) / WROWS, WROWS, H, W);
+  const HeadTaps map = head_taps(blk, h, w, H, W);
+  const long b = blk.b;
+  const int x = blk.x, ya = blk.ya, yb = blk.yb;
+  const bool xin = blk.xin;
+  const float sy = map.sy;
+  const Tap tx = map.tx;
   const T* const img = low + b * h * (long)w * ldl;
   auto load_row = [&](int r, int c0, float* a) {
     wide_load_row<T>(img + ((long)r * w + tx.i0) * ldl, img + ((long)r * w + tx.i1) * ldl, tx, c0, C, 1.f, a);
@@ -490,18 +434,16 @@ __global__ __launch_bounds__(NT, 2) void wide_upsample_argmax_kernel(const T* lo
   if (counts) wide_counts_out<LDSCM>(scm, cm, C);
 }
 
-// The descriptors as the kernel takes them: by value, in the kernel argument segment (as in msflip.hip).
-struct MsMap { const void* low; long first; int ldl, h, w, flip; };
-struct MsArgs { MsMap m[MS_MAXK]; };
-
 // the logits of the chunk c0 of one map at the MSW_ROWS rows of a band: f(j, z) per row y = ya + j < H, z[c] past C is 0
 template <typename T, typename F>
-__device__ __forceinline__ void ms_walk(const MsMap mp, long b, int xc, int ya, int H, int W, int C, int c0, F&& f) {
+__device__ __forceinline__ void ms_walk(const MsMap mp, const HeadBlock& blk, int H, int W, int C, int c0, F&& f) {
   const int h = mp.h, w = mp.w;
   const long ldl = mp.ldl;
-  const float sy = ac_scale(h, H), sx = ac_scale(w, W);
-  const Tap tx = ac_tap(sx, mp.flip ? W - 1 - xc : xc, w);
-  const T* const img = reinterpret_cast<const T*>(mp.low) + (mp.first + b) * h * (long)w * ldl;
+  const HeadTaps map = head_taps(blk, h, w, H, W, mp.flip);
+  const float sy = map.sy;
+  const Tap tx = map.tx;
+  const int ya = blk.ya;
+  const T* const img = reinterpret_cast<const T*>(mp.low) + (mp.first + blk.b) * h * (long)w * ldl;
   float aA[WK], aB[WK];
   int rA = ac_tap(sy, ya, h).i0;
   int rB = rA + (rA < h - 1 ? 1 : 0);
@@ -549,15 +491,10 @@ __global__ __launch_bounds__(NT, 2) void wide_multiscale_argmax_kernel(const MsA
     for (int i = tid; i < C * C; i += NT) scm[i] = 0u;
     __syncthreads();
   }
-  const int nstrip = (W + NT - 1) / NT, nband = (H + MSW_ROWS - 1) / MSW_ROWS;
-  int bid = blockIdx.x;
-  const int strip = bid % nstrip; bid /= nstrip;
-  const int band = bid % nband;
-  const long b = bid / nband;
-  const int x = strip * NT + tid;
-  const bool xin = x < W;
-  const int xc = xin ? x : W - 1;              // lanes past the edge compute column W-1 and write nothing
-  const int ya = band * MSW_ROWS;
+  const HeadBlock blk = head_block((W + NT - 1) / NT, (H + MSW_ROWS - 1) / MSW_ROWS, MSW_ROWS, H, W);
+  const long b = blk.b;
+  const int x = blk.x, ya = blk.ya;
+  const bool xin = blk.xin;
 
   if (MODE == 0) {
     for (int k = 0; k < K; ++k) {
@@ -566,12 +503,12 @@ __global__ __launch_bounds__(NT, 2) void wide_multiscale_argmax_kernel(const MsA
 #pragma unroll
       for (int j = 0; j < MSW_ROWS; ++j) { m[j] = -TSS_INF; s[j] = 0.f; }
       for (int c0 = 0; c0 < C; c0 += WK)
-        ms_walk<T>(mp, b, xc, ya, H, W, C, c0, [&](int j, const float* z) {
+        ms_walk<T>(mp, blk, H, W, C, c0, [&](int j, const float* z) {
 #pragma unroll
           for (int c = 0; c < WK; ++c) m[j] = (c0 + c < C) ? fmaxf(m[j], z[c]) : m[j];
         });
       for (int c0 = 0; c0 < C; c0 += WK)
-        ms_walk<T>(mp, b, xc, ya, H, W, C, c0, [&](int j, const float* z) {
+        ms_walk<T>(mp, blk, H, W, C, c0, [&](int j, const float* z) {
 #pragma unroll
           for (int c = 0; c < WK; ++c) s[j] += (c0 + c < C) ? __expf(z[c] - m[j]) : 0.f;
         });
@@ -594,7 +531,7 @@ __global__ __launch_bounds__(NT, 2) void wide_multiscale_argmax_kernel(const MsA
 #pragma unroll
       for (int c = 0; c < WK; ++c) score[j][c] = 0.f;
     for (int k = 0; k < K; ++k) {
-      ms_walk<T>(args.m[k], b, xc, ya, H, W, C, c0, [&](int j, const float* z) {
+      ms_walk<T>(args.m[k], blk, H, W, C, c0, [&](int j, const float* z) {
         if (MODE == 1) {
 #pragma unroll
           for (int c = 0; c < WK; ++c) score[j][c] += z[c];
@@ -662,26 +599,6 @@ __global__ __launch_bounds__(NT) void wide_planar_argmax_kernel(const T* logits,
   if (counts) wide_counts_out<LDSCM>(scm, cm, C);
 }
 
-// What every wide entry of the upsampled family asks of its shapes: the rules of upsample_ce_shape_ok (loss.hip) up to 256 classes.
-inline bool wide_shape_ok(int C, long ldl, int h, int w, int H, int W) {
-  return C > 0 && C <= WMAXC && (ldl % 8) == 0 && ldl >= (C + 3) / 4 * 4 && h > 0 && w > 0 && H >= h && W >= w;
-}
-
-// Geometry of the pass (the same on the host, in the pass and in the gather): bands of WROWS rows, strips of 256 columns, and
-// the tile every block owns.  A band of R output rows touches at most floor((R - 1) (h - 1) / (H - 1)) + 3 low-res rows.
-WGeom wide_geom(int C, int h, int w, int H, int W) {
-  WGeom g;
-  g.nstrip = (W + NT - 1) / NT;
-  g.nband = (H + WROWS - 1) / WROWS;
-  const double sy = H > 1 ? (double)(h - 1) / (double)(H - 1) : 0.0, sx = W > 1 ? (double)(w - 1) / (double)(W - 1) : 0.0;
-  g.tile_rows = (int)((WROWS - 1) * sy) + 3;
-  g.tile_cells = (int)((NT - 1) * sx) + 3;
-  if (g.tile_rows > h) g.tile_rows = h;
-  if (g.tile_cells > w) g.tile_cells = w;
-  g.cpw = (C + 3) / 4 * 4;
-  return g;
-}
-
 // the kernels ask for more dynamic LDS than the default limit: raised once per instance and device
 template <typename KernelT>
 void wide_allow_lds(KernelT kernel, tss::DevOnce& once) {
@@ -690,7 +607,7 @@ void wide_allow_lds(KernelT kernel, tss::DevOnce& once) {
 
 template <typename T, int MODE>
 void launch_wide_ce(long grid, hipStream_t stream, const void* low, long ldl, const long long* target, float* tiles, double* lossrows,
-                    int C, int h, int w, int H, int W, int ignore_index, const WGeom& geo, float* pix, const float* sel,
+                    int C, int h, int w, int H, int W, int ignore_index, const HeadGeom& geo, float* pix, const float* sel,
                     const float* cw, float eps) {
   static tss::DevOnce attr;
   wide_allow_lds(wide_ce_kernel<T, MODE>, attr);
@@ -713,22 +630,17 @@ extern "C" {
 
 int tss_widehead_max_classes(void) { return WMAXC; }
 
-long tss_upsample_ce_wide_ws(int B, int C, int h, int w, int H, int W) {
-  if (B <= 0 || C <= 0 || C > WMAXC || h <= 0 || w <= 0 || H < h || W < w) return 0;
-  const WGeom g = wide_geom(C, h, w, H, W);
-  const long nblocks = (long)B * g.nband * g.nstrip;
-  return nblocks * 4 /* 2 doubles */ + nblocks * g.tile_rows * g.tile_cells * g.cpw;
-}
+long tss_upsample_ce_wide_ws(int B, int C, int h, int w, int H, int W) { return head_ws_floats(B, C, WMAXC, h, w, H, W, true); }
 
 int tss_upsample_ce_wide_fwd(const void* low, long ldl, const long long* target, const float* weight, float label_smoothing, float* ws,
                              float* loss, float* inv_count, int B, int C, int h, int w, int H, int W, int ignore_index, int dtype,
                              void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(wide_shape_ok(C, ldl, h, w, H, W) && label_smoothing >= 0.f && label_smoothing <= 1.f && B >= 0, TSS_ERR_SHAPE);
+  TSS_REQUIRE(head_shape_ok(C, WMAXC, ldl, h, w, H, W) && label_smoothing >= 0.f && label_smoothing <= 1.f && B >= 0, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(low) && tss::aligned16(ws), TSS_ERR_ALIGN);
   if ((long)B * H * W == 0) return TSS_OK;
-  const WGeom geo = wide_geom(C, h, w, H, W);
-  const long grid = (long)B * geo.nstrip * geo.nband;
+  const HeadGeom geo = head_geom(B, C, h, w, H, W, true);
+  const long grid = head_blocks(B, geo);
   TSS_REQUIRE(grid <= 0x7fffffffL, TSS_ERR_SHAPE);
   double* lossrows = reinterpret_cast<double*>(ws);
   float* tiles = ws + grid * 4;
@@ -746,19 +658,19 @@ int tss_upsample_ce_wide_fwd(const void* low, long ldl, const long long* target,
       TSS_WITH_DTYPE(dtype, (launch_wide_ce<TT, 3>(grid, st, low, ldl, target, tiles, lossrows, C, h, w, H, W, ignore_index, geo, nullptr,
                                                    nullptr, weight, 0.f)));
   }
-  if (plain) hipLaunchKernelGGL(wide_ce_finalize_kernel<false>, dim3(1), dim3(NT), 0, st, lossrows, (int)grid, loss, inv_count);
-  else hipLaunchKernelGGL(wide_ce_finalize_kernel<true>, dim3(1), dim3(NT), 0, st, lossrows, (int)grid, loss, inv_count);
+  if (plain) hipLaunchKernelGGL(ce_finalize_rows_kernel<false>, dim3(1), dim3(NT), 0, st, lossrows, (int)grid, loss, inv_count);
+  else hipLaunchKernelGGL(ce_finalize_rows_kernel<true>, dim3(1), dim3(NT), 0, st, lossrows, (int)grid, loss, inv_count);
   return tss::check_last("upsample_ce_wide_fwd");
 }
 
 int tss_upsample_pixel_ce_wide(const void* low, long ldl, const long long* target, float* pix, int B, int C, int h, int w, int H, int W,
                                int ignore_index, int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(wide_shape_ok(C, ldl, h, w, H, W) && pix && B >= 0, TSS_ERR_SHAPE);
+  TSS_REQUIRE(head_shape_ok(C, WMAXC, ldl, h, w, H, W) && pix && B >= 0, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(low), TSS_ERR_ALIGN);
   if ((long)B * H * W == 0) return TSS_OK;
-  const WGeom geo = wide_geom(C, h, w, H, W);
-  const long grid = (long)B * geo.nstrip * geo.nband;
+  const HeadGeom geo = head_geom(B, C, h, w, H, W, true);
+  const long grid = head_blocks(B, geo);
   TSS_REQUIRE(grid <= 0x7fffffffL, TSS_ERR_SHAPE);
   tss::ProfScope prof(TSS_K_WIDE_CE_FWD, (hipStream_t)stream, (double)B * h * w * C * tss::esz(dtype) + (double)B * H * W * 12.0, 0);
   TSS_WITH_DTYPE(dtype, (launch_wide_ce<TT, 1>(grid, (hipStream_t)stream, low, ldl, target, nullptr, nullptr, C, h, w, H, W, ignore_index, geo,
@@ -769,11 +681,11 @@ int tss_upsample_pixel_ce_wide(const void* low, long ldl, const long long* targe
 int tss_upsample_ohem_grad_wide(const void* low, long ldl, const long long* target, const float* pix, const float* sel, float* ws,
                                 int B, int C, int h, int w, int H, int W, int ignore_index, int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(wide_shape_ok(C, ldl, h, w, H, W) && pix && sel && ws && B >= 0, TSS_ERR_SHAPE);
+  TSS_REQUIRE(head_shape_ok(C, WMAXC, ldl, h, w, H, W) && pix && sel && ws && B >= 0, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(low) && tss::aligned16(ws), TSS_ERR_ALIGN);
   if ((long)B * H * W == 0) return TSS_OK;
-  const WGeom geo = wide_geom(C, h, w, H, W);
-  const long grid = (long)B * geo.nstrip * geo.nband;
+  const HeadGeom geo = head_geom(B, C, h, w, H, W, true);
+  const long grid = head_blocks(B, geo);
   TSS_REQUIRE(grid <= 0x7fffffffL, TSS_ERR_SHAPE);
   float* tiles = ws + grid * 4;
   tss::ProfScope prof(TSS_K_WIDE_CE_FWD, (hipStream_t)stream, (double)B * h * w * C * (tss::esz(dtype) + 8.0) + (double)B * H * W * 12.0, 0);
@@ -787,11 +699,11 @@ int tss_upsample_ohem_grad_wide(const void* low, long ldl, const long long* targ
 int tss_upsample_coef_grad_wide(const void* low, long ldl, const long long* target, const float* coef, float* ws, int B, int C, int h,
                                 int w, int H, int W, int ignore_index, int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(wide_shape_ok(C, ldl, h, w, H, W) && coef && ws && B >= 0, TSS_ERR_SHAPE);
+  TSS_REQUIRE(head_shape_ok(C, WMAXC, ldl, h, w, H, W) && coef && ws && B >= 0, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(low) && tss::aligned16(ws), TSS_ERR_ALIGN);
   if ((long)B * H * W == 0) return TSS_OK;
-  const WGeom geo = wide_geom(C, h, w, H, W);
-  const long grid = (long)B * geo.nstrip * geo.nband;
+  const HeadGeom geo = head_geom(B, C, h, w, H, W, true);
+  const long grid = head_blocks(B, geo);
   TSS_REQUIRE(grid <= 0x7fffffffL, TSS_ERR_SHAPE);
   float* tiles = ws + grid * 4;
   tss::ProfScope prof(TSS_K_WIDE_CE_FWD, (hipStream_t)stream, (double)B * h * w * C * (tss::esz(dtype) + 8.0) + (double)B * H * W * 12.0, 0);
@@ -803,12 +715,12 @@ int tss_upsample_coef_grad_wide(const void* low, long ldl, const long long* targ
 int tss_upsample_ce_wide_bwd(const float* ws, const float* inv_count, const float* grad_out, void* dlow, long ldl,
                              int B, int C, int h, int w, int H, int W, int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(wide_shape_ok(C, ldl, h, w, H, W) && B >= 0, TSS_ERR_SHAPE);
+  TSS_REQUIRE(head_shape_ok(C, WMAXC, ldl, h, w, H, W) && B >= 0, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(ws) && tss::aligned16(dlow), TSS_ERR_ALIGN);
   const long n = (long)B * h * w * ldl;
   if (n == 0) return TSS_OK;
-  const WGeom geo = wide_geom(C, h, w, H, W);
-  const float* tiles = ws + (long)B * geo.nstrip * geo.nband * 4;
+  const HeadGeom geo = head_geom(B, C, h, w, H, W, true);
+  const float* tiles = ws + head_blocks(B, geo) * 4;
   tss::ProfScope prof(TSS_K_WIDE_CE_BWD, (hipStream_t)stream, (double)n * (4.0 + tss::esz(dtype)), 0);
   TSS_WITH_DTYPE(dtype, hipLaunchKernelGGL(wide_ce_gather_kernel<TT>, dim3(tss::grid_for(n / 8, NT)), dim3(NT), 0, (hipStream_t)stream,
                                            tiles, inv_count, grad_out, (TT*)dlow, ldl, B, h, w, H, W, geo));
@@ -819,7 +731,7 @@ int tss_upsample_argmax_confusion_wide(const void* low, long ldl, const long lon
                                        unsigned long long* confusion /*[C*C] accumulated*/, int B, int C, int h, int w,
                                        int H, int W, int ignore_index, int dtype, void* stream) {
   TSS_CHECK_DTYPE(dtype);
-  TSS_REQUIRE(wide_shape_ok(C, ldl, h, w, H, W) && B >= 0, TSS_ERR_SHAPE);
+  TSS_REQUIRE(head_shape_ok(C, WMAXC, ldl, h, w, H, W) && B >= 0, TSS_ERR_SHAPE);
   TSS_REQUIRE(tss::aligned16(low), TSS_ERR_ALIGN);
   if ((long)B * H * W == 0) return TSS_OK;
   const long grid = (long)B * ((W + NT - 1) / NT) * ((H + WROWS - 1) / WROWS);
@@ -841,16 +753,9 @@ int tss_multiscale_argmax_confusion_wide(const tss_msmap* maps, int K, const lon
   TSS_REQUIRE(maps && K >= 1 && K <= MS_MAXK && C >= 1 && C <= WMAXC && B >= 0 && H >= 0 && W >= 0 && (mode == 0 || mode == 1),
               TSS_ERR_SHAPE);
   MsArgs args = {};
-  double low_bytes = 0.0;
-  for (int k = 0; k < K; ++k) {
-    const tss_msmap& m = maps[k];
-    TSS_REQUIRE(m.low && (m.ldl % 8) == 0 && m.ldl >= (C + 3) / 4 * 4 && m.ldl <= (1L << 30) && m.h >= 1 && m.w >= 1 &&
-                m.h <= H && m.w <= W && m.first >= 0, TSS_ERR_SHAPE);
-    TSS_REQUIRE(tss::aligned16(m.low), TSS_ERR_ALIGN);
-    args.m[k].low = m.low; args.m[k].first = m.first; args.m[k].ldl = (int)m.ldl;
-    args.m[k].h = m.h; args.m[k].w = m.w; args.m[k].flip = m.flip ? 1 : 0;
-    low_bytes += (double)B * m.h * m.w * C * tss::esz(dtype);
-  }
+  double low_bytes;
+  const int err = ms_args(maps, K, B, C, H, W, dtype, &args, &low_bytes);
+  if (err != TSS_OK) return err;
   const bool counts = confusion && target;
   if ((long)B * H * W == 0 || (!pred && !counts)) return TSS_OK;
   const long grid = (long)B * ((W + NT - 1) / NT) * ((H + MSW_ROWS - 1) / MSW_ROWS);
