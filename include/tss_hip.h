@@ -341,6 +341,18 @@ int tss_stem3x3_bwd_weight(const void* e, long lde, const void* yraw, long ldyr,
                            const void* x_nchw, int x_is_f32, float* dw,
                            float* ws /* [tss_stat_slabs()][N*28] f32 workspace, may be NULL (slower path) */,
                            int B, int Cin, int Hin, int Win, int N, int stride, int dtype, void* stream);
+/* The same gradient, dw += sum_p g[p][n] * patch[p][j] with g = ga*(e - gce) + gb*(y - gmu), for the case that y IS the output of
+ * tss_stem3x3_fwd on (x_nchw, w): y is not read, the kernel forms it again from the taps it gathers anyway and the bf16 weights,
+ * with the forward's own instruction and rounding, so dw has the bits of tss_stem3x3_bwd_weight(yraw = y) while a third of its
+ * memory traffic is gone.  The caller guarantees that x_nchw and w are what that forward read (same contents); with any other w
+ * the result is the gradient for the y that w would have produced.
+ * Covers exactly what the direct forward kernel covers, and returns TSS_ERR_SHAPE without a launch for anything else (it never
+ * falls back): dtype == TSS_BF16, 1 <= Cin <= 3, N == 32, fast paths not disabled, ws [tss_stat_slabs()][N*28] f32 and the four
+ * coefficient arrays non-NULL, lde % 8 == 0; e off 16 bytes: TSS_ERR_ALIGN.  Profiled as stem3x3_bwd_weight. */
+int tss_stem3x3_bwd_weight_rc(const void* e, long lde, const float* w,
+                              const float* ga, const float* gb, const float* gce, const float* gmu,
+                              const void* x_nchw, int x_is_f32, float* dw, float* ws,
+                              int B, int Cin, int Hin, int Win, int N, int stride, int dtype, void* stream);
 
 /* ---- depthwise 3x3 convolution, padding = dilation, weight [C][3][3] --------------------------------
  * replaces: nn.Conv2d(groups=in_channels) of DWConv2dBlock TSS/models/fastscnn.py:176-185, DSConv2dBlock :191-192,

@@ -2,7 +2,7 @@
 // gradient.  One lane gathers the 27 taps of one output pixel straight from the image planes (9 dword-aligned 16-byte
 // loads), both contractions run on v_mfma_f32_16x16x32_bf16 with the taps padded to one 32-deep k-step.
 // History (profiles/README.md): VALU kernels first (864 FMAs per pixel forward: 196 us; an LDS-bound per-pixel outer
-// product for the gradient: 368 us), then these: 120 us and 158 us.
+// product for the gradient: 368 us), then these: 120 us and 158 us; the gradient with y recomputed instead of read: 114 us.
 #include "common.h"
 
 namespace {
@@ -58,6 +58,83 @@ __device__ __forceinline__ void stem_taps(const TX* x, long b, int oy, int ox, b
         const long off = (b * Cin + (c < Cin ? c : 0)) * plane + (vy ? iy : 0) * (long)Win + (ix < 0 ? 0 : (ix >= Win ? Win - 1 : ix));
         const float t = (float)x[off];
         v[c * 9 + ky * 3 + kx] = ok ? t : 0.f;
+      }
+    }
+}
+
+// stem_taps in two halves, for a kernel that keeps the loads of its NEXT tile in flight: stem_taps_issue computes the addresses
+// and issues the loads (nothing reads the results, so nothing waits), stem_taps_select picks the same 27 values from them later.
+// VEC: the 16-byte window path (f32 image, stride 2, Win >= 4), chosen by the host so that the raw values stay in registers.
+typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+template <typename TX, bool VEC> struct StemRaw { f32x4 f[VEC ? 9 : 1]; TX t[VEC ? 1 : 27]; int oy, ox; bool in; };
+template <typename TX, bool VEC>
+__device__ __forceinline__ void stem_taps_issue(const TX* x, long b, int oy, int ox, bool in, int Cin, int Hin, int Win, int stride,
+                                                long plane, StemRaw<TX, VEC>& r) {
+  r.oy = oy; r.ox = ox; r.in = in;
+  if constexpr (VEC) {
+    const int ix0 = 2 * ox - 1;
+    const int base = ix0 < 0 ? 0 : (ix0 > Win - 4 ? Win - 4 : ix0);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky) {
+        const int iy = 2 * oy + ky - 1;
+        const bool vy = c < Cin && iy >= 0 && iy < Hin;   // (not `in`: a pixel past the end is clamped to pixel 0 and loads ITS rows;
+                                                          // a branch on `in` would split the loads and wait between them)
+        const float* row = reinterpret_cast<const float*>(x) + (b * Cin + (c < Cin ? c : 0)) * plane + (long)(vy ? iy : 0) * Win + base;
+        r.f[c * 3 + ky] = *reinterpret_cast<const f32x4_a4*>(row);
+      }
+    return;
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+      const int iy = oy * stride + ky - 1;
+      const bool vy = iy >= 0 && iy < Hin;
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const int ix = ox * stride + kx - 1;
+        const long off = (b * Cin + (c < Cin ? c : 0)) * plane + (vy ? iy : 0) * (long)Win + (ix < 0 ? 0 : (ix >= Win ? Win - 1 : ix));
+        r.t[c * 9 + ky * 3 + kx] = x[off];
+      }
+    }
+}
+template <typename TX, bool VEC>
+__device__ __forceinline__ void stem_taps_select(const StemRaw<TX, VEC>& r, int Cin, int Hin, int Win, int stride, float v[27]) {
+  const int oy = r.oy, ox = r.ox;
+  const bool in = r.in;
+  if constexpr (VEC) {
+    const int ix0 = 2 * ox - 1;
+    const int base = ix0 < 0 ? 0 : (ix0 > Win - 4 ? Win - 4 : ix0);
+    const int sh = ix0 - base;                      // -1 (left edge), 0, or +1 (right edge)
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky) {
+        const int iy = 2 * oy + ky - 1;
+        const bool vy = in && c < Cin && iy >= 0 && iy < Hin;
+        const f32x4 f = r.f[c * 3 + ky];
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+          const int idx = kx + sh;                  // position of tap kx inside the window; -1 = left padding
+          const float t = idx <= 0 ? f[0] : (idx == 1 ? f[1] : (idx == 2 ? f[2] : f[3]));
+          v[c * 9 + ky * 3 + kx] = (vy && idx >= 0 && ix0 + kx < Win) ? t : 0.f;
+        }
+      }
+    return;
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+      const int iy = oy * stride + ky - 1;
+      const bool vy = iy >= 0 && iy < Hin;
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const int ix = ox * stride + kx - 1;
+        const bool ok = in && c < Cin && vy && ix >= 0 && ix < Win;
+        v[c * 9 + ky * 3 + kx] = ok ? (float)r.t[c * 9 + ky * 3 + kx] : 0.f;
       }
     }
 }
@@ -158,6 +235,7 @@ struct StemWgradArgs {
   const void* e; long lde; const void* yraw; long ldyr; const float* ga; const float* gb; const float* gce; const float* gmu;
   const void* x; float* ws; float* dw;
   int B, Cin, Hin, Win, Hout, Wout, stride;
+  const float* w;   // recompute form only: the weights the forward ran with (yraw is not read)
 };
 
 template <typename T, typename TX>
@@ -368,6 +446,165 @@ __global__ __launch_bounds__(NT, 2) void stem_wgrad_mfma_kernel(const StemWgradA
   }
 }
 
+// LDS hand-over between the lanes of ONE wave: a wave's DS operations complete in issue order, so no counter wait and no block
+// barrier is needed, only that the compiler keeps the stores in front of the loads.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Recompute form of stem_wgrad_mfma_kernel: y is not read back (268 of the 737 MB of the flagship launch), it is formed again
+// from operands the kernel holds anyway -- the tile's taps, stored a second time pixel-major (Xp, the forward's [pixel][32] rows
+// with its 80-byte pitch), and the bf16 weights as two A-fragments per lane -- with the forward's own instruction: one
+// v_mfma_f32_16x16x32_bf16 from a zero accumulator, rounded to bf16, gives the bits stem_fwd_mfma_kernel stored.  Only valid
+// when `w` is what that forward ran with; tile plan, accumulation order, wave meeting and workspace row are those of
+// stem_wgrad_mfma_kernel, so dW has the same bits.
+// The A rows are permuted against the forward's (row r of fragment i is channel (r/4)*8 + i*4 + r%4; a D element is the dot
+// product of its row and column wherever they sit), so that the lane owning pixel `fr` holds channels fq*8 .. fq*8+7 of it: e is
+// loaded 16 bytes per lane, and the coefficients are indexed as in the old kernel.
+// A wave gathers, recomputes and contracts its own 64-pixel quarter of the tile: every LDS hand-over is inside one wave
+// (wave_lds_sync), the tile loop has no block barrier and the eight waves of a CU drift apart, gathers under MFMAs.
+// With two waves per SIMD the kernel lives on loads in flight: a wave requests its next tile (13 loads of 16 bytes per lane) as
+// soon as the current one is in LDS, so the requests fly while it recomputes and contracts.
+template <typename TX, bool VEC>
+__global__ __launch_bounds__(NT, 2) void stem_wgrad_rc_mfma_kernel(const StemWgradArgs g) {
+  typedef bf16_t T;
+  constexpr int N = 32, TP = 256, KP = 28, ROW = TP + 8, PITCH = 40;
+  __shared__ __align__(16) T Gt[N * ROW];
+  __shared__ __align__(16) T Xt[32 * ROW];
+  __shared__ __align__(16) T Xp[TP * PITCH];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int fr = lane & 15, fq = lane >> 4;
+  const T* e = reinterpret_cast<const T*>(g.e);
+  const TX* x = reinterpret_cast<const TX*>(g.x);
+  const int K = g.Cin * 9;
+  const long P = (long)g.B * g.Hout * g.Wout;
+  const long HWo = (long)g.Hout * g.Wout;
+  const long plane = (long)g.Hin * g.Win;
+  const long ntiles = (P + TP - 1) / TP;
+  bf16x8 wf[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int k = fq * 8 + j;
+      const int n = (fr >> 2) * 8 + i * 4 + (fr & 3);
+      wf[i][j] = (T)(g.w[n * K + (k < K ? k : 0)] * (k < K ? 1.f : 0.f));
+    }
+  for (int i = tid; i < 5 * ROW; i += NT) Xt[27 * ROW + i] = (T)0.f;   // taps 27..31 pad the MFMA k-fragment
+  float ca[8], cb[8], cc[8];
+  {
+    float v0[8], v1[8], v2[8], v3[8];
+#pragma unroll
+    for (int h = 0; h < 8; h += 4) {
+      V4<float>::load(g.ga + fq * 8 + h, v0 + h); V4<float>::load(g.gb + fq * 8 + h, v1 + h);
+      V4<float>::load(g.gce + fq * 8 + h, v2 + h); V4<float>::load(g.gmu + fq * 8 + h, v3 + h);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { ca[j] = v0[j]; cb[j] = v1[j]; cc[j] = -(v0[j] * v2[j]) - v1[j] * v3[j]; }   // g = ca*e + cb*y + cc
+  }
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  __syncthreads();   // the padding rows (the only LDS the waves share before the end)
+
+  // the loads of a tile: gradient vectors first (one 16-byte load x 4), then the strided tap loads of this lane's pixel
+  StemRaw<TX, VEC> raw;
+  uint4 rn[4];
+  auto issue = [&](long tile) __attribute__((always_inline)) {
+    const long p0 = tile * TP;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const long p = p0 + wave * 64 + m * 16 + fr;
+      const long pc = p < P ? p : 0;
+      rn[m] = *reinterpret_cast<const uint4*>(e + pc * g.lde + fq * 8);
+    }
+    const long p = p0 + tid;
+    const bool in = p < P;
+    const long pc = in ? p : 0;
+    const long b = pc / HWo; const long rem = pc - b * HWo;
+    const int oy = (int)(rem / g.Wout), ox = (int)(rem - (long)oy * g.Wout);
+    stem_taps_issue<TX, VEC>(x, b, oy, ox, in, g.Cin, g.Hin, g.Win, g.stride, plane, raw);
+  };
+  if ((long)blockIdx.x < ntiles) issue(blockIdx.x);
+
+  for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const long p0 = tile * TP;
+    wave_lds_sync();   // this wave's fragment reads of the previous tile are issued
+    uint4 re[4];
+    {
+      float v[32];
+      stem_taps_select<TX, VEC>(raw, g.Cin, g.Hin, g.Win, g.stride, v);
+#pragma unroll
+      for (int k = 27; k < 32; ++k) v[k] = 0.f;
+#pragma unroll
+      for (int k = 0; k < 27; ++k) Xt[k * ROW + tid] = (T)v[k];
+#pragma unroll
+      for (int h = 0; h < 4; ++h) V8<T>::store(Xp + tid * PITCH + h * 8, v + h * 8);
+#pragma unroll
+      for (int m = 0; m < 4; ++m) re[m] = rn[m];
+    }
+    // the next tile's loads stay in flight under this tile's MFMAs and LDS traffic (nothing below reads global memory)
+    if (tile + gridDim.x < ntiles) issue(tile + gridDim.x);
+    wave_lds_sync();
+    // y of this wave's 64 pixels, 16 at a time, as the forward computes it; g = ca*e + (cb*y + cc) goes to Gt
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const int prow = wave * 64 + m * 16 + fr;
+      const bf16x8 xf = *reinterpret_cast<const bf16x8*>(Xp + prow * PITCH + fq * 8);
+      const bool in = p0 + prow < P;
+      const uint32_t* ue = reinterpret_cast<const uint32_t*>(&re[m]);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const f32x4 d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i], xf, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int c = i * 4 + 2 * h;   // channels fq*8 + c, + c + 1: one dword of e
+          const float ylo = (float)(T)d[2 * h], yhi = (float)(T)d[2 * h + 1];
+          const float lo = ca[c] * __uint_as_float(ue[c >> 1] << 16) + (cb[c] * ylo + cc[c]);
+          const float hi = ca[c + 1] * __uint_as_float(ue[c >> 1] & 0xffff0000u) + (cb[c + 1] * yhi + cc[c + 1]);
+          Gt[(fq * 8 + c) * ROW + prow] = (T)(in ? lo : 0.f);
+          Gt[(fq * 8 + c + 1) * ROW + prow] = (T)(in ? hi : 0.f);
+        }
+      }
+    }
+    wave_lds_sync();
+    // this wave's 64 pixels: two k-steps of 32
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const int col = wave * 64 + ks * 32 + fq * 8;
+      bf16x8 gf[2], xf[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        gf[i] = *reinterpret_cast<const bf16x8*>(Gt + (i * 16 + fr) * ROW + col);
+        xf[i] = *reinterpret_cast<const bf16x8*>(Xt + (i * 16 + fr) * ROW + col);
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gf[i], xf[j], acc[i][j], 0, 0, 0);
+    }
+  }
+  // the four waves' partials meet in LDS (Gt is dead): red[wave][n][k], then one thread per (n, k < 28)
+  __syncthreads();
+  float* red = reinterpret_cast<float*>(Gt);   // 4 * 32 * 32 floats = 16 KB <= sizeof(Gt)
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[(wave * 32 + i * 16 + fq * 4 + r) * 32 + j * 16 + fr] = acc[i][j][r];
+  __syncthreads();
+  float* row = g.ws + (long)blockIdx.x * N * KP;
+  for (int i = tid; i < N * KP; i += NT) {
+    const int n = i / KP, k = i - n * KP;
+    row[i] = red[n * 32 + k] + red[(32 + n) * 32 + k] + red[(64 + n) * 32 + k] + red[(96 + n) * 32 + k];
+  }
+}
+
 // dW[n][j] += sum over the `rows` workspace rows (16 columns x 16 row-groups per block, 8 loads in flight per lane)
 __global__ __launch_bounds__(256) void stem_wgrad_reduce_kernel(const float* ws, float* dw, int K, int rows) {
   constexpr int N = 32, KP = 28;
@@ -432,6 +669,26 @@ bool tss_stem_direct_wgrad(const void* e, long lde, const void* yraw, long ldyr,
     else hipLaunchKernelGGL((stem_wgrad_mfma_kernel<bf16_t>), dim3((int)grid), dim3(NT), 0, stream, g);
   } else if (x_is_f32) hipLaunchKernelGGL((stem_wgrad_kernel<bf16_t, float>), dim3((int)grid), dim3(NT), 0, stream, g);
   else hipLaunchKernelGGL((stem_wgrad_kernel<bf16_t, bf16_t>), dim3((int)grid), dim3(NT), 0, stream, g);
+  hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((32 * 28 + 15) / 16), dim3(256), 0, stream, ws, dw, Cin * 9, (int)grid);
+  return true;
+}
+
+// recompute form of the direct stem weight gradient: `w` (the forward's weights) in place of yraw; same grid, same reduce
+bool tss_stem_direct_wgrad_rc(const void* e, long lde, const float* w, const float* ga, const float* gb,
+                              const float* gce, const float* gmu, const void* x_nchw, int x_is_f32, float* dw, float* ws,
+                              int B, int Cin, int Hin, int Win, int N, int stride, int dtype, hipStream_t stream) {
+  if (dtype != TSS_BF16 || Cin > 3 || N != 32 || !ws || !w || !ga || !gb || !gce || !gmu) return false;
+  StemWgradArgs g = {};
+  g.e = e; g.lde = lde; g.w = w; g.ga = ga; g.gb = gb; g.gce = gce; g.gmu = gmu;
+  g.x = x_nchw; g.ws = ws; g.dw = dw;
+  g.B = B; g.Cin = Cin; g.Hin = Hin; g.Win = Win; g.stride = stride;
+  g.Hout = (Hin - 1) / stride + 1; g.Wout = (Win - 1) / stride + 1;
+  const long P = (long)B * g.Hout * g.Wout;
+  long grid = (P + 255) / 256;
+  if (grid > TSS_STAT_SLABS) grid = TSS_STAT_SLABS;
+  if (x_is_f32 && stride == 2 && Win >= 4) hipLaunchKernelGGL((stem_wgrad_rc_mfma_kernel<float, true>), dim3((int)grid), dim3(NT), 0, stream, g);
+  else if (x_is_f32) hipLaunchKernelGGL((stem_wgrad_rc_mfma_kernel<float, false>), dim3((int)grid), dim3(NT), 0, stream, g);
+  else hipLaunchKernelGGL((stem_wgrad_rc_mfma_kernel<bf16_t, false>), dim3((int)grid), dim3(NT), 0, stream, g);
   hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((32 * 28 + 15) / 16), dim3(256), 0, stream, ws, dw, Cin * 9, (int)grid);
   return true;
 }

@@ -633,6 +633,9 @@ int launch(WgradArgs& g, int dtype, int kernel_id, hipStream_t stream, double al
 bool tss_stem_direct_wgrad(const void* e, long lde, const void* yraw, long ldyr, const float* ga, const float* gb,
                            const float* gce, const float* gmu, const void* x_nchw, int x_is_f32, float* dw, float* ws,
                            int B, int Cin, int Hin, int Win, int N, int stride, int dtype, hipStream_t stream);  // stem.hip
+bool tss_stem_direct_wgrad_rc(const void* e, long lde, const float* w, const float* ga, const float* gb,
+                              const float* gce, const float* gmu, const void* x_nchw, int x_is_f32, float* dw, float* ws,
+                              int B, int Cin, int Hin, int Win, int N, int stride, int dtype, hipStream_t stream);  // stem.hip
 
 // pending slot reduction of a layer, launched on its own (pwfast.hip calls this when its kernels cannot carry it)
 void tss_wg_reduce_standalone(const float* ws, float* dw, long P, int K, int N, hipStream_t stream) {
@@ -769,6 +772,24 @@ int tss_stem3x3_bwd_weight(const void* e, long lde, const void* yraw, long ldyr,
       return tss::check_last("stem_direct_wgrad");
   }
   return launch(g, dtype, TSS_K_STEM_BWD_WEIGHT, (hipStream_t)stream, bytes);
+}
+
+// the same gradient with y recomputed from (x, w) inside the kernel: only what the direct forward covers, never a fall-back
+int tss_stem3x3_bwd_weight_rc(const void* e, long lde, const float* w,
+                              const float* ga, const float* gb, const float* gce, const float* gmu,
+                              const void* x_nchw, int x_is_f32, float* dw, float* ws,
+                              int B, int Cin, int Hin, int Win, int N, int stride, int dtype, void* stream) {
+  TSS_CHECK_DTYPE(dtype);
+  TSS_REQUIRE(dtype == TSS_BF16 && !g_tss_disable_fast && Cin >= 1 && Cin <= 3 && N == 32 && B >= 1 && Hin >= 1 && Win >= 1 &&
+              stride >= 1 && (lde % 8) == 0 && lde >= N && e && w && ga && gb && gce && gmu && x_nchw && dw && ws, TSS_ERR_SHAPE);
+  TSS_REQUIRE(tss::aligned16(e), TSS_ERR_ALIGN);
+  const long P = (long)B * ((Hin - 1) / stride + 1) * ((Win - 1) / stride + 1);
+  const double bytes = (double)P * N * tss::esz(dtype) + (double)B * Cin * Hin * Win * (x_is_f32 ? 4 : tss::esz(dtype));
+  tss::ProfScope prof(TSS_K_STEM_BWD_WEIGHT, (hipStream_t)stream, bytes, 2.0 * (double)P * N * Cin * 9);
+  if (!tss_stem_direct_wgrad_rc(e, lde, w, ga, gb, gce, gmu, x_nchw, x_is_f32, dw, ws, B, Cin, Hin, Win, N, stride, dtype,
+                                (hipStream_t)stream))
+    return TSS_ERR_SHAPE;
+  return tss::check_last("stem_direct_wgrad_rc");
 }
 
 #ifdef TSS_TIMING

@@ -71,6 +71,9 @@ sweep_pw_backward = os.environ.get('TSS_PW_SWEEP', '1') != '0'        # csrc/pws
 postpone_wgrad = os.environ.get('TSS_POSTPONE_WGRAD', '1') != '0'
 # weight gradient of the three-tap (1x3 / 3x1) layers: unfold + the pipelined pointwise kernel (0: the generic tap-loop kernel)
 unfold_1d_wgrad = os.environ.get('TSS_FC1D_WGRAD', '1') != '0'
+# stem weight gradient: y recomputed from the taps and the weights inside the kernel instead of read back (csrc/stem.hip,
+# tss_stem3x3_bwd_weight_rc; the same bits, a third less memory traffic).  0: the kernel that reads y.
+stem_wgrad_recompute = os.environ.get('TSS_STEM_WGRAD_RC', '1') != '0'
 _CONST_ROWS = {}
 
 
@@ -861,7 +864,8 @@ def materialize(d, relu_override=None):
 
 class UnitCfg:
     __slots__ = ('kind', 'stride', 'dil', 'in_link', 'in_relu', 'bn', 'training', 'out_dtype', 'out_link',
-                 'image_f32', 'cin', 'cout', 'params', 'res_fork', 'stash_fork', 'overlapped', 'kh', 'kw', 'drop_p', 'prev_join')
+                 'image_f32', 'cin', 'cout', 'params', 'res_fork', 'stash_fork', 'overlapped', 'kh', 'kw', 'drop_p', 'prev_join',
+                 'stem_rc')
 
 
 def _classify(conv, x_is_image):
@@ -939,6 +943,7 @@ def conv_unit(x, conv, bn=None, relu=False, out_dtype=None, weight=None, bias=_K
     cfg = UnitCfg()
     cfg.kind, cfg.stride, cfg.dil = kind, stride, dil
     cfg.drop_p = float(drop_p)
+    cfg.stem_rc = None      # (weight, its _version) once the direct stem kernel has run this unit's forward (_fwd_stem)
     if cfg.drop_p and (kind != 'pw' or bn is not None):
         raise RuntimeError('conv_unit: dropout on load needs a 1x1 convolution without BatchNorm (drop_conv_supported)')
     cfg.overlapped = _overlap_depth[0] > 0 and not postpone_in_overlap
@@ -1223,6 +1228,9 @@ def _fwd_stem(f):
         raise NotImplementedError('HIP path: stem convolution with bias')
     call('tss_stem3x3_fwd', ptr(f.x), int(cfg.image_f32), ptr(f.weight), ptr(y), ld(y), f.stats,
          f.B, cfg.cin, f.Hin, f.Win, f.Cout, f.s, f.dt, f.st)
+    if y.dtype == torch.bfloat16 and cfg.cin <= 3 and f.Cout == 32 and not N.fast_paths_disabled():
+        # the direct kernel (csrc/stem.hip) wrote y: the backward may form it again from (x, this weight as it is now)
+        cfg.stem_rc = (f.weight, f.weight._version)
 
 
 def _fwd_pw(f):
@@ -1341,10 +1349,24 @@ def _res_grad(cfg):
     return fork, (fork.g2 if fork is not None else None)
 
 
+def _stem_recompute(c):
+    """The stem's y need not be read back: the direct kernel wrote it in this unit's forward from the weight tensor that is still
+    the same object at the same version, a train-mode BatchNorm is pending behind it, and nothing has switched the fast paths off."""
+    rc = c.cfg.stem_rc
+    return bool(stem_wgrad_recompute and rc is not None and c.y is not None and c.link is not None and c.link.training
+                and c.weight is rc[0] and c.weight._version == rc[1] and c.e.dtype == torch.bfloat16 and c.Cin <= 3 and c.Cout == 32
+                and not N.fast_paths_disabled())
+
+
 def _bwd_stem(c):
     ws = c.tmp((N.stat_slabs(), c.Cout * 28))
-    call('tss_stem3x3_bwd_weight', *c.gargs, ptr(c.x), int(c.cfg.image_f32), ptr(c.dw), ptr(ws),
-         c.B, c.Cin, c.Hin, c.Win, c.Cout, c.s, c.dt, c.st)
+    if _stem_recompute(c):
+        e, lde, _, _, ga, gb, gce, gmu = c.gargs
+        call('tss_stem3x3_bwd_weight_rc', e, lde, ptr(c.weight), ga, gb, gce, gmu, ptr(c.x), int(c.cfg.image_f32), ptr(c.dw), ptr(ws),
+             c.B, c.Cin, c.Hin, c.Win, c.Cout, c.s, c.dt, c.st)
+    else:
+        call('tss_stem3x3_bwd_weight', *c.gargs, ptr(c.x), int(c.cfg.image_f32), ptr(c.dw), ptr(ws),
+             c.B, c.Cin, c.Hin, c.Win, c.Cout, c.s, c.dt, c.st)
     if c.need_dx:
         raise NotImplementedError('HIP path: gradient with respect to the input image is not implemented')
     return None, _NO_EXTRAS
