@@ -110,8 +110,12 @@ int tss_pwconv_fwd_joined(const void* x, long ldx, const float* in_mean, const f
  *           6x-expanded tensors live in LDS only.  x: materialised NHWC [B][H][W][Cin]; y: NHWC [B][Ho][Wo][Cout], Ho = (H-1)/stride + 1.
  * w1 [Cmid][Cin], wdw [Cmid][3][3], w3 [Cout][Cmid]: the f32 parameters; w1_bf16 / w3_bf16: optional current bf16 copies (tss_cast_weights).
  * (mean_i, scale_i, beta_i): the BatchNorm behind layer i as tss_bn_eval_affine / tss_bn_eval_affine_batched write it.
- * Cin <= 128 (multiple of 8), Cmid a multiple of 64, Cout <= 128 (multiple of 4); residual needs stride 1 and Cin == Cout. */
+ * Cin <= 128 (multiple of 8), Cmid a multiple of 64, 16 <= Cout <= 128 (multiple of 4); residual needs stride 1 and Cin == Cout; stride 2
+ * needs its one tile form to fit the LDS (any Cout at Cin <= 64; Cin = 128 never).
+ * tss_bneck_eval_tile: the tile form tss_bneck_eval_fwd would launch for a shape, as TH * 100 + TW output pixels (816, 808 or 408 at stride 1,
+ * 416 at stride 2); launches nothing. */
 int tss_bneck_eval_supported(int Cin, int Cmid, int Cout, int stride, int residual, int dtype);
+int tss_bneck_eval_tile(int B, int H, int W, int Cin, int Cout, int stride);
 int tss_bneck_eval_fwd(const void* x, long ldx, const float* w1, const void* w1_bf16, const float* mean1, const float* scale1,
                        const float* beta1, const float* wdw, const float* mean2, const float* scale2, const float* beta2,
                        const float* w3, const void* w3_bf16, const float* mean3, const float* scale3, const float* beta3,

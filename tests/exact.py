@@ -1,6 +1,16 @@
 """Exact-operand f64 references for the bf16 convolution kernels (tests/test_exact_bounds.py, tests/test_gpu_zoo_exact.py,
-tests/test_gpu_dw_exact.py, tests/test_gpu_pw_exact.py, tests/test_gpu_dense_exact.py) and for the resample, pyramid and gate kernels
-(tests/test_gpu_resample_exact.py: the last section of this file, with its own tiers).
+tests/test_gpu_dw_exact.py, tests/test_gpu_pw_exact.py, tests/test_gpu_dense_exact.py), for the resample, pyramid and gate kernels
+(tests/test_gpu_resample_exact.py: a section of its own, with its own tiers) and for the eval bottleneck kernel, the frozen-BatchNorm
+affines and the joins (tests/test_gpu_bneck_exact.py: the last section of this file).  That section's tiers and cases:
+  bottleneck tier 1   bit for bit on fixed-point operands (multiples of 2^-2, power-of-two scales, stage grids 2^-4 / 2^-6 / 2^-8), the
+                      budget asserted per case (bneck_exact); BK_TIER1: 8 x 16 (2 cases), 8 x 8 (3), 4 x 8 (9) at stride 1 with an f32 E,
+                      4 x 16 at stride 2 with a bf16 E (6); bf16 weight copies given, absent, and misaligned with other values
+  bottleneck tier 2   8-bit dyadic operands, ordinary BatchNorm values through tss_bn_eval_affine_batched; BK_TIER2 (6 cases, every
+                      form) within the running error bound bneck_ref carries
+  BK_REFUSED          shapes the entry refuses, among them the stride-2 (128, 768, 128) whose only tile form does not fit the LDS
+  affines             mean bit for bit, invstd within 3 u, scale within 4 u (affine_ref); batched == single
+  joins               forward bit for bit (every branch and the sum exact in f32); backward e bit for bit and the statistics rows
+                      within stats_excess with join_stats_chain, rows in use against join_geometry
 
 Every operand is a DYADIC bf16 value, +-(1 + k/128) * 2^e with e in [-4, 2): 8 significant bits.  BatchNorm scales are powers of two in
 [1/2, 4], the backward pair (ga, gb) powers of two in [1/4, 2] and [2^-6, 2^-3].  Then the on-load transforms of the kernels
@@ -1346,3 +1356,329 @@ def arms_bwd_ref(o, training, accumulate):
     out['near'] = near
     out['gq'] = gq
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------- eval bottleneck, affines, joins
+# csrc/bneck.hip (tss_bneck_eval_fwd), tss_bn_eval_affine / _batched and tss_join_fwd / tss_join_bwd of csrc/pointwise.hip;
+# tests/test_gpu_bneck_exact.py.  The bottleneck has two tiers:
+#   1  bit for bit on FIXED-POINT operands.  x, w1, wdw, w3 are multiples of 2^-2 (|x| < 2, |w| < 1), the BatchNorm scales powers of two
+#      in [1, 4] and the means and betas multiples of the stage's grid: 2^-4 behind the expand, 2^-6 behind the depthwise layer, 2^-8
+#      behind the projection.  Every product and every partial sum of a stage, in ANY order and with or without FMA contraction, is a
+#      multiple of the stage's grid and at most S = |scale| sum|terms| + |shift| (+ |x| with the skip) in magnitude: with
+#      S < 2^(24 + lsb) (bneck_bits: the bits a stage uses, < 24) nothing rounds in f32.  What rounds is what the kernel rounds on
+#      purpose -- D, E at stride 2, y, each to bf16, nearest even -- and bneck_ref rounds at the same points.
+#   2  8-bit X.dyadic operands and ordinary BatchNorm values; a forward running error is carried next to the reference (bneck_ref).
+BK_CM, BK_LDS = 64, 160 * 1024              # CM and the LDS cap of csrc/bneck.hip
+BK_FORMS = {816: (1, 8, 16), 808: (1, 8, 8), 408: (1, 4, 8), 416: (2, 4, 16)}      # TH * 100 + TW -> (stride, TH, TW)
+
+
+def bneck_lds(S, TH, TW, Cin, Cout):
+    """Geo<S, TH, TW>::lds: Xh | E (f32 at stride 1, bf16 at stride 2) | D | 2 x (W1c, W3c, chunk constants) | bn3 | validity"""
+    TP, HP = TH * TW, (S * (TH - 1) + 3) * (S * (TW - 1) + 3)
+    HPp = (HP + 15) & ~15
+    PE = BK_CM * 2 + 16
+    PEE = BK_CM * 4 + 16 if S == 1 else PE
+    px, cop = ((Cin + 31) & ~31) * 2 + 16, (Cout + 15) & ~15
+    kset = (4 * BK_CM + 9 * BK_CM) * 4
+    return HPp * px + HPp * PEE + TP * PE + 2 * (BK_CM * px + cop * PE + kset) + 2 * 128 * 4 + HPp * 4
+
+
+def bneck_route(B, H, W, Cin, Cout, stride):
+    """the tile form tss_bneck_eval_fwd launches, TH * 100 + TW (tss_bneck_eval_tile): 4 x 16 at stride 2; 8 x 16 when that makes >= 256
+    blocks and fits the LDS; 8 x 8 when that makes >= 200 blocks; else 4 x 8"""
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if stride == 2:
+        return 416
+    if B * cdiv(Ho, 8) * cdiv(Wo, 16) >= 256 and bneck_lds(1, 8, 16, Cin, Cout) <= BK_LDS:
+        return 816
+    if B * cdiv(Ho, 8) * cdiv(Wo, 8) >= 200:
+        return 808
+    return 408
+
+
+def bneck_supported(Cin, Cmid, Cout, stride, residual):
+    """tss_bneck_eval_supported for bf16: the channel rules, the residual rule, and the one stride-2 tile form fitting the LDS"""
+    if stride not in (1, 2) or Cin < 8 or Cin > 128 or Cin % 8 or Cmid < BK_CM or Cmid % BK_CM or Cout < 16 or Cout > 128 or Cout % 4:
+        return False
+    if residual and (stride != 1 or Cin != Cout):
+        return False
+    return stride == 1 or bneck_lds(2, 4, 16, Cin, Cout) <= BK_LDS
+
+
+class BkCase:
+    """one bottleneck case: shape, the tile form it must reach, where the 1x1 weights come from ('shadow': both bf16 copies given;
+    'f32': neither, the f32 parameters carry low bits; 'skew': a copy pointer off 16-byte alignment that holds OTHER values -- the entry
+    must fall back to the f32 parameter) and the seed of its operands"""
+    def __init__(self, form, Cin, Cmid, Cout, B, H, W, res=0, wmode='shadow', seed=0):
+        self.form, self.Cin, self.Cmid, self.Cout, self.B, self.H, self.W = form, Cin, Cmid, Cout, B, H, W
+        self.stride, self.res, self.wmode, self.seed = BK_FORMS[form][0], res, wmode, seed
+        self.Ho, self.Wo = (H - 1) // self.stride + 1, (W - 1) // self.stride + 1
+
+    def __repr__(self):
+        return '%d-c%d.%d.%d-b%dx%dx%d-s%d%s-%s' % (self.form, self.Cin, self.Cmid, self.Cout, self.B, self.H, self.W, self.stride,
+                                                   'r' if self.res else '', self.wmode)
+
+
+BK_TIER1 = [
+    BkCase(816, 64, 192, 64, 2, 57, 250, res=1),               # 256 blocks exactly, ragged on both axes, three chunks: both sets reused
+    BkCase(816, 64, 128, 48, 2, 57, 250, wmode='f32'),
+    BkCase(808, 128, 128, 128, 1, 113, 105, res=1),            # 8 x 16 would not fit the LDS
+    BkCase(808, 32, 64, 32, 1, 80, 160, wmode='f32'),          # 200 tiles of 8 x 8 exactly, too few blocks for 8 x 16
+    BkCase(408, 128, 768, 128, 1, 13, 21, res=1),              # twelve chunks, the widest sums
+    BkCase(408, 96, 128, 96, 3, 5, 9, res=1, wmode='skew'),
+    BkCase(408, 8, 64, 16, 1, 4, 8),                           # Cin padded 8 -> 32, one chunk: no second set is ever staged; one whole tile
+    BkCase(408, 8, 64, 16, 1, 5, 9, wmode='f32'),              # four tiles, three of them one row or one column
+    BkCase(408, 40, 128, 20, 1, 1, 9, wmode='f32'),            # Cin padded to 64; Cout 20: a quarter fragment, ldy = 28
+    BkCase(408, 40, 128, 20, 1, 9, 1),
+    BkCase(408, 40, 128, 20, 1, 13, 21, wmode='skew'),
+    BkCase(408, 48, 64, 48, 3, 1, 1, res=1, wmode='f32', seed=3),   # 1 x 1 maps: every halo pixel but one outside the image
+    BkCase(408, 48, 64, 48, 3, 5, 9),
+    BkCase(416, 64, 128, 96, 1, 9, 33),                        # -> 5 x 17: a second tile on both axes with one row / column
+    BkCase(416, 8, 64, 20, 1, 8, 32, wmode='f32'),             # -> 4 x 16: one whole tile, the last halo row and column outside the image
+    BkCase(416, 8, 64, 20, 1, 2, 2, seed=1),                   # -> 1 x 1
+    BkCase(416, 64, 128, 96, 2, 1, 1, wmode='skew'),           # -> 1 x 1
+    BkCase(416, 64, 768, 128, 1, 13, 21),                      # twelve chunks at stride 2 (Cin 128 does not fit the stride-2 tile: BK_REFUSED)
+    BkCase(416, 64, 128, 96, 2, 13, 21, wmode='f32'),
+    BkCase(808, 96, 64, 96, 2, 57, 250, res=1, wmode='skew'),  # 256 blocks of 8 x 16, which do not fit the LDS at 96 channels
+]
+BK_TIER2 = [BkCase(816, 64, 192, 64, 2, 57, 250, res=1), BkCase(808, 128, 128, 128, 1, 113, 105, res=1, wmode='f32'),
+            BkCase(408, 128, 768, 128, 1, 13, 21, res=1), BkCase(408, 40, 128, 20, 3, 5, 9), BkCase(416, 64, 128, 96, 1, 9, 33),
+            BkCase(416, 64, 768, 128, 1, 13, 21, wmode='f32')]
+# (Cin, Cmid, Cout, stride, residual) the entry refuses with TSS_ERR_SHAPE.  The last one has legal channel counts but its stride-2 tile
+# (a 9 x 33 halo of 128 input channels) needs 211 KB of LDS
+BK_REFUSED = [(64, 128, 96, 1, 1), (64, 128, 64, 2, 1), (64, 96, 64, 1, 0), (64, 128, 132, 1, 0), (128, 768, 128, 2, 0)]
+BK_ZERO_CAP, BK_ROUNDED_MIN, BK_EPS = 0.70, 0.10, 1e-5
+
+
+def grid_q(shape, gen, lsb, lim, zero_frac=0.0, pos_frac=0.5):
+    """multiples of 2^lsb with 0 < |v| < lim, positive with probability pos_frac; a fraction of exact zeros"""
+    n = int(round(lim * 2.0 ** -lsb))
+    k = torch.randint(1, n, shape, generator=gen).double()
+    s = (torch.rand(shape, generator=gen, dtype=torch.float64) < pos_frac).double() * 2 - 1
+    v = s * k * 2.0 ** lsb
+    if zero_frac > 0:
+        v = torch.where(torch.rand(shape, generator=gen, dtype=torch.float64) < zero_frac, torch.zeros_like(v), v)
+    return v
+
+
+BK_LSB = (-4, -6, -8)          # the grid behind each stage of a tier-1 case
+
+
+class BkOperands:
+    """x [B][Cin][H][W], w1 [Cmid][Cin], wdw [Cmid][3][3], w3 [Cout][Cmid] (f64, exact bf16 values; w1p / w3p: the f32 parameters the
+    entry is given, with low bits in wmode 'f32' and 'skew') and per stage either the frozen BatchNorm itself (tier 2: gamma,
+    running_mean, running_var, beta as f32 numbers) or its affine (tier 1: bn = [(mean, scale, beta)])"""
+    def __init__(self, c, tier, eight_bit=False):
+        g = case_gen(71, tier, c.form, c.Cin, c.Cmid, c.Cout, c.B, c.H, c.W, c.stride, c.res, c.seed)
+        self.c, self.tier = c, tier
+        chans = (c.Cmid, c.Cmid, c.Cout)
+        if tier == 1 and not eight_bit:
+            self.x = grid_q((c.B, c.Cin, c.H, c.W), g, -2, 2.0)
+            self.w1, self.w3 = grid_q((c.Cmid, c.Cin), g, -2, 1.0, 0.5), grid_q((c.Cout, c.Cmid), g, -2, 1.0, 0.5)
+            self.wdw = grid_q((c.Cmid, 3, 3), g, -2, 1.0, 0.2)
+        else:
+            self.x = dyadic((c.B, c.Cin, c.H, c.W), g, -3, 1, 0.02)
+            self.w1, self.w3 = dyadic((c.Cmid, c.Cin), g, -5, -2), dyadic((c.Cout, c.Cmid), g, -5, -2)
+            self.wdw = dyadic((c.Cmid, 3, 3), g, -3, 0)
+        if tier == 1:
+            # the shift t = beta - mean scale is drawn on the stage's grid, then beta = t + mean scale: both products are shifts.  Behind
+            # the expand t > 0 on about 2/3 of the channels: relu(bn1(0)) instead of 0 outside the image then shows in the border outputs
+            self.bn = []
+            for i, C in enumerate(chans):
+                scale, mean = pow2((C,), g, 1, 4), grid_q((C,), g, BK_LSB[i], 2.0)
+                t = grid_q((C,), g, BK_LSB[i], 4.0, pos_frac=0.66 if i == 0 else 0.5)
+                self.bn.append((mean, scale, exact_f32(t + mean * scale)))
+        else:
+            f32 = lambda v: v.float().double()
+            u = lambda C, lo, hi: lo + (hi - lo) * torch.rand((C,), generator=g, dtype=torch.float64)
+            self.frozen = [(f32(u(C, 0.5, 1.5)), f32(u(C, -0.5, 0.5)), f32(u(C, 0.5, 2.0)), f32(u(C, -0.25, 0.5 if i == 0 else 0.25)))
+                           for i, C in enumerate(chans)]          # gamma, running_mean, running_var, beta
+        low = (lambda w: w + torch.sign(w) * 2.0 ** -20) if c.wmode != 'shadow' else (lambda w: w)
+        self.w1p, self.w3p = exact_f32(low(self.w1)), exact_f32(low(self.w3))
+        assert torch.equal(rne_bf16(self.w1p), self.w1) and torch.equal(rne_bf16(self.w3p), self.w3)
+
+
+def fma_f32(a, b, c):
+    """fl32(a b + c), ONE rounding, of f64 vectors that hold f32 numbers (the per-channel shift of csrc/bneck.hip's stage):
+    exact rational arithmetic, then the nearest f32 (ties to even) among the f64-rounded candidate and its two neighbours"""
+    from fractions import Fraction
+    out = []
+    for x, y, z in zip(a.tolist(), b.tolist(), c.tolist()):
+        t = Fraction(x) * Fraction(y) + Fraction(z)
+        f = F32(float(t))
+        cands = (f, np.nextafter(f, F32(np.inf)), np.nextafter(f, F32(-np.inf)))
+        out.append(float(min(cands, key=lambda q: (abs(Fraction(float(q)) - t), int(q.view(np.uint32)) & 1))))
+    return torch.tensor(out, dtype=torch.float64)
+
+
+def round_interval(v, err):
+    """(R(v), bound on |R(k) - R(v)| for every k with |k - v| <= err), R = one bf16 rounding: rounding is monotone, so R(k) lies
+    between R(v - err) and R(v + err).  Where no rounding tie lies within err of v the bound is 0: the kernel must store the
+    reference's bits; where one does it is the one-ulp flip (plus err's own ulps)"""
+    q = bf16_of_f64(v)[0]
+    return q, torch.maximum((bf16_of_f64(v - err)[0] - q).abs(), (bf16_of_f64(v + err)[0] - q).abs())
+
+
+def _gam(n):
+    return 2.0 ** -23 * n          # gamma_n <= 2 n u, the convention of this file
+
+
+def bneck_ref(o, bn, bound=False):
+    """The eval bottleneck in f64 with the kernel's rounding points.  bn: [(mean, scale, beta)] per stage, f64 vectors of f32 numbers
+    (tier 2: the kernel's own vectors read back); shift = fma_f32(-mean, scale, beta) as `stage` forms it.
+
+        E = relu(bn1(conv1(x))), zero outside the image;  stride 2: E := rne_bf16(E)
+        D = rne_bf16(relu(bn2(dw(E))))
+        y = rne_bf16(relu(bn3(conv3(D)) + x?))
+
+    bound=False (tier 1): every rounding goes through rne_bf16, which asserts that its argument is an f32 number; 'S' holds the per
+    stage S = |scale| sum|terms| + |shift| (+ |x|) for bneck_bits.
+    bound=True (tier 2): a forward running error is carried next to every tensor (key 'bound': on |out - y|), u = 2^-24:
+      expand     acc1 = f32 sum of Cin exact products (bf16 x bf16):            |acc1 - c1| <= gamma_Cin A1,  A1 = sum|x||w1|
+                 e = fl(acc1 s1 + t1), one FMA:                                 err1 = |s1| gamma_Cin A1 (1 + u) + u |e|
+                 ReLU is 1-Lipschitz and the validity factor 0 / 1 exact.  Stride 2 rounds E to bf16: round_interval(E, err1)
+      depthwise  9 products of an f32 E and an f32 tap, each rounded and added (FMA: one rounding fewer; 18 counted):
+                                   |acc2 - c2| <= sum|w| errE + gamma_18 sum|w| (|E| + errE)
+                 d = fl(acc2 s2 + t2): err2 = |s2| (that) (1 + u) + u |d|;  D = R(relu(d)): round_interval -- 2^-8 |d| at most, and 0
+                 wherever no tie lies within err2 of d
+      project    acc3 = f32 sum of Cmid exact products over the chunks:         |acc3 - c3| <= sum|w3| errD + gamma_Cmid sum|w3| (|D| + errD)
+                 v = fl(acc3 s3 + t3): err3 = |s3| (that) (1 + u) + u |v|;  the skip is one more f32 addition: + u (|v + x| + err3)
+                 y = R(relu(v)): round_interval(relu(v), err3)
+    Each stage's error reaches the next through |scale| sum|w| of that stage, as the convolutions of errE / errD with |w| above."""
+    Fn, c = torch.nn.functional, o.c
+    v4 = lambda t: t.view(1, -1, 1, 1)
+    sc = [v4(s) for _, s, _ in bn]
+    sh = [v4(fma_f32(-m, s, b)) for m, s, b in bn]
+    if not bound:
+        for (m, s, b), t in zip(bn, sh):
+            assert torch.equal(t.flatten(), b - m * s), 'tier 1: the shift is not exact'
+    R = (lambda v: bf16_of_f64(v)[0]) if bound else rne_bf16
+    w1, w3, wd = o.w1[:, :, None, None], o.w3[:, :, None, None], o.wdw[:, None]
+    dw = lambda t, w: Fn.conv2d(t, w, stride=c.stride, padding=1, groups=c.Cmid)
+    r = {}
+    # expand
+    c1, A1 = Fn.conv2d(o.x, w1), Fn.conv2d(o.x.abs(), w1.abs())
+    e = c1 * sc[0] + sh[0]
+    S1 = sc[0].abs() * A1 + sh[0].abs()
+    E = e.clamp_min(0.0)
+    errE = None
+    if bound:
+        errE = sc[0].abs() * _gam(c.Cin) * A1 * (1 + U32) + U32 * e.abs()
+    r['E_f32'] = E
+    if c.stride == 2:
+        E, errE = round_interval(E, errE) if bound else (R(E), None)
+    # depthwise
+    c2, A2 = dw(E, wd), dw(E.abs(), wd.abs())
+    d = c2 * sc[1] + sh[1]
+    S2 = sc[1].abs() * A2 + sh[1].abs()
+    Dp = d.clamp_min(0.0)
+    if bound:
+        pe = dw(errE, wd.abs())
+        err2 = sc[1].abs() * (pe + _gam(18) * (A2 + pe)) * (1 + U32) + U32 * d.abs()
+        D, errD = round_interval(Dp, err2)
+    else:
+        D = R(exact_f32(Dp))
+    # project
+    c3, A3 = Fn.conv2d(D, w3), Fn.conv2d(D.abs(), w3.abs())
+    v = c3 * sc[2] + sh[2]
+    S3 = sc[2].abs() * A3 + sh[2].abs()
+    if bound:
+        pd = Fn.conv2d(errD, w3.abs())
+        err3 = sc[2].abs() * (pd + _gam(c.Cmid) * (A3 + pd)) * (1 + U32) + U32 * v.abs()
+    if c.res:
+        v, S3 = v + o.x, S3 + o.x.abs()
+        if bound:
+            err3 = err3 + U32 * (v.abs() + err3)
+    yp = v.clamp_min(0.0)
+    if bound:
+        y, r['bound'] = round_interval(yp, err3)
+        r['err3'] = err3
+    else:
+        y = R(exact_f32(yp))
+    r.update(E=E, Dp=Dp, D=D, yp=yp, y=y, S=(S1, S2, S3))
+    return r
+
+
+def bneck_bits(r):
+    """bits of the f32 significand each stage of a tier-1 case uses: log2(max S) - lsb; < 24 means no f32 operation of it rounds"""
+    return [math.log2(float(S.max())) - lsb for S, lsb in zip(r['S'], BK_LSB)]
+
+
+def bneck_exact(o, r):
+    """the tier-1 premise of a case from its own operands (X.exact_budget per stage) and that its operands sit on their grids"""
+    grids = all(lsb_exp(t) >= -2 for t in (o.x, o.w1, o.wdw, o.w3)) and all(
+        lsb_exp(torch.cat([m, b])) >= lsb and bool(((s == 1) | (s == 2) | (s == 4)).all()) for (m, s, b), lsb in zip(o.bn, BK_LSB))
+    return grids and all(exact_budget(S, lsb) for S, lsb in zip(r['S'], BK_LSB))
+
+
+def rounding_census(pre, q):
+    """(fraction of the elements their bf16 rounding changes, number of exact ties among them)"""
+    return float((pre != q).double().mean()), int(((bf16_of_f64(pre)[2] == 0) & (pre != q)).sum())
+
+
+def bneck_conditions(o, r):
+    """what a tier-1 case must exercise, from the reference alone: output zeros under the cap (ReLU must not hide a stage), both
+    roundings at work including ties to even, and relu(bn1(0)) > 0 on at least half of the expanded channels"""
+    zeros = float((r['y'] == 0).double().mean())
+    (fd, td), (fy, ty) = rounding_census(r['Dp'], r['D']), rounding_census(r['yp'], r['y'])
+    m, s, b = o.bn[0]
+    pos = float((b - m * s > 0).double().mean())
+    ok = zeros <= BK_ZERO_CAP and fd >= BK_ROUNDED_MIN and fy >= BK_ROUNDED_MIN and td >= 1 and ty >= 1 and pos >= 0.5
+    return ok, dict(zeros=zeros, rounded_D=fd, ties_D=td, rounded_y=fy, ties_y=ty, positive_shift1=pos)
+
+
+# --- frozen-BatchNorm affines (bn_eval_affine_kernel, bn_eval_affine_batched_kernel)
+AFFINE_U = (3, 4)      # u-counts of invstd and scale, below
+
+
+def affine_ref(gamma, rmean, rvar, eps):
+    """(mean, invstd, scale) in f64 from f64 vectors of f32 numbers, eps the f32 number the entry receives.  The kernel computes
+        t = fl(var + eps)  (1 + d1);   r = fl(sqrt(t))  (1 + d2);   invstd = fl(1 / r)  (1 + d3);   scale = fl(gamma invstd)  (1 + d4)
+    with |d_i| <= u (correctly rounded sqrt and divide), so invstd = (var + eps)^-1/2 (1 + d1)^-1/2 (1 + d2)^-1 (1 + d3): relative error
+    <= u / 2 + u + u + O(u^2) < 3 u, and scale one rounding more: < 4 u.  mean is a copy: bit for bit.  gamma None: scale = invstd"""
+    invstd = 1.0 / torch.sqrt(rvar + float(F32(eps)))
+    return rmean, invstd, (gamma * invstd if gamma is not None else invstd)
+
+
+def affine_excess(out, ref, n):
+    return ((out - ref).abs() - n * U32 * ref.abs()).max().item()
+
+
+# --- joins (join_fwd_kernel, join_bwd_kernel)
+JOIN_NT, JOIN_FWD_BLOCKS = 256, 512
+
+
+def join_geometry(P, C, max_blocks=STAT_SLABS):
+    """join_geometry of csrc/pointwise.hip: (NPL pixels per block trip, grid).  A lane owns one 8-channel group of pixels
+    blk NPL + pl + k grid NPL; the forward's grid cap is 512 blocks, the backward's the slab rows"""
+    NPL = JOIN_NT // (C // 8)
+    return NPL, max(1, min(cdiv(P, NPL), max_blocks))
+
+
+def join_P(kind, C):
+    """the pixel counts of the join cases, from the restated geometry: one pixel; a block's last lane row idle; the 512-block grid filled
+    exactly; five whole sweeps and 7 pixels, so that a lane's second 4-pixel trip is only partly inside"""
+    NPL = JOIN_NT // (C // 8)
+    return {'one': 1, 'short': max(NPL - 1, 1), 'grid': JOIN_FWD_BLOCKS * NPL, 'second': JOIN_FWD_BLOCKS * NPL * 5 + 7}[kind]
+
+
+def join_stats_chain(P, C):
+    """f32 chain of a lane of join_bwd_kernel<bf16>: one addition per pixel it owns, ceil(P / (grid NPL)); lanes meet in f64 (1 when the
+    grid covers P)"""
+    NPL, grid = join_geometry(P, C)
+    return cdiv(P, grid * NPL)
+
+
+def join_fwd_ref(a, affa, b=None, affb=None, relu=False):
+    """relu?(a' + b'), each branch (v - mean) scale + beta or v itself: every branch and the sum exact in f32 (checked)"""
+    br = lambda v, aff: exact_f32(pre_act(v, *aff)) if aff is not None else v
+    s = br(a, affa)
+    if b is not None:
+        s = exact_f32(s + br(b, affb))
+    return s.clamp_min(0.0) if relu else s
+
+
+def join_bwd_ref(dout, out, relu, dscale=1.0):
+    """e = dout dscale (a power of two: exact) where out > 0 (or everywhere without ReLU), else 0"""
+    e = dout * dscale
+    return e * (out > 0).double() if relu else e

@@ -1,5 +1,5 @@
 """GPU harness of the exact-operand tests (tests/test_gpu_zoo_exact.py, tests/test_gpu_dw_exact.py, tests/test_gpu_pw_exact.py,
-tests/test_gpu_dense_exact.py, tests/test_gpu_resample_exact.py):
+tests/test_gpu_dense_exact.py, tests/test_gpu_resample_exact.py, tests/test_gpu_bneck_exact.py):
 sentinel-padded device buffers with spare rows, NaN statistics slabs, the dyadic operands of a layer with planted exact zeros, and the
 checks against tests/exact.py's bounds."""
 import contextlib
@@ -26,9 +26,11 @@ def dev(v):
 class Buf:
     """a [P + SPARE][ld] bf16 device buffer, sentinel everywhere, the tensor's rows (f64 [P][C], exact bf16 values) at columns
     [off, off + C); .ptr points at column off"""
-    def __init__(self, P, C, ld, off=0, rows=None, dtype=torch.bfloat16, nan_spare=False):
+    def __init__(self, P, C, ld, off=0, rows=None, dtype=torch.bfloat16, nan_spare=False, nan_pad=False):
         self.P, self.C, self.ld, self.off = P, C, ld, off
         t = X.sentinel((P + SPARE, ld), dtype=dtype)
+        if nan_pad:          # an INPUT whose pad columns poison whatever reads them too
+            t[:] = float('nan')
         if rows is not None:
             t[:P, off:off + C] = rows.to(dtype)
         if nan_spare:        # an INPUT whose spare rows poison whatever reads them, even with the weight 0 (an unclamped i1 tap)
@@ -227,3 +229,56 @@ def check_stats_sums(slabs, sums, chain, what, rows_used=None, f64=False):
         return
     ex = X.stats_excess_sums(s.sum(0), sums[0], sums[1], chain)
     assert ex <= 0, (what, 'statistics excess', ex, 'chain', chain)
+
+
+# ----------------------------------------------------------------------------------------------------- eval bottleneck, affines
+def bneck_tile(c):
+    """the library's own answer to X.bneck_route"""
+    return N_().lib().tss_bneck_eval_tile(c.B, c.H, c.W, c.Cin, c.Cout, c.stride)
+
+
+def skewed_copy(w):
+    """a bf16 copy pointer 2 bytes off 16-byte alignment whose memory holds OTHER values (the negated weights): an entry that used it
+    instead of falling back to the f32 parameter would change every output.  Returns (tensor to keep alive, pointer)"""
+    t = torch.zeros(w.numel() + 8, dtype=torch.bfloat16)
+    t[1:1 + w.numel()] = (-w).reshape(-1).to(torch.bfloat16)
+    t = t.to(DEV)
+    return t, t.data_ptr() + 2
+
+
+def bneck_call(o, bn):
+    """ONE tss_bneck_eval_fwd on a case's operands (X.BkOperands).  bn: [(mean, scale, beta)] device f32 vectors.  x sits at a 16-byte
+    column offset of a pitch Cin + 16 whose pad columns and spare rows are NaN; y at an 8-byte column offset of a pitch Cout + 8,
+    sentinel around it and in SPARE rows behind it.  Returns the output Buf (not synchronised)"""
+    n, c = N_(), o.c
+    xb = Buf(c.B * c.H * c.W, c.Cin, c.Cin + 16, 8, to_rows(o.x), nan_spare=True, nan_pad=True)
+    yb = Buf(c.B * c.Ho * c.Wo, c.Cout, c.Cout + 8, 4)
+    w1, wdw, w3 = dev(o.w1p), dev(o.wdw.reshape(c.Cmid, 9)), dev(o.w3p)
+    keep, s1, s3 = [], None, None
+    if c.wmode == 'shadow':
+        keep = [o.w1.to(torch.bfloat16).to(DEV), o.w3.to(torch.bfloat16).to(DEV)]
+        s1, s3 = keep[0].data_ptr(), keep[1].data_ptr()
+    elif c.wmode == 'skew':
+        (k1, s1), (k3, s3) = skewed_copy(o.w1), skewed_copy(o.w3)
+        keep = [k1, k3]
+    p = lambda t: t.data_ptr()
+    (m1, c1, b1), (m2, c2, b2), (m3, c3, b3) = bn
+    n.call('tss_bneck_eval_fwd', xb.ptr, xb.ld, p(w1), s1, p(m1), p(c1), p(b1), p(wdw), p(m2), p(c2), p(b2), p(w3), s3, p(m3), p(c3), p(b3),
+           c.res, yb.ptr, yb.ld, c.B, c.H, c.W, c.Cin, c.Cmid, c.Cout, c.stride, n.TSS_BF16, n.stream())
+    torch.cuda.synchronize()
+    return yb
+
+
+def eps_bits(eps):
+    import struct
+    return struct.unpack('<i', struct.pack('<f', eps))[0]
+
+
+def affine_batched(jobs, max_channels=None):
+    """tss_bn_eval_affine_batched over [(gamma or None, running_mean, running_var, out, C, eps)] (device f32 tensors; out: a tensor or a
+    pointer to 3 C floats)"""
+    n = N_()
+    p = lambda t: 0 if t is None else t if isinstance(t, int) else t.data_ptr()
+    table = torch.tensor([[p(g), p(rm), p(rv), p(out), C, eps_bits(eps)] for g, rm, rv, out, C, eps in jobs], dtype=torch.int64).to(DEV)
+    n.call('tss_bn_eval_affine_batched', table.data_ptr(), len(jobs), max_channels or max(j[4] for j in jobs), n.stream())
+    torch.cuda.synchronize()

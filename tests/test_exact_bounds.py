@@ -1319,3 +1319,295 @@ def test_f32_emulation_of_the_arms_backward_meets_tier_3_and_a_mirrored_channel_
         _, _, bad = _arms_bwd32(o, R, training, accumulate, mirror=True)          # defect: a mirrored cv in the transposed store
         ref, bound = R['dw']
         assert ((bad - ref).abs() - bound).max() > 0
+
+
+# ---------------------------------------------------------------------------------------------------------- eval bottleneck, affines, joins
+def test_bneck_route_and_lds_reach_every_tile_form_of_the_case_tables():
+    lds = X.bneck_lds
+    assert 140 * 1024 < lds(1, 8, 16, 64, 64) <= X.BK_LDS                     # about 144 KB
+    assert lds(1, 8, 16, 96, 96) > X.BK_LDS and lds(1, 8, 16, 128, 128) > X.BK_LDS
+    assert lds(1, 8, 8, 128, 128) <= X.BK_LDS and lds(1, 4, 8, 128, 128) <= X.BK_LDS      # stride 1 always has a form that fits
+    assert lds(2, 4, 16, 64, 128) <= X.BK_LDS < min(lds(2, 4, 16, 128, 16), lds(2, 4, 16, 96, 128))     # stride 2: any Cout at Cin <= 64
+    assert X.bneck_route(2, 57, 250, 64, 64, 1) == 816 and X.bneck_route(2, 57, 250, 128, 128, 1) == 808      # enough blocks, no fit
+    assert X.bneck_route(2, 57, 240, 64, 64, 1) == 808                         # 240 blocks of 8 x 16 only
+    assert X.bneck_route(1, 80, 160, 32, 32, 1) == 808 and X.bneck_route(1, 80, 152, 32, 32, 1) == 408       # 200 / 190 tiles of 8 x 8
+    for c in X.BK_TIER1 + X.BK_TIER2:
+        S, TH, TW = X.BK_FORMS[c.form]
+        assert X.bneck_route(c.B, c.H, c.W, c.Cin, c.Cout, c.stride) == c.form and S == c.stride, c
+        assert lds(S, TH, TW, c.Cin, c.Cout) <= X.BK_LDS and X.bneck_supported(c.Cin, c.Cmid, c.Cout, c.stride, c.res), c
+    c = X.BK_TIER1[0]
+    assert c.B * X.cdiv(c.Ho, 8) * X.cdiv(c.Wo, 16) == 256 and c.Ho % 8 and c.Wo % 16 and c.Cmid // X.BK_CM == 3
+    for table in (X.BK_TIER1, X.BK_TIER2):       # the four tile forms and both numeric forms at least twice (tier 1), once (tier 2)
+        forms = [c.form for c in table]
+        assert all(forms.count(f) >= (2 if table is X.BK_TIER1 else 1) for f in X.BK_FORMS)
+    assert {c.wmode for c in X.BK_TIER1 if c.stride == 1} == {c.wmode for c in X.BK_TIER1 if c.stride == 2} == {'shadow', 'f32', 'skew'}
+    assert not any(X.bneck_supported(*r) for r in X.BK_REFUSED)
+
+
+@pytest.mark.parametrize('c', X.BK_TIER1, ids=repr)
+def test_bneck_budget_accepts_every_tier1_case_and_rejects_8_bit_operands(c):
+    o = X.BkOperands(c, 1)
+    r = X.bneck_ref(o, o.bn)
+    assert X.bneck_exact(o, r) and max(X.bneck_bits(r)) < 24
+    ok, census = X.bneck_conditions(o, r)
+    assert ok, census
+    o8 = X.BkOperands(c, 1, eight_bit=True)
+    assert not X.bneck_exact(o8, X.bneck_ref(o8, o8.bn, bound=True))
+    with pytest.raises(AssertionError):          # and the reference itself refuses to round what is not an f32 number
+        X.bneck_ref(o8, o8.bn)
+
+
+def _fma32(a, b, c):
+    """one FMA in f32: the product of two f32 numbers is exact in f64"""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def _bk_tile(c):
+    """the last tile of the last image, the ragged end of the map: (b, oy0, oy1, ox0, ox1) in output pixels"""
+    _, TH, TW = X.BK_FORMS[c.form]
+    oy0, ox0 = (c.Ho - 1) // TH * TH, (c.Wo - 1) // TW * TW
+    return c.B - 1, oy0, c.Ho, ox0, c.Wo
+
+
+def _bk_emulate(o, bn, defect=None):
+    """f32 emulation of the three stages of csrc/bneck.hip from the same operands in a deliberately bad accumulation order -- channels
+    last to first, one rounded addition per product; taps last to first with the product and the addition rounded apart -- rounding to
+    bf16 where the kernel does.  defect: one realistic kernel defect in ONE tile (_bk_tile) of the case's tile form"""
+    c = o.c
+    f, v4 = (lambda t: t.float()), (lambda t: t.float().view(1, -1, 1, 1))
+    bf = lambda t: t.bfloat16().float()
+    x, w1, wd, w3 = f(o.x), f(o.w1), f(o.wdw), f(o.w3)
+    sc = [v4(s) for _, s, _ in bn]
+    sh = [v4(X.fma_f32(-m, s, b)) for m, s, b in bn]
+    b_, oy0, oy1, ox0, ox1 = _bk_tile(c)
+    S = c.stride
+
+    def splice(good, bad, x0=ox0, x1=ox1, ch=slice(None)):
+        out = good.clone()
+        out[b_, ch, oy0:oy1, x0:x1] = bad[b_, ch, oy0:oy1, x0:x1]
+        return out
+
+    acc = torch.zeros(c.B, c.Cmid, c.H, c.W)
+    for ci in reversed(range(c.Cin)):
+        acc = acc + x[:, ci:ci + 1] * w1[:, ci].view(1, -1, 1, 1)
+    E = _fma32(acc, sc[0], sh[0]).clamp_min(0.0)
+    if S == 2:
+        E = bf(E)
+
+    def depthwise(E, pad_value=None, s2=sc[1], t2=sh[1], shift_col=None):
+        Ep = torch.nn.functional.pad(E, (1, 1, 1, 1))
+        if pad_value is not None:                   # defect: relu(bn1(0)) instead of 0 outside the image
+            border = torch.ones(1, 1, c.H + 2, c.W + 2)
+            border[:, :, 1:-1, 1:-1] = 0
+            Ep = Ep + border * pad_value
+        if shift_col is not None:                   # defect: the tile's left halo column read one pixel too far left
+            Ep = Ep.clone()
+            Ep[:, :, :, shift_col + 1] = Ep[:, :, :, shift_col]
+        acc = torch.zeros(c.B, c.Cmid, c.Ho, c.Wo)
+        for t in reversed(range(9)):
+            ky, kx = divmod(t, 3)
+            win = Ep[:, :, ky:ky + S * (c.Ho - 1) + 1:S, kx:kx + S * (c.Wo - 1) + 1:S]
+            acc = acc + win * wd[:, ky, kx].view(1, -1, 1, 1)
+        return bf(_fma32(acc, s2, t2).clamp_min(0.0))
+
+    D = depthwise(E)
+    if defect == 'E not zeroed':
+        D = splice(D, depthwise(E, pad_value=sh[0].clamp_min(0.0)))
+    elif defect == 'halo shifted':
+        assert ox0 > 0
+        D = splice(D, depthwise(E, shift_col=ox0 * S - 1))
+    elif defect == 'stale bn2':
+        st = lambda t: torch.cat([t[:, :X.BK_CM], t[:, :X.BK_CM], t[:, 2 * X.BK_CM:]], 1)
+        D = splice(D, depthwise(E, s2=st(sc[1]), t2=st(sh[1])))
+    elif defect == 'E in bf16':
+        assert S == 1
+        D = splice(D, depthwise(bf(E)))
+
+    acc = torch.zeros(c.B, c.Cout, c.Ho, c.Wo)
+    for cm in reversed(range(c.Cmid)):
+        acc = acc + D[:, cm:cm + 1] * w3[:, cm].view(1, -1, 1, 1)
+    if defect == 'Cout tail':
+        assert c.Cout % 16 == 4                       # the quarter fragment takes the next quarter's accumulators: padded channels, zeros
+        acc = splice(acc, torch.zeros_like(acc), ch=slice(c.Cout - 4, c.Cout))
+    v = _fma32(acc, sc[2], sh[2])
+    if c.res:
+        skip = x
+        if defect == 'skip from the neighbour':       # the tile's first column adds the pixel to its right
+            skip = splice(x, torch.roll(x, -1, 3), x1=ox0 + 1)
+        v = v + skip
+    return bf(v.clamp_min(0.0)).double()
+
+
+def _affine32(gamma, rm, rv, eps, eps_outside=False):
+    """bn_eval_affine_kernel step by step in f32: (mean, invstd, scale) as f64.  eps_outside: a defect, 1 / (sqrt(var) + eps)"""
+    f = lambda t: t.numpy().astype(X.F32)
+    e = X.F32(eps)
+    invstd = X.F32(1) / (np.sqrt(f(rv)) + e if eps_outside else np.sqrt(f(rv) + e))
+    scale = invstd if gamma is None else f(gamma) * invstd
+    t = lambda a: torch.from_numpy(a.astype(np.float64))
+    return rm, t(invstd), t(scale)
+
+
+T1_EMU = [X.BK_TIER1[4], X.BK_TIER1[10], X.BK_TIER1[13], X.BK_TIER1[8]]      # (128, 768, 128) + skip; (40, 128, 20) 13 x 21; stride 2; 1 x 9
+T1_DEFECTS = [(4, 'E not zeroed'), (4, 'halo shifted'), (4, 'skip from the neighbour'), (4, 'stale bn2'), (4, 'E in bf16'), (10, 'Cout tail'),
+              (13, 'E not zeroed'), (13, 'halo shifted')]
+
+
+@pytest.mark.parametrize('c', T1_EMU, ids=repr)
+def test_bneck_f32_emulation_in_a_bad_order_is_bit_for_bit_on_tier1_operands(c):
+    o = X.BkOperands(c, 1)
+    r = X.bneck_ref(o, o.bn)
+    assert X.bneck_exact(o, r)
+    assert torch.equal(_bk_emulate(o, o.bn), r['y'])
+
+
+@pytest.mark.parametrize('i,defect', T1_DEFECTS)
+def test_bneck_tier1_fails_with_one_defect_in_one_tile(i, defect):
+    o = X.BkOperands(X.BK_TIER1[i], 1)
+    r = X.bneck_ref(o, o.bn)
+    bad = _bk_emulate(o, o.bn, defect)
+    wrong = (bad != r['y']).nonzero()
+    assert len(wrong) > 0, defect
+    b_, oy0, oy1, ox0, ox1 = _bk_tile(o.c)           # and only that tile is wrong
+    assert bool(((wrong[:, 0] == b_) & (wrong[:, 2] >= oy0) & (wrong[:, 3] >= ox0)).all())
+
+
+def _t2_affines(o):
+    return [_affine32(g, rm, rv, X.BK_EPS)[::2] + (beta,) for g, rm, rv, beta in o.frozen]
+
+
+T2_EMU = [X.BK_TIER2[2], X.BK_TIER2[3], X.BK_TIER2[4]]                        # (128, 768, 128) + skip; (40, 128, 20); stride 2
+T2_DEFECTS = [(2, 'E not zeroed'), (2, 'halo shifted'), (2, 'skip from the neighbour'), (2, 'stale bn2'), (3, 'Cout tail'), (4, 'E not zeroed')]
+
+
+@pytest.mark.parametrize('c', T2_EMU, ids=repr)
+def test_bneck_f32_emulation_in_a_bad_order_meets_the_tier2_bound(c):
+    o = X.BkOperands(c, 2)
+    bn = _t2_affines(o)
+    r = X.bneck_ref(o, bn, bound=True)
+    out = _bk_emulate(o, bn)
+    assert bool(((out - r['y']).abs() <= r['bound']).all())
+    assert bool((torch.isfinite(r['bound']) & (r['bound'] >= 0)).all())
+    assert float((r['y'] == 0).double().mean()) <= X.BK_ZERO_CAP
+
+
+@pytest.mark.parametrize('i,defect', T2_DEFECTS)
+def test_bneck_tier2_fails_with_one_defect_in_one_tile(i, defect):
+    o = X.BkOperands(X.BK_TIER2[i], 2)
+    bn = _t2_affines(o)
+    r = X.bneck_ref(o, bn, bound=True)
+    assert not bool(((_bk_emulate(o, bn, defect) - r['y']).abs() <= r['bound']).all()), defect
+
+
+def test_fma_f32_rounds_once():
+    g = _gen(5)
+    a, b, c = (X.full_f32((512,), g) for _ in range(3))
+    got = X.fma_f32(a, b, c)
+    assert torch.equal(got.float().double(), got)
+    exact = a * b + c                                 # f64: off by at most 2^-53 relative, so the f32 neighbours bracket it
+    assert bool(((got - exact).abs() <= 2.0 ** -24 * exact.abs() * (1 + 2.0 ** -20)).all())
+    assert torch.equal(X.fma_f32(torch.tensor([3.0]), torch.tensor([0.5]), torch.tensor([0.25])), torch.tensor([1.75], dtype=torch.float64))
+
+
+def test_affine_u_counts_hold_for_an_f32_emulation_over_a_sweep_of_variances():
+    g = _gen(6)
+    n = 200000
+    rv = torch.exp(torch.rand((n,), generator=g, dtype=torch.float64) * 30 - 18).float().double()      # 1.5e-8 .. 1.6e5
+    gamma, rm = X.dyadic((n,), g) * 1.37, X.dyadic((n,), g)
+    gamma = gamma.float().double()
+    for eps in (1e-5, 1e-3):
+        for gm in (gamma, None):
+            mean, invstd, scale = X.affine_ref(gm, rm, rv, eps)
+            m32, i32, s32 = _affine32(gm, rm, rv, eps)
+            assert torch.equal(m32, mean)
+            assert X.affine_excess(i32, invstd, X.AFFINE_U[0]) <= 0 and X.affine_excess(s32, scale, X.AFFINE_U[1]) <= 0
+            assert X.affine_excess(i32, invstd, 1) > 0            # three roundings do show: one u would not hold
+            _, ibad, _ = _affine32(gm, rm, rv, eps, eps_outside=True)
+            assert X.affine_excess(ibad, invstd, X.AFFINE_U[0]) > 0
+
+
+def test_join_geometry_edges_and_the_lane_chain():
+    assert X.join_geometry(1, 8) == (256, 1) and X.join_geometry(38407, 136) == (15, 512) and X.join_geometry(512, 2048) == (1, 512)
+    for C in (8, 24, 136, 2048):
+        NPL = X.JOIN_NT // (C // 8)
+        assert X.join_P('grid', C) == 512 * NPL and X.join_geometry(X.join_P('grid', C), C, X.JOIN_FWD_BLOCKS)[1] == 512
+        assert X.join_stats_chain(X.join_P('grid', C), C) == 1 and X.join_stats_chain(X.join_P('grid', C) + 1, C) == 2
+    assert X.JOIN_NT // (136 // 8) * (136 // 8) == 255            # C = 136: the block's last thread owns no pixel
+    P = X.join_P('second', 136)
+    assert P == 38407 and X.join_stats_chain(P, 136) == 6
+    # a lane's second trip (pixels p0 + 4 k stride, k = 0 .. 3) is partly inside for the first 7 lanes of block 0 and wholly outside for none
+    stride = 512 * 15
+    inside = [sum(p0 + 4 * stride + u * stride < P for u in range(4)) for p0 in range(stride)]
+    assert set(inside) == {1, 2} and inside.count(2) == 7
+
+
+def _join32(a, A, b, Bf, relu, dtype, relu_first=False):
+    """join_fwd_kernel in f32, in the kernel's order; relu_first: a defect, the ReLU applied before the second branch is added"""
+    br = lambda v, aff: (v.float() - aff[0].float()) * aff[1].float() + aff[2].float() if aff is not None else v.float()
+    s = br(a, A)
+    if relu_first and relu:
+        s = s.clamp_min(0.0)
+    if b is not None:
+        s = s + br(b, Bf)
+    if relu:
+        s = s.clamp_min(0.0)
+    return (s.bfloat16() if dtype == torch.bfloat16 else s).double()
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float32])
+def test_join_emulation_is_bit_for_bit_and_a_relu_before_the_second_branch_fails(dtype):
+    g = _gen(7)
+    P, C = 300, 24
+    mk = lambda: (X.dyadic((C,), g), X.pow2((C,), g, 0.5, 4), X.dyadic((C,), g))
+    A, Bf = mk(), mk()
+    a, b = X.plant_zeros(X.dyadic((P, C), g), *A, g, 0.25), X.plant_zeros(X.dyadic((P, C), g), *Bf, g, 0.25)
+    for relu in (0, 1):
+        for aa, bb, AA, BB in ((a, b, A, Bf), (a, b, None, Bf), (a, b, A, None), (a, None, A, None), (a, None, None, None)):
+            want = X.out_bits_ref(X.join_fwd_ref(aa, AA, bb, BB, relu), dtype == torch.bfloat16)
+            assert torch.equal(_join32(aa, AA, bb, BB, relu, dtype), want)
+    want = X.out_bits_ref(X.join_fwd_ref(a, A, b, Bf, 1), dtype == torch.bfloat16)
+    assert bool((X.join_fwd_ref(a, A, b, Bf, 0) == 0).any())
+    assert not torch.equal(_join32(a, A, b, Bf, 1, dtype, relu_first=True), want)
+
+
+def _join_bwd_slabs(e, raw, mean, C, P, skip_zeroing=None):
+    """join_bwd_kernel<bf16>'s statistics rows on the CPU from NaN slabs: a lane adds the pixels it owns in f32, the block's lanes meet
+    in f64, and the blocks zero the rows nobody owns.  skip_zeroing: a defect, that row is left as it was"""
+    NPL, grid = X.join_geometry(P, C)
+    slabs = torch.full((X.STAT_SLABS, 2 * C), float('nan'), dtype=torch.float64)
+    terms = torch.cat([e, e * (raw - mean)], 1).float()
+    span = grid * NPL
+    trips = X.cdiv(P, span)
+    padded = torch.zeros(trips * span, 2 * C)
+    padded[:P] = terms
+    lanes = torch.zeros(span, 2 * C)
+    for k in range(trips):
+        lanes = lanes + padded[k * span:(k + 1) * span]
+    slabs[:grid] = lanes.double().reshape(grid, NPL, 2 * C).sum(1)
+    for r in range(grid, X.STAT_SLABS):
+        if r != skip_zeroing:
+            slabs[r] = 0.0
+    return slabs, grid
+
+
+def test_join_backward_statistics_emulation_and_an_unowned_row_left_unzeroed_fails():
+    from tests.exact_gpu import check_slab_rows
+    g = _gen(8)
+    for C, kind in ((136, 'second'), (24, 'short')):
+        P = X.join_P(kind, C)
+        dout, out = X.dyadic((P, C), g, zero_frac=0.03), X.dyadic((P, C), g).clamp_min(0.0)
+        raw, mean = X.dyadic((P, C), g), X.dyadic((C,), g)
+        e = X.join_bwd_ref(dout, out, 1, 2.0)
+        assert torch.equal(e, X.rne_bf16(e)) and bool(((e == 0) == ((out <= 0) | (dout == 0))).all())
+        slabs, grid = _join_bwd_slabs(e, raw, mean, C, P)
+        check_slab_rows(slabs, range(grid), kind)
+        terms = X.exact_f32(torch.cat([e, e * X.exact_f32(raw - mean)], 1))
+        assert X.stats_excess(slabs.sum(0), terms, X.join_stats_chain(P, C)) <= 0
+        bad, _ = _join_bwd_slabs(e, raw, mean, C, P, skip_zeroing=X.STAT_SLABS - 1 if grid < X.STAT_SLABS else None)
+        if grid < X.STAT_SLABS:
+            with pytest.raises(AssertionError):
+                check_slab_rows(bad, range(grid), kind)
+        else:                                     # every row owned: a block that wrote nothing leaves its NaN
+            slabs[grid - 1] = float('nan')
+            with pytest.raises(AssertionError):
+                check_slab_rows(slabs, range(grid), kind)

@@ -428,7 +428,17 @@ __global__ __launch_bounds__(NT, 2) void bneck_eval_kernel(const BkArgs g) {
 }
 
 template <int S, int TH, int TW>
-bool fits(const BkArgs& g) { return Geo<S, TH, TW>::lds(g.Cin, g.Cout) <= 160 * 1024; }
+bool fits(int Cin, int Cout) { return Geo<S, TH, TW>::lds(Cin, Cout) <= 160 * 1024; }
+
+// the instance a shape runs, as TH * 100 + TW.  8 x 16 tiles when they fill the chip (and fit the LDS), else 8 x 8, else 4 x 8 (a block per
+// CU matters more than the halo: the 1/32 maps of a 2048 x 4096 image are 128 tiles of 8 x 8); stride 2: 4 x 16 outputs over a 9 x 33 input tile
+int tile_for(int B, int H, int W, int Cin, int Cout, int stride) {
+  const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  if (stride == 2) return 416;
+  if ((long)B * ((Ho + 7) / 8) * ((Wo + 15) / 16) >= 256 && fits<1, 8, 16>(Cin, Cout)) return 816;
+  if ((long)B * ((Ho + 7) / 8) * ((Wo + 7) / 8) >= 200) return 808;
+  return 408;
+}
 
 template <int S, int TH, int TW>
 int launch(BkArgs& g, hipStream_t stream) {
@@ -463,7 +473,14 @@ int tss_bneck_eval_supported(int Cin, int Cmid, int Cout, int stride, int residu
   if (stride != 1 && stride != 2) return 0;
   if (Cin < 8 || Cin > 128 || (Cin % 8) != 0 || Cmid < CM || (Cmid % CM) != 0 || Cout < 16 || Cout > 128 || (Cout % 4) != 0) return 0;
   if (residual && (stride != 1 || Cin != Cout)) return 0;
+  if (stride == 2 && !fits<2, 4, 16>(Cin, Cout)) return 0;     // the only stride-2 tile; Cin <= 64 always fits, Cin = 128 never (stride 1 always fits 4 x 8)
   return 1;
+}
+
+// which instance tss_bneck_eval_fwd would launch for this shape: TH * 100 + TW (816, 808, 408; 416 at stride 2).  Read-only
+int tss_bneck_eval_tile(int B, int H, int W, int Cin, int Cout, int stride) {
+  if (B <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return TSS_ERR_SHAPE;
+  return tile_for(B, H, W, Cin, Cout, stride);
 }
 
 // x: bf16 NHWC [B][H][W][Cin] (pitch ldx), materialised.  y: bf16 NHWC [B][Ho][Wo][Cout], Ho = (H - 1) / stride + 1.
@@ -492,13 +509,12 @@ int tss_bneck_eval_fwd(const void* x, long ldx, const float* w1, const void* w1_
   tss::ProfScope prof(TSS_K_PWCONV_FWD, (hipStream_t)stream, ((double)B * H * W * Cin + (double)P * Cout) * 2.0,
                       2.0 * ((double)B * H * W * Cin * Cmid + (double)P * Cmid * (9 + Cout)));
   int rc;
-  // 8 x 16 tiles when they fill the chip (and fit the LDS), else 8 x 8, else 4 x 8 (a block per CU matters more than the halo: the 1/32
-  // maps of a 2048 x 4096 image are 128 tiles of 8 x 8); stride 2: 4 x 16 outputs over a 9 x 33 input tile
-  const long t88 = (long)B * ((g.Ho + 7) / 8) * ((g.Wo + 7) / 8);
-  if (stride == 2) rc = launch<2, 4, 16>(g, (hipStream_t)stream);
-  else if ((long)B * ((g.Ho + 7) / 8) * ((g.Wo + 15) / 16) >= 256 && fits<1, 8, 16>(g)) rc = launch<1, 8, 16>(g, (hipStream_t)stream);
-  else if (t88 >= 200) rc = launch<1, 8, 8>(g, (hipStream_t)stream);
-  else rc = launch<1, 4, 8>(g, (hipStream_t)stream);
+  switch (tile_for(B, H, W, Cin, Cout, stride)) {
+    case 416: rc = launch<2, 4, 16>(g, (hipStream_t)stream); break;
+    case 816: rc = launch<1, 8, 16>(g, (hipStream_t)stream); break;
+    case 808: rc = launch<1, 8, 8>(g, (hipStream_t)stream); break;
+    default: rc = launch<1, 4, 8>(g, (hipStream_t)stream); break;
+  }
   if (rc) return rc;
   return tss::check_last("bneck_eval_fwd");
 }
