@@ -775,7 +775,12 @@ int tss_label_histogram(const long long* target, long long* counts, long n, int 
  * One pass computes the loss AND the unscaled low-res gradient, as per-block tiles and per-block loss rows in `ws`
  * (tss_upsample_ce_ws(...) floats, 16-byte aligned, NOT initialised by the caller: every element that is read was written by
  * the pass); backward = tss_upsample_ce_bwd gathers the tiles of every low-res cell in a fixed order: dlow = sum * grad_out /
- * count ([B][h][w][ldl], pitch padding zeroed).  No atomics anywhere: bit-identical from run to run.  C <= 24, H >= h, W >= w. */
+ * count ([B][h][w][ldl], pitch padding zeroed).  No atomics anywhere: bit-identical from run to run.  C <= 24, H >= h, W >= w.
+ * Read extent of `low` (every entry of the family: ldl % 8 == 0, ldl >= round_up(C, 4), pad channels may hold anything, NaN included):
+ * no entry reads a channel at or past ldl of any pixel, nor anything behind the last pixel's pitch.  The register entries (C <= 24:
+ * tss_upsample_ce_fwd / _fwd_ex, tss_upsample_pixel_ce, tss_upsample_ohem_grad, tss_upsample_argmax_confusion) read the first 20
+ * (C <= 20) or 24 channels of a pixel when ldl holds them, else only the 4-channel groups that start below C (round_up(C, 4)
+ * channels), as the focal / Dice / multi-scale entries always do; the wide entries read the 8-channel groups that start below C. */
 long tss_upsample_ce_ws(int B, int C, int h, int w, int H, int W);
 int tss_upsample_ce_fwd(const void* low, long ldl, const long long* target, float* ws, float* loss, float* inv_count,
                         int B, int C, int h, int w, int H, int W, int ignore_index, int dtype, void* stream);

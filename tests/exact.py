@@ -1,7 +1,8 @@
 """Exact-operand f64 references for the bf16 convolution kernels (tests/test_exact_bounds.py, tests/test_gpu_zoo_exact.py,
 tests/test_gpu_dw_exact.py, tests/test_gpu_pw_exact.py, tests/test_gpu_dense_exact.py), for the resample, pyramid and gate kernels
 (tests/test_gpu_resample_exact.py: a section of its own, with its own tiers) and for the eval bottleneck kernel, the frozen-BatchNorm
-affines and the joins (tests/test_gpu_bneck_exact.py: the last section of this file).  That section's tiers and cases:
+affines and the joins (tests/test_gpu_bneck_exact.py), and for the fused decoder head (tests/test_gpu_head_exact.py: the last section of
+this file, with its own tiers, f64 reference and counted bounds).  The bottleneck section's tiers and cases:
   bottleneck tier 1   bit for bit on fixed-point operands (multiples of 2^-2, power-of-two scales, stage grids 2^-4 / 2^-6 / 2^-8), the
                       budget asserted per case (bneck_exact); BK_TIER1: 8 x 16 (2 cases), 8 x 8 (3), 4 x 8 (9) at stride 1 with an f32 E,
                       4 x 16 at stride 2 with a bf16 E (6); bf16 weight copies given, absent, and misaligned with other values
@@ -1682,3 +1683,438 @@ def join_bwd_ref(dout, out, relu, dscale=1.0):
     """e = dout dscale (a power of two: exact) where out > 0 (or everywhere without ReLU), else 0"""
     e = dout * dscale
     return e * (out > 0).double() if relu else e
+
+
+# ---------------------------------------------------------------------------------------------------------- fused decoder head
+# csrc/loss.hip (upsample_ce_onepass_kernel MODE 0..4, upsample_argmax_kernel, upsample_ce_gather_kernel), csrc/widehead.hip (the
+# class-chunked twins), csrc/ohem.hip (the radix select) and csrc/headgeom.h (the band walk and the tile gather they share);
+# tests/test_gpu_head_exact.py.  Two tiers (the GPU file names the tier of every case):
+#   1  bit for bit: the arg-max kernels on an exact_resize pair with logits that are multiples of 2^-2 in [-8, 8].  Every interpolated
+#      logit is then an f32 number whatever the contraction (exact_budget, asserted per case), neither arg-max kernel multiplies by
+#      log2 e, and the prediction must be the f64 arg-max (lowest index on ties) at EVERY pixel, the confusion matrix equal.
+#   2  derived bound, elementwise: everything with an exponential (per-pixel cross-entropy, loss, gradient) and every size pair that is
+#      not exact.  head_pix_bound / head_loss_bound / head_grad_bound below count the roundings; the arg-max of a pair that is not
+#      exact follows tests/msflip_ref.margin with K = 1.
+# The f64 reference interpolates with bilinear_matrix (exact coordinates).  On an exact_resize pair the kernels' taps ARE those weights
+# and the coordinate slack is zero; elsewhere head_slack bounds what the f32 coordinates (both contractions of l1) can move.
+HEAD_NT = 256             # NT: output columns of a strip, lanes of a block (csrc/headgeom.h)
+HEAD_WROWS = 16           # WROWS: output rows of a band of the wide head
+HEAD_WK = 16              # WK: classes per chunk of the wide head (csrc/widehead.hip)
+HEAD_WTAB = 1024          # WTAB: floats of the gather-weight table
+HEAD_WCM_LDS = 96         # WCM_LDS: classes up to which the wide evaluators count in LDS
+HEAD_REG_CAP, HEAD_WIDE_CAP = 24, 256
+HEAD_FULL_GRID = 2048     # blocks below which head_geom halves the band
+
+
+def head_cp(C, wide=False):
+    """class pitch of a tile: TSS_WITH_CLASS_REGS (20 up to 20 classes, else 24) for the register kernels, round_up(C, 4) for the wide"""
+    return cdiv(C, 4) * 4 if wide else (20 if C <= 20 else 24)
+
+
+def head_geom(B, C, h, w, H, W, wide=False):
+    """head_geom / head_blocks / head_ws_floats of csrc/headgeom.h: strips of NT columns; bands of 64 rows, halved while above 16 and
+    B nstrip ceil(H / band_rows) < 2048 (the wide head: always WROWS); the conservative tile extents, in double as the host computes
+    them; the class pitch; blocks; floats of the workspace (2 doubles per block, then the tiles)"""
+    nstrip = cdiv(W, HEAD_NT)
+    band_rows = HEAD_WROWS if wide else 64
+    while not wide and band_rows > 16 and B * nstrip * cdiv(H, band_rows) < HEAD_FULL_GRID:
+        band_rows //= 2
+    nband = cdiv(H, band_rows)
+    sy = (h - 1) / (H - 1) if H > 1 else 0.0
+    sx = (w - 1) / (W - 1) if W > 1 else 0.0
+    tile_rows = min(int((band_rows - 1) * sy) + 3, h)
+    tile_cells = min(int((HEAD_NT - 1) * sx) + 3, w)
+    cp = head_cp(C, wide)
+    nblocks = B * nstrip * nband
+    return dict(nstrip=nstrip, band_rows=band_rows, nband=nband, tile_rows=tile_rows, tile_cells=tile_cells, cp=cp, nblocks=nblocks,
+                ws_floats=nblocks * 4 + nblocks * tile_rows * tile_cells * cp)
+
+
+def head_band(geo, band, H):
+    """head_band: output rows [ya, yb) of a band"""
+    ya = band * geo['band_rows']
+    return ya, min(ya + geo['band_rows'], H)
+
+
+def head_band_rows(h, H, ya, yb):
+    """head_band_rows: first / last low-resolution row the block of output rows [ya, yb) touches, on the restated f32 taps"""
+    i0, i1, _, _ = ac_taps_np(h, H)
+    return int(i0[ya]), int(i1[yb - 1])
+
+
+def head_strip_cells(w, W, strip):
+    """head_strip_cells and the table switch of gather_windows: first cell c0 and cell count of a strip, its live lanes, maxwin =
+    (int)(2 / sx) + 6 (NT for sx == 0), wtab = ncell maxwin <= WTAB"""
+    i0, i1, _, _ = ac_taps_np(w, W)
+    x0 = strip * HEAD_NT
+    xl = min(x0 + HEAD_NT - 1, W - 1)
+    c0 = int(i0[x0])
+    ncell = int(i1[xl]) - c0 + 1
+    sx = ac_scale_f32(w, W)
+    maxwin = int(F32(2.0) / sx) + 6 if sx > 0 else HEAD_NT
+    return dict(c0=c0, ncell=ncell, lanes=xl - x0 + 1, maxwin=maxwin, wtab=ncell * maxwin <= HEAD_WTAB)
+
+
+ac_window = ac_window_f32     # ac_window of csrc/common.h: the conservative range of outputs whose taps can include a source index
+
+
+def head_lane_window(w, W, strip, cell):
+    """the lanes [lo, hi] of a strip that gather_windows lets the flush sum for the strip's cell `cell`: ac_window of column c0 + cell,
+    relative to the strip, clamped to its NT lanes and (with the table) to maxwin"""
+    s = head_strip_cells(w, W, strip)
+    lo, hi = ac_window(w, W, s['c0'] + cell)
+    lo, hi = max(lo - strip * HEAD_NT, 0), min(hi - strip * HEAD_NT, HEAD_NT - 1)
+    if s['wtab'] and hi - lo + 1 > s['maxwin']:
+        hi = lo + s['maxwin'] - 1
+    return lo, hi
+
+
+def head_longest_window(w, W):
+    """longest gather window (lanes) over every strip and cell of a case: the chain of one flush sum"""
+    best = 0
+    for strip in range(cdiv(W, HEAD_NT)):
+        for cell in range(head_strip_cells(w, W, strip)['ncell']):
+            lo, hi = head_lane_window(w, W, strip, cell)
+            best = max(best, hi - lo + 1)
+    return best
+
+
+def head_band_chain(h, H, band_rows):
+    """most output rows of one band that feed one low-resolution row: the chain of a lane's gA / gB / Hh accumulators"""
+    i0, i1, _, _ = ac_taps_np(h, H)
+    best = 0
+    for ya in range(0, H, band_rows):
+        rows = np.concatenate([i0[ya:ya + band_rows], i1[ya:ya + band_rows]])
+        best = max(best, int(max(((i0[ya:ya + band_rows] == r) | (i1[ya:ya + band_rows] == r)).sum() for r in np.unique(rows))))
+    return best
+
+
+HEAD_KERNELS = ('ce_onepass', 'argmax', 'softhead', 'msflip', 'wide_ce', 'wide_argmax', 'wide_msflip')
+
+
+def head_read_extent(C, ldl, kernel, guarded=True):
+    """channels of a pixel (from its first) that an instance of the family reads.  The two register kernels of loss.hip keep their
+    load_row written out over all CP channels when the pitch holds them (ldl >= CP) and take the GUARD instance otherwise, which
+    skips the 4-channel groups that start at or past C like headgeom.h's load_row (softhead.hip, msflip.hip): round_up(C, 4).
+    widehead.hip loads 8-channel groups that start below C: round_up(C, 8).  guarded=False: loss.hip before the GUARD instances
+    existed, CP whatever the pitch -- past the pitch for C <= 16 at ldl = round_up(C, 8), past the buffer at its last pixel"""
+    assert kernel in HEAD_KERNELS
+    if kernel.startswith('wide'):
+        return cdiv(C, 8) * 8
+    if kernel in ('ce_onepass', 'argmax'):
+        cp = head_cp(C)
+        if not guarded or ldl >= cp:
+            return cp
+    return cdiv(C, 4) * 4
+
+
+def head_logits(shape, gen):
+    """tier-1 logits: multiples of 2^-2 in [-8, 8], bf16-exact (7 significant bits), so the f32 and the bf16 kernels read the same"""
+    return torch.randint(-32, 33, shape, generator=gen).double() / 4
+
+
+def head_labels(B, H, W, C, gen, ignore_index=255):
+    """labels in [0, C) with pixels of ignore_index, -1 and 300 (out of range: they do not count) scattered in"""
+    t = torch.randint(0, C, (B, H, W), generator=gen)
+    r = torch.rand((B, H, W), generator=gen)
+    t[r < 0.06] = ignore_index
+    t[(r >= 0.06) & (r < 0.08)] = -1
+    t[(r >= 0.08) & (r < 0.10)] = 300
+    return t
+
+
+def argmax_lowest(z):
+    """arg-max over dim 1, the lowest index among equal maxima (torch.argmax's rule, spelled out)"""
+    C = z.shape[1]
+    idx = torch.arange(C).reshape(1, C, *([1] * (z.dim() - 2)))
+    return torch.where(z == z.max(1, keepdim=True).values, idx, C).min(1).values
+
+
+class HeadRef:
+    """f64 reference of the fused head on low-resolution logits x [B][C][h][w] and int64 labels [B][H][W]:
+      z, zabs   the upsampled logits My x Mx^T and their absolute twin My |x| Mx^T (>= |z|: what the blends' roundings scale with)
+      arg       arg-max of z, lowest index on ties;  gap: best minus second-best
+      valid     label != ignore_index and 0 <= label < C
+      lse, pix  log-sum-exp and per-pixel cross-entropy lse - z_t (0 where not valid)
+    and, for pixel weights (s, hot) -- tests/wce_ref.py's: s = (1 - eps) w_t + eps W / C, hot_c = (1 - eps) w_t [c == t] + eps w_c / C,
+    den = sum_valid w_t; or, with pixw [B][H][W] (OHEM's selection weights), s = pixw, hot_c = pixw [c == t], den = 1 --
+      loss      sum_valid (s lse - sum_c hot_c z_c) / den
+      S         the loss's twin sum_valid (s |lse| + sum_c hot_c zabs_c)      (= sum omega (|lse| + |z_t|) where no blend cancels)
+      ssum      sum_valid s
+      g         gs sum_pixels My Mx (s p_c - hot_c) on the low-resolution grid, gs = grad_out / den
+      A         its absolute twin gs sum_pixels My Mx (s p_c + hot_c)"""
+    def __init__(self, x, labels, weight=None, eps=0.0, ignore_index=255, pixw=None, grad_out=1.0, weighted=True):
+        from tests import wce_ref
+        B, C, h, w = x.shape
+        H, W = labels.shape[-2:]
+        self.x, self.labels, self.C, self.size, self.low = x, labels, C, (H, W), (h, w)
+        My, Mx = bilinear_matrix(h, H), bilinear_matrix(w, W)
+        self.My, self.Mx = My, Mx
+        self.z = torch.einsum('oh,bchw,pw->bcop', My, x, Mx)
+        self.zabs = torch.einsum('oh,bchw,pw->bcop', My, x.abs(), Mx)
+        self.zmax = float(x.abs().max())
+        self.arg = argmax_lowest(self.z)
+        self.valid = wce_ref.valid_mask(labels, C, ignore_index)
+        self.t = labels.clamp(0, C - 1)
+        self.lse = torch.logsumexp(self.z, 1)
+        v = self.valid.double()
+        self.pix = (self.lse - self.z.gather(1, self.t[:, None])[:, 0]) * v
+        if weighted:
+            self.weights(weight, eps, pixw, grad_out)
+
+    @property
+    def gap(self):
+        top = self.z.topk(2, dim=1).values if self.C > 1 else torch.cat([self.z, self.z - float('inf')], 1)
+        return top[:, 0] - top[:, 1]
+
+    def weights(self, weight=None, eps=0.0, pixw=None, grad_out=1.0):
+        """(re)compute loss, S, ssum, den, g, A for other pixel weights on the same logits and labels"""
+        C, v = self.C, self.valid.double()
+        onehot = torch.zeros_like(self.z).scatter_(1, self.t[:, None], 1.0)
+        if pixw is None:
+            wv = torch.ones(C, dtype=torch.float64) if weight is None else weight.double()
+            wt = wv[self.t] * v
+            s = ((1 - eps) * wv[self.t] + eps * wv.sum() / C) * v
+            hot = ((1 - eps) * wv[self.t][:, None] * onehot + eps / C * wv[None, :, None, None]) * v[:, None]
+            self.den = float(wt.sum())
+        else:
+            s = pixw.double() * v
+            hot = s[:, None] * onehot
+            self.den = 1.0
+        self.ssum = float(s.sum())
+        self.S = float((s * self.lse.abs() + (hot * self.zabs).sum(1)).sum())
+        self.loss = float((s * self.lse - (hot * self.z).sum(1)).sum()) / self.den if self.den > 0 else float('nan')
+        self.gs = grad_out / self.den if self.den > 0 else 0.0
+        p = torch.softmax(self.z, 1) * s[:, None]
+        self.T = p + hot
+        self.g = self.gs * torch.einsum('oh,bcop,pw->bchw', self.My, p - hot, self.Mx)
+        self.A = self.gs * torch.einsum('oh,bcop,pw->bchw', self.My, self.T, self.Mx)
+        return self
+
+
+def ohem_pixel_weights(pix, sel):
+    """the weight upsample_ce_onepass_kernel<MODE 2> / wide_ce_kernel<2> derive from a stored per-pixel loss and sel = [mode, cut,
+    weight of l > cut, weight of l == cut (top-n mode only)]"""
+    mode, cut, wgt, weq = [float(v) for v in sel]
+    weq = 0.0 if mode != 0 else weq
+    pix = pix.double()
+    return torch.where(pix > cut, torch.full_like(pix, wgt), torch.where(pix == cut, torch.full_like(pix, weq), torch.zeros_like(pix)))
+
+
+def ohem_ref(pix, thresh, n_top):
+    """f64 restatement of tss_ohem_select on f32 losses `pix` (>= 0): oracle.recipe.ohem's rule -- v = the (n_top + 1)-th largest; v >
+    thresh: the mean of the losses above thresh, else the mean of the n_top largest -- and the params [mode, cut, weight of l > cut,
+    weight of l == cut]; ties at v share what is left of n_top evenly.  n_top == 0 in top-n mode: nan, like torch's empty mean"""
+    l = pix.double().reshape(-1)
+    order = torch.sort(l, descending=True).values
+    v = float(order[n_top])
+    if v > thresh:
+        k = float((l > thresh).sum())
+        return float(l[l > thresh].sum()) / k, [1.0, float(thresh), 1.0 / k, 0.0]
+    if n_top == 0:
+        return float('nan'), [0.0, v, float('inf'), float('nan')]
+    above, ties_n = l[l > v], float((l == v).sum())
+    ties = n_top - float(above.numel())
+    return (float(above.sum()) + ties * v) / n_top, [0.0, v, 1.0 / n_top, ties / (ties_n * n_top) if ties_n > 0 else 0.0]
+
+
+def head_slack_z(ref):
+    """what the f32 coordinates may move one interpolated logit by on a pair that is not exact_resize (0 on one that is).  As
+    tests/msflip_ref.margin: the bilinear surface has slope <= 2 zmax per source pixel along each axis, so
+        slack_z = 2 zmax (coord_error(h, H) + coord_error(w, W))           (both contractions of l1 are inside coord_error)"""
+    from tests import msflip_ref
+    (h, w), (H, W) = ref.low, ref.size
+    if exact_resize(h, H) is not None and exact_resize(w, W) is not None:
+        return 0.0
+    return 2.0 * ref.zmax * (msflip_ref.coord_error(h, H) + msflip_ref.coord_error(w, W))
+
+
+def head_slack(ref):
+    """(slack_pix, slack_loss, slack_g [B][C][h][w]) from head_slack_z; all zero on an exact_resize pair.  lse is 1-Lipschitz in the
+    logits (max norm): a per-pixel cross-entropy moves by <= 2 slack_z, the loss by <= 2 slack_z ssum / den.
+    Gradient: a softmax value moves by <= 2 p_c slack_z (|dp_c| <= 2 p_c (1 - p_c) d); and the gather's own weights are the hat
+    function of the coordinate, 1-Lipschitz: a weight of the row axis is off by <= ey = coord_error(h, H) wherever the f32 tap (either
+    contraction) or the exact tap reads the row (the support Sy), likewise ex / Sx, so the product My Mx is off by <=
+    ey Sy Mx + ex My Sx + ey ex Sy Sx, applied to the |terms| T = s p + hot of the window"""
+    from tests import msflip_ref
+    sz = head_slack_z(ref)
+    if sz == 0.0:
+        return 0.0, 0.0, 0.0
+    (h, w), (H, W) = ref.low, ref.size
+    ey, ex = msflip_ref.coord_error(h, H), msflip_ref.coord_error(w, W)
+    Sy = ((ref.My != 0) | (tap_matrix_f32(h, H) != 0) | (tap_matrix_f32(h, H, fused=False) != 0)).double()
+    Sx = ((ref.Mx != 0) | (tap_matrix_f32(w, W) != 0) | (tap_matrix_f32(w, W, fused=False) != 0)).double()
+    e = lambda a, b: torch.einsum('oh,bcop,pw->bchw', a, ref.T, b)
+    sg = 2.0 * sz * ref.A + ref.gs * (ey * e(Sy, ref.Mx) + ex * e(ref.My, Sx) + ey * ex * e(Sy, Sx))
+    return 2.0 * sz, (2.0 * sz * ref.ssum / ref.den if ref.den > 0 else 0.0), sg
+
+
+def head_counts(B, C, h, w, H, W, wide=False):
+    """the chain lengths of a case from the restated geometry: Ry = rows of a band that feed one low-resolution row, Lx = the longest
+    gather window of lanes, the band height, the tile rows (flushes of a band) and the wide head's chunks"""
+    geo = head_geom(B, C, h, w, H, W, wide)
+    return dict(Ry=head_band_chain(h, H, geo['band_rows']), Lx=head_longest_window(w, W), band_rows=geo['band_rows'],
+                tile_rows=geo['tile_rows'], nchunk=cdiv(C, HEAD_WK) if wide else 0)
+
+
+def head_lse_err(zmax, C, nchunk=0):
+    """roundings (units of u = 2^-24, nats) of one log-sum-exp of C logits of magnitude <= zmax.  The hardware transcendentals
+    V_EXP_F32 / V_LOG_F32 / V_RCP_F32 are taken at 1 ulp (<= 2 u relative), the figure sigmoid_rel_err already takes for V_EXP_F32
+    from the vendor's ISA guide; it has not been measured here.
+      8 zmax     one interpolated logit in log2 units: the horizontal blend (l0x = 1 - l1x, two products whose magnitudes add up to
+                 <= zmax, one sum: 3), the product with LOG2E and LOG2E's own rounding (2), the vertical blend (3); lse is
+                 1-Lipschitz in the logits
+      2 zmax     the subtractions z_c - m, |z_c - m| <= 2 zmax, as perturbations of the logits
+      2          V_EXP_F32 on every term of the sum
+      C - 1      the additions of the positive terms
+      2 ln C     V_LOG_F32, relative on |log2 sum| <= log2 C
+      zmax + ln C    the addition m + log2 sum
+    widehead.hip's running maximum and sum add, per chunk, one rescale exp2(mo - mn): the subtraction (2 zmax), V_EXP_F32 (2), the
+    product (1) and the carry's addition (1)"""
+    return 11.0 * zmax + 1 + C + 3.0 * math.log(C) + nchunk * (2.0 * zmax + 4)
+
+
+def head_pix_bound(zmax, C, nchunk=0):
+    """|pix - ref| <= u (a + b zmax) on an exact pair (+ 2 slack_z elsewhere).  loss.hip MODE 1: d = ((m - z_t) + log2 sum) ln 2 --
+    head_lse_err without its last line (m enters through m - z_t), + 8 zmax for z_t, 2 zmax for m - z_t, 2 zmax + ln C for the
+    addition, 2 (2 zmax + ln C) for the product with ln 2 and that constant's rounding: b = 26, a = C + 1 + 5 ln C.  widehead.hip
+    MODE 1: (lse - z_t) ln 2 with the running sum: head_lse_err + 8 zmax + 3 (2 zmax + ln C).  The clamp max(d, 0) moves d towards
+    the reference, which is >= 0"""
+    if nchunk:
+        return U32 * (head_lse_err(zmax, C, nchunk) + 14.0 * zmax + 3.0 * math.log(C))
+    return U32 * (26.0 * zmax + C + 1 + 5.0 * math.log(C))
+
+
+def head_grad_counts(n, zmax, C, weighted, nchunk=0):
+    """(n_g, r_p) of |dlow - g| <= u (n_g + r_p) A + slack_g (+ 2^-8 (|g| + bound) for a bf16 gradient).
+    n_g, the longest f32 chain a term of the gather goes through.  Both halves: l0y = 1 - l1y and its product (2), the Ry additions
+    of a band's rows into gA / gB or Hh, g - Hh (1), the gather weight 1 - l1x and its product (2), the Lx additions of the window, up
+    to four tiles (4), gs = fl(1 / n) grad_out applied (3): Ry + Lx + 12.  The one-hot half also carries its weight (1 - eps) w_t (2)
+    and, smoothed, the row-weight sum Nn (Ry additions), eps / C, Nn eC, its product with w_c and the addition (4):
+    n_g = 2 Ry + Lx + 18; with class weights the denominator is an f32 chain of band_rows additions per lane: + band_rows.
+    r_p, the roundings of one softmax value times its pixel weight.  Register kernels: 2 (8 + 2) zmax (a softmax value moves by <=
+    2 p_c d under a perturbation d of the logits: the interpolation and the subtraction z - m of head_lse_err), V_EXP_F32 on the
+    value and on the sum (4), the C - 1 additions, V_RCP_F32 (2), its product with the pixel weight and the product e_c inv (2);
+    the pixel weight s = (1 - eps) w_t + eps W / C adds C + 4 (the C - 1 additions of W; eps / C and its product with W; 1 - eps and
+    its product with w_t; the sum).  widehead.hip: p_c = exp2(z_c - lse) s: head_lse_err for lse, 8 zmax for z_c, 2 zmax + ln C for
+    the subtraction (|z_c - lse| <= 2 zmax + ln C), V_EXP_F32 (2), the product with s (1).
+    The transcendentals' 1 ulp is the vendor's figure (head_lse_err), not measured here"""
+    n_g = 2 * n['Ry'] + n['Lx'] + 18 + (n['band_rows'] if weighted else 0)
+    if nchunk:
+        r_p = head_lse_err(zmax, C, nchunk) + 10.0 * zmax + math.log(C) + 3
+    else:
+        r_p = 20.0 * zmax + 4 + (C - 1) + 4
+    return n_g, r_p + (C + 4 if weighted else 0)
+
+
+def head_grad_bound(ref, n, weighted, bf16, nchunk=0, slack=0.0):
+    n_g, r_p = head_grad_counts(n, ref.zmax, ref.C, weighted, nchunk)
+    k = U32 * (n_g + r_p)
+    bound = k / (1 - k) * ref.A + slack
+    return bound + (2.0 ** -8 * (ref.g.abs() + bound) if bf16 else 0.0)
+
+
+def head_loss_counts(n, zmax, C, weighted, nchunk=0):
+    """(n_l, r_l) of |loss - ref| <= [u n_l S + u r_l ssum + 2^-50 S] / den + slack: n_l counts the roundings relative to a term's
+    magnitude (S sums them), r_l the ones that scale with zmax whatever the term (per unit of pixel weight; ssum sums the weights;
+    with unit weights and no smoothing ssum = den <= S / lse and the form is the issue's u (n_l + r_l) S / den).
+    loss.hip: the lane's f32 sum takes one addition per row of the band and one subtraction per flush (band_rows + tile_rows); a
+    lse term m + log2 sum (1) times its weight (1); a target-logit term sum_c a[c] Hh[c]: the C products and additions (C + 1) on
+    Hh's chain (l0y, its product with the weight (1 - eps) w_t: 4; Ry additions; smoothed: Nn's Ry additions and 4 more); the f32
+    loss (1) and, weighted, the denominator's chain (band_rows): n_l = 2 band_rows + tile_rows + 2 Ry + C + 10.
+    r_l = head_lse_err for the lse + 5 zmax for a horizontally blended row a[c] (the vertical weights are Hh's) + C + 4, weighted.
+    widehead.hip sums in f64: a lse term times its weight (2), a target-logit term times its weight (3), the smoothing's sum over
+    a chunk (WK + 2), the denominator's chain (WROWS), the f32 loss (1): n_l = WK + WROWS + 8; r_l = head_lse_err + 8 zmax"""
+    if nchunk:
+        return HEAD_WK + HEAD_WROWS + 8 + (C + 4 if weighted else 0), head_lse_err(zmax, C, nchunk) + 8.0 * zmax
+    return 2 * n['band_rows'] + n['tile_rows'] + 2 * n['Ry'] + C + 10 + (C + 4 if weighted else 0), head_lse_err(zmax, C) + 5.0 * zmax
+
+
+def head_loss_bound(ref, n, weighted, nchunk=0, slack=0.0):
+    n_l, r_l = head_loss_counts(n, ref.zmax, ref.C, weighted, nchunk)
+    return (U32 * (n_l * ref.S + r_l * ref.ssum) * 1.001 + 2.0 ** -50 * ref.S) / ref.den + slack
+
+
+# --- the cases (tests/test_exact_bounds.py asserts from the restated geometry that each reaches what it is listed for)
+class HeadCase:
+    """(B, C, h, w) -> (H, W) at pitch ldl (default round_up(C, 8)); tier 1: an exact_resize pair with planted ties"""
+    def __init__(self, name, B, C, h, w, H, W, ldl=None, wide=False, dtypes=('f32', 'bf16')):
+        self.name, self.B, self.C, self.h, self.w, self.H, self.W, self.wide, self.dtypes = name, B, C, h, w, H, W, wide, dtypes
+        self.ldl = ldl or cdiv(C, 8) * 8
+        self.exact = exact_resize(h, H) is not None and exact_resize(w, W) is not None
+
+    def geom(self):
+        return head_geom(self.B, self.C, self.h, self.w, self.H, self.W, self.wide)
+
+    def counts(self):
+        return head_counts(self.B, self.C, self.h, self.w, self.H, self.W, self.wide)
+
+    def strips(self):
+        return [head_strip_cells(self.w, self.W, s) for s in range(cdiv(self.W, HEAD_NT))]
+
+    def __repr__(self):
+        return self.name
+
+
+HEAD_REG = [HeadCase('one_lane_strip', 1, 19, 5, 33, 33, 257),      # two strips, the second of one lane; three bands, the last of one row
+            HeadCase('no_table', 1, 19, 9, 129, 17, 257),            # sx = 1/2: strip 0 gathers without the table, strip 1 with it
+            HeadCase('identity', 1, 19, 18, 300, 18, 300),           # a flush on every row, rB == rA at the end; 16 + 2 rows, 256 + 44 lanes
+            HeadCase('few_class', 2, 5, 3, 5, 9, 17),                # ldl = 8 < CP: the GUARD instances
+            HeadCase('c20', 1, 20, 3, 3, 17, 17),                    # CP 20 with no pad class
+            HeadCase('cp24', 1, 21, 5, 9, 33, 65),                   # CP 24 with pad classes
+            HeadCase('c24', 1, 24, 3, 3, 17, 17),                    # CP 24, pitch equal to CP
+            HeadCase('h1', 1, 19, 1, 5, 17, 33),
+            HeadCase('w1', 1, 19, 5, 1, 33, 17),                     # sx = 0: the window is the whole strip
+            HeadCase('pitch32', 1, 19, 5, 9, 33, 65, ldl=32),
+            HeadCase('band32', 16, 19, 513, 3, 4097, 5),             # band_rows = 32, the benchmark's; 129 bands, the last of one row
+            HeadCase('band64', 32, 19, 513, 3, 4097, 5, dtypes=('f32',))]
+HEAD_REG_T2 = [HeadCase('prod', 2, 19, 16, 32, 128, 256), HeadCase('near', 1, 19, 15, 29, 16, 32), HeadCase('edge', 1, 19, 5, 7, 40, 56)]
+HEAD_WIDE = [HeadCase('c25', 1, 25, 5, 33, 33, 257, wide=True),
+             HeadCase('c33', 1, 33, 3, 5, 9, 17, wide=True),         # a one-class chunk
+             HeadCase('c66', 2, 66, 3, 5, 17, 33, wide=True),
+             HeadCase('c130', 1, 130, 18, 300, 18, 300, wide=True),
+             HeadCase('c256', 1, 256, 3, 3, 9, 9, wide=True),
+             HeadCase('c97', 1, 97, 3, 5, 9, 17, wide=True)]         # the first count past the LDS counters
+HEAD_WIDE_T2 = [HeadCase('wide_t2', 2, 66, 6, 9, 48, 72, wide=True)]
+HEAD_BY_NAME = {c.name: c for c in HEAD_REG + HEAD_REG_T2 + HEAD_WIDE + HEAD_WIDE_T2}
+HEAD_TIE_PAIRS = ((3, 4), (19, 20), (0, 1), (1, 2))           # across the 4-class register groups; with class 0
+HEAD_TIE_PAIRS_WIDE = ((15, 16), (0, 255), (0, 1), (3, 4))    # across the 16-class chunks; the first and the last class
+
+
+def head_plants(x, gen):
+    """plant ties into tier-1 logits x [B][C][h][w] (in place), each at sites of its own: for every pair (a, b) of HEAD_TIE_PAIRS
+    (HEAD_TIE_PAIRS_WIDE past 24 classes) the case has classes for, as far as its sites go round, (i) two equal planes over a horizontal cell pair -- a = b = 8 there, every other class <= 7.75 -- and (ii) a
+    tie that exists only after interpolation -- a goes 0 -> 4 across the cell pair, b 4 -> 0, the others <= 1.75: equal (2) at the
+    midpoint only; and one low-resolution pixel where every class holds 1.  With w == 1 the sites are single pixels and (ii) is
+    left out.  Returns [(kind, a, b, r, c)]"""
+    B, C, h, w = x.shape
+    step = 2 if w > 1 else 1
+    sites = [(r, c) for r in range(h) for c in range(0, w - step + 1, step + 1)]
+    perm = torch.randperm(len(sites), generator=gen).tolist()
+    sites = [sites[i] for i in perm]
+    pairs = [p for p in (HEAD_TIE_PAIRS_WIDE if C > HEAD_REG_CAP else HEAD_TIE_PAIRS) if p[1] < C]
+    plants = [('planes',) + p for p in pairs] + ([('cross',) + p for p in pairs] if w > 1 else []) + [('all', 0, C - 1)]
+    done = []
+    for k, (kind, a, b) in enumerate(plants):
+        for (r, c) in sites[k::len(plants)][:3]:
+            cols = slice(c, c + step)
+            if kind == 'planes':
+                x[:, :, r, cols] = x[:, :, r, cols].clamp(max=7.75)
+                x[:, a, r, cols] = 8.0
+                x[:, b, r, cols] = 8.0
+            elif kind == 'cross':
+                x[:, :, r, cols] = x[:, :, r, cols].clamp(max=1.75)
+                x[:, a, r, c], x[:, a, r, c + 1] = 0.0, 4.0
+                x[:, b, r, c], x[:, b, r, c + 1] = 4.0, 0.0
+            else:
+                x[:, :, r, c] = 1.0
+            done.append((kind, a, b, r, c))
+    return done
+
+
+def head_inputs(case, seed=0):
+    """(x [B][C][h][w] f64 tier-1 logits, labels [B][H][W] int64, plants); tier-2 pairs carry no plants"""
+    g = case_gen(*[ord(ch) for ch in case.name], seed)
+    x = head_logits((case.B, case.C, case.h, case.w), g)
+    plants = head_plants(x, g) if case.exact else []
+    return x, head_labels(case.B, case.H, case.W, case.C, g), plants

@@ -1611,3 +1611,248 @@ def test_join_backward_statistics_emulation_and_an_unowned_row_left_unzeroed_fai
             slabs[grid - 1] = float('nan')
             with pytest.raises(AssertionError):
                 check_slab_rows(slabs, range(grid), kind)
+
+
+# ---------------------------------------------------------------------------------------------------------- fused decoder head
+from tests import head_emu as HE          # noqa: E402
+from tests import msflip_ref, wce_ref     # noqa: E402
+
+HEAD_ALL = X.HEAD_REG + X.HEAD_REG_T2 + X.HEAD_WIDE + X.HEAD_WIDE_T2
+HEAD_EMU = [c for c in X.HEAD_REG + X.HEAD_REG_T2 if c.name not in ('band32', 'band64')]        # what the emulation walks in seconds
+_head_refs = {}
+
+
+def _head(case):
+    if case.name not in _head_refs:
+        x, labels, plants = X.head_inputs(case)
+        _head_refs[case.name] = (x, labels, plants, X.HeadRef(x, labels, weighted=False))
+    return _head_refs[case.name]
+
+
+@pytest.mark.parametrize('c', HEAD_ALL, ids=repr)
+def test_head_restated_geometry_holds_every_tap(c):
+    """every tap of every output pixel lies inside the band rows and strip cells the restatement gives, the tile extents cover that
+    footprint, the gather windows hold every lane that touches a cell (one lane short does not) and the table clamp never cuts"""
+    geo = c.geom()
+    yi0, yi1, _, _ = X.ac_taps_np(c.h, c.H)
+    xi0, xi1, xl0, xl1 = X.ac_taps_np(c.w, c.W)
+    assert geo['nband'] * geo['band_rows'] >= c.H > (geo['nband'] - 1) * geo['band_rows']
+    for band in range(geo['nband']):
+        ya, yb = X.head_band(geo, band, c.H)
+        r0, r1 = X.head_band_rows(c.h, c.H, ya, yb)
+        assert r0 <= yi0[ya:yb].min() and yi1[ya:yb].max() <= r1 and r1 - r0 + 1 <= geo['tile_rows'] <= c.h
+        assert (np.diff(yi0[ya:yb]) <= 1).all()                 # loss.hip's `if (ty.i0 != rA)` advances by one row at most
+    for strip in range(geo['nstrip']):
+        s = X.head_strip_cells(c.w, c.W, strip)
+        x0 = strip * X.HEAD_NT
+        assert s['c0'] <= xi0[x0:x0 + s['lanes']].min() and xi1[x0:x0 + s['lanes']].max() < s['c0'] + s['ncell']
+        assert s['ncell'] <= geo['tile_cells'] and s['ncell'] <= X.HEAD_NT + 2
+        for cell in range(s['ncell']):
+            lo, hi = X.head_lane_window(c.w, c.W, strip, cell)
+            lanes = np.arange(s['lanes'])
+            col = s['c0'] + cell
+            touch = lanes[((xi0[x0 + lanes] == col) & (xl0[x0 + lanes] != 0)) | ((xi1[x0 + lanes] == col) & (xl1[x0 + lanes] != 0))]
+            assert touch.size == 0 or (lo <= touch.min() and touch.max() <= hi), (strip, cell)
+            full = X.ac_window(c.w, c.W, col)
+            assert (not s['wtab']) or min(full[1] - x0, X.HEAD_NT - 1) - max(full[0] - x0, 0) + 1 <= s['maxwin']      # "cannot happen"
+    assert X.window_misses(c.w, c.W) == 0 and X.window_misses(c.w, c.W, short=1) > 0
+    assert X.window_misses(c.h, c.H) == 0
+    assert geo['ws_floats'] == geo['nblocks'] * (4 + geo['tile_rows'] * geo['tile_cells'] * geo['cp'])
+
+
+def test_head_cases_reach_what_they_are_listed_for():
+    by = X.HEAD_BY_NAME
+    last_band = lambda c: c.H - (c.geom()['nband'] - 1) * c.geom()['band_rows']
+    c = by['one_lane_strip']
+    assert (c.geom()['nstrip'], c.geom()['nband'], last_band(c)) == (2, 3, 1) and [s['lanes'] for s in c.strips()] == [256, 1]
+    assert all(s['wtab'] for s in c.strips())
+    c = by['no_table']
+    assert X.ac_scale_f32(c.w, c.W) == 0.5 and [s['wtab'] for s in c.strips()] == [False, True] and c.strips()[0]['ncell'] * 10 > X.HEAD_WTAB
+    c = by['identity']
+    yi0 = X.ac_taps_np(c.h, c.H)[0]
+    assert (np.diff(yi0) == 1).all() and yi0[-1] == c.h - 1                     # a flush on every row; rB == rA at the end
+    assert (c.geom()['nband'], last_band(c)) == (2, 2) and [s['lanes'] for s in c.strips()] == [256, 44]
+    assert [s['wtab'] for s in c.strips()] == [False, True]       # 257 x 8 > 1024: the full strip gathers without the table, the 44-lane one with it
+    assert by['few_class'].ldl == 8 < X.head_cp(5)
+    assert X.head_cp(20) == 20 == by['c20'].C and X.head_cp(21) == 24 > by['cp24'].C and X.head_cp(24) == 24 == by['c24'].ldl == by['c24'].C
+    assert by['h1'].h == 1 and by['w1'].w == 1 and X.head_lane_window(1, by['w1'].W, 0, 0) == (0, by['w1'].W - 1)
+    assert by['pitch32'].ldl == 32
+    assert (by['band32'].geom()['band_rows'], by['band32'].geom()['nband'], last_band(by['band32'])) == (32, 129, 1)
+    assert by['band64'].geom()['band_rows'] == 64 and by['band64'].geom()['nblocks'] >= X.HEAD_FULL_GRID
+    assert all(c.geom()['band_rows'] == 16 for c in HEAD_ALL if c.name not in ('band32', 'band64'))
+    assert all(c.exact for c in X.HEAD_REG + X.HEAD_WIDE) and not any(c.exact for c in X.HEAD_REG_T2 + X.HEAD_WIDE_T2)
+    assert all(c.C <= X.HEAD_REG_CAP for c in X.HEAD_REG + X.HEAD_REG_T2) and all(X.HEAD_REG_CAP < c.C <= X.HEAD_WIDE_CAP for c in X.HEAD_WIDE)
+    assert by['c33'].C % X.HEAD_WK == 1 and by['c97'].C == X.HEAD_WCM_LDS + 1 and by['c256'].counts()['nchunk'] == 16
+    assert [c.counts()['nchunk'] for c in X.HEAD_WIDE] == [2, 3, 5, 9, 16, 7]
+
+
+@pytest.mark.parametrize('c', [c for c in X.HEAD_REG + X.HEAD_WIDE if c.name not in ('band32', 'band64')], ids=repr)
+def test_head_tier1_premise_and_planted_ties(c):
+    """the budget of every tier-1 case, and the planted ties where the case has room for them: the pair's classes tie for the maximum
+    somewhere and the reference gives the lower index"""
+    x, labels, plants, ref = _head(c)
+    ky, kx = X.exact_resize(c.h, c.H), X.exact_resize(c.w, c.W)
+    assert X.lsb_exp(x) >= -2 and ref.zmax <= 8 and X.exact_budget(ref.zabs, -2, ky, kx)
+    assert torch.equal(ref.z.float().double(), ref.z)                        # every interpolated logit is an f32 number
+    assert float((ref.gap == 0).double().mean()) > 0
+    ry, rx = (c.H - 1) // max(c.h - 1, 1), (c.W - 1) // max(c.w - 1, 1)         # whole ratios on every case of the tables
+    for (kind, a, b, r, col) in plants:
+        oy, ox = r * ry, col * rx
+        if kind == 'cross':
+            if rx % 2:
+                continue                                                     # no output pixel at the midpoint
+            ox += rx // 2
+            assert (ref.z[:, a, oy, ox] == 2).all()
+        zp = ref.z[:, :, oy, ox]
+        if kind == 'all':
+            assert (zp == 1).all() and (ref.arg[:, oy, ox] == 0).all(), (c, kind)
+        else:
+            assert (zp[:, a] == zp[:, b]).all() and (zp[:, a] == zp.max(1).values).all() and (ref.arg[:, oy, ox] == a).all(), (c, kind, a, b)
+    pairs = {(p[1], p[2]) for p in plants if p[0] == 'planes'}
+    if c.name in ('one_lane_strip', 'cp24', 'pitch32'):
+        assert {(3, 4), (0, 1)} <= pairs
+    if c.name in ('cp24', 'c24'):
+        assert (19, 20) in pairs
+    if c.wide:
+        assert (15, 16) in pairs and (c.C < 256 or (0, 255) in pairs)
+
+
+def test_head_read_extent_stays_inside_the_pitch():
+    """every kernel of the family, every case: the channels read of a pixel end inside its pitch; the extents of loss.hip before its
+    GUARD instances did not ('few_class', C = 5 at ldl = 8: 20 channels)"""
+    import os
+    for c in HEAD_ALL:
+        for k in X.HEAD_KERNELS:
+            if k.startswith('wide') == c.wide:
+                assert X.head_read_extent(c.C, c.ldl, k) <= c.ldl, (c, k)
+    old = [c.name for c in X.HEAD_REG + X.HEAD_REG_T2 if X.head_read_extent(c.C, c.ldl, 'ce_onepass', guarded=False) > c.ldl]
+    assert old == ['few_class'] and X.head_read_extent(5, 8, 'argmax', guarded=False) == 20
+    for C in range(1, 25):                          # ops.new_nhwc's pitch, and the narrowest pitch head_shape_ok lets through
+        for ldl in (X.cdiv(C, 8) * 8, X.cdiv(X.cdiv(C, 4) * 4, 8) * 8):
+            assert X.head_read_extent(C, ldl, 'ce_onepass') <= ldl and X.head_read_extent(C, ldl, 'argmax') <= ldl
+            assert (X.head_read_extent(C, ldl, 'ce_onepass', guarded=False) > ldl) == (C <= 16)
+    src = open(os.path.join(os.path.dirname(__file__), '..', 'torch_semantic_segmentation_amd', 'csrc', 'loss.hip')).read()
+    assert src.count('TSS_WITH_ROW_GUARD(ldl < CPV,') == 6 and src.count('if (!GUARD || c4 < C)') == 2      # the host rule restated above
+
+
+def test_head_reference_is_wce_ref_and_the_recipe_ohem():
+    """X.HeadRef against tests/wce_ref.py (loss and autograd gradient, f64) on an exact pair, where bilinear_matrix is torch's
+    align_corners=True; X.ohem_ref against oracle.recipe.ohem"""
+    from oracle import recipe
+    c = X.HEAD_BY_NAME['cp24']
+    x, labels, _, ref = _head(c)
+    g = _gen(3)
+    cw = torch.randint(1, 9, (c.C,), generator=g).double() / 4
+    cw[c.C // 2] = 0
+    for (w_, eps) in ((None, 0.0), (cw, 0.0), (None, 0.125), (cw, 0.125)):
+        import copy
+        r = copy.copy(ref).weights(w_, eps, grad_out=0.7)
+        loss, grad = wce_ref.loss_and_grad(wce_ref.upsampled_wce_loss, x, labels, torch.float64, w_, 255, eps)
+        assert abs(r.loss - float(loss)) <= 1e-12 * abs(r.loss)
+        assert float((r.g - 0.7 * grad).abs().max()) <= 1e-12 * float(r.A.max())
+        assert (r.A >= r.g.abs() - 1e-18).all() and r.S >= abs(r.loss) * r.den
+    logits = torch.randn(2, 5, 8, 16, generator=g, dtype=torch.float64) * 3
+    tgt = torch.randint(0, 5, (2, 8, 16), generator=g)
+    tgt[0, :2] = 255
+    per = torch.nn.functional.cross_entropy(logits, tgt, ignore_index=255, reduction='none')
+    for (thresh, frac) in ((0.35, 0.1), (0.35, 0.9), (50.0, 0.25)):
+        want = recipe.ohem(logits, tgt, 255, thresh, frac)
+        got, sel = X.ohem_ref(per, thresh, int(per.numel() * frac))
+        assert abs(got - float(want)) <= 1e-12 * abs(float(want))
+        pw = X.ohem_pixel_weights(per, sel)                                  # the params reproduce the loss as a weighted sum
+        assert abs(float((pw * per).sum()) - got) <= 1e-12 * abs(got)
+
+
+def _ratio(out, ref, bound):
+    err = (torch.as_tensor(np.asarray(out, dtype=np.float64)) - ref).abs()
+    bound = torch.as_tensor(bound, dtype=torch.float64).expand_as(err)
+    r = torch.where(bound > 0, err / bound, torch.where(err == 0, torch.zeros_like(err), torch.full_like(err, float('inf'))))
+    r = torch.where(torch.isnan(err), torch.full_like(r, float('inf')), r)
+    return float(r.max())
+
+
+def _head_variants(c):
+    cw = torch.randint(1, 9, (c.C,), generator=_gen(11)).double() / 4
+    cw[c.C // 2] = 0
+    return ((0, None, 0.0), (3, cw, 0.0), (4, None, 0.125), (4, cw, 0.125))
+
+
+def _emu_ratios(c, mode, cw, eps, defect=None, order=1):
+    """(loss ratio, gradient ratio) of the emulated pass against the case's bounds"""
+    import copy
+    x, labels, _, ref = _head(c)
+    r = copy.copy(ref).weights(cw, eps, grad_out=float(np.float32(0.7)))
+    n = c.counts()
+    o = HE.ce_pass(x.numpy(), labels.numpy(), c.H, c.W, mode=mode, weight=None if cw is None else cw.numpy(), eps=eps, grad_out=0.7,
+                   defect=defect, class_order=order)
+    weighted = mode >= 3
+    spix, sloss, sg = X.head_slack(r)
+    rl = abs(float(o['loss']) - r.loss) / X.head_loss_bound(r, n, weighted, 0, sloss)
+    assert defect is not None or abs(float(o['inv_count']) - 1 / r.den) <= X.U32 * (n['band_rows'] + 2) / r.den
+    return rl, _ratio(o['dlow'], r.g, X.head_grad_bound(r, n, weighted, False, 0, sg))
+
+
+@pytest.mark.parametrize('c', HEAD_EMU, ids=repr)
+def test_head_f32_emulation_meets_the_tier2_bounds(c):
+    """loss, gradient (plain, class weights, smoothing, both; the class loop also backwards), per-pixel cross-entropy and the OHEM
+    gradient of the emulated pass within head_loss_bound / head_grad_bound / head_pix_bound"""
+    import copy
+    x, labels, _, ref = _head(c)
+    n = c.counts()
+    for i, (mode, cw, eps) in enumerate(_head_variants(c)):
+        rl, rg = _emu_ratios(c, mode, cw, eps, order=-1 if i == 1 else 1)
+        assert rl <= 1 and rg <= 1, (c, mode, rl, rg)
+    pix = HE.ce_pass(x.numpy(), labels.numpy(), c.H, c.W, mode=1)['pix']
+    assert (pix >= 0).all() and (pix[~ref.valid.numpy()] == 0).all()
+    assert _ratio(pix, ref.pix, X.head_pix_bound(ref.zmax, c.C) + 2 * X.head_slack_z(ref)) <= 1
+    cut = np.float32(np.median(pix))
+    planted = pix.copy()
+    planted[torch.rand(pix.shape, generator=_gen(12)).numpy() < 0.1] = cut
+    sel = [0.0, float(cut), 0.0078125, 0.00390625]
+    o = HE.ce_pass(x.numpy(), labels.numpy(), c.H, c.W, mode=2, pix=planted, sel=sel, grad_out=1.0)
+    r = copy.copy(ref).weights(pixw=X.ohem_pixel_weights(torch.from_numpy(planted), sel), grad_out=1.0)
+    assert _ratio(o['dlow'], r.g, X.head_grad_bound(r, n, False, False, 0, X.head_slack(r)[2])) <= 1
+
+
+@pytest.mark.parametrize('c', [c for c in HEAD_ALL if c.name not in ('band32', 'band64')], ids=repr)
+def test_head_argmax_emulation_is_bit_for_bit_on_tier1_and_inside_the_margin_elsewhere(c):
+    """tier 1: the f32 walk gives the f64 arg-max at every pixel, forwards, with the class loop run backwards, and chunk by chunk;
+    elsewhere every pixel whose top-2 gap exceeds msflip_ref.margin (K = 1) agrees and at most 1 % of the pixels are left out"""
+    x, labels, _, ref = _head(c)
+    chunk = X.HEAD_WK if c.wide else None
+    for order in (1, -1):
+        arg = torch.from_numpy(HE.argmax_walk(x.numpy(), c.H, c.W, class_order=order, chunk=chunk))
+        if c.exact:
+            assert torch.equal(arg, ref.arg), (c, order)
+        else:
+            m = msflip_ref.margin(1, c.C, ref.zmax, [(c.h, c.w)], (c.H, c.W), 'logits')
+            decided = ref.gap > m
+            assert 1 - float(decided.double().mean()) <= X.NEAR_TIE_CAP and torch.equal(arg[decided], ref.arg[decided])
+
+
+HEAD_DEFECTS = (('edge_lane', 0), ('no_last_flush', 0), ('one_tile', 0), ('swap_last_row', 0), ('drop_onehot', 0), ('smooth_once', 4))
+
+
+@pytest.mark.parametrize('defect,mode', HEAD_DEFECTS)
+def test_head_emulation_with_one_defect_fails_the_gradient_bound(defect, mode):
+    c = X.HEAD_BY_NAME['one_lane_strip']
+    rl, rg = _emu_ratios(c, mode, None, 0.125 if mode == 4 else 0.0, defect=defect)
+    assert rg > 1, (defect, rg)
+    if defect in ('drop_onehot', 'smooth_once'):                  # the one-hot half also carries the target logits of the loss
+        assert rl > 1, (defect, rl)
+
+
+def test_head_emulation_arg_max_and_pixel_defects_fail():
+    c = X.HEAD_BY_NAME['one_lane_strip']
+    x, labels, _, ref = _head(c)
+    ge = torch.from_numpy(HE.argmax_walk(x.numpy(), c.H, c.W, ge=True))
+    assert not torch.equal(ge, ref.arg) and ((ge != ref.arg) <= (ref.gap == 0)).all()        # `>=`: wrong exactly on ties
+    c = X.HEAD_BY_NAME['c33']
+    x, labels, _, ref = _head(c)
+    late = torch.from_numpy(HE.argmax_walk(x.numpy(), c.H, c.W, chunk=X.HEAD_WK, chunk_ge=True))
+    assert not torch.equal(late, ref.arg) and set(late[late != ref.arg].tolist()) <= {16, 32}     # the later chunk's first class
+    for name in ('one_lane_strip', 'few_class'):
+        c = X.HEAD_BY_NAME[name]
+        x, labels, _, ref = _head(c)
+        pix = HE.ce_pass(x.numpy(), labels.numpy(), c.H, c.W, mode=1, defect='unclamped_i1')['pix']
+        assert _ratio(pix, ref.pix, X.head_pix_bound(ref.zmax, c.C)) > 1

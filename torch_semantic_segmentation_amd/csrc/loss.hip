@@ -6,6 +6,14 @@
 // ce_fwd_ex / ce_bwd_ex: the same with class weights and label smoothing, per-block partial rows instead of the atomics
 #include "headgeom.h"
 
+// The two register kernels of the fused head read CPV channels of a pixel when its pitch holds them; a narrower pitch (C <= 16 with
+// ldl = round_up(C, 8)) takes the instance that skips the class groups past C.  Inside TSS_WITH_CLASS_REGS.
+#define TSS_WITH_ROW_GUARD(cond, ...)                         \
+  do {                                                        \
+    if (cond) { constexpr bool GUARDV = true; __VA_ARGS__; }  \
+    else { constexpr bool GUARDV = false; __VA_ARGS__; }      \
+  } while (0)
+
 namespace {
 
 template <typename T>
@@ -144,7 +152,10 @@ __global__ __launch_bounds__(NT) void ce_bwd_ex_kernel(const T* logits, const lo
 // MODE 4: MODE 3 with label smoothing `eps`: the softmax half carries s = (1 - eps) w_t + eps W / C, the one-hot half (1 - eps) w_t,
 // and the uniform part eps w_c / C of the target distribution enters Hh at flush time, once per low-res row, scaled by the sum
 // of the row weights of the valid pixels seen (nA, nB: one scalar per row buffer).  MODE 0 / 1 / 2 do not read cw and eps.
-template <typename T, int CP, int MODE>
+// GUARD: the instance for a pitch below CP (ldl < CP, TSS_WITH_ROW_GUARD): its load_row skips the 4-channel groups that start at or
+// past C, the contract of headgeom.h's load_row, so that a pixel's reads end inside its pitch.  The instances for ldl >= CP read all
+// CP channels of a pixel (inside the pitch) and are the kernels they always were.
+template <typename T, int CP, int MODE, bool GUARD>
 __global__ __launch_bounds__(NT, (CP <= 20 ? 3 : 2)) void upsample_ce_onepass_kernel(const T* low, long ldl, const long long* target,
                                                                  float* tiles, double* lossrows, int B, int C, int h, int w,
                                                                  int H, int W, int ignore_index, const HeadGeom geo,
@@ -224,8 +235,13 @@ __global__ __launch_bounds__(NT, (CP <= 20 ? 3 : 2)) void upsample_ce_onepass_ke
 #pragma unroll
     for (int c4 = 0; c4 < CP; c4 += 4) {
       float u[4], v[4];
-      V4<T>::load(p0 + c4, u);
-      V4<T>::load(p1 + c4, v);
+      if (!GUARD || c4 < C) {                // uniform
+        V4<T>::load(p0 + c4, u);
+        V4<T>::load(p1 + c4, v);
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) u[q] = v[q] = 0.f;
+      }
 #pragma unroll
       for (int q = 0; q < 4; ++q) a[c4 + q] = (c4 + q < C) ? (tx.l0 * u[q] + tx.l1 * v[q]) * LOG2E : -TSS_INF;
     }
@@ -423,8 +439,8 @@ __global__ __launch_bounds__(NT) void argmax_confusion_kernel(const T* logits, c
 // Fused evaluation head (eval half): argmax over the classes of the bilinearly upsampled logits
 // + confusion-matrix update, straight from the low-res NHWC logits.  Same lane / register layout as
 // upsample_ce_onepass_kernel (lane = output column, the two horizontally interpolated low-res rows in registers, one
-// FMA per logit); lowest class index wins ties like torch.argmax; rows = truth.
-template <typename T, int CP>
+// FMA per logit); lowest class index wins ties like torch.argmax; rows = truth.  GUARD: as in upsample_ce_onepass_kernel.
+template <typename T, int CP, bool GUARD>
 __global__ __launch_bounds__(NT, 3) void upsample_argmax_kernel(const T* low, long ldl, const long long* target,
                                                                 unsigned char* pred_out, unsigned long long* cm, int B,
                                                                 int C, int h, int w, int H, int W, int ignore_index,
@@ -453,8 +469,13 @@ __global__ __launch_bounds__(NT, 3) void upsample_argmax_kernel(const T* low, lo
 #pragma unroll
     for (int c4 = 0; c4 < CP; c4 += 4) {
       float u[4], v[4];
-      V4<T>::load(p0 + c4, u);
-      V4<T>::load(p1 + c4, v);
+      if (!GUARD || c4 < C) {                // uniform
+        V4<T>::load(p0 + c4, u);
+        V4<T>::load(p1 + c4, v);
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) u[q] = v[q] = 0.f;
+      }
 #pragma unroll
       for (int q = 0; q < 4; ++q) a[c4 + q] = (c4 + q < C) ? tx.l0 * u[q] + tx.l1 * v[q] : -TSS_INF;
     }
@@ -602,9 +623,9 @@ int tss_upsample_argmax_confusion(const void* low, long ldl, const long long* ta
   const long grid = head_blocks(B, geo);
   tss::ProfScope prof(TSS_K_ARGMAX, (hipStream_t)stream, (double)B * h * w * C * tss::esz(dtype) + (double)B * H * W * 9.0, 0);
   const size_t sh = (size_t)C * C * sizeof(unsigned int);
-  TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
-    hipLaunchKernelGGL((upsample_argmax_kernel<TT, CPV>), dim3((int)grid), dim3(NT), sh, (hipStream_t)stream,
-                       (const TT*)low, ldl, target, pred, confusion, B, C, h, w, H, W, ignore_index, geo.band_rows)));
+  TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C, TSS_WITH_ROW_GUARD(ldl < CPV,
+    hipLaunchKernelGGL((upsample_argmax_kernel<TT, CPV, GUARDV>), dim3((int)grid), dim3(NT), sh, (hipStream_t)stream,
+                       (const TT*)low, ldl, target, pred, confusion, B, C, h, w, H, W, ignore_index, geo.band_rows))));
   return tss::check_last("upsample_argmax_confusion");
 }
 
@@ -624,9 +645,9 @@ int tss_upsample_ce_fwd(const void* low, long ldl, const long long* target, floa
   {
     tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream,
                         (double)B * h * w * C * (tss::esz(dtype) + 8.0) + (double)B * H * W * 8.0, 0);
-    TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
-      hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 0>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,
-                         (const TT*)low, ldl, target, tiles, lossrows, B, C, h, w, H, W, ignore_index, geo, nullptr, nullptr, nullptr, 0.f)));
+    TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C, TSS_WITH_ROW_GUARD(ldl < CPV,
+      hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 0, GUARDV>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,
+                         (const TT*)low, ldl, target, tiles, lossrows, B, C, h, w, H, W, ignore_index, geo, nullptr, nullptr, nullptr, 0.f))));
   }
   hipLaunchKernelGGL(ce_finalize_rows_kernel<false>, dim3(1), dim3(NT), 0, (hipStream_t)stream, lossrows, (int)grid, loss, inv_count);
   return tss::check_last("upsample_ce_fwd");
@@ -649,13 +670,13 @@ int tss_upsample_ce_fwd_ex(const void* low, long ldl, const long long* target, c
     tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream,
                         (double)B * h * w * C * (tss::esz(dtype) + 8.0) + (double)B * H * W * 8.0, 0);
     if (label_smoothing > 0.f)
-      TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
-        hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 4>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const TT*)low, ldl,
-                           target, tiles, lossrows, B, C, h, w, H, W, ignore_index, geo, nullptr, nullptr, weight, label_smoothing)));
+      TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C, TSS_WITH_ROW_GUARD(ldl < CPV,
+        hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 4, GUARDV>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const TT*)low, ldl,
+                           target, tiles, lossrows, B, C, h, w, H, W, ignore_index, geo, nullptr, nullptr, weight, label_smoothing))));
     else
-      TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
-        hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 3>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const TT*)low, ldl,
-                           target, tiles, lossrows, B, C, h, w, H, W, ignore_index, geo, nullptr, nullptr, weight, 0.f)));
+      TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C, TSS_WITH_ROW_GUARD(ldl < CPV,
+        hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 3, GUARDV>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream, (const TT*)low, ldl,
+                           target, tiles, lossrows, B, C, h, w, H, W, ignore_index, geo, nullptr, nullptr, weight, 0.f))));
   }
   hipLaunchKernelGGL(ce_finalize_rows_kernel<true>, dim3(1), dim3(NT), 0, (hipStream_t)stream, lossrows, (int)grid, loss, inv_count);
   return tss::check_last("upsample_ce_fwd_ex");
@@ -671,9 +692,9 @@ int tss_upsample_pixel_ce(const void* low, long ldl, const long long* target, fl
   const HeadGeom geo = head_geom(B, C, h, w, H, W, false);
   const long grid = head_blocks(B, geo);
   tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream, (double)B * h * w * C * tss::esz(dtype) + (double)B * H * W * 12.0, 0);
-  TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
-    hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 1>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,
-                       (const TT*)low, ldl, target, nullptr, nullptr, B, C, h, w, H, W, ignore_index, geo, pix, nullptr, nullptr, 0.f)));
+  TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C, TSS_WITH_ROW_GUARD(ldl < CPV,
+    hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 1, GUARDV>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,
+                       (const TT*)low, ldl, target, nullptr, nullptr, B, C, h, w, H, W, ignore_index, geo, pix, nullptr, nullptr, 0.f))));
   return tss::check_last("upsample_pixel_ce");
 }
 
@@ -689,9 +710,9 @@ int tss_upsample_ohem_grad(const void* low, long ldl, const long long* target, c
   const long grid = head_blocks(B, geo);
   float* tiles = ws + grid * 4;
   tss::ProfScope prof(TSS_K_UPSAMPLE_CE_FWD, (hipStream_t)stream, (double)B * h * w * C * (tss::esz(dtype) + 8.0) + (double)B * H * W * 12.0, 0);
-  TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C,
-    hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 2>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,
-                       (const TT*)low, ldl, target, tiles, nullptr, B, C, h, w, H, W, ignore_index, geo, const_cast<float*>(pix), sel, nullptr, 0.f)));
+  TSS_WITH_DTYPE(dtype, TSS_WITH_CLASS_REGS(C, TSS_WITH_ROW_GUARD(ldl < CPV,
+    hipLaunchKernelGGL((upsample_ce_onepass_kernel<TT, CPV, 2, GUARDV>), dim3((int)grid), dim3(NT), 0, (hipStream_t)stream,
+                       (const TT*)low, ldl, target, tiles, nullptr, B, C, h, w, H, W, ignore_index, geo, const_cast<float*>(pix), sel, nullptr, 0.f))));
   return tss::check_last("upsample_ohem_grad");
 }
 
