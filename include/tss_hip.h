@@ -472,7 +472,11 @@ int tss_updw_bwd(const void* e, long lde, const void* yraw, long ldyr, const flo
 int tss_stat_slabs(void);
 
 /* ---- BatchNorm2d bookkeeping (eps, momentum, running stats exactly as torch.nn.BatchNorm2d) ----------
- * replaces: nn.BatchNorm2d in every block above (training: batch statistics + running update; eval: running stats). */
+ * replaces: nn.BatchNorm2d in every block above (training: batch statistics + running update; eval: running stats).
+ * tss_bn_finalize: mean = s / count, var = max(q / count - mean^2, 0) in f64 over the slab rows; invstd = f32(1 / sqrt(var + eps)),
+ *   scale = gamma * invstd (gamma NULL: 1).  running_mean / running_var (each may be NULL) are updated in place with the momentum and
+ *   the UNBIASED variance var * count / (count - 1) (var itself at count = 1); *num_batches_tracked (may be NULL) += 1 per call.
+ *   count >= 1 and C > 0, else TSS_ERR_SHAPE. */
 int tss_bn_finalize(const double* sums, double count, const float* gamma, float eps,
                     float momentum, float* running_mean, float* running_var, long long* num_batches_tracked,
                     float* mean_out, float* invstd_out, float* scale, int C, void* stream);
@@ -481,7 +485,9 @@ int tss_bn_eval_affine(const float* gamma, const float* running_mean, const floa
 /* all eval-mode BatchNorm layers of a model in one launch.  table: njobs x 6 int64 on the device: (gamma or 0, running_mean,
  * running_var, out [3][C] = mean | invstd | scale, C, eps as f32 bits); max_channels = the largest C of the table. */
 int tss_bn_eval_affine_batched(const long long* table, int njobs, int max_channels, void* stream);
-/* bstats = [sum(e), sum(e*(y-mean))]; writes d(gamma), d(beta) (+= when accumulate) and ga, gb, gce */
+/* bstats = [sum(e), sum(e*(y-mean))]; writes d(gamma), d(beta) (+= when accumulate; each may be NULL) and ga, gb, gce:
+ * ga = gamma * invstd, gb = -ga * invstd^2 * sum(e*(y-mean)) / count, gce = sum(e) / count (training = 0: gb = gce = 0), so that
+ * g = ga * (e - gce) + gb * (y - mean).  gamma NULL: 1.  count >= 1 and C > 0, else TSS_ERR_SHAPE. */
 int tss_bn_bwd_finalize(const double* bstats, double count, const float* invstd,
                         const float* gamma, int training, int accumulate, float* dgamma, float* dbeta,
                         float* ga, float* gb, float* gce, int C, void* stream);
@@ -519,6 +525,11 @@ int tss_join_bwd(const void* dout, long lddo, const void* out, long ldo, int rel
 /* ---- dropout / bias gradient / optimizer ------------------------------------------------------------
  * replaces: nn.Dropout(0.1) TSS/models/fastscnn.py:96, TSS/models/contextnet.py:85 (Philox; mask recomputed in backward);
  *           torch.optim.AdamW.step() as called by TSS/engine.py:38 (single flat tensor, torch arithmetic). */
+/* tss_dropout_tick: *seed_slot = *counter; *counter += 1 (on the device: replays from a captured graph draw fresh masks).
+ * tss_dropout: y = x * keep / (1 - p); element i = pixel * C + channel (the LOGICAL index: the pitches play no part) is kept iff word
+ *   i & 3 of Philox4x32-10(counter = i >> 2, key = (low32(*seed_slot), high32(*seed_slot) ^ 0x5EED)) >= floor(p * 2^32); the same call
+ *   on the gradient with the same slot is its backward.  p = 0 copies.  C and both pitches multiples of 8, 0 <= p < 1.
+ * tss_bias_grad: dbias[n] += sum_p e[p][n] -- it ACCUMULATES (f32 atomics) onto what dbias holds; N <= 64, any pitch lde >= N. */
 int tss_dropout_tick(unsigned long long* counter, unsigned long long* seed_slot, void* stream);
 int tss_dropout(const void* x, long ldx, void* y, long ldy, long P, int C, float p,
                 const unsigned long long* seed_slot, int dtype, void* stream);
@@ -528,6 +539,7 @@ int tss_bias_grad(const void* e, long lde, long P, int N, float* dbias, int dtyp
  * own over the 128-channel activation (forward and backward).
  * tss_dropout_mask: mask = [P][16] bytes (C <= 128: a pixel's bytes are one aligned 16-byte row), bit j of byte (p, v) = channel
  *   8 v + j of pixel p is kept; Philox4x32-10 keyed by *counter (device), 16 bits per element.  It does NOT advance the counter: the consumer does.
+ *   ALL 16 bytes of every pixel are written whatever C is (byte b = 16 p + v has the Philox counter b); C > 128 and p = 0 are refused.
  * tss_pwconv_fwd_drop: y = (keep / (1 - p) * act(x)) W^T + bias, act = the pending BatchNorm(+ReLU) of x; advances *counter.
  * tss_pwconv_bwd_fused_drop: tss_pwconv_bwd_fused with the same mask on the weight gradient's activation operand and on e_in;
  *   ws rows: tss_pwconv_bwd_fused_drop_rows(P); yraw must be NULL (no BatchNorm behind the convolution).  bf16; K = Cin <= 128 (multiple of 8), N = Cout <= 64 (>= 8, may be ragged). */
@@ -547,7 +559,8 @@ int tss_pwconv_bwd_fused_drop(const void* e, long lde, const void* yraw, long ld
 /* bf16 shadows of 1x1 weights, all layers in one launch.  table: njobs x 5 int64 on the device:
  * (f32 source [N][K], bf16 copy [N][K], bf16 transpose [K][N], N, K); blocks_per_job x njobs blocks of 256 threads.
  * zero / zero_n (optional): a float buffer cleared by the same launch -- the step's flat gradient buffer (optimizer.zero_grad()
- * of TSS/engine.py:28), which is due at the same point of the step. */
+ * of TSS/engine.py:28), which is due at the same point of the step.  zero must be 16-byte aligned; zero_n need not be a multiple of 4.
+ * The conversion rounds to nearest even and keeps denormals. */
 int tss_cast_weights(const long long* table, int njobs, int blocks_per_job, float* zero, long zero_n, void* stream);
 /* torch.optim.AdamW.step() on one flat buffer.  state != NULL: [step, 1 - beta1^step, sqrt(1 - beta2^step)] and the learning
  * rate *lr live on the device (a tick kernel advances them: the step can be replayed from a captured graph); state == NULL:

@@ -12,6 +12,11 @@ this file, with its own tiers, f64 reference and counted bounds).  The bottlenec
   affines             mean bit for bit, invstd within 3 u, scale within 4 u (affine_ref); batched == single
   joins               forward bit for bit (every branch and the sum exact in f32); backward e bit for bit and the statistics rows
                       within stats_excess with join_stats_chain, rows in use against join_geometry
+The BatchNorm finalize chain (tss_bn_finalize, tss_bn_bwd_finalize, tss_slab_reduce and the _sync pair), tss_tensor_stats, tss_bias_grad
+and tss_cast_weights (tests/test_gpu_bnfin_exact.py) have the last section of this file: numpy restatements of the kernels' f64 formulas
+whose last steps are IEEE float32 operations, integer slab rows on which every output but invstd is held bit for bit (invstd: one f32
+rounding of an f64 value), a bounded tier whose slabs tss_tensor_stats writes from stored values near 30, and the restated grids and
+chains of the statistics and column-sum kernels.  The dropout masks are predicted by tests/philox_ref.py (Philox4x32-10 in numpy).
 
 Every operand is a DYADIC bf16 value, +-(1 + k/128) * 2^e with e in [-4, 2): 8 significant bits.  BatchNorm scales are powers of two in
 [1/2, 4], the backward pair (ga, gb) powers of two in [1/4, 2] and [2^-6, 2^-3].  Then the on-load transforms of the kernels
@@ -2118,3 +2123,256 @@ def head_inputs(case, seed=0):
     x = head_logits((case.B, case.C, case.h, case.w), g)
     plants = head_plants(x, g) if case.exact else []
     return x, head_labels(case.B, case.H, case.W, case.C, g), plants
+
+
+# ---------------------------------------------------------------------------------------------------------- BatchNorm finalize chain
+# csrc/bnfin.h (slab_sum, bn_bwd_finalize_block) and csrc/pointwise.hip (bn_finalize_kernel, slab_reduce_kernel, the _sync pair,
+# colsum_kernel, cast_weights_kernel), csrc/zoo.hip (tensor_stats_kernel, tensor_stats_vec_kernel); tests/test_gpu_bnfin_exact.py.
+# The mask rules of the dropout kernels live in tests/philox_ref.py.  All of this section is numpy: float64 for the kernels' f64
+# formulas, float32 (IEEE, one rounding per operation) for their last f32 steps.
+#   tier 1  bit for bit.  Slab rows are integers (every f64 sum exact in any order), count = 2^k, the channel sum s an integer of at
+#           most 26 bits: mean = s / 2^k and mean^2 are exact, q / 2^k is exact, and var = q / 2^k - mean^2 is a multiple of 2^-2k
+#           below 2^4, i.e. an f64 number: the subtraction returns it exactly, and so does an FMA that rounds the exact
+#           q / 2^k - mean mean once (fin_tier1_premise checks both with rationals).  Running statistics are 8-bit dyadic and the
+#           momentum 2^-3 or 2^-1: (1 - m) rm and m f32(mean) are exact products, so `(1 - m) rm + m x` rounds once with or without a
+#           contraction.  invstd alone is held to one f32 rounding of an f64 value, FIN_INVSTD_REL.
+#   tier 2  bounded (fin_tier2_bounds): slabs written by tss_tensor_stats from stored 12-bit values with mean ~ 30 and deviation ~ 2^-3.
+FIN_CH, FIN_ROWS_PER_LOAD = 8, 16      # channels of a finalize block; FIN_WAVES x FIN_RG rows per load instruction (csrc/bnfin.h)
+FIN_INVSTD_REL = 2.0 ** -24 + 2.0 ** -48   # one f32 rounding of the f64 1 / sqrt(var + eps), itself within a few 2^-53
+FIN_CHANNELS = (4, 8, 19, 132, 264, 768)
+
+
+def np_rng(*key):
+    s = 29
+    for k in key:
+        s = (s * 1000003 + int(k)) % (2 ** 31 - 1)
+    return np.random.RandomState(s)
+
+
+def bn_finalize_ref(s, q, count, gamma, eps, momentum, rmean=None, rvar=None):
+    """bn_finalize_kernel / bn_finalize_sync_kernel from the column sums s, q (f64 [C]) in the kernel's operation order:
+        mean = s / count;  var = max(q / count - mean^2, 0);  invstd = f32(1 / sqrt(var + f64(eps)));  scale = f32(gamma) *_f32 invstd
+        running_mean = (1 - m) rm + m f32(mean)  in f32;  running_var likewise with f32(var count / (count - 1)) (var itself at count 1)
+    gamma None: 1.  Returns a dict of numpy arrays: mean64 / var64 / invstd64 (f64, before their f32 rounding), mean / invstd / scale /
+    running_mean / running_var (f32)"""
+    s, q, count = np.asarray(s, np.float64), np.asarray(q, np.float64), np.float64(count)
+    mean = s / count
+    var = np.maximum(q / count - mean * mean, 0.0)
+    inv64 = 1.0 / np.sqrt(var + np.float64(F32(eps)))
+    r = dict(mean64=mean, var64=var, invstd64=inv64, mean=mean.astype(F32), invstd=inv64.astype(F32))
+    r['scale'] = bn_scale_ref(gamma, r['invstd'])
+    m = F32(momentum)
+    if rmean is not None:
+        r['running_mean'] = (F32(1) - m) * np.asarray(rmean, F32) + m * r['mean']
+    unbiased = var * count / (count - 1.0) if count > 1.0 else var
+    r['unbiased64'] = unbiased
+    if rvar is not None:
+        r['running_var'] = (F32(1) - m) * np.asarray(rvar, F32) + m * unbiased.astype(F32)
+    return r
+
+
+def bn_scale_ref(gamma, invstd32):
+    """scale from the STORED invstd bits: one f32 product"""
+    invstd32 = np.asarray(invstd32, F32)
+    return invstd32.copy() if gamma is None else np.asarray(gamma, F32) * invstd32
+
+
+def bn_bwd_finalize_ref(se, sey, count, invstd, gamma, training=1, accumulate=0, dgamma=None, dbeta=None, local=None):
+    """bn_bwd_finalize_block / bn_bwd_finalize_sync_kernel: r = f64(invstd), k = gamma r,
+        dgamma = (acc ? old : 0) +_f32 f32(r sey);  dbeta = (acc ? old : 0) +_f32 f32(se);  ga = f32(k);
+        gb = f32(((-k) (r sey / cnt)) r);  gce = f32(se / cnt);  frozen: gb = gce = 0.
+    local = (se, sey) of this replica for dgamma / dbeta when (se, sey, count) are the sums over all replicas (the _sync kernel).
+    No addition follows the sums in f64, so no contraction can change a bit"""
+    se, sey, cnt = np.asarray(se, np.float64), np.asarray(sey, np.float64), np.float64(count)
+    lse, lsey = (se, sey) if local is None else (np.asarray(local[0], np.float64), np.asarray(local[1], np.float64))
+    r = np.asarray(invstd, F32).astype(np.float64)
+    old = lambda v: np.asarray(v, F32) if accumulate else np.zeros(se.shape, F32)
+    out = dict(dgamma=old(dgamma) + (r * lsey).astype(F32), dbeta=old(dbeta) + lse.astype(F32))
+    k = (np.asarray(gamma, F32).astype(np.float64) if gamma is not None else 1.0) * r
+    out['ga'] = k.astype(F32)
+    if training:
+        c2 = r * sey / cnt
+        out['gb'], out['gce'] = (-k * c2 * r).astype(F32), (se / cnt).astype(F32)
+    else:
+        out['gb'], out['gce'] = np.zeros(se.shape, F32), np.zeros(se.shape, F32)
+    return out
+
+
+def spread_rows(total, rows, rng, zero_half=True):
+    """int64 [rows][n] whose columns sum to total (int64 [n]): a random half of the rows all zero (a producer with fewer blocks leaves
+    them so), the others total / their number plus a random integer below 2^30 in magnitude, the last of them the remainder"""
+    total = np.asarray(total, np.int64)
+    nz = np.sort(rng.permutation(rows)[:rows // 2] if zero_half else np.arange(rows))
+    v = total // len(nz) + rng.randint(-2 ** 30, 2 ** 30, size=(len(nz), total.size)).astype(np.int64)
+    v[-1] += total - v.sum(0)
+    out = np.zeros((rows, total.size), np.int64)
+    out[nz] = v
+    assert (out.sum(0) == total).all() and int(np.abs(out).max()) < 2 ** 40 and int(np.abs(out).sum(0).max()) < 2 ** 53
+    return out
+
+
+def fin_tier1_sums(C, k, rng):
+    """(s, q) int64 [C] of a tier-1 case with count 2^k: s of up to min(26, (47 + k) / 2) bits, either sign; q = ceil(s^2 / 2^k) + v,
+    v in [1, 2^(k+3)): var in (v - 1, v] 2^-k.  Channel 0: s a multiple of 2^k and q = s^2 / 2^k, var exactly 0.  Channel 1: v =
+    -max(2, 2^(k-2)): var in (-1/4, -1/8] (-2 at count 1) BEFORE the clamp, far below -eps: without the clamp invstd is a NaN"""
+    tb = min(26, (47 + k) // 2)
+    s = rng.randint(2 ** (tb - 2), 2 ** tb, size=C).astype(np.int64) * rng.choice([-1, 1], size=C)
+    s[0] = (s[0] >> k) << k if abs(int(s[0])) >> k else 1 << k
+    sq = s * s
+    up = -((-sq) >> k)                                   # ceil(s^2 / 2^k)
+    q = up + rng.randint(1, 2 ** (k + 3), size=C).astype(np.int64)
+    q[0] = sq[0] >> k
+    if C > 1:
+        q[1] = up[1] - max(2, 2 ** (k - 2))
+    return s, q
+
+
+def fin_tier1_premise(s, q, k):
+    """mean, mean^2, q / count and q / count - mean^2 are f64 numbers (rationals against floats): the subtraction is exact, and an FMA,
+    which rounds the exact q / count - mean mean once, returns the same bits"""
+    from fractions import Fraction
+    cnt = float(2 ** k)
+    for si, qi in zip(s.tolist(), q.tolist()):
+        mean = si / cnt
+        if abs(si) >= 2 ** 26 or Fraction(mean) != Fraction(si, 2 ** k) or Fraction(mean * mean) != Fraction(si, 2 ** k) ** 2:
+            return False
+        exact = Fraction(qi, 2 ** k) - Fraction(si, 2 ** k) ** 2
+        if Fraction(qi / cnt) != Fraction(qi, 2 ** k) or Fraction(qi / cnt - mean * mean) != exact or Fraction(float(exact)) != exact:
+            return False
+    return True
+
+
+def fin_tier1_slabs(C, k, rng, rows=STAT_SLABS):
+    """f64 [rows][2 C] slab rows (sums | second moments) of fin_tier1_sums, and the column sums (s, q) as f64"""
+    s, q = fin_tier1_sums(C, k, rng)
+    assert fin_tier1_premise(s, q, k)
+    slabs = spread_rows(np.concatenate([s, q]), rows, rng).astype(np.float64)
+    return slabs, s.astype(np.float64), q.astype(np.float64)
+
+
+def dyadic8_np(n, rng, positive=False):
+    """8-bit dyadic f32 values +-(1 + j/128) 2^e, e in [-3, 2): the running statistics of tier 1"""
+    v = (1 + rng.randint(0, 128, size=n) / 128.0) * 2.0 ** rng.randint(-3, 2, size=n)
+    return (v if positive else v * rng.choice([-1, 1], size=n)).astype(F32)
+
+
+def fin_bwd_slabs(C, rng, rows=STAT_SLABS):
+    """integer slab rows [rows][2 C] of a backward case (sums of e | of e (y - mean)), either sign, column sums below 2^44"""
+    tot = rng.randint(-2 ** 43, 2 ** 43, size=2 * C).astype(np.int64)
+    slabs = spread_rows(tot, rows, rng).astype(np.float64)
+    return slabs, tot[:C].astype(np.float64), tot[C:].astype(np.float64)
+
+
+def fin_tier2_bounds(ref_var, qc, mean, eps, count, momentum, rmean, rvar):
+    """Tier 2: the slab sums are EXACT (12-bit stored values: every term and every partial sum is an f64 integer multiple of 2^-14), so
+    only the finalize's own roundings separate its var from the f64 BatchNorm of the stored values: mean = fl(s / count) (relative
+    2^-53), fl(q / count) (2^-53), fl(mean mean) (2^-53; none if contracted) and the subtraction (2^-53 |var|):
+        |var - var_ref| <= 2^-53 q/count + 3 2^-53 mean^2 (1 + 2^-52) + 2^-53 |var|  <  Dv = 2^-51 (q / count + mean^2).
+    invstd: t -> t^-1/2 is convex and decreasing, so a var within Dv of var_ref (clamped at 0, which only moves it towards
+    var_ref >= 0) gives |(var + eps)^-1/2 - (var_ref + eps)^-1/2| <= (var_ref + eps - Dv)^-1/2 - (var_ref + eps)^-1/2 = Di; the f64
+    sqrt and division and the f32 rounding add FIN_INVSTD_REL of the value.  The running statistics go through at most three f32
+    roundings per term (fl(1 - m), a product, the sum; f32(mean) or f32(unbiased), a product, the sum): 4 u (|a| + |b|), u = 2^-24,
+    plus m times the error the new statistic inherits.  An f32 variance is off by about 2^-24 mean^2 = 2^27 Dv.
+    Returns dict(var, invstd, running_mean, running_var) of f64 bounds"""
+    Dv = 2.0 ** -51 * (qc + mean * mean)
+    t = ref_var + np.float64(F32(eps))
+    Di = (t - Dv) ** -0.5 - t ** -0.5
+    inv = t ** -0.5
+    m = np.float64(F32(momentum))
+    ub = count / (count - 1.0) if count > 1 else 1.0
+    return dict(var=Dv, invstd=Di * (1 + FIN_INVSTD_REL) + FIN_INVSTD_REL * inv,
+                running_mean=4 * U32 * (np.abs((1 - m) * rmean) + np.abs(m * mean)) + m * 2.0 ** -52 * np.abs(mean),
+                running_var=4 * U32 * (np.abs((1 - m) * rvar) + np.abs(m * ref_var * ub)) + m * ub * Dv * 1.001)
+
+
+def offset_values(P, C, rng):
+    """stored values of tier 2, f64 [P][C]: multiples of 2^-7 near 30 (12 significant bits: exact in f32; the squares have 24), standard
+    deviation about 2^-3 (16 steps); channel 0 constant, so that its variance is exactly 0"""
+    n = np.rint(3840 + 16 * rng.standard_normal((P, C)) + rng.randint(-200, 200, size=C)).astype(np.int64).clip(2049, 4095)
+    n[:, 0] = 3872
+    return n / 128.0
+
+
+def exact_moments(x, scale_bits=7):
+    """(mean, var, q / count) of the columns of x (multiples of 2^-scale_bits) as correctly rounded f64, through integers"""
+    from fractions import Fraction
+    n = np.rint(x * 2 ** scale_bits).astype(np.int64)
+    assert (n / 2.0 ** scale_bits == x).all()
+    P = x.shape[0]
+    out = []
+    for c in range(x.shape[1]):
+        s1, s2 = int(n[:, c].sum()), int((n[:, c] * n[:, c]).sum())
+        out.append((float(Fraction(s1, P << scale_bits)), float(Fraction(P * s2 - s1 * s1, (P * P) << (2 * scale_bits))),
+                    float(Fraction(s2, P << (2 * scale_bits)))))
+    return tuple(np.array(v) for v in zip(*out))
+
+
+# --- tss_tensor_stats (csrc/zoo.hip)
+TS_NT = 256
+
+
+def tensor_stats_plan(P, C, ldz, aligned=True):
+    """('vec' | 'scalar', per, npl): block i of the 512 owns pixels [i per, (i + 1) per).  The vector kernel (C a multiple of 8 up to
+    1024, pitch a multiple of 8, 16-byte aligned, P >= 2048): a lane owns 8 channels of every npl-th pixel of the block's range.  The
+    scalar kernel sweeps the channels in passes of 256"""
+    per = cdiv(P, STAT_SLABS)
+    if C % 8 == 0 and C <= TS_NT * 4 and ldz % 8 == 0 and aligned and P >= 4 * STAT_SLABS:
+        return 'vec', per, TS_NT // (C // 8)
+    return 'scalar', per, None
+
+
+def tensor_stats_chain(P, C):
+    """f32 chain of a lane of tensor_stats_vec_kernel<bf16>: its ceil(per / npl) terms (a bf16 value or its square: exact in f32) and
+    one for the step into f64; lanes, blocks and slab rows meet in f64 (the 2^-50 of stats_excess)"""
+    _, per, npl = tensor_stats_plan(P, C, 8)
+    return cdiv(per, npl) + 1
+
+
+def block_sums(v, per, rows=STAT_SLABS):
+    """f64 [rows][C]: the sums over each block's pixel range [i per, (i + 1) per) of v [P][C]"""
+    out = torch.zeros(rows, v.shape[1], dtype=torch.float64)
+    if per > 0:
+        full = v.shape[0] // per
+        out[:full] = v[:full * per].reshape(full, per, -1).sum(1)
+        if full < rows and full * per < v.shape[0]:
+            out[full] = v[full * per:].sum(0)
+    return out
+
+
+# --- tss_bias_grad (colsum_kernel), tss_cast_weights
+def colsum_plan(P):
+    """(grid, terms of a lane): blocks of 4 pixel lanes x 64 channels, at most 1024; a lane walks pixels blk 4 + pl + j 4 grid"""
+    grid = min(cdiv(P, 4), 1024)
+    return grid, cdiv(P, 4 * grid)
+
+
+def colsum_chain(P):
+    """f32 roundings a term of colsum_kernel goes through: the lane's own sum, 3 additions of the four lane rows in LDS, and one f32
+    atomic per block onto the same address, in any order"""
+    grid, lane = colsum_plan(P)
+    return lane + 3 + grid
+
+
+def colsum_exact_values(P, N, rng, bf16=True):
+    """multiples of 2^-6 up to 255/64 in magnitude (8 bits: bf16 numbers): every partial sum of up to 2^16 of them plus the initial
+    dbias (a non-zero multiple of 2^-6 below 2^9) is a multiple of 2^-6 below 2^18, an f32 number: f32 additions in any order are exact"""
+    assert P * 255 + 2 ** 16 < 2 ** 24
+    return rng.randint(-255, 256, size=(P, N)) / 64.0, rng.randint(1, 2 ** 15, size=N) * rng.choice([-1, 1], size=N) / 64.0
+
+
+def cast_sources(N, K, rng):
+    """f32 [N][K] sources of tss_cast_weights: ordinary values, and planted bf16 rounding ties (low half 0x8000, to an even and to an
+    odd neighbour), values one f32 ulp past a tie, f32 denormals, the smallest normals, +-0, values that round up into the next binade"""
+    v = rng.standard_normal(N * K).astype(F32)
+    b = v.view(np.uint32).copy()
+    pick = rng.permutation(N * K)
+    m = max(1, N * K // 16)
+    sl = [pick[i * m:(i + 1) * m] for i in range(7)]
+    b[sl[0]] = (b[sl[0]] & np.uint32(0xFFFF0000)) | np.uint32(0x8000)                       # ties, either parity of the kept half
+    b[sl[1]] = (b[sl[1]] & np.uint32(0xFFFF0000)) | np.uint32(0x8001)                       # just past a tie
+    b[sl[2]] = (b[sl[2]] & np.uint32(0xFFFF0000)) | np.uint32(0x7FFF)                       # just short of one
+    b[sl[3]] = (b[sl[3]] & np.uint32(0x80000000)) | rng.randint(1, 2 ** 23, size=len(sl[3])).astype(np.uint32)     # f32 denormals
+    b[sl[4]] = (b[sl[4]] & np.uint32(0x80000000)) | np.uint32(0x00800000) | rng.randint(0, 2 ** 17, size=len(sl[4])).astype(np.uint32)
+    b[sl[5]] = b[sl[5]] & np.uint32(0x80000000)                                              # +-0
+    b[sl[6]] = (b[sl[6]] & np.uint32(0xFF800000)) | np.uint32(0x007FC000)                    # carries into the exponent
+    return torch.from_numpy(b.view(F32).reshape(N, K).copy())

@@ -1,5 +1,5 @@
 """GPU harness of the exact-operand tests (tests/test_gpu_zoo_exact.py, tests/test_gpu_dw_exact.py, tests/test_gpu_pw_exact.py,
-tests/test_gpu_dense_exact.py, tests/test_gpu_resample_exact.py, tests/test_gpu_bneck_exact.py):
+tests/test_gpu_dense_exact.py, tests/test_gpu_resample_exact.py, tests/test_gpu_bneck_exact.py, tests/test_gpu_bnfin_exact.py):
 sentinel-padded device buffers with spare rows, NaN statistics slabs, the dyadic operands of a layer with planted exact zeros, and the
 checks against tests/exact.py's bounds."""
 import contextlib

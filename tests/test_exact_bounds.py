@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from tests import exact as X
+from tests import philox_ref as PR
 
 
 def _gen(seed):
@@ -1856,3 +1857,378 @@ def test_head_emulation_arg_max_and_pixel_defects_fail():
         x, labels, _, ref = _head(c)
         pix = HE.ce_pass(x.numpy(), labels.numpy(), c.H, c.W, mode=1, defect='unclamped_i1')['pix']
         assert _ratio(pix, ref.pix, X.head_pix_bound(ref.zmax, c.C)) > 1
+
+
+# ---------------------------------------------------------------------------------------------------------- Philox and the dropout masks
+PHILOX_KAT = [((0, 0, 0, 0), (0, 0), (0x6627e8d5, 0xe169c58d, 0xbc57ac4c, 0x9b00dbd8)),
+              ((0xffffffff,) * 4, (0xffffffff, 0xffffffff), (0x408f276d, 0x41c83b0e, 0xa20bc7c6, 0x6d5451fd)),
+              ((0x243f6a88, 0x85a308d3, 0x13198a2e, 0x03707344), (0xa4093822, 0x299f31d0), (0xd16cfe09, 0x94fdcceb, 0x5001e420, 0x24126ea1))]
+SEED_HI = (7 << 32) | 3
+
+
+def test_philox4x32_10_known_answers():
+    """the Random123 known-answer vectors, one by one and as one batch"""
+    for ctr, key, want in PHILOX_KAT:
+        assert tuple(int(v) for v in PR.philox4x32_10([ctr], *key)[0]) == want
+    same_key = PR.philox4x32_10([PHILOX_KAT[0][0], (1, 0, 0, 0), PHILOX_KAT[0][0]], 0, 0)
+    assert tuple(int(v) for v in same_key[0]) == PHILOX_KAT[0][2] and (same_key[0] == same_key[2]).all() and (same_key[0] != same_key[1]).all()
+
+
+@pytest.mark.parametrize('p', [0.1, 0.3, 0.5, 0.75])
+def test_dropout_rules_keep_a_share_of_one_minus_p(p):
+    """2^20 elements: the kept share within 6 standard deviations of the rule's exact probability (threshold / 2^32, / 2^16)"""
+    n = 1 << 20
+    keep = PR.dropout_keep(n // 128, 128, p, SEED_HI)
+    q = 1 - PR.keep_threshold(p) / 2.0 ** 32
+    assert abs(q - (1 - p)) < 2.0 ** -24 and abs(keep.mean() - q) <= 6 * np.sqrt(q * (1 - q) / n)
+    bits_ = np.unpackbits(PR.dropout_mask_bytes(n // 128, p, SEED_HI))
+    q = 1 - PR.mask_threshold(p) / 65536.0
+    assert abs(q - (1 - p)) <= 2.0 ** -16 and bits_.size == n and abs(bits_.mean() - q) <= 6 * np.sqrt(q * (1 - q) / n)
+    assert not np.array_equal(keep, PR.dropout_keep(n // 128, 128, p, 12345))
+
+
+def _keep_mutant(P, C, p, seed, ld=None, high_word=True):
+    """dropout_keep with the counter built from pix ld + c, or the key without the seed's high word"""
+    idx = (np.arange(P, dtype=np.uint64)[:, None] * np.uint64(ld or C) + np.arange(C, dtype=np.uint64)[None, :]).reshape(-1)
+    k0, k1 = PR.seed_key(seed)
+    cw = np.zeros((idx.size, 4), np.uint64)
+    cw[:, 0], cw[:, 1] = (idx >> np.uint64(2)) & np.uint64(0xFFFFFFFF), idx >> np.uint64(34)
+    w = PR.philox4x32_10(cw, k0, k1 if high_word else PR.KEY_XOR)
+    return (w[np.arange(idx.size), (idx & np.uint64(3)).astype(np.int64)] >= np.uint32(PR.keep_threshold(p))).reshape(P, C)
+
+
+def test_dropout_rule_defects_change_the_mask():
+    P, C, p = 37, 24, 0.5
+    ref = PR.dropout_keep(P, C, p, SEED_HI)
+    assert np.array_equal(_keep_mutant(P, C, p, SEED_HI), ref)                       # the mutant's own plumbing is sound
+    assert not np.array_equal(_keep_mutant(P, C, p, SEED_HI, ld=40), ref)            # the counter from the pitch
+    assert np.array_equal(_keep_mutant(P, C, p, SEED_HI, ld=40)[0], ref[0])          # ... which the first pixel alone cannot show
+    assert not np.array_equal(_keep_mutant(P, C, p, SEED_HI, high_word=False), ref)  # the key without the seed's high word
+    assert np.array_equal(_keep_mutant(P, C, p, 12345, high_word=False), PR.dropout_keep(P, C, p, 12345))   # ... invisible below 2^32
+    # two elements sharing one word: every element of a counter's four has its own
+    w = PR.dropout_words(1 << 12, SEED_HI)
+    assert len(set(w.tolist())) > (1 << 12) - 4
+    # the mask byte indexed by pix (C / 8) + v instead of pix 16 + v
+    C8 = 1
+    want = PR.dropout_mask_bytes(P, p, SEED_HI)
+    dense = PR.dropout_mask_bytes(P, p, SEED_HI).reshape(-1)[:P * C8].reshape(P, C8)        # byte b of the dense numbering
+    assert np.array_equal(dense[0], want[0, :C8]) and not np.array_equal(dense[1:, 0], want[1:, 0])
+    assert len(set(want[:, 0].tolist())) > 8, 'a byte that repeats across pixels'
+
+
+# ---------------------------------------------------------------------------------------------------------- BatchNorm finalize chain
+def _slabs_of(x, rows=X.STAT_SLABS):
+    """[rows][2 C] f64 slab rows of x [P][C] (numpy f64) as tss_tensor_stats lays them out: block i owns [i per, (i + 1) per)"""
+    t = torch.from_numpy(x)
+    per = X.cdiv(x.shape[0], rows)
+    return torch.cat([X.block_sums(t, per, rows), X.block_sums(t * t, per, rows)], 1).numpy()
+
+
+def test_bn_finalize_ref_is_torch_batchnorm_in_training_mode():
+    """two training steps of torch.nn.BatchNorm2d in float64: batch statistics (through the normalised output), running statistics
+    with the unbiased variance, to the f32 roundings the reference makes on purpose"""
+    rng = X.np_rng(301)
+    C, eps, mom = 5, 1e-5, 0.1
+    bn = torch.nn.BatchNorm2d(C, eps=float(np.float32(eps)), momentum=float(np.float32(mom))).double().train()
+    with torch.no_grad():
+        bn.weight.copy_(torch.from_numpy(rng.uniform(0.5, 2, C).astype(np.float32).astype(np.float64)))
+        bn.bias.zero_()
+    rm, rv = np.zeros(C, np.float32), np.ones(C, np.float32)
+    for step in range(2):
+        x = rng.standard_normal((3, C, 7, 5)) * rng.uniform(0.5, 3, (1, C, 1, 1)) + rng.uniform(-2, 2, (1, C, 1, 1))
+        y = bn(torch.from_numpy(x)).detach().numpy()
+        rows = x.transpose(0, 2, 3, 1).reshape(-1, C)
+        r = X.bn_finalize_ref(rows.sum(0), (rows * rows).sum(0), rows.shape[0], bn.weight.detach().numpy(), eps, mom, rm, rv)
+        mine = (x - r['mean'].reshape(1, C, 1, 1).astype(np.float64)) * r['scale'].reshape(1, C, 1, 1).astype(np.float64)
+        assert np.abs(mine - y).max() <= 2.0 ** -21 * np.abs(y).max()
+        rm, rv = r['running_mean'], r['running_var']
+        assert np.allclose(r['unbiased64'], rows.var(0, ddof=1), rtol=1e-12)
+        assert np.allclose(rm, bn.running_mean.numpy(), rtol=2.0 ** -21, atol=2.0 ** -24)
+        assert np.allclose(rv, bn.running_var.numpy(), rtol=2.0 ** -21)
+    assert bn.num_batches_tracked.item() == 2
+    one = X.bn_finalize_ref(np.array([3.0]), np.array([9.0]), 1.0, None, eps, mom, np.zeros(1), np.ones(1))
+    assert one['var64'][0] == 0 and one['running_var'][0] == np.float32(1) - np.float32(mom)       # count 1: var itself, no division by 0
+
+
+@pytest.mark.parametrize('training', [1, 0])
+def test_bn_bwd_finalize_ref_is_torch_autograd(training):
+    """ga (e - gce) + gb (y - mean) against torch's float64 input gradient of BatchNorm2d, dgamma / dbeta its parameter gradients"""
+    rng = X.np_rng(303, training)
+    C, eps = 6, 1e-5
+    bn = torch.nn.BatchNorm2d(C, eps=float(np.float32(eps))).double()
+    with torch.no_grad():
+        bn.weight.copy_(torch.from_numpy(rng.uniform(0.5, 2, C).astype(np.float32).astype(np.float64)))
+        bn.running_mean.copy_(torch.from_numpy(rng.uniform(-1, 1, C)))
+        bn.running_var.copy_(torch.from_numpy(rng.uniform(0.5, 2, C)))
+    bn.train(bool(training))
+    y = torch.from_numpy(rng.standard_normal((2, C, 5, 3)) * 2 + 1).requires_grad_(True)
+    e = torch.from_numpy(rng.standard_normal((2, C, 5, 3)))
+    rows = lambda t: t.detach().numpy().transpose(0, 2, 3, 1).reshape(-1, C)
+    yr, er = rows(y), rows(e)
+    if training:
+        f = X.bn_finalize_ref(yr.sum(0), (yr * yr).sum(0), yr.shape[0], None, eps, 0.1)
+        mean, invstd = f['mean'].astype(np.float64), f['invstd']
+    else:
+        mean, invstd = bn.running_mean.numpy(), (1.0 / np.sqrt(bn.running_var.numpy() + np.float64(np.float32(eps)))).astype(np.float32)
+    bn(y).backward(e)
+    b = X.bn_bwd_finalize_ref(er.sum(0), (er * (yr - mean)).sum(0), yr.shape[0], invstd, bn.weight.detach().numpy(), training, 1,
+                              np.ones(C, np.float32), np.full(C, 2, np.float32))
+    g = b['ga'].astype(np.float64) * (er - b['gce']) + b['gb'].astype(np.float64) * (yr - mean)
+    assert np.abs(g - rows(y.grad)).max() <= 2.0 ** -19 * np.abs(rows(y.grad)).max()
+    assert np.allclose(b['dgamma'] - 1, bn.weight.grad.numpy(), rtol=2.0 ** -18, atol=2.0 ** -20)
+    assert np.allclose(b['dbeta'] - 2, bn.bias.grad.numpy(), rtol=2.0 ** -18, atol=2.0 ** -20)
+    if not training:
+        assert (b['gb'] == 0).all() and (b['gce'] == 0).all()
+
+
+@pytest.mark.parametrize('k', [0, 3, 10, 16])
+def test_finalize_tier1_premise(k):
+    """integer slab rows sum exactly in any order; mean, mean^2, q / count and the variance are f64 numbers, with or without an FMA; the
+    constant channel has var 0 and channel 1 is negative before the clamp; the running-statistics products are exact in f32"""
+    rng = X.np_rng(305, k)
+    C = 19
+    slabs, s, q = X.fin_tier1_slabs(C, k, rng)
+    assert slabs.shape == (X.STAT_SLABS, 2 * C) and ((slabs != 0).any(1).sum() <= X.STAT_SLABS // 2 + 1)
+    for order in (np.arange(X.STAT_SLABS), rng.permutation(X.STAT_SLABS), np.arange(X.STAT_SLABS)[::-1]):
+        acc = np.zeros(2 * C)
+        for r in order:
+            acc = acc + slabs[r]
+        assert (acc[:C] == s).all() and (acc[C:] == q).all()
+    si, qi = s.astype(np.int64), q.astype(np.int64)
+    assert X.fin_tier1_premise(si, qi, k)
+    bad = si.copy()
+    bad[2] = 2 ** 27 + 1                                          # 28 bits: mean^2 is no f64 number any more
+    assert not X.fin_tier1_premise(bad, qi, k)
+    cnt = 2.0 ** k
+    raw = q / cnt - (s / cnt) ** 2
+    assert raw[0] == 0 and raw[1] <= -0.125 and raw[1] >= -2 and (raw[2:] > 0).all()
+    assert int(np.abs(s).max()) >= 2 ** 21 and (k < 10 or (s / cnt).astype(np.float32).astype(np.float64).tolist() != (s / cnt).tolist())
+    for m in (0.125, 0.5):
+        rm = X.dyadic8_np(4096, rng).astype(np.float64)
+        x = rng.standard_normal(4096).astype(np.float32).astype(np.float64)
+        assert (((1 - m) * rm).astype(np.float32) == (1 - m) * rm).all() and ((m * x).astype(np.float32) == m * x).all()
+
+
+def _emu_slab_sum(slabs, C, defect=None):
+    """slab_sum of csrc/bnfin.h in its own order: lane (row group, column half, channel) adds rows wave 4 + rg + 16 u, u = 0 .. 31, the 16
+    lane sums of a column meet in wave-major order.  Returns [2][8 blocks]; lanes past C hold 0 (no_guard: what they read and summed)"""
+    rows, nblk = slabs.shape[0], X.cdiv(C, X.FIN_CH)
+    flat = np.concatenate([slabs.reshape(-1), np.zeros(2 * C + 8)])
+    out = np.zeros((2, nblk * X.FIN_CH))
+    trips = rows // X.FIN_ROWS_PER_LOAD - (1 if defect == 'skip_row' else 0)
+    for c in range(nblk * X.FIN_CH):
+        inside = c < C
+        for hs in range(2):
+            col = flat[np.arange(rows) * 2 * C + hs * C + (c if inside or defect == 'no_guard' else 0)].reshape(-1, X.FIN_ROWS_PER_LOAD)
+            lane = np.zeros(X.FIN_ROWS_PER_LOAD)
+            for u in range(trips):
+                lane = lane + col[u]
+            a = 0.0
+            for v in lane:
+                a = a + v
+            out[hs, c] = a if inside or defect == 'no_guard' else 0.0
+    return out
+
+
+PADV = 8
+SENT = np.float32(0.8529)
+
+
+def _emu_finalize(slabs, count, gamma, eps, momentum, rm, rv, C, defect=None):
+    """bn_finalize_kernel in numpy: f64 up to invstd, f32 behind it; outputs in vectors with PADV sentinels behind C"""
+    f32 = np.float32
+    ss = _emu_slab_sum(slabs, C, defect)
+    n = ss.shape[1] if defect == 'no_guard' else C
+    s, q = ss[0, :n], ss[1, :n]
+    if defect == 'f32_var':
+        mean = (s.astype(f32) / f32(count))
+        var = ((q.astype(f32) / f32(count)) - mean * mean).astype(np.float64)
+        mean = mean.astype(np.float64)
+    else:
+        mean = s / count
+        var = q / count - mean * mean
+    if defect != 'no_clamp':
+        var = np.maximum(var, 0.0)
+    with np.errstate(invalid='ignore'):
+        invstd = (1.0 / np.sqrt(var + np.float64(f32(eps)))).astype(f32)
+    pad = lambda v: np.concatenate([np.asarray(v, f32), np.full(max(0, C + PADV - len(v)), SENT, f32)])[:C + PADV]
+    g = np.ones(n, f32) if gamma is None else pad(gamma)[:n]
+    m = f32(momentum)
+    a, b = (m, f32(1) - m) if defect == 'swap_momentum' else (f32(1) - m, m)
+    unbiased = var * count / (count - 1.0) if count > 1 and defect != 'biased' else var
+    return dict(mean=pad(mean.astype(f32)), invstd=pad(invstd), scale=pad(g * invstd), running_mean=pad(a * pad(rm)[:n] + b * mean.astype(f32)),
+                running_var=pad(a * pad(rv)[:n] + b * unbiased.astype(f32)))
+
+
+def _tier1_faults(out, ref, gamma, C):
+    """the checks of tests/test_gpu_bnfin_exact.py::check_tier1 and check_frame as a list of what fails"""
+    bitsof = lambda v: np.ascontiguousarray(v, np.float32).view(np.uint32)
+    bad = [k for k in ('mean', 'running_mean', 'running_var') if not np.array_equal(bitsof(out[k][:C]), bitsof(ref[k]))]
+    inv = out['invstd'][:C].astype(np.float64)
+    if not np.isfinite(inv).all() or (np.abs(inv - ref['invstd64']) > X.FIN_INVSTD_REL * ref['invstd64']).any():
+        bad.append('invstd')
+    if not np.array_equal(bitsof(out['scale'][:C]), bitsof(X.bn_scale_ref(gamma, out['invstd'][:C]))):
+        bad.append('scale')
+    if any((v[C:] != SENT).any() for v in out.values()):
+        bad.append('tail')
+    return bad
+
+
+FIN_DEFECTS = {'f32_var': 'invstd', 'biased': 'running_var', 'swap_momentum': 'running_mean', 'skip_row': 'mean', 'no_guard': 'tail',
+               'no_clamp': 'invstd'}
+
+
+@pytest.mark.parametrize('C', [4, 19, 132])
+def test_finalize_emulation_is_bit_for_bit_on_tier1_and_each_defect_is_not(C):
+    rng = X.np_rng(307, C)
+    slabs, s, q = X.fin_tier1_slabs(C, 10, rng)
+    gamma, rm, rv = rng.uniform(-2, 2, C).astype(np.float32), X.dyadic8_np(C, rng), X.dyadic8_np(C, rng, True)
+    ref = X.bn_finalize_ref(s, q, 1024.0, gamma, 1e-5, 0.125, rm, rv)
+    assert _tier1_faults(_emu_finalize(slabs, 1024.0, gamma, 1e-5, 0.125, rm, rv, C), ref, gamma, C) == []
+    for defect, shows in FIN_DEFECTS.items():
+        faults = _tier1_faults(_emu_finalize(slabs, 1024.0, gamma, 1e-5, 0.125, rm, rv, C, defect), ref, gamma, C)
+        if defect == 'no_guard' and C % X.FIN_CH == 0:
+            assert faults == []                                   # only a ragged channel count has lanes past C
+        else:
+            assert shows in faults, (defect, faults)
+
+
+def test_finalize_tier2_bound_holds_for_the_emulation_and_rejects_an_f32_variance():
+    """stored values near 30, deviation 2^-3: the f64 finalize sits orders of magnitude inside fin_tier2_bounds, an f32 variance orders of
+    magnitude outside; a biased running_var and a swapped momentum fail their bounds too"""
+    rng = X.np_rng(309)
+    P, C, eps, mom = 3000, 24, 1e-5, 0.1
+    x = X.offset_values(P, C, rng)
+    slabs = _slabs_of(x)
+    assert (slabs.sum(0)[:C] == x.sum(0)).all() and (slabs.sum(0)[C:] == (x * x).sum(0)).all()
+    mean, var, qc = X.exact_moments(x)
+    assert var[0] == 0 and np.allclose(var[1:], x.var(0)[1:], rtol=1e-9) and np.allclose(mean, x.mean(0), rtol=1e-14)
+    rm, rv = rng.uniform(-3, 3, C).astype(np.float32), rng.uniform(0.01, 0.03, C).astype(np.float32)
+    b = X.fin_tier2_bounds(var, qc, mean, eps, float(P), mom, rm.astype(np.float64), rv.astype(np.float64))
+    m64, t = np.float64(np.float32(mom)), var + np.float64(np.float32(eps))
+    refs = dict(invstd=t ** -0.5, running_mean=(1 - m64) * rm.astype(np.float64) + m64 * mean,
+                running_var=(1 - m64) * rv.astype(np.float64) + m64 * var * P / (P - 1.0))
+
+    def ratios(defect=None):
+        o = _emu_finalize(slabs, float(P), None, eps, mom, rm, rv, C, defect)
+        return {k: float((np.abs(o[k][:C].astype(np.float64) - refs[k]) / b[k]).max()) for k in refs}
+    ok = ratios()
+    assert max(ok.values()) <= 1, ok
+    assert (b['invstd'][1:] <= 1.01 * X.FIN_INVSTD_REL * refs['invstd'][1:]).all()        # the bound is one f32 rounding, not slack
+    assert ratios('f32_var')['invstd'] > 1000 and ratios('biased')['running_var'] > 100 and ratios('swap_momentum')['running_mean'] > 1000
+
+
+def _emu_bwd(slabs, count, invstd, gamma, C, defect=None):
+    ss = _emu_slab_sum(slabs, C, 'skip_row' if defect == 'skip_row' else None)
+    se, sey, r = ss[0, :C], ss[1, :C], invstd.astype(np.float64)
+    k = gamma.astype(np.float64) * r
+    c2 = r * sey / count
+    gb = -k * c2 if defect == 'gb_one_invstd' else -k * c2 * r
+    return dict(dgamma=np.float32(0) + (r * sey).astype(np.float32), dbeta=np.float32(0) + se.astype(np.float32), ga=k.astype(np.float32),
+                gb=gb.astype(np.float32), gce=(se / count).astype(np.float32))
+
+
+def test_bwd_finalize_emulation_is_bit_for_bit_and_each_defect_is_not():
+    C = 19
+    rng = X.np_rng(311)
+    slabs, se, sey = X.fin_bwd_slabs(C, rng)
+    invstd, gamma = rng.uniform(0.05, 40, C).astype(np.float32), rng.uniform(-2, 2, C).astype(np.float32)
+    ref = X.bn_bwd_finalize_ref(se, sey, 1000.0, invstd, gamma)
+    same = lambda o: [k for k in ref if not np.array_equal(o[k].view(np.uint32), ref[k].view(np.uint32))]
+    assert same(_emu_bwd(slabs, 1000.0, invstd, gamma, C)) == []
+    assert same(_emu_bwd(slabs, 1000.0, invstd, gamma, C, 'gb_one_invstd')) == ['gb']
+    assert set(same(_emu_bwd(slabs, 1000.0, invstd, gamma, C, 'skip_row'))) >= {'dgamma', 'dbeta', 'gb', 'gce'}
+    # the sign convention of gb: g = ga (e - gce) + gb (y - mean) must REMOVE the component along y - mean
+    assert (np.sign(ref['gb']) == -np.sign(gamma.astype(np.float64) * sey)).all()
+    frozen = X.bn_bwd_finalize_ref(se, sey, 1000.0, invstd, gamma, training=0, accumulate=1, dgamma=np.ones(C), dbeta=np.ones(C))
+    assert (frozen['gb'] == 0).all() and (frozen['gce'] == 0).all() and np.array_equal(frozen['dbeta'], np.float32(1) + se.astype(np.float32))
+    two = X.bn_bwd_finalize_ref(se * 2, sey * 2, 2000.0, invstd, gamma, local=(se, sey))       # two equal replicas: the same coefficients
+    assert same(two) == []
+
+
+def _emu_tensor_stats_vec(v, P, C):
+    """tensor_stats_vec_kernel<bf16>: a lane's f32 partial sums over its pixels p0 + pl + j npl in order, lanes and rows in f64"""
+    _, per, npl = X.tensor_stats_plan(P, C, 8)
+    rows = np.zeros((X.STAT_SLABS, 2 * C))
+    x = v.astype(np.float32)
+    for i in range(X.STAT_SLABS):
+        blk = x[i * per:min(P, (i + 1) * per)]
+        trips = X.cdiv(len(blk), npl)
+        if trips == 0:
+            continue
+        padded = np.zeros((trips * npl, C), np.float32)
+        padded[:len(blk)] = blk
+        padded = padded.reshape(trips, npl, C)
+        s, q = np.zeros((npl, C), np.float32), np.zeros((npl, C), np.float32)
+        for j in range(trips):
+            s, q = s + padded[j], q + padded[j] * padded[j]
+        rows[i, :C], rows[i, C:] = s.astype(np.float64).sum(0), q.astype(np.float64).sum(0)
+    return rows
+
+
+@pytest.mark.parametrize('P,C', [(70001, 16), (2100, 1024), (20000, 128)])
+def test_tensor_stats_emulation_meets_the_row_bound(P, C):
+    v = X.dyadic((P, C), _gen(313))
+    rows = torch.from_numpy(_emu_tensor_stats_vec(v.numpy(), P, C))
+    _, per, npl = X.tensor_stats_plan(P, C, 8)
+    chain = X.tensor_stats_chain(P, C)
+    assert chain == X.cdiv(X.cdiv(P, 512), npl) + 1
+    worst = 0.0
+    for half, terms in ((0, v), (1, v * v)):
+        ref, mag = X.block_sums(terms, per), X.block_sums(terms.abs(), per)
+        worst = max(worst, float(((rows[:, half * C:(half + 1) * C] - ref).abs() / ((2.0 ** -23 * chain + 2.0 ** -50) * mag.clamp_min(1e-300))).max()))
+    assert worst <= 1
+    assert X.stats_excess(rows.sum(0), torch.cat([v, v * v], 1), chain) <= 0
+    shifted = torch.from_numpy(_emu_tensor_stats_vec(np.roll(v.numpy(), 1, 0), P, C))           # every block owns the pixel before its range
+    assert float(((shifted[:, :C] - X.block_sums(v, per)).abs() - (2.0 ** -23 * chain + 2.0 ** -50) * X.block_sums(v.abs(), per)).max()) > 0
+    assert X.tensor_stats_plan(2047, 128, 128)[0] == 'scalar' and X.tensor_stats_plan(2048, 1032, 1032)[0] == 'scalar' and \
+        X.tensor_stats_plan(2048, 128, 133)[0] == 'scalar' and X.tensor_stats_plan(2048, 1024, 1024) == ('vec', 4, 2)
+
+
+def _emu_colsum(e, init, defect=None):
+    """colsum_kernel in f32: lane sums in pixel order, the four lane rows of a block, one atomic per block in block order"""
+    P, N = e.shape
+    grid, lane = X.colsum_plan(P)
+    x = np.zeros((lane * grid * 4, N), np.float32)
+    x[:P] = e.astype(np.float32)
+    x = x.reshape(lane, grid, 4, N)
+    s = np.zeros((grid, 4, N), np.float32)
+    for j in range(lane):
+        s = s + x[j]
+    blk = ((s[:, 0] + s[:, 1]) + s[:, 2]) + s[:, 3]
+    out = init.astype(np.float32)
+    for b in range(grid):
+        out = blk[b] if defect == 'overwrite' else out + blk[b]
+    return out
+
+
+def test_colsum_emulation_is_exact_on_tier1_within_the_chain_bound_on_tier2_and_overwriting_is_not():
+    for P in (3, 4101, 40000):
+        e, init = X.colsum_exact_values(P, 19, X.np_rng(315, P))
+        want = (init + e.sum(0)).astype(np.float32)
+        assert (want.astype(np.float64) == init + e.sum(0)).all() and (init != 0).all()
+        assert np.array_equal(_emu_colsum(e, init), want) and not np.array_equal(_emu_colsum(e, init, 'overwrite'), want)
+        assert X.colsum_plan(P) == (min(X.cdiv(P, 4), 1024), X.cdiv(P, 4 * min(X.cdiv(P, 4), 1024)))
+    rng = X.np_rng(317)
+    P, N = 40000, 19
+    e = rng.standard_normal((P, N)).astype(np.float32).astype(np.float64)
+    init = rng.standard_normal(N).astype(np.float32)
+    assert X.colsum_chain(P) == 10 + 3 + 1024
+    bound = 2.0 ** -23 * X.colsum_chain(P) * (np.abs(init) + np.abs(e).sum(0))
+    assert (np.abs(_emu_colsum(e, init).astype(np.float64) - (init + e.sum(0))) <= bound).all()
+    assert not (np.abs(_emu_colsum(e, init, 'overwrite').astype(np.float64) - (init + e.sum(0))) <= bound).all()
+
+
+def test_cast_sources_hold_the_planted_roundings():
+    src = X.cast_sources(19, 128, X.np_rng(319))
+    b = src.numpy().view(np.uint32)
+    low = b & 0xFFFF
+    assert ((low == 0x8000) & (((b >> 16) & 1) == 0)).any() and ((low == 0x8000) & (((b >> 16) & 1) == 1)).any()     # ties to even: down, up
+    assert (low == 0x8001).any() and (low == 0x7FFF).any()
+    expo = (b >> 23) & 0xFF
+    assert ((expo == 0) & ((b & 0x7FFFFF) != 0)).any() and (b == 0).any() and (b == 0x80000000).any() and torch.isfinite(src).all()
+    r = src.to(torch.bfloat16)
+    rb = r.view(torch.int16).numpy().astype(np.int64) & 0xFFFF
+    tie = low == 0x8000
+    assert ((rb[tie] & 1) == 0).all()                             # torch rounds ties to even: the reference of the GPU test
+    assert (rb[low == 0x8001] == ((b[low == 0x8001] >> 16) + 1) & 0xFFFF).all() and (rb[low == 0x7FFF] == (b[low == 0x7FFF] >> 16)).all()

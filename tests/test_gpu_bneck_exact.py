@@ -29,12 +29,17 @@ the case names, so a planner that moves fails the case instead of silently uncov
           form needs 211 KB of LDS: TSS_ERR_SHAPE, tss_bneck_eval_supported 0, nothing written
 Affines.  mean bit for bit, invstd within 3 u and scale within 4 u of f64 (X.affine_ref); batched == single bit for bit; sentinels intact.
 Joins.  Forward: X.dyadic operands and power-of-two scales make each branch and the sum exact in f32 (asserted): f32 output == the value,
-bf16 output == its rne_bf16.  Backward: e bit for bit (ReLU mask, dout_scale 2, in place), the statistics rows within X.stats_excess of
+bf16 output == its rne_bf16.  With a seed slot the forward also applies nn.Dropout: the kept set is predicted by tests/philox_ref.py
+(Philox4x32-10 in numpy), kept values times 1 / (1 - p) (p = 1/2, 3/4: exact), bit for bit, and bit for bit tss_dropout of the plain join.
+Backward: e bit for bit (ReLU mask, dout_scale 2 and 4, in place), the statistics rows within X.stats_excess of
 the STORED e with the restated lane chain, the rows in use against the restated grid (check_slab_rows)."""
+import ctypes
+
 import pytest
 import torch
 
 from tests import exact as X
+from tests import philox_ref
 from tests.exact_gpu import (DEV, Buf, N_, affine_batched, bneck_call, bneck_tile, check_slab_rows, dev, nan_slabs, to_rows)
 
 pytestmark = pytest.mark.gpu
@@ -271,6 +276,76 @@ def test_join_fwd(C, kind, two, affa, affb, relu, dtype):
     assert ob.untouched(), (what, 'sentinel overwritten')
 
 
+# (C, P kind, two branches): 'second' -- ceil(P / NPL) = 2561 tiles over the 512 blocks, a block takes more than one
+JOIN_DROP = [(8, 'one', 1), (24, 'short', 1), (24, 'short', 0), (24, 'grid', 1), (136, 'short', 0), (136, 'second', 1), (136, 'second', 0)]
+JOIN_DROP_SEEDS = {0.5: (7 << 32) | 3, 0.75: 2 ** 64 - 1}
+
+
+def seed_slot(seed):
+    return torch.tensor([ctypes.c_int64(seed).value], dtype=torch.int64, device=DEV)
+
+
+@pytest.mark.parametrize('dtype', DTYPES)
+@pytest.mark.parametrize('p', [0.5, 0.75])
+@pytest.mark.parametrize('C,kind,two', JOIN_DROP)
+def test_join_fwd_with_dropout(C, kind, two, p, dtype):
+    """the dropout folded into a ReLU join: relu(affA(a) + affB(b)) in f64 (exact), rounded to the dtype, kept elements (the mask of
+    philox_ref.dropout_keep on the LOGICAL index pix C + c) times 1 / (1 - p), a power of two, dropped ones 0, rounded again: bit for
+    bit; and bit for bit what tss_dropout makes of the plain join's output with the same slot"""
+    n, P = N_(), X.join_P(kind, C)
+    NPL, grid = X.join_geometry(P, C, X.JOIN_FWD_BLOCKS)
+    assert kind != 'second' or X.cdiv(P, NPL) > X.JOIN_FWD_BLOCKS
+    g = gen(95, C, P, two)
+    a, A = join_branch(P, C, g, True)
+    b, Bf = join_branch(P, C, g, True) if two else (None, None)
+    seed = JOIN_DROP_SEEDS[p]
+    slot = seed_slot(seed)
+    bf = dtype == BF
+    plain = X.out_bits_ref(X.join_fwd_ref(a, A, b, Bf, True), bf)
+    keep = torch.from_numpy(philox_ref.dropout_keep(P, C, p, seed))
+    want = X.out_bits_ref(torch.where(keep, plain / (1 - p), torch.zeros_like(plain)), bf)
+    assert bool((plain[keep] > 0).any()) and bool((plain[~keep] > 0).any()) or P * C < 100
+    ab = Buf(P, C, C + 8, 0, a, dtype, nan_spare=True)
+    bb = Buf(P, C, C + 16, 8, b, dtype, nan_spare=True) if two else None
+    ka, pa = aff_ptrs(A)
+    kb, pb = aff_ptrs(Bf)
+    outs = []
+    for drop in (True, False):
+        ob = Buf(P, C, C + 16, 8, dtype=dtype)
+        n.call('tss_join_fwd', ab.ptr, ab.ld, pa[0], pa[1], pa[2], bb.ptr if two else None, bb.ld if two else 0, pb[0], pb[1], pb[2],
+               ob.ptr, ob.ld, 1, p if drop else 0.0, slot.data_ptr() if drop else None, P, C, code(dtype), n.stream())
+        sync()
+        assert ob.untouched(), ('join fwd dropout', C, kind, drop, 'sentinel overwritten')
+        outs.append(ob)
+    what = ('join fwd dropout', C, kind, P, two, p, dtype)
+    same_bits(outs[0].rows(), want, what)
+    same_bits(outs[1].rows(), plain, what + ('plain',))
+    db = Buf(P, C, C + 8, 0, dtype=dtype)
+    n.call('tss_dropout', outs[1].ptr, outs[1].ld, db.ptr, db.ld, P, C, p, slot.data_ptr(), code(dtype), n.stream())
+    sync()
+    assert torch.equal(X.bits(db.t[:P, :C].cpu()), X.bits(outs[0].t[:P, 8:8 + C].cpu())), (what, 'tss_dropout of the plain join differs')
+    assert db.untouched() and slot.item() == ctypes.c_int64(seed).value
+
+
+def test_join_dropout_refusals():
+    """seed_slot without relu; dout_scale != 1 without relu; dout_scale <= 0: TSS_ERR_SHAPE, nothing written"""
+    n = N_()
+    P, C = 5, 8
+    ab, ob, eb = Buf(P, C, C, 0, torch.ones(P, C)), Buf(P, C, C + 8, 0), Buf(P, C, C + 8, 0)
+    slot = seed_slot(3)
+    with pytest.raises(RuntimeError):
+        n.call('tss_join_fwd', ab.ptr, ab.ld, None, None, None, None, 0, None, None, None, ob.ptr, ob.ld, 0, 0.5, slot.data_ptr(), P, C,
+               n.TSS_BF16, n.stream())
+    bwd = lambda relu, scale: n.call('tss_join_bwd', ab.ptr, ab.ld, ab.ptr if relu else None, ab.ld if relu else 0, relu, None, 0, None, None,
+                                     None, 0, None, None, eb.ptr, eb.ld, scale, P, C, n.TSS_BF16, n.stream())
+    for relu, scale in ((0, 2.0), (1, 0.0), (1, -2.0), (0, 0.0)):
+        with pytest.raises(RuntimeError):
+            bwd(relu, scale)
+    sync()
+    ob.C = eb.C = 0
+    assert ob.untouched() and eb.untouched()
+
+
 def test_join_refuses_2056_channels():
     n = N_()
     ab, ob = Buf(1, 2056, 2056, 0, torch.zeros(1, 2056)), Buf(1, 2056, 2056, 0)
@@ -290,7 +365,10 @@ JOIN_BWD = [(8, 'one', 1, 1, 1, 'out', 1.0), (8, 'short', 1, 1, 1, 'out', 1.0), 
             (24, 'short', 1, 1, 0, 'out', 1.0), (24, 'short', 1, 0, 1, 'out', 2.0), (24, 'short', 1, 0, 0, 'out', 1.0),
             (24, 'short', 0, 1, 1, 'out', 1.0), (24, 'grid', 1, 1, 1, 'inplace', 1.0), (24, 'short', 1, 1, 1, None, 1.0),
             (136, 'one', 1, 1, 1, 'out', 1.0), (136, 'short', 1, 1, 1, 'inplace', 2.0), (136, 'grid', 1, 1, 1, 'out', 1.0),
-            (136, 'second', 1, 1, 1, 'out', 1.0), (2048, 'one', 1, 1, 1, 'out', 1.0), (2048, 'grid', 1, 1, 0, 'out', 1.0)]
+            (136, 'second', 1, 1, 1, 'out', 1.0), (2048, 'one', 1, 1, 1, 'out', 1.0), (2048, 'grid', 1, 1, 0, 'out', 1.0),
+            # the backward of a join with dropout folded in: dout_scale = 1 / (1 - p) for p = 1/2 and 3/4
+            (8, 'short', 1, 1, 1, 'out', 4.0), (24, 'grid', 1, 1, 1, 'out', 4.0), (24, 'short', 1, 1, 1, 'inplace', 4.0),
+            (136, 'second', 1, 1, 1, 'out', 2.0), (136, 'second', 1, 1, 0, 'out', 4.0), (2048, 'one', 1, 0, 1, 'out', 4.0)]
 
 
 @pytest.mark.parametrize('dtype', DTYPES)
