@@ -594,6 +594,36 @@ int tss_adamw_step_groups(float* params, const float* grads, float* exp_avg, flo
  * (columns 1, 2 of a state row are not used). */
 int tss_sgd_step_groups(float* params, const float* grads, float* momentum_buf, long n, const tss_optgroup* groups, int ngroups,
                         const float* lr, float* state, const float* scale, float grad_scale, long step_host, void* stream);
+/* ---- exponential moving average of the weights (csrc/optim.hip) -----------------------------------------------------------
+ * replaces: torch.optim.swa_utils.AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(decay)) / torch._foreach_lerp_ after the step.
+ * Per element  t = p_new - e;  u = t * omd;  e' = e + u,  each operation rounded on its own (the lerp form: d*e + (1 - d)*p loses
+ * the update in f32 at decay = 0.9999).  omd = 1 - d_k in f32, k = the updates done before this one: d_k = decay, or with
+ * warmup != 0  d_k = fminf(decay, (1 + k) / (10 + k)).
+ * tss_adamw_step_groups_ema / tss_sgd_step_groups_ema: tss_adamw_step_groups / tss_sgd_step_groups (same arguments, same kernels,
+ * params and state buffers come out bit-identical) whose step kernel also averages the new parameters into ema[n]: 8 more bytes
+ * per element, no extra launch.  state == NULL: omd_host (computed by the caller with the formula above, 0 < omd_host <= 1) is a
+ * kernel argument; ema_state is not read.  state != NULL: ema_state = {k, omd} (two floats on the device, {0, 0} before the first
+ * update) is advanced by the tick launch that precedes the step -- omd from k, then k + 1 -- so a captured step replays correctly.
+ * Else TSS_ERR_SHAPE, nothing launched: ema NULL, decay outside [0, 1) (NaN included), ema_state NULL with a state, omd_host
+ * outside (0, 1] without one, and whatever the entries without _ema reject. */
+int tss_adamw_step_groups_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, long n,
+                              const tss_optgroup* groups, int ngroups, const float* lr, float* state, const float* scale,
+                              float grad_scale, long step_host, float decay, int warmup, float omd_host, float* ema_state,
+                              void* stream);
+int tss_sgd_step_groups_ema(float* params, const float* grads, float* momentum_buf, float* ema, long n, const tss_optgroup* groups,
+                            int ngroups, const float* lr, float* state, const float* scale, float grad_scale, long step_host,
+                            float decay, int warmup, float omd_host, float* ema_state, void* stream);
+/* The same update over a DEVICE table of nrows x 4 int64 rows {src, dst, n, mode} in one launch: what the step kernel does not hold
+ * (BatchNorm running statistics, parameters outside the optimizer, or every tensor of a model under a stock optimizer).
+ * TSS_EMA_LERP_F32: dst = dst + (src - dst) * omd over n floats; TSS_EMA_COPY_F32 / TSS_EMA_COPY_I64: dst = src over n floats /
+ * n 64-bit integers.  src and dst are 4-byte (I64: 8-byte) aligned, anything more is optional: 16-byte accesses are used only over
+ * the part of a row where both sides are 16-byte aligned.  n may be 0.  Rows must not overlap; bytes outside [dst, dst + n) are
+ * never written; no atomics.  omd = ema_state[1] when ema_state != NULL (a device pointer, after the step's tick), else omd_host
+ * (0 < omd_host <= 1, else TSS_ERR_SHAPE).  nrows == 0: TSS_OK, nothing launched; nrows < 0 or a NULL table: TSS_ERR_SHAPE. */
+#define TSS_EMA_LERP_F32 0
+#define TSS_EMA_COPY_F32 1
+#define TSS_EMA_COPY_I64 2
+int tss_ema_rows(const long long* table, int nrows, float omd_host, const float* ema_state, void* stream);
 /* Global gradient norm and clip factor of the flat gradient buffer, deterministic and without atomics: every block widens its f32
  * elements to f64 (the squares are exact), sums in f64 and writes one row of `workspace` (tss_grad_sqnorm_workspace_bytes(n) bytes,
  * need not be initialised; the block count depends on n only); a one-block pass adds the rows in a fixed order and writes

@@ -15,10 +15,12 @@ MI355X specifics
     xGMI on GPUs, "gloo" on CPU for tests).  BatchNorm statistics stay per replica unless the model
     went through `convert_syncbn_model` (ops.SyncBatchNorm: one small all-reduce per BatchNorm layer and direction).
 """
+import copy
 import ctypes
 import os
 from functools import partial
 
+import numpy as np
 import torch
 import torch.distributed as dist
 from torch import nn
@@ -37,6 +39,21 @@ class _OptGroup(ctypes.Structure):
     """tss_optgroup of include/tss_hip.h."""
     _fields_ = [('begin', ctypes.c_long), ('end', ctypes.c_long), ('lr', ctypes.c_float), ('weight_decay', ctypes.c_float),
                 ('beta1', ctypes.c_float), ('beta2', ctypes.c_float), ('eps', ctypes.c_float), ('flags', ctypes.c_int)]
+
+
+def ema_omd(k, decay, warmup=False):
+    """The factor 1 - d_k of update number k (0-based) of the weight average, as a numpy float32: d_k = decay, or warming up
+    min(decay, (1 + k) / (10 + k)).  Every operation is a float32 one, as in the tick kernel of csrc/optim.hip: the same bits."""
+    d = np.float32(decay)
+    if warmup:
+        d = np.minimum(d, (np.float32(1.0) + np.float32(k)) / (np.float32(10.0) + np.float32(k)))
+    return np.float32(1.0) - d
+
+
+def _check_decay(decay, who):
+    if not (0.0 <= float(decay) < 1.0) or not (0.0 <= float(np.float32(decay)) < 1.0):
+        raise ValueError('%s: decay must lie in [0, 1) (in float32 too), got %r' % (who, decay))
+    return float(decay)
 
 
 class FlatOptimizer(torch.optim.Optimizer):
@@ -112,6 +129,33 @@ class FlatOptimizer(torch.optim.Optimizer):
             if dev.type == 'cuda':
                 self._clip_ws = torch.empty(N.lib().tss_grad_sqnorm_workspace_bytes(n) // 8, dtype=torch.float64, device=dev)
             self.last_grad_norm = self._clip_out[0]
+        self.ema_flat = None             # attach_ema(): a third flat buffer the step kernel averages the new parameters into
+
+    def attach_ema(self, ema_flat, decay, warmup=False):
+        """From now on every step() also updates `ema_flat` (float32, laid out as flat_param) in the step kernel itself:
+        e += (p_new - e) * (1 - d_k), d_k = decay, or with warmup min(decay, (1 + k) / (10 + k)) for update number k.  No extra launch,
+        8 more bytes per element.  The counter k and the factor live on the host (kernel arguments) or, with device_state, in
+        `ema_state` behind the tick kernel, so a captured step() replays them.  engine.ModelEMA is the owner of such a buffer."""
+        name = type(self).__name__
+        decay = _check_decay(decay, name + '.attach_ema')
+        if (ema_flat.dtype != torch.float32 or ema_flat.shape != self.flat_param.shape or ema_flat.device != self.flat_param.device
+                or not ema_flat.is_contiguous()):
+            raise ValueError('%s.attach_ema: the average is a contiguous float32 buffer of %d elements on %s'
+                             % (name, self.flat_param.numel(), self.flat_param.device))
+        if ema_flat.data_ptr() == self.flat_param.data_ptr():
+            raise ValueError('%s.attach_ema: the average must not alias the parameters' % name)
+        self.ema_flat, self.ema_decay, self.ema_warmup = ema_flat, decay, bool(warmup)
+        self.ema_updates = 0             # k: the updates done so far (host mirror of ema_state[0])
+        self.ema_state = torch.zeros(2, dtype=torch.float32, device=ema_flat.device)      # device_state: {k, 1 - d_(k-1)}
+
+    def _ema_row(self, k):
+        """{k, factor of the latest update}: what the tick kernel leaves in ema_state after k updates."""
+        return [float(k), float(ema_omd(k - 1, self.ema_decay, self.ema_warmup)) if k > 0 else 0.0]
+
+    def _ema_args(self):
+        """The trailing arguments of the _ema entries: decay, warmup, the host's factor for this update, the device row."""
+        return (self.ema_decay, int(self.ema_warmup), float(ema_omd(self.ema_updates, self.ema_decay, self.ema_warmup)),
+                N.ptr(self.ema_state) if self.device_state else None)
 
     @staticmethod
     def _reject_flags(mapping):
@@ -184,6 +228,9 @@ class FlatOptimizer(torch.optim.Optimizer):
         flat = {name: (None if getattr(self, name) is None else getattr(self, name).clone()) for name in self._state_names}
         flat['state_vec'] = sv
         flat['group_ranges'] = [list(r) for r in self.group_ranges]
+        if self.ema_flat is not None:    # the counter and latest factor of the average (its values: ModelEMA.state_dict())
+            flat['ema_state'] = self.ema_state.clone() if self.device_state else \
+                torch.tensor(self._ema_row(self.ema_updates), dtype=torch.float32, device=sv.device)
         sd['flat'] = flat
         return sd
 
@@ -216,6 +263,10 @@ class FlatOptimizer(torch.optim.Optimizer):
                         getattr(self, k).copy_(flat[k])
                 self.state_vec.copy_(flat['state_vec'])
             self.step_count = int(round(float(flat['state_vec'][0])))
+            if self.ema_flat is not None and flat.get('ema_state') is not None:
+                with torch.no_grad():
+                    self.ema_state.copy_(flat['ema_state'])
+                self.ema_updates = int(round(float(flat['ema_state'][0])))
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -233,6 +284,8 @@ class FlatOptimizer(torch.optim.Optimizer):
                    self.max_grad_norm, N.ptr(self._clip_out), N.stream())
             scale = self._clip_out.data_ptr() + self._clip_out.element_size()
         self._launch(rows, scale)
+        if self.ema_flat is not None:
+            self.ema_updates += 1
 
 
 class FlatAdamW(FlatOptimizer):
@@ -260,9 +313,13 @@ class FlatAdamW(FlatOptimizer):
 
     def _launch(self, rows, scale):
         dev = self.device_state
-        N.call('tss_adamw_step_groups', N.ptr(self.flat_param), N.ptr(self.flat_grad), N.ptr(self.exp_avg), N.ptr(self.exp_avg_sq),
-               self.flat_param.numel(), rows, len(rows), N.ptr(self.lr_dev) if dev else None, N.ptr(self.state_vec) if dev else None,
-               scale, float(self.grad_scale), int(self.step_count), N.stream())
+        tail = (self.flat_param.numel(), rows, len(rows), N.ptr(self.lr_dev) if dev else None, N.ptr(self.state_vec) if dev else None,
+                scale, float(self.grad_scale), int(self.step_count))
+        head = (N.ptr(self.flat_param), N.ptr(self.flat_grad), N.ptr(self.exp_avg), N.ptr(self.exp_avg_sq))
+        if self.ema_flat is not None:
+            N.call('tss_adamw_step_groups_ema', *head, N.ptr(self.ema_flat), *tail, *self._ema_args(), N.stream())
+        else:
+            N.call('tss_adamw_step_groups', *head, *tail, N.stream())
 
 
 class FlatSGD(FlatOptimizer):
@@ -292,9 +349,130 @@ class FlatSGD(FlatOptimizer):
 
     def _launch(self, rows, scale):
         dev = self.device_state
-        N.call('tss_sgd_step_groups', N.ptr(self.flat_param), N.ptr(self.flat_grad), N.ptr(self.momentum_buffer),
-               self.flat_param.numel(), rows, len(rows), N.ptr(self.lr_dev) if dev else None, N.ptr(self.state_vec) if dev else None,
-               scale, float(self.grad_scale), int(self.step_count), N.stream())
+        tail = (self.flat_param.numel(), rows, len(rows), N.ptr(self.lr_dev) if dev else None, N.ptr(self.state_vec) if dev else None,
+                scale, float(self.grad_scale), int(self.step_count))
+        head = (N.ptr(self.flat_param), N.ptr(self.flat_grad), N.ptr(self.momentum_buffer))
+        if self.ema_flat is not None:
+            N.call('tss_sgd_step_groups_ema', *head, N.ptr(self.ema_flat), *tail, *self._ema_args(), N.stream())
+        else:
+            N.call('tss_sgd_step_groups', *head, *tail, N.stream())
+
+
+# ----------------------------------------------------------------------------- weight average
+
+EMA_LERP_F32, EMA_COPY_F32, EMA_COPY_I64 = 0, 1, 2       # TSS_EMA_* of include/tss_hip.h
+
+
+class ModelEMA:
+    """Exponential moving average of a model's weights, the model that segmentation recipes evaluate, checkpoint and (as a mean
+    teacher) distill from:  e += (p - e) * (1 - d_k) after every optimizer step, d_k = decay, or with warmup=True
+    min(decay, (1 + k) / (10 + k)) for update number k = 0, 1, ...  (torch.optim.swa_utils.AveragedModel with
+    get_ema_multi_avg_fn(decay) and use_buffers=True, in float32 and without its host loop).
+
+    `.module` is the averaged model: copy.deepcopy(model), or `module`, a second instance with the same state_dict keys and shapes
+    (it is overwritten with the model's values).  It is in eval(), none of its parameters requires grad, and it keeps the compute
+    dtype of `model`.  It shares no storage with `model`.
+
+    With a FlatOptimizer the parameters of `.module` that the optimizer holds become views into ONE flat buffer laid out as the
+    optimizer's flat_param, and the optimizer's own step kernel averages them (FlatOptimizer.attach_ema): update() then launches
+    one kernel (tss_ema_rows) for the rest -- floating-point buffers (BatchNorm running statistics) are averaged, integer ones
+    (num_batches_tracked) and parameters outside the optimizer are copied.  Call update() once after every optimizer.step(), on its
+    stream (Trainer(ema=...) does).  With any other optimizer, or none, update() is that one launch over every parameter and buffer.
+
+    Data parallel: after the all-reduced step every rank holds identical parameters, so every rank computes the same average of them
+    and no communication is needed; the running statistics are per replica (or identical under SyncBatchNorm), and so are their
+    averages.
+
+    The table of the rows kernel holds device addresses: build a new ModelEMA after anything that reallocates the model's tensors
+    (model.to(...)); load_state_dict() and optimizer steps write in place and are fine."""
+
+    def __init__(self, model, optimizer=None, decay=0.999, warmup=False, module=None):
+        self.decay, self.warmup = _check_decay(decay, 'ModelEMA'), bool(warmup)
+        src = dict(model.state_dict(keep_vars=True))
+        if module is None:
+            module = copy.deepcopy(model)
+        elif module is model:
+            raise ValueError('ModelEMA: `module` must be a second instance, not the model itself')
+        dst = dict(module.state_dict(keep_vars=True))
+        if list(src) != list(dst):
+            raise ValueError('ModelEMA: the state_dict keys of `module` differ from the model\'s: %s'
+                             % sorted(set(src) ^ set(dst))[:8])
+        for k in src:
+            if src[k].shape != dst[k].shape or src[k].dtype != dst[k].dtype:
+                raise ValueError('ModelEMA: %s is %s %s in the model, %s %s in `module`'
+                                 % (k, tuple(src[k].shape), src[k].dtype, tuple(dst[k].shape), dst[k].dtype))
+        if any(not t.is_cuda for t in src.values()) or any(not t.is_cuda for t in dst.values()):
+            raise RuntimeError('ModelEMA runs on the HIP path only (no CPU fallback): move the model to the GPU first')
+        for k, t in src.items():
+            if t.dtype not in (torch.float32, torch.int64) or not t.is_contiguous() or not dst[k].is_contiguous():
+                raise ValueError('ModelEMA: %s is %s%s; the average takes contiguous float32 tensors and int64 counters'
+                                 % (k, t.dtype, '' if t.is_contiguous() else ', not contiguous'))
+        self.module, self.optimizer, self.num_updates = module, optimizer, 0
+        self.flat = isinstance(optimizer, FlatOptimizer)
+        self.ema_flat = None             # with a FlatOptimizer: the buffer its step kernel averages into
+        if hasattr(model, 'compute_dtype'):
+            from .models import set_compute_dtype
+            set_compute_dtype(module, model.compute_dtype)
+        module.eval()
+        params = dict(model.named_parameters())
+        held = set()                     # the names of the parameters the optimizer's step kernel averages
+        with torch.no_grad():
+            for k in src:
+                dst[k].copy_(src[k])
+            if self.flat:
+                names = {id(p): k for k, p in params.items()}
+                self.ema_flat = optimizer.flat_param.clone()
+                off = 0
+                for p in optimizer._params():
+                    n = p.numel()
+                    k = names.get(id(p))
+                    if k is not None:    # (a parameter of another model in the same optimizer is averaged too, into the flat buffer only)
+                        dst[k].data = self.ema_flat[off:off + n].view_as(p)
+                        held.add(k)
+                    off += n
+                optimizer.attach_ema(self.ema_flat, self.decay, self.warmup)
+        for p in module.parameters():
+            p.requires_grad_(False)
+            p.grad = None
+        rows = []
+        for k, t in src.items():
+            if k in held or t.numel() == 0:
+                continue
+            mode = EMA_COPY_I64 if t.dtype == torch.int64 else (EMA_COPY_F32 if (self.flat and k in params) else EMA_LERP_F32)
+            rows.append([t.data_ptr(), dst[k].data_ptr(), t.numel(), mode])
+        self._keep = [(src[k], dst[k]) for k in src]        # the table's addresses stay allocated as long as it is used
+        dev = next(iter(src.values())).device if src else None
+        self.table = torch.tensor(rows, dtype=torch.int64, device=dev).reshape(-1, 4) if rows else None
+
+    def update(self):
+        """One update of everything the optimizer's step kernel does not average: one launch, on the current stream."""
+        k = self.num_updates
+        state = None
+        if self.flat:
+            opt = self.optimizer
+            if opt.device_state:
+                state = N.ptr(opt.ema_state)          # the factor the step's tick wrote
+            elif opt.ema_updates != k + 1:
+                raise RuntimeError('ModelEMA.update() follows optimizer.step(), once: the optimizer has averaged %d steps, this is '
+                                   'update %d' % (opt.ema_updates, k + 1))
+        if self.table is not None:
+            N.call('tss_ema_rows', N.ptr(self.table), self.table.shape[0], float(ema_omd(k, self.decay, self.warmup)), state, N.stream())
+        self.num_updates = k + 1
+
+    @torch.no_grad()
+    def copy_to(self, model):
+        """Write the averaged parameters and buffers into `model`, in place."""
+        model.load_state_dict(self.module.state_dict(), strict=True)
+
+    def state_dict(self):
+        return {'module': {k: v.detach().clone() for k, v in self.module.state_dict().items()}, 'num_updates': self.num_updates,
+                'decay': self.decay, 'warmup': self.warmup}
+
+    def load_state_dict(self, state_dict):
+        """The averaged values and the update counter (in place: the flat views stay).  With a FlatOptimizer load the optimizer's
+        own state_dict too: it carries the counter of the step kernel's part."""
+        self.module.load_state_dict(state_dict['module'], strict=True)
+        self.num_updates = int(state_dict['num_updates'])
 
 # ----------------------------------------------------------------------------- distributed helpers
 
@@ -333,8 +511,15 @@ def allreduce_mean_(flat, world_size, group=None):
 
 class Trainer:
     def __init__(self, model, optimizer, loss_fn, device=None, use_graph=False, world_size=None,
-                 non_blocking=True, fuse_head_loss=True, graph_allreduce=None, teacher=None, distill_loss=None, distill_weight=1.0):
+                 non_blocking=True, fuse_head_loss=True, graph_allreduce=None, teacher=None, distill_loss=None, distill_weight=1.0,
+                 ema=None):
         self.model, self.optimizer, self.loss_fn = model, optimizer, loss_fn
+        # `ema`: a ModelEMA of `model` (built over `optimizer`), updated right after every optimizer step on the step's stream.
+        # teacher=ema.module makes it a mean teacher: its preparation (bf16 shadows, eval affines, 3x3 copies) is then refreshed
+        # inside every step, captured or not, because its weights move.
+        if ema is not None and ema.optimizer is not None and ema.optimizer is not optimizer:
+            raise ValueError('Trainer: `ema` was built over another optimizer than the one that steps')
+        self.ema = ema
         # Logit distillation: `distill_weight * distill_loss(low, teacher_low)` on the low-resolution logits is added to the loss.  The
         # teacher is frozen: eval() once and for all, forward under no_grad inside an EvalPrep(frozen=True) whose preparation launches
         # run once (its weights never change), on the step's stream and, with use_graph, inside the captured step.
@@ -471,7 +656,7 @@ class Trainer:
 
     def _distill_term(self, x, low):
         if self._teacher_prep is None:
-            self._teacher_prep = EvalPrep(self.teacher, frozen=True)
+            self._teacher_prep = EvalPrep(self.teacher, frozen=not (self.ema is not None and self.teacher is self.ema.module))
         with torch.no_grad(), self._teacher_prep:
             t_low = ops.materialize(self.teacher.forward_lowres(x))
         if tuple(t_low.shape) != tuple(low.shape):
@@ -492,6 +677,8 @@ class Trainer:
                         dist.all_reduce(p.grad)
                         p.grad.div_(self.world_size)
         self.optimizer.step()
+        if self.ema is not None:
+            self.ema.update()
 
     def new_slots(self, n):
         """`n` fresh input-slot numbers (for a loader that captures one step per staging buffer).  Slot numbers are never
@@ -799,18 +986,21 @@ class HostBatchPipeline:
 
 def create_segmentation_trainer(model, optimizer, loss_fn, device, use_f16=False, logging=True,
                                 non_blocking=True, use_graph=False, world_size=None, fuse_head_loss=True,
-                                teacher=None, distill_loss=None, distill_weight=1.0):
-    """Same arguments as TSS/engine.py:22; `teacher`, `distill_loss` and `distill_weight` add a logit-distillation term (Trainer).  `use_f16` selects bf16 activations (f32 master parameters), the
+                                teacher=None, distill_loss=None, distill_weight=1.0, ema=None):
+    """Same arguments as TSS/engine.py:22; `teacher`, `distill_loss` and `distill_weight` add a logit-distillation term (Trainer), `ema` a
+    ModelEMA updated after every step (teacher=ema.module: a mean teacher).  `use_f16` selects bf16 activations (f32 master parameters), the
     MI355X counterpart of the reference's apex amp O2 branch (TSS/engine.py:32-34); no loss scaling is needed."""
     from .models import set_compute_dtype
     set_compute_dtype(model, torch.bfloat16 if use_f16 else torch.float32)
     if teacher is not None:         # the distillation kernels read student and teacher logits of one dtype
         set_compute_dtype(teacher, torch.bfloat16 if use_f16 else torch.float32)
+    if ema is not None:             # the averaged model computes as the model it averages
+        set_compute_dtype(ema.module, torch.bfloat16 if use_f16 else torch.float32)
     if world_size is None:
         world_size = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     return Trainer(model, optimizer, loss_fn, device=device, use_graph=use_graph, world_size=world_size,
                    non_blocking=non_blocking, fuse_head_loss=fuse_head_loss, teacher=teacher, distill_loss=distill_loss,
-                   distill_weight=distill_weight)
+                   distill_weight=distill_weight, ema=ema)
 
 
 # ----------------------------------------------------------------------------- evaluator
