@@ -64,6 +64,7 @@ enum {
   TSS_K_RESIZE_FLIP_PLANAR, TSS_K_MULTISCALE_ARGMAX,
   TSS_K_SGD, TSS_K_GRAD_NORM,
   TSS_K_WIDE_CE_FWD, TSS_K_WIDE_CE_BWD, TSS_K_WIDE_ARGMAX, TSS_K_WIDE_MULTISCALE_ARGMAX,
+  TSS_K_PSEUDO_LABEL, TSS_K_WIDE_PSEUDO_LABEL,
   TSS_K_COUNT
 };
 
@@ -992,6 +993,46 @@ int tss_upsample_dice_fwd(const void* low, long ldl, const long long* target, fl
                           int H, int W, int ignore_index, int has_ignore, float smooth, int dtype, void* stream);
 int tss_upsample_dice_grad(const void* low, long ldl, const long long* target, const float* dice_ws, float* ws, int B, int C, int h,
                            int w, int H, int W, int ignore_index, int has_ignore, int dtype, void* stream);
+
+/* ---- mean-teacher self-training: pseudo-labels from the fused head (csrc/pseudo.hip), ClassMix / CutMix (csrc/mix.hip) ------
+ * tss_upsample_pseudo_label (1 <= C <= 24, class scores in registers) and tss_upsample_pseudo_label_wide (1 <= C <= 255, chunks of
+ * 16 classes): for every output pixel, z = the align_corners=True bilinear upsample of the low-res NHWC logits [B][h][w][ldl] (the
+ * band walk, taps and blend of tss_upsample_argmax_confusion[_wide]; ldl % 8 == 0, ldl >= round_up(C, 4), pad channels never reach a
+ * result), arg = its arg-max (lowest index wins ties), conf = 1 / sum_c exp(z_c - z_arg) (f32, classes summed in index order: the
+ * softmax probability of arg),
+ *   label[b][y][x] = conf >= *threshold ? arg : ignore_index      (uint8)
+ *   conf[b][y][x]  = conf for EVERY pixel (f32; may be NULL)
+ *   kept[b]       += number of pixels of sample b with conf >= *threshold (u64, ACCUMULATED; may be NULL): lane counts, one LDS
+ *                    word per block, one 64-bit integer atomic per block -- exact, the same bits on every run.
+ * threshold: DEVICE memory, one float, read by the kernel (one captured graph follows a threshold schedule; 0 keeps every pixel and
+ * label is then the pred of tss_upsample_argmax_confusion[_wide] bit for bit, a value above 1 keeps none).  The full-resolution
+ * logits never exist (replaces F.interpolate -> softmax -> max -> where).  No float atomics, no host read-back: capturable.
+ * Contract (else TSS_ERR_SHAPE, nothing launched): the head's shape rules (H >= h, W >= w) with the class caps above, and
+ * C <= ignore_index <= 255 -- the label is a byte and must not collide with a class, so C = 256 is refused; threshold and label
+ * not NULL.  low off 16 bytes: TSS_ERR_ALIGN.  B*H*W == 0: TSS_OK without a launch. */
+int tss_upsample_pseudo_label(const void* low, long ldl, const float* threshold, unsigned char* label, float* conf,
+                              unsigned long long* kept, int B, int C, int h, int w, int H, int W, int ignore_index, int dtype,
+                              void* stream);
+int tss_upsample_pseudo_label_wide(const void* low, long ldl, const float* threshold, unsigned char* label, float* conf,
+                                   unsigned long long* kept, int B, int C, int h, int w, int H, int W, int ignore_index, int dtype,
+                                   void* stream);
+/* ClassMix's class pick.  label: uint8 [B][HW]; keys: DEVICE u32 [B][256], drawn by the host and shipped with the batch like the
+ * augmentation rows.  Per sample: the classes < C that occur in the map (bytes >= C, the ignore byte included, never count), ranked
+ * by (key, class index) with an unsigned compare; sel[b][c] = 1 for the ceil(n / 2) present classes of smallest rank, 0 for every
+ * other of the 256 entries (n = 0: an all-zero row).  Integer arithmetic only, exact; the row is the call's own workspace on the way
+ * (two launches, no zero-fill, no atomics on memory).  1 <= C <= 256, B <= 65535, sel and keys 4-byte aligned (TSS_ERR_ALIGN). */
+int tss_classmix_select(const unsigned char* label, const unsigned int* keys, unsigned char* sel, long B, long HW, int C, void* stream);
+/* The mixing select, one launch.  image [B][Ci][H][W] (TSS_F32 | TSS_BF16), label uint8 [B][H][W], partner DEVICE int32 [B].
+ * Exactly one of sel (DEVICE uint8 [B][256]: mask = sel[b][label[b][y][x]], ClassMix) and boxes (DEVICE int32 [B][4] = y0, x0, y1,
+ * x1: mask = y0 <= y < y1 && x0 <= x < x1, CutMix) is given, else TSS_ERR_SHAPE.
+ *   image_out[b]  = mask ? image[b] : image[partner[b]]
+ *   target_out[b] = (int64)(mask ? label[b] : label[partner[b]])          (255 stays 255)
+ * A select on bits, not a blend: a NaN or -0.0 in the source that is not chosen never reaches the output, the chosen value arrives
+ * bit for bit.  partner and boxes rows are clamped into range (0..B-1; 0..H, 0..W) and NOT validated, as the augmentation rows.
+ * W % 8 == 0 (16-byte vectors per lane), B <= 65535; outputs must not alias inputs; image, image_out, target_out 16-byte and label
+ * 8-byte aligned (TSS_ERR_ALIGN).  DACS (a labelled sample pasted onto an unlabelled one) is the same call on a concatenated batch. */
+int tss_mix_batch(const void* image, const unsigned char* label, const int* partner, const unsigned char* sel, const int* boxes,
+                  void* image_out, long long* target_out, long B, int Ci, int H, int W, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

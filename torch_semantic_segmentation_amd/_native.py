@@ -107,7 +107,7 @@ def dtype_code(dtype):
 
 # ----------------------------------------------------------------------------- profiler helpers
 
-K_COUNT = 41
+K_COUNT = 43
 
 
 def prof_enable(on=True):

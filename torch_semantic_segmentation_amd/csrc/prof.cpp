@@ -38,6 +38,7 @@ const KernelInfo kInfo[TSS_K_COUNT] = {
     {"upsample_ce_wide_fwd", "wide_ce_kernel"}, {"upsample_ce_wide_bwd", "wide_ce_gather_kernel"},
     {"argmax_confusion_wide", "wide_upsample_argmax_kernel|wide_planar_argmax_kernel"},
     {"multiscale_argmax_confusion_wide", "wide_multiscale_argmax_kernel"},
+    {"upsample_pseudo_label", "pseudo_label_kernel"}, {"upsample_pseudo_label_wide", "wide_pseudo_label_kernel"},
 };
 
 struct Rec { int kid; hipEvent_t a, b; double bytes, flops; };
