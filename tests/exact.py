@@ -2376,3 +2376,764 @@ def cast_sources(N, K, rng):
     b[sl[5]] = b[sl[5]] & np.uint32(0x80000000)                                              # +-0
     b[sl[6]] = (b[sl[6]] & np.uint32(0xFF800000)) | np.uint32(0x007FC000)                    # carries into the exponent
     return torch.from_numpy(b.view(F32).reshape(N, K).copy())
+
+
+# ---------------------------------------------------------------------------------------------------------- soft losses and distillation
+# csrc/distill.hip (pixel- and channel-wise KL), then csrc/softloss.hip (planar focal and soft Dice), tss_focal_coef_from_ce and the
+# focal and Dice passes of the fused head (csrc/softhead.hip); tests/test_gpu_softloss_exact.py, the f32 emulations in
+# tests/softloss_emu.py and tests/head_emu.py and their CPU proofs in tests/test_exact_bounds.py.  The distillation part, first, is numpy float64
+# on operands [B][HW][C] that are f32 (and bf16) numbers.
+# u = 2^-24.  The hardware V_EXP_F32 is taken at 1 ulp (<= 2 u relative), the figure head_lse_err takes: the vendor's, not measured
+# here; logf is the library's (also taken at 1 ulp).  A result below the smallest normal f32 may be flushed: the floors of 2^-126.
+DISTILL_NT = 256                 # lsw::NT
+DISTILL_PIXEL_BLOCKS = 4096      # default block caps of csrc/distill.hip
+DISTILL_CHANNEL_BLOCKS = 512
+DISTILL_TAUS = (1.0, 4.0, 0.5, 3.0)       # 1 / tau is exact for the powers of two; fl(1 / 3) carries one rounding, which the reference
+DISTILL_FLOOR = 2.0 ** -126               # reads as the entry forms it (inv_tau below), so no case pays for it in the bound
+
+
+def distill_pixel_grid(P, max_blocks=0):
+    """pixel_grid: tss::grid_for(P, NT, cap); the workspace is 2 doubles per block"""
+    return max(1, min(cdiv(P, DISTILL_NT), max_blocks if max_blocks > 0 else DISTILL_PIXEL_BLOCKS))
+
+
+def distill_channel_split(B, C, HW, max_blocks=0):
+    """channel_split and Strip of csrc/distill.hip: vectors per row, positions per block and trip, segments per image S (as many as
+    the cap allows while it allows one item per image), positions per segment, items, grid, floats of the workspace (5 rows of
+    round_up(C, 8) per item: two of maxima, three of sums)"""
+    cap = max_blocks if max_blocks > 0 else DISTILL_CHANNEL_BLOCKS
+    nch = cdiv(C, 8)
+    ppb = DISTILL_NT // nch
+    S = min(cdiv(HW, ppb), max(cap // B, 1))
+    return dict(nch=nch, ppb=ppb, S=S, len=cdiv(HW, S), items=B * S, grid=min(B * S, cap), ws_floats=5 * 8 * nch * B * S)
+
+
+def distill_segments(HW, S):
+    """[(i0, i1)] of the S segments of a plane; an EMPTY one has i0 >= i1 (its partial rows are the identities -inf and 0)"""
+    n = cdiv(HW, S)
+    return [(q * n, min(q * n + n, HW)) for q in range(S)]
+
+
+def distill_depth(kind, B, C, HW, max_blocks=0):
+    """additions a term of Z_S, Z_T or A goes through.  pixel: the lane's C.  channel: the lane's trips over its segment, the levels
+    of slot_reduce's tree over the ppb position slots, the S partial rows of the finalize"""
+    if kind == 'pixel':
+        return C
+    sp = distill_channel_split(B, C, HW, max_blocks)
+    return cdiv(sp['len'], sp['ppb']) + max(sp['ppb'] - 1, 0).bit_length() + sp['S']
+
+
+class DistillRef:
+    """f64 reference of csrc/distill.hip on s, t [B][HW][C] (f64 arrays of f32 numbers), from the f32 scalars the entry forms:
+    inv_tau = fl(1 / tau), norm = fl(tau / #units), grad_out as an f32.  x = logit * inv_tau in f64 (exact: 24 x 24 bits); a unit is
+    a pixel (axis C) or a plane (axis HW):
+      ms, mt        fl(max * inv_tau): what stats[.].x / .z must hold bit for bit (the product is exact in f64, then ONE f32 rounding)
+      Ds, Dt        x - m (m the f32 number), <= 0 up to m's rounding
+      lzs, lzt      log sum exp(D): what stats[.].y / .w approximate
+      q, p          softmax values, exp(D - lz)
+      kl, loss      sum p (log p - log q) per unit;  (double)tau^2 / #units * sum kl
+      g             norm * grad_out * (q - p)
+    and the terms of the bounds: dbs, dbt = sum q |Ds|, sum p |Dt| (what the exponent's roundings weigh on the sum), r = |sum p d|,
+    ra = sum p |d| (3 |Dt| + 4 + depth), d = (t - s) inv_tau"""
+    def __init__(self, s, t, tau, kind, grad_out=1.0, max_blocks=0):
+        B, HW, C = s.shape
+        self.kind, self.shape, self.tau = kind, (B, C, HW), float(F32(tau))
+        ax = 2 if kind == 'pixel' else 1
+        self.ax, self.units = ax, (B * HW if kind == 'pixel' else B * C)
+        self.inv = float(F32(1.0) / F32(tau))
+        self.norm = float(F32(float(F32(tau)) / self.units))
+        self.go = float(F32(grad_out))
+        self.depth = distill_depth(kind, B, C, HW, max_blocks)
+        xs, xt = s * self.inv, t * self.inv
+        self.ms = (s.max(ax, keepdims=True) * self.inv).astype(F32).astype(np.float64)
+        self.mt = (t.max(ax, keepdims=True) * self.inv).astype(F32).astype(np.float64)
+        self.Ds, self.Dt = xs - self.ms, xt - self.mt
+        es, et = np.exp(self.Ds), np.exp(self.Dt)
+        zs, zt = es.sum(ax, keepdims=True), et.sum(ax, keepdims=True)
+        self.lzs, self.lzt = np.log(zs), np.log(zt)
+        self.lq, self.lp = self.Ds - self.lzs, self.Dt - self.lzt
+        self.q, self.p = np.exp(self.lq), np.exp(self.lp)
+        self.kl = (self.p * (self.lp - self.lq)).sum(ax, keepdims=True)
+        self.loss = self.tau * self.tau / self.units * float(self.kl.sum())
+        self.g = self.norm * self.go * (self.q - self.p)
+        self.dbs, self.dbt = (self.q * np.abs(self.Ds)).sum(ax, keepdims=True), (self.p * np.abs(self.Dt)).sum(ax, keepdims=True)
+        d = (t - s) * self.inv
+        self.r = np.abs((self.p * d).sum(ax, keepdims=True))
+        self.ra = (self.p * np.abs(d) * (3 * np.abs(self.Dt) + 4 + self.depth)).sum(ax, keepdims=True)
+
+
+def _first_order(k):
+    """u k / (1 - u k): a relative error of k roundings, and of exp of an exponent off by u k"""
+    return U32 * k / (1 - U32 * k)
+
+
+def distill_logz_counts(ref):
+    """(L_S, L_T) per unit, units of u, of |stats.y - lzs| and |stats.w - lzt|, counted from the second sweep of
+    distill_pixel_fwd_kernel / distill_channel_sum_kernel and the finalize.  A term e_i = __expf(fmaf(x_i, inv_tau, -m)), which the
+    compiler makes V_EXP_F32(fl(fl(x_i inv_tau - m) LOG2E)): the fma's rounding (|D_i|), the constant LOG2E's own (|D_i|), the product
+    (|D_i|), V_EXP_F32 (2): relative 3 |D_i| + 2.  Weighted by e_i / Z that is 3 sum q_i |D_i| + 2 on Z.  The sum adds positive
+    terms: `depth` (distill_depth).  logf: 2 |log Z|.  + 1 for the terms below the smallest normal that V_EXP_F32 may flush (the
+    largest term is >= 1 - u |m|, N 2^-126 is far below one u of Z) and the second order of the lot"""
+    return (3 * ref.dbs + 2 + ref.depth + 2 * np.abs(ref.lzs) + 1, 3 * ref.dbt + 2 + ref.depth + 2 * np.abs(ref.lzt) + 1)
+
+
+def distill_logz_bound(ref):
+    Ls, Lt = distill_logz_counts(ref)
+    return _first_order(Ls), _first_order(Lt)
+
+
+def distill_grad_bound(ref, bf16):
+    """|d - g| <= norm go [u' (kq + 3) q + u' (kp + 3) p] + floor, per ELEMENT, u' k = u k / (1 - u k); the form u k(x) norm go
+    (q + p) with k taken per softmax.  Counted from distill_bwd_kernel, q = __expf(fmaf(s, inv_tau, -m_S) - log Z_S):
+      |D|          the fma's rounding, of x - m
+      L_S          the stored log Z_S (distill_logz_counts)
+      |log q|      the subtraction's rounding
+      2 |log q|    the product with LOG2E and that constant's rounding
+      2            V_EXP_F32
+    kq = |D| + 3 |log q| + L_S + 2, likewise kp.  Then q - p (one rounding of |q - p| <= q + p) and the products with norm and with
+    grad_out (two more, each of a value <= q + p): 3 u (q + p), written below as + 3 in kq AND in kp -- u (kq + 3) q + u (kp + 3) p
+    = u kq q + u kp p + 3 u (q + p), each of the three roundings counted once.  The bound is relative to q + p, not to |q - p|: the exponent's error is absolute in nats, so each softmax value
+    carries an error relative to ITSELF, which does not cancel in the difference.  Floor: each exponential and the stored element may
+    be flushed below the smallest normal, 2^-126 (2 norm go + 1).  A bf16 gradient adds 2^-8 (|g| + bound)"""
+    Ls, Lt = distill_logz_counts(ref)
+    kq = np.abs(ref.Ds) + 3 * np.abs(ref.lq) + Ls + 2 + 3
+    kp = np.abs(ref.Dt) + 3 * np.abs(ref.lp) + Lt + 2 + 3
+    bound = ref.norm * ref.go * (_first_order(kq) * ref.q + _first_order(kp) * ref.p) + DISTILL_FLOOR * (2 * ref.norm * ref.go + 1)
+    return bound + (2.0 ** -8 * (np.abs(ref.g) + bound) if bf16 else 0.0)
+
+
+def distill_kl_bound(ref):
+    """per unit, |KL_f32 - kl| of KL = a / zt + (ms - mt) + logf(zs / zt), counted from the forward kernels:
+      A = sum e_i d_i    d_i = fl(fl(t - s) inv_tau) (2), e_i (3 |D_i| + 2), the fma sum (depth): ra = sum p |d| (3 |Dt| + 4 + depth);
+      a / zt             zt's own 3 dbt + 2 + depth and the division (1), on r = |A / Z_T|
+      ms - mt            one rounding
+      logf(zs / zt)      both sums (3 dbs + 3 dbt + 4 + 2 depth), the division (1), logf (2 |log(Z_S / Z_T)|)
+      the two additions  on |a / zt| + |ms - mt| and on that + |log|
+    The kernel header's own count k = 16 (on M = max|x| + ln N) takes every sum as ONE rounding whatever its length; that is an
+    expectation, not a bound -- a worst case pays `depth` per sum, as here"""
+    lr = np.abs(ref.lzs - ref.lzt)
+    dm = np.abs(ref.ms - ref.mt)
+    k = (ref.ra + ref.r * (3 * ref.dbt + ref.depth + 3) + dm + 3 * ref.dbs + 3 * ref.dbt + 2 * ref.depth + 5 + 2 * lr
+         + (ref.r + dm) + (ref.r + dm + lr))
+    return U32 * k * 1.001
+
+
+def distill_loss_bound(ref):
+    """the units' bounds through the f64 partial sums (2^-45 of the terms' magnitudes covers any order) and ONE f32 rounding of
+    (double)tau^2 / #units * sum"""
+    mag = float((ref.r + np.abs(ref.ms - ref.mt) + np.abs(ref.lzs - ref.lzt)).sum())
+    return ref.tau * ref.tau / ref.units * (float(distill_kl_bound(ref).sum()) + 2.0 ** -45 * mag) + U32 * abs(ref.loss) * 1.001
+
+
+def worst_ratio(err, bound):
+    """max err / bound; inf where the bound is 0 and the error is not, and where the error is NaN"""
+    err, bound = np.broadcast_arrays(np.asarray(err, np.float64), np.asarray(bound, np.float64))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        r = np.where(bound > 0, err / bound, np.where(err == 0, 0.0, np.inf))
+    return float(np.where(np.isnan(err), np.inf, r).max())
+
+
+def distill_ratios(ref, loss, stats, d, bf16):
+    """a result (loss, stats [units][4], d [B][HW][C]) against the reference: dict(max: the stored maxima hold the reference's bits,
+    logz, loss, grad: the largest |out - ref| / bound)"""
+    B, C, HW = ref.shape
+    st = np.asarray(stats, np.float64).reshape((B, HW, 1, 4) if ref.kind == 'pixel' else (B, 1, C, 4))
+    bs, bt = distill_logz_bound(ref)
+    return dict(max=bool((st[..., 0] == ref.ms).all() and (st[..., 2] == ref.mt).all()),
+                logz=max(worst_ratio(np.abs(st[..., 1] - ref.lzs), bs), worst_ratio(np.abs(st[..., 3] - ref.lzt), bt)),
+                loss=worst_ratio(abs(float(loss) - ref.loss), distill_loss_bound(ref)),
+                grad=worst_ratio(np.abs(np.asarray(d, np.float64) - ref.g), distill_grad_bound(ref, bf16)))
+
+
+def distill_operands(B, C, HW, seed, hot=False):
+    """(s, t) [B][HW][C]: head_logits (multiples of 2^-2 in [-8, 8], exact in bf16); hot (needs HW >= 8, C >= 8): logits of
+    magnitude 200 (bf16 numbers) on a 3 x 3 block of (position, class) whose rows and columns hold one, two and three of them in
+    the student -- so a pixel and a plane have m = 200 / tau with log Z = 0, ln 2 and ln 3, where m + log Z in ONE float rounds at
+    the size of m -- some matched in the teacher, some opposed, and a -200 in each"""
+    g = case_gen(4711, B, C, HW, seed)
+    s, t = head_logits((B, HW, C), g).numpy(), head_logits((B, HW, C), g).numpy()
+    if hot:
+        i, c = HW // 2, C // 2
+        for di, dc in ((0, 0), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2)):
+            s[B - 1, i + di, c + dc] = 200.0
+        for di, dc in ((0, 0), (1, 1), (2, 1), (2, 2), (0, 2)):
+            t[B - 1, i + di, c + dc] = 200.0
+        s[B - 1, i + 3, c], t[B - 1, i, c + 1], t[B - 1, i + 2, c] = -200.0, -200.0, -200.0
+    return s, t
+
+
+DISTILL_PIXEL_C = (1, 7, 8, 9, 19, 25, 256)
+DISTILL_PIXEL_P = ((1, 0), (257, 0), (600, 1))            # (B HW, max_blocks)
+DISTILL_CHANNEL_C = (8, 9, 19, 256)                       # 1, 2, 3 and 32 vectors per row; 19: 85 slots, one thread of the block idle
+
+
+def distill_pixel_cases(C):
+    """[(name, B, HW, max_blocks, tau, hot)]: 257 pixels as one image, 600 as 3 x 200 under one block; tau cycles through DISTILL_TAUS"""
+    out = []
+    for i, (P, cap) in enumerate(DISTILL_PIXEL_P):
+        B = 3 if P % 3 == 0 else 1
+        out.append(('pixel_c%d_p%d' % (C, P), B, P // B, cap, DISTILL_TAUS[(i + C) % 4], False))
+    if C == 19:
+        out.append(('pixel_c19_p257_hot', 1, 257, 0, 0.5, True))
+    return out
+
+
+def distill_channel_cases(C):
+    """[(name, B, HW, max_blocks, tau, hot)]: HW in {1, ppb - 1, ppb + 1, 3 ppb + 2}, B in {1, 3}, max_blocks in {0, 1, 2, B}"""
+    ppb = DISTILL_NT // cdiv(C, 8)
+    out, i = [], 0
+    for HW in (1, ppb - 1, ppb + 1, 3 * ppb + 2):
+        for B in (1, 3):
+            for cap in sorted({0, 1, 2, B}):
+                out.append(('channel_c%d_hw%d_b%d_cap%d' % (C, HW, B, cap), B, HW, cap, DISTILL_TAUS[i % 4], False))
+                i += 1
+    if C == 19:
+        out.append(('channel_c19_hw%d_b3_cap0_hot' % (3 * ppb + 2), 3, 3 * ppb + 2, 0, 0.5, True))
+    if C == 256:      # S = 10 segments of 9 positions: the tenth is EMPTY (the smallest such shape; none of the shapes above has one)
+        out.append(('channel_c256_hw81_b1_cap10_empty', 1, 81, 10, 4.0, False))
+    return out
+
+
+# --- planar focal and soft Dice (csrc/softloss.hip on the class-plane sweep of csrc/losssweep.h): logits x [B][C][HW], labels [B][HW]
+SOFT_NT = 256                    # lsw::NT: lanes of a block, one group of 8 pixels per lane and trip
+SOFT_FOCAL_BLOCKS = 4096         # default grid caps
+SOFT_DICE_BLOCKS = 768
+SOFT_DICE_CP = 24                # DICE_CP: classes per sweep of dice_fwd_kernel
+SOFT_GAMMAS = (0.0, 0.5, 2.0)
+#               B, C, HW
+SOFT_PLANAR = [(1, 1, 8),         # one class: q == 0 at every pixel
+               (2, 2, 8),
+               (1, 19, 2056),     # 257 groups: the second block has one lane
+               (3, 19, 1000),     # 375 groups, not a multiple of the block
+               (1, 24, 64), (1, 25, 64), (1, 48, 64), (1, 49, 64),      # one, two, two and three Dice sweeps of DICE_CP classes
+               (1, 256, 16)]      # label 255 is a class: ignored with has_ignore, counted without
+SOFT_BEHIND = (1, 2, 64)          # added: every pixel valid with its target 6 BELOW the other class (p = 2.5e-3): the second term of
+                                  # coef is 0.7 % of the first at gamma = 0.5, under the whole-tensor criterion of a bf16 gradient
+
+
+def soft_grid(B, HW, max_blocks, default_cap):
+    """(grid, trips of a lane) of a class-plane sweep over the B HW / 8 groups"""
+    groups = B * (HW // 8)
+    grid = max(1, min(cdiv(groups, SOFT_NT), max_blocks if max_blocks > 0 else default_cap))
+    return grid, cdiv(groups, grid * SOFT_NT)
+
+
+def soft_planar_operands(B, C, HW, behind=False):
+    """(x [B][C][HW] head_logits, labels [B][HW] head_labels, {name: (class or pixel)}).  With C >= 19, planted in image 0:
+    pixels 0..3 whose target (classes C-2 .. C-5, never 255) holds the maximum by 0 (a tie with the next class), by 2^-2 and by 16, and lies 16
+    below it; class 1 ABSENT from the labels and class 2 present at pixel 5 only.  C == 2: the lead-by-16 and the 16-below pixel.
+    behind: every pixel valid, its target at -3 and every other class at 3"""
+    g = case_gen(4712, B, C, HW)
+    x = head_logits((B, C, HW), g).numpy()
+    lab = head_labels(B, 1, HW, C, g).reshape(B, HW).numpy().copy()
+    plants = {}
+    if behind:
+        lab = torch.randint(0, C, (B, HW), generator=g).numpy()
+        x[:] = 3.0
+        np.put_along_axis(x, lab[:, None, :], -3.0, 1)
+        return x, lab, plants
+    if C >= 19:
+        lab[lab == 1] = 3
+        lab[lab == 2] = 4
+        lab[0, 5] = 2
+        plants.update(absent=1, single=2)
+    if C >= 2:
+        gaps = ((0.0, 0), (0.25, 1), (16.0, 2), (-16.0, 3)) if C >= 19 else ((16.0, 2), (-16.0, 3))
+        for gap, i in gaps:
+            t = (C - 2 - i) % C
+            o = (t + 1) % C
+            lab[0, i] = t
+            if gap == 16.0:
+                x[0, :, i], x[0, t, i] = -8.0, 8.0
+            elif gap == -16.0:
+                x[0, t, i], x[0, o, i] = -8.0, 8.0
+            else:
+                x[0, :, i] = np.minimum(x[0, :, i], 4.0 - max(gap, 0.25))
+                x[0, t, i], x[0, o, i] = 4.0, 4.0 - gap
+            plants['gap%g' % gap] = i
+    return x, lab, plants
+
+
+def focal_terms(p, q, lp, gamma, variant):
+    """f64 terms of the focal loss as the kernels define them, per pixel: p the target's probability, q the SUM of the other
+    classes', lp = log p.  w = exp(q^gamma) (variant 0, the reference's) or q^gamma (variant 1, Lin et al.); w' = dw/dp =
+    -gamma q^(gamma - 1) w (variant 1: -gamma q^(gamma - 1)); the second term p w' lp is 0 at q == 0 or gamma == 0.
+    Returns (w, w', coef = -(p w' lp + w), the loss term w lp)"""
+    q = np.asarray(q, np.float64)
+    pos = q > 0
+    qs = np.where(pos, q, 1.0)
+    if gamma == 0:
+        qg, dqg = np.ones_like(q), np.zeros_like(q)
+    else:
+        qg, dqg = np.where(pos, qs ** gamma, 0.0), np.where(pos, gamma * qs ** (gamma - 1), 0.0)
+    w = np.exp(qg) if variant == 0 else qg
+    wp = -dqg * w if variant == 0 else -dqg
+    return w, wp, -(p * wp * lp + w), w * lp
+
+
+class PlanarRef:
+    """f64 softmax state of planar logits x [B][C][HW] with labels [B][HW]: valid (the one validity rule), t (clamped), onehot,
+    m = max_c, D = x - m, s = sum exp D, lse, lp = log softmax, p = softmax, dbar = sum_c p_c |D_c|; per pixel for the focal
+    kernel, which keeps the target out of its running sum: so = sum_{c != t} exp D_c (all classes where not valid), et = exp D_t, pt, q = so / s, lpt,
+    dbo = sum_{c != t} exp(D_c) |D_c| / so, lead = the target holds the maximum (et == 1.f: the log1pf branch)"""
+    def __init__(self, x, labels, ignore_index=255, has_ignore=True):
+        B, C, HW = x.shape
+        self.x, self.labels, self.shape = x, labels, (B, C, HW)
+        self.valid = (labels >= 0) & (labels < C) & ((labels != ignore_index) | (not has_ignore))
+        self.t = np.clip(labels, 0, C - 1)
+        self.onehot = (np.arange(C)[None, :, None] == self.t[:, None, :]) & self.valid[:, None, :]
+        self.m = x.max(1)
+        self.D = x - self.m[:, None]
+        E = np.exp(self.D)
+        self.s = E.sum(1)
+        self.lse = self.m + np.log(self.s)
+        self.lp = self.D - np.log(self.s)[:, None]
+        self.p = np.exp(self.lp)
+        self.dbar = (self.p * np.abs(self.D)).sum(1)
+        self.et = (E * self.onehot).sum(1)
+        self.so = (E * ~self.onehot).sum(1)
+        self.Dt = (self.D * self.onehot).sum(1)
+        self.dbo = (E * ~self.onehot * np.abs(self.D)).sum(1) / np.where(self.so > 0, self.so, 1.0)
+        self.pt, self.q = self.et / self.s, self.so / self.s
+        self.lead = self.valid & (self.Dt == 0)
+        self.lg = np.where(self.lead, np.log1p(self.so), np.log(self.s))
+        self.lpt = np.where(self.valid, self.Dt - self.lg, 0.0)
+        self.nvalid = int(self.valid.sum())
+        # premises of the counts: the logits are spaced wider than 2^-24 (et == 1.f iff the target holds the maximum) and no q
+        # is so small that f32 loses it (q == 0 only with a single class)
+        assert (self.q[self.valid] > 2.0 ** -100).all() or C == 1
+
+
+def soft_lse_count(ref):
+    """roundings (units of u, nats) of lsw::lse8's stored l = m + __logf(s), the online log-sum-exp.  Per class one rescale and one
+    new term, s = s __expf(m - mn) + __expf(v - mn): the rescale's V_EXP_F32 (2), the product (1), the addition (1) -- 4 for every
+    later class a term lives through, <= 4 (C - 1) -- and V_EXP_F32 on the term itself (2).  The exponents: every subtraction
+    (v - mn, m - mn), the product with LOG2E and that constant's own rounding are relative to a step of the running maximum, and the
+    steps a term sees add up to |D_c| = m - x_c: 3 |D_c|, weighted by p_c on the sum: 3 dbar.  __logf(s) = fl(V_LOG_F32(s) LN2):
+    V_LOG_F32 (2), the constant and the product: 4 |log s|.  m + log s and the store: |lse|.  + 1 for the second order"""
+    C = ref.shape[1]
+    return 3 * ref.dbar + 4 * C + 4 * np.abs(np.log(ref.s)) + np.abs(ref.lse) + 1
+
+
+def soft_p_count(ref, lse_count):
+    """relative error (units of u) of a softmax value recomputed as __expf(x - l) from the stored l (grad8, the Dice sweeps): l's own
+    error, the subtraction's rounding (|log p|), the product with LOG2E and that constant (2 |log p|), V_EXP_F32 (2).  The
+    exponent's error is ABSOLUTE in nats -- u (|x| + 2 |lse|) at the least -- so p_c carries an error relative to ITSELF and the
+    gradient's bound is relative to p_c + [c == t], not to |p_c - [c == t]|: near p_t = 1 the difference is far smaller than
+    either term's error"""
+    return lse_count[:, None] + 3 * np.abs(ref.lp) + 2
+
+
+def focal_planar_counts(ref, gamma, variant):
+    """per valid pixel, from focal_fwd_kernel (units of u): dict of
+      lse     absolute, of the stored l = m + lg
+      coef    absolute, of pixel_coef = -(p w' lp + w)
+      term    absolute, of the loss term w lp
+    and the f64 terms (w, wp, coef, wlp).  The chain, rounding by rounding:
+      so      the running sum WITHOUT the target: Kso = 3 dbo + 4 C (soft_lse_count's sum)
+      et      __expf(xt - m): Ket = 3 |Dt| + 2
+      s       so + et: Ks = q Kso + p Ket + 1
+      lg      the target holds the maximum (et == 1.f): log1pf(so), q Kso + 2 lg -- RELATIVE to lg ~ q when q is small, which
+              __logf(1 + so) is not; otherwise __logf(s): Ks + 4 |lg|
+      lp      (xt - m) - lg: at a leading target 0 - lg, exact; otherwise |Dt| + |lp| for the two subtractions
+      p, q    et inv, so inv with inv = 1 / s (correctly rounded): Kp = Ket + Ks + 2, Kq = Kso + Ks + 2
+      q^gamma exp2f(gamma __log2f(q)): V_LOG_F32 (2 |log2 q|) and q's own error through the logarithm (Kq / ln 2), both times gamma;
+              the product (|gamma log2 q|); exp2f (2): in nats Kqg = gamma Kq + 3 |gamma ln q| + 2 -- the first term is the
+              conditioning of q^gamma in the relative error of q
+      gamma q^(gamma-1)   gamma qg / q: Kdqg = Kqg + Kq + 2 (>= the conditioning |gamma - 1| Kq)
+      w       variant 0: __expf(qg), qg (Kqg + 2) + 2;  variant 1: Kqg
+      w'      variant 0: dqg w, Kdqg + Kw + 1;  variant 1: Kdqg
+      coef    T1 = p w' lp >= 0 and w >= 0 add without cancellation: T1 (Kp + Kwp + 2) + p |w'| E(lp) + w Kw + (T1 + w)
+      w lp    |w lp| (Kw + 1) + w E(lp)
+    V_EXP_F32 / V_LOG_F32 at 1 ulp: the vendor's figure, not measured here; exp2f, log1pf and the division at 1 ulp or better"""
+    C = ref.shape[1]
+    v = ref.valid
+    Kso = np.where(ref.so > 0, 3 * ref.dbo + 4 * C, 0.0)
+    Ket = 3 * np.abs(ref.Dt) + 2
+    Ks = np.where(v, ref.q * Kso + ref.pt * Ket + 1, Kso)
+    lg = np.abs(ref.lg)
+    Elg = np.where(ref.lead, ref.q * Kso + 2 * lg, Ks + 4 * lg)
+    Elp = np.where(ref.lead, Elg, np.abs(ref.Dt) + Elg + np.abs(ref.lpt))
+    Kp, Kq = Ket + Ks + 2, Kso + Ks + 2
+    w, wp, coef, wlp = focal_terms(ref.pt, ref.q, ref.lpt, gamma, variant)
+    live = (ref.q > 0) & (gamma != 0)
+    lnq = np.abs(np.log(np.where(ref.q > 0, ref.q, 1.0)))
+    Kqg = np.where(live, gamma * Kq + 3 * gamma * lnq + 2, 0.0)
+    Kdqg = np.where(live, Kqg + Kq + 2, 0.0)
+    qg = np.ones_like(ref.q) if gamma == 0 else np.where(ref.q > 0, np.where(ref.q > 0, ref.q, 1.0) ** gamma, 0.0)
+    Kw = qg * (Kqg + 2) + 2 if variant == 0 else Kqg
+    Kwp = np.where(live, Kdqg + Kw + 1, 0.0) if variant == 0 else Kdqg
+    T1 = np.abs(ref.pt * wp * ref.lpt)
+    Ecoef = T1 * (Kp + Kwp + 2) + ref.pt * np.abs(wp) * Elp + w * Kw + (T1 + w)
+    Eterm = np.abs(wlp) * (Kw + 1) + w * Elp
+    z = lambda a: np.where(v, a, 0.0)
+    return dict(lse=Elg + np.abs(ref.m + ref.lg) + 1, coef=z(Ecoef), term=z(Eterm), w=z(w), wp=z(wp), A=z(coef), wlp=z(wlp))
+
+
+def focal_coef_err(ref, gamma, variant):
+    """(relative error of one coef, of one w lp), units of u, per valid pixel (0 elsewhere) of the PLANAR kernel: focal_planar_counts, on
+    a PlanarRef.  The same two figures of the fused head's softhead_pass_kernel<., ., SH_FOCAL> are head_focal_coef_err (on a
+    HeadFocalRef, counted in its docstring); those of focal_coef_kernel are inside focal_coef_ref"""
+    k = focal_planar_counts(ref, gamma, variant)
+    rel = lambda e, v: np.where(v != 0, e / np.where(v != 0, np.abs(v), 1.0), 0.0)
+    return rel(k['coef'], k['A']), rel(k['term'], k['wlp'])
+
+
+class FocalPlanarRef:
+    """reference and bounds of tss_focal_fwd / tss_focal_bwd: lse, coef, loss, scale = (float)((double)alpha / n) exactly, g"""
+    def __init__(self, ref, gamma, variant, alpha, grad_out):
+        k = focal_planar_counts(ref, gamma, variant)
+        n = ref.nvalid
+        a32, go = float(F32(alpha)), float(F32(grad_out))
+        self.lse = ref.m + ref.lg
+        self.lse_bound = U32 * k['lse'] * 1.001
+        self.coef, self.coef_bound = k['A'], U32 * k['coef'] * 1.001
+        self.scale = float(F32(a32 / n)) if n else 0.0
+        self.nvalid = n
+        self.loss = -a32 * float(k['wlp'].sum()) / n if n else 0.0
+        self.loss_bound = (a32 / n * (U32 * float(k['term'].sum()) * 1.001 + 2.0 ** -45 * float(np.abs(k['wlp']).sum()))
+                           + U32 * abs(self.loss) * 1.001) if n else 0.0
+        gs = self.scale * go
+        h = ref.onehot.astype(np.float64)
+        self.g = (h - ref.p) * (self.coef * gs)[:, None]
+        # gs = fl(scale go) and a gs (2); e = __expf(x - l) (soft_p_count on the focal lse); h - e (1, of |h - e| <= p + h); times w (1)
+        kp = _first_order(soft_p_count(ref, k['lse']))
+        A = np.abs(self.coef)[:, None]
+        self.g_bound = gs * (A * ref.p * kp + (ref.p + h) * (U32 * 1.001 * (4 * A + k['coef'][:, None])))
+
+    def grad_bound(self, bf16):
+        return self.g_bound + (2.0 ** -8 * (np.abs(self.g) + self.g_bound) if bf16 else 0.0)
+
+
+def dice_coef_ref(P, I, N, dP, dI, smooth, any_valid):
+    """the f64 finalize of both Dice routes on class sums P, I, N with errors dP, dI (N is exact): (a, b, da, db, loss, loss bound);
+    den = P + N + smooth, num = 2 I + smooth, a = -2 / (C den), b = num / (C den^2), loss = mean 1 - num / den.  da = |a| dP / den,
+    db = 2 dI / (C den^2) + 2 b dP / den (both over (1 - dP / den)^2 for the second order) and the cast to f32 (1); the loss:
+    sum (2 dI + (num / den) dP) / den / C and its cast.  No valid pixel: everything 0"""
+    C = len(P)
+    if not any_valid:
+        z = np.zeros(C)
+        return z, z, z, z, 0.0, 0.0
+    sm = float(F32(smooth))
+    den, num = P + N + sm, 2 * I + sm
+    assert (den > 0).all()
+    tight = 1.0 / (1.0 - dP / den) ** 2
+    a, b = -2.0 / (C * den), num / (C * den * den)
+    da = (np.abs(a) * dP / den * tight + U32 * np.abs(a)) * 1.001
+    db = ((2 * dI / (C * den * den) + 2 * b * dP / den) * tight + U32 * b) * 1.001
+    loss = float((1 - num / den).mean())
+    return a, b, da, db, loss, float(((2 * dI + num / den * dP) / den * tight).sum()) / C + U32 * abs(loss) * 1.001
+
+
+class DicePlanarRef:
+    """reference and bounds of tss_dice_fwd / tss_dice_bwd at a grid (max_blocks): P_c = sum_V p_c, I_c, N_c, den_c = P_c + N_c +
+    smooth, loss, coef a_c, b_c, the gradient p_k (G_k - sum_c p_c G_c) grad_out, and
+      dP, dI    of the statistics: every p = __expf(x - l) (soft_p_count), the lane's f32 chain -- the 8 pixels of a group and one
+                addition per trip, 8 + trips -- then f64.  Past DICE_CP classes the later sweeps read l back: the same float, nothing more
+      da, db    through the f64 finalize (a = -2 / (C den): |a| dP / den; b = num / (C den^2): 2 dI / (C den^2) + 2 |b| dP / den)
+                and the cast to f32 (1)
+      loss      sum_c (2 dI_c + (num / den) dP_c) / den_c / C and the cast
+      gradient  dot = sum_c p_c G_c in f32: per term p_c's error, the addition b_c + a_c at the target (1), the product (1) and the C
+                accumulations, plus the coefficients' own error; then e ((G_k) - dot) gv: the subtraction and two products (3)"""
+    def __init__(self, ref, smooth, grad_out, max_blocks=0):
+        B, C, HW = ref.shape
+        self.grid, trips = soft_grid(B, HW, max_blocks, SOFT_DICE_BLOCKS)
+        v = ref.valid[:, None, :]
+        h = ref.onehot.astype(np.float64)
+        pv = ref.p * v
+        kl = soft_lse_count(ref)
+        kp = soft_p_count(ref, kl)
+        cls = lambda a: a.sum((0, 2))
+        self.lse, self.lse_bound = ref.lse, U32 * kl * 1.001
+        self.P, self.I, self.N = cls(pv), cls(pv * h), cls(h)
+        chain = 8 + trips
+        dP = U32 * 1.001 * (cls(pv * kp) + chain * self.P) + 2.0 ** -45 * self.P
+        dI = U32 * 1.001 * (cls(pv * h * kp) + chain * self.I) + 2.0 ** -45 * self.I
+        go = float(F32(grad_out))
+        self.a, self.b, self.da, self.db, self.loss, self.loss_bound = dice_coef_ref(self.P, self.I, self.N, dP, dI, smooth, ref.nvalid > 0)
+        a, b, da, db = (q[None, :, None] for q in (self.a, self.b, self.da, self.db))
+        G = b + h * a
+        dG = db + h * (da + U32 * np.abs(G))
+        dot = (ref.p * G).sum(1, keepdims=True)
+        Edot = (ref.p * (np.abs(G) * (_first_order(kp) + U32 * (1 + C) * 1.001) + dG)).sum(1, keepdims=True)
+        self.g = ref.p * (G - dot) * go * v
+        self.g_bound = go * v * ref.p * (_first_order(kp) * np.abs(G - dot) + dG + Edot + 3 * U32 * 1.001 * np.abs(G - dot))
+
+    def grad_bound(self, bf16):
+        return self.g_bound + (2.0 ** -8 * (np.abs(self.g) + self.g_bound) if bf16 else 0.0)
+
+
+def _err(out, ref):
+    return np.abs(np.asarray(out, np.float64) - ref)
+
+
+# --- tss_focal_coef_from_ce (focal_coef_kernel of csrc/softhead.hip): the wide route's planar step on a stored cross-entropy
+SOFT_CE_VALUES = (0.0, 1e-40, 2.0 ** -24, 1.0, 40.0, 200.0)       # p = 1 and q = 0; a denormal; q = 2^-24; ordinary; p ~ 4e-18; p below f32
+SOFT_CE_N = (1, 3, 4, 5, 1027)                                    # tail groups of 1 and 3 pixels, one whole group, 257 groups in two blocks
+
+
+def soft_ce_operands(n, C=19):
+    """(ce f32 [n], labels [n]): SOFT_CE_VALUES in turn, then multiples of 2^-4 below 16; about 10 % of the labels 255, -1 or 300"""
+    g = case_gen(4713, n)
+    ce = (torch.randint(0, 256, (n,), generator=g).double() / 16).numpy()
+    k = min(n, len(SOFT_CE_VALUES))
+    ce[:k] = SOFT_CE_VALUES[:k]
+    if n > 2 * len(SOFT_CE_VALUES):
+        ce[-len(SOFT_CE_VALUES):] = SOFT_CE_VALUES                # again at the far end: the tail group and the second block
+    lab = head_labels(1, 1, n, C, g).reshape(n).numpy().copy()
+    lab[:k] = np.arange(k) % C
+    return ce.astype(F32), lab
+
+
+def focal_coef_ref(ce, labels, C, gamma, variant, alpha, ignore_index=255, has_ignore=True):
+    """f64 reference of tss_focal_coef_from_ce on the STORED f32 ce: p = exp(-ce), q = -expm1(-ce), lp = -ce, coef = w - w'(q) p lp
+    of X.focal_terms (0 where the pixel does not count), loss = -alpha sum w lp / n, scale = (float)((double)alpha / n), and bounds
+    counted from focal_coef_kernel and softhead.hip's focal_terms (units of u):
+      p       __expf(lp): the product with LOG2E and that constant (2 |lp|), V_EXP_F32 (2); below the smallest normal it may be flushed
+      q       -expm1f(lp), the library's, taken at 1 ulp (2)
+      q^gamma, gamma q^(gamma-1), w, w'      as focal_planar_counts: Kqg = gamma Kq + 3 |gamma ln q| + 2, Kdqg = Kqg + Kq + 2,
+              Kw = qg (Kqg + 2) + 2 (variant 0) or Kqg, Kdw = Kdqg + Kw + 1 or Kdqg
+      coef    wq - (dw p) lp, both terms >= 0: wq Kw + T1 (Kdw + Kp + 2) + (wq + T1), T1 = |dw p lp|
+      w lp    |w lp| (Kw + 1)
+    A q below the smallest normal (ce = 1e-40) may be flushed by V_LOG_F32, and then q^gamma is taken as 0: (1 + gamma) q^gamma e
+    covers both terms of coef there.  The hardware's and the library's 1 ulp are the vendor's figures, not measured here"""
+    ce = np.asarray(ce, F32).astype(np.float64)
+    valid = (labels >= 0) & (labels < C) & ((labels != ignore_index) | (not has_ignore))
+    lp = -ce
+    p, q = np.exp(lp), -np.expm1(lp)
+    w, wp, negcoef, wlp = focal_terms(p, q, lp, gamma, variant)
+    live = (q > 0) & (gamma != 0)
+    qs = np.where(q > 0, q, 1.0)
+    Kp, Kq = 2 * ce + 2, 2.0
+    Kqg = np.where(live, gamma * Kq + 3 * gamma * np.abs(np.log(qs)) + 2, 0.0)
+    Kdqg = np.where(live, Kqg + Kq + 2, 0.0)
+    qg = np.ones_like(q) if gamma == 0 else np.where(q > 0, qs ** gamma, 0.0)
+    Kw = qg * (Kqg + 2) + 2 if variant == 0 else Kqg
+    Kdw = np.where(live, Kdqg + Kw + 1, 0.0) if variant == 0 else Kdqg
+    T1 = np.abs(wp * p * lp)
+    tiny = DISTILL_FLOOR
+    flushed = np.where(live & (q < tiny), (1 + gamma) * qg * math.e, 0.0)
+    Ecoef = U32 * 1.001 * (w * Kw + T1 * (Kdw + Kp + 2) + (w + T1)) + np.abs(wp * lp) * tiny + flushed + tiny
+    Eterm = U32 * 1.001 * np.abs(wlp) * (Kw + 1) + flushed * ce + tiny
+    n = int(valid.sum())
+    a32 = float(F32(alpha))
+    z = lambda a: np.where(valid, a, 0.0)
+    loss = -a32 * float(z(wlp).sum()) / n if n else 0.0
+    return dict(valid=valid, coef=z(-negcoef), coef_bound=z(Ecoef), loss=loss, scale=float(F32(a32 / n)) if n else 0.0, nvalid=n,
+                loss_bound=(a32 / n * float(z(Eterm).sum()) * (1 + 2.0 ** -40) + U32 * abs(loss) * 1.001) if n else 0.0)
+
+
+def focal_planar_ratios(fr, lse, coef, loss, scale, d, bf16):
+    """a result of tss_focal_fwd / _bwd against a FocalPlanarRef: the largest |out - ref| / bound of lse, pixel_coef, loss and
+    dlogits; scale: the stored bits are (float)((double)alpha / n)"""
+    return dict(lse=worst_ratio(_err(lse, fr.lse), fr.lse_bound), coef=worst_ratio(_err(coef, fr.coef), fr.coef_bound),
+                loss=worst_ratio(abs(float(loss) - fr.loss), fr.loss_bound), grad=worst_ratio(_err(d, fr.g), fr.grad_bound(bf16)),
+                scale=float(scale) == fr.scale)
+
+
+def dice_planar_ratios(dr, lse, coef, loss, d, bf16):
+    """a result of tss_dice_fwd / _bwd (coef: a_c then b_c) against a DicePlanarRef"""
+    C = len(dr.a)
+    return dict(lse=worst_ratio(_err(lse, dr.lse), dr.lse_bound), a=worst_ratio(_err(coef[:C], dr.a), dr.da),
+                b=worst_ratio(_err(coef[C:2 * C], dr.b), dr.db), loss=worst_ratio(abs(float(loss) - dr.loss), dr.loss_bound),
+                grad=worst_ratio(_err(d, dr.g), dr.grad_bound(bf16)))
+
+
+# --- focal and soft Dice on the fused head (csrc/softhead.hip: softhead_pass_kernel<T, CP, SH_FOCAL | SH_DICE_STATS | SH_DICE_GRAD>, the
+# finalize kernels, then the gather of tss_upsample_ce_bwd).  The references stand on HeadRef (z, valid, softmax, My, Mx); the chains of
+# the band walk and the gather are head_grad_counts', the coordinate slack of a pair that is not exact is head_slack's.
+HEAD_SOFT_EXTRA = HeadCase('edge_few', 1, 19, 3, 33, 9, 255)     # added, CPU only: ONE lane past the image edge (W = 255), so that counting
+                                                                 # its N_c moves the coefficients by less than the old criterion sees
+
+
+def head_soft_p_count(zmax, CP):
+    """relative error (units of u) of one softmax value p_c = e_c inv of softhead_pass_kernel, head_grad_counts' register r_p without a
+    pixel weight: 20 zmax (the interpolation and z - m as perturbations d of the logits, which move p_c by <= 2 p_c d), V_EXP_F32 on
+    the value and on the terms of the sum (4), the CP - 1 additions (the pad classes add exact zeros), V_RCP_F32 (2), the product (1)"""
+    return 20.0 * zmax + CP + 6
+
+
+class HeadDiceRef:
+    """dice_ref: f64 soft Dice on the fused head from a HeadRef (its valid mask decides has_ignore), with the bounds.
+      P, I, N       sum_V p_c, sum_V p_c [t == c], sum_V [t == c];  a, b, loss as softhead_dice_finalize_kernel forms them
+      dz            p_k (b_k - S) + [k == t] a_t p_t, S = sum_c b_c p_c + a_t p_t, on V;  g = grad_out My dz Mx^T (inv_count = 1)
+      T, A          the absolute twin p_k (|b_k| + sum_c |b_c| p_c + |a_t| p_t) + [k == t] |a_t| p_t and its gather
+    Coefficients: every p (head_soft_p_count, + 2 slack_z relative on a pair that is not exact), the lane's f32 sum over the rows
+    of its band (band_rows additions; the one-hot sums in LDS likewise; N counts to at most band_rows, exact), then f64, the
+    finalize's divisions and the cast: dice_coef_ref.
+    Gradient: |dlow - g| <= u (n_g + r_dz) A + grad_out My Tc Mx^T + slack, n_g head_grad_counts' chain of the band walk and the
+    gather; r_dz = 2 r_p + CP + 6 -- p_k and the p_c inside S (2 r_p), S's CP products and additions and the one-hot term's product
+    and addition (CP + 3), b_k - S, the product with p_k (2), one spare; Tc the twin with (da, db) in place of (|a|, |b|): the
+    coefficients' own error carried through.  slack: head_slack on T (a softmax value moves by 2 p slack_z) + 2 slack_z A once more
+    for S, which moves with every p_c"""
+    def __init__(self, ref, smooth, grad_out, n):
+        C, CP = ref.C, head_cp(ref.C)
+        self.low, self.size, self.zmax, self.My, self.Mx = ref.low, ref.size, ref.zmax, ref.My, ref.Mx
+        p = torch.softmax(ref.z, 1)
+        v = ref.valid.double()[:, None]
+        onehot = torch.zeros_like(ref.z).scatter_(1, ref.t[:, None], 1.0) * v
+        sz = head_slack_z(ref)
+        r_p = head_soft_p_count(ref.zmax, CP)
+        cls = lambda q: q.sum((0, 2, 3)).numpy()
+        self.P, self.I, self.N = cls(p * v), cls(p * onehot), cls(onehot)
+        rel = U32 * 1.001 * (r_p + n['band_rows']) + 2 * sz + 2.0 ** -45
+        self.a, self.b, self.da, self.db, self.loss, self.loss_bound = dice_coef_ref(self.P, self.I, self.N, rel * self.P, rel * self.I, smooth,
+                                                                                     bool(ref.valid.any()))
+        self.go = self.gs = float(F32(grad_out))
+        self.den, self.ssum = 1.0, 0.0          # head_slack's loss part is not used
+        col = lambda q: torch.from_numpy(np.ascontiguousarray(q))[None, :, None, None]
+
+        def terms(a, b):
+            pt = (p * onehot).sum(1, keepdim=True)
+            at = (col(a) * onehot).sum(1, keepdim=True)
+            return (col(b) * p).sum(1, keepdim=True) + at * pt, at * pt
+        S, hot = terms(self.a, self.b)
+        Sabs, hotabs = terms(np.abs(self.a), np.abs(self.b))
+        Sd, hotd = terms(self.da, self.db)
+        dz = (p * (col(self.b) - S) + onehot * hot) * v
+        self.T = (p * (col(np.abs(self.b)) + Sabs) + onehot * hotabs) * v
+        Tc = (p * (col(self.db) + Sd) + onehot * hotd) * v
+        gather = lambda q: self.go * torch.einsum('oh,bcop,pw->bchw', ref.My, q, ref.Mx)
+        self.g, self.A = gather(dz), gather(self.T)
+        k = U32 * (head_grad_counts(n, ref.zmax, C, False)[0] + 2 * r_p + CP + 6)
+        slack = head_slack(self)[2] + 2 * sz * self.A if sz else 0.0
+        self.g_bound = k / (1 - k) * self.A + 1.001 * gather(Tc) + slack
+
+    def grad_bound(self, bf16):
+        return self.g_bound + (2.0 ** -8 * (self.g.abs() + self.g_bound) if bf16 else 0.0)
+
+
+def dice_ref(ref, smooth, grad_out=1.0, n=None):
+    """HeadDiceRef of a HeadRef with the chain lengths of its shape; n: the case's head_counts, restated from the shape when not given"""
+    (h, w), (H, W) = ref.low, ref.size
+    return HeadDiceRef(ref, smooth, grad_out, n or head_counts(ref.x.shape[0], ref.C, h, w, H, W))
+
+
+def head_soft_inputs(case, rare=False, focal=False):
+    """head_inputs with the labels the soft losses are listed for -- class 1 ABSENT (its pixels go to class 3), class 2 at exactly ONE
+    pixel (the others go to class 4; C >= 5).  rare (C > 20): the classes from 20 on lie at -8
+    everywhere and never occur as a label, and classes 0 and 7 lie at +8 everywhere: p_c < 1e-7 on those planes, so
+    a wrong b_c there (coef[c] read for coef[24 + c]) moves nothing the largest gradient element could show"""
+    x, labels, plants = head_inputs(case)
+    labels = labels.clone()
+    if focal:                     # the focal operands: head_focal_plants instead of the Dice label plants
+        return x, labels, head_focal_plants(case, x, labels)
+    if case.C >= 5:
+        labels[labels == 1] = 3
+        labels[labels == 2] = 4
+        labels[0, case.H // 2, case.W // 2] = 2
+    if rare:
+        assert case.C > 20
+        B, C, h, w = x.shape
+        x[:, 20:] = -8.0
+        x[:, :20] = x[:, :20].clamp(max=4.0)
+        x[:, 0], x[:, 7] = 8.0, 8.0
+        labels[(labels >= 20) & (labels < C)] = 5
+    return x, labels, plants
+
+
+def head_focal_plants(case, x, labels):
+    """in place, on an exact pair with at least four low-resolution cells: at the first four cells of image 0 (row-major) the logits of
+    a pixel whose target holds the maximum by 0 (a tie with the next class), by 2^-2 and by 16, and lies 16 below it, and that target
+    at the output pixel that sits ON the cell (where the interpolation returns the cell itself): the et == 1.f, s == 1.f-or-nearly
+    and q -> 0 branches of softhead_pass_kernel<SH_FOCAL>.  Returns [(gap, output y, output x)]"""
+    B, C, h, w = x.shape
+    H, W = labels.shape[-2:]
+    if not case.exact or h * w < 4 or C < 2:
+        return []
+    out = []
+    for i, gap in enumerate((0.0, 0.25, 16.0, -16.0)):
+        r, c = divmod(i, w)
+        y, xo = (r * (H - 1) // (h - 1) if h > 1 else 0), (c * (W - 1) // (w - 1) if w > 1 else 0)
+        t = (C - 2 - i) % C
+        o = (t + 1) % C
+        if gap == 16.0:
+            x[0, :, r, c], x[0, t, r, c] = -8.0, 8.0
+        elif gap == -16.0:
+            x[0, t, r, c], x[0, o, r, c] = -8.0, 8.0
+        else:
+            x[0, :, r, c] = x[0, :, r, c].clamp(max=4.0 - max(gap, 0.25))
+            x[0, t, r, c], x[0, o, r, c] = 4.0, 4.0 - gap
+        labels[0, y, xo] = t
+        out.append((gap, y, xo))
+    return out
+
+
+class HeadFocalRef:
+    """f64 focal loss on the fused head from a HeadRef, with the bounds of softhead_pass_kernel<., ., SH_FOCAL>, its finalize and the
+    gather.  Per valid pixel (nats): D = z - max, so = sum_{c != t} exp D_c, et = exp D_t, s = so + et, p = et / s, q = so / s, lp,
+    (w, coef = w - w' p lp) of focal_terms; loss = -alpha sum w lp / n, scale = (float)((double)alpha / n), g = scale grad_out
+    My (coef (p_k - [k == t])) Mx^T -- HeadRef.weights with pixw = coef.  Counts, units of u; d = 10 zmax + slack_z / u is what the
+    interpolation, the product with LOG2E, z - m (head_lse_err) and, on a pair that is not exact, the f32 coordinates move a logit by:
+      so, et   e_c = V_EXP_F32(z_c - m): 2 d (z_c and m both move) + 2; the CP - 1 additions: Kso = 2 d + 2 + CP, Ket = 2 d + 2
+      s        so + et: Ks = q Kso + p Ket + 1;  inv = V_RCP_F32(s) (2): Kp = Ket + Ks + 3, Kq = Kso + Ks + 3
+      lg       the target holds the maximum (et == 1.f; exact pairs only -- elsewhere the f32 taps decide the branch and the absolute
+               form, which is never the smaller, is taken): s == 1.f: so itself (so^2 / 2 < u so); else __logf(u) so V_RCP_F32(u - 1)
+               with u = fl(1 + so): log1p without the rounding of 1 + so; __logf (4), the reciprocal (2), two products (2), the
+               formula's own O(u) (1), so's Kso: (Kso + 10) lg, RELATIVE to lg ~ q.  Otherwise __logf(s): Ks + 4 |lg|
+      lp       (zt - m) LN2F - lg: at a leading target -lg; otherwise 2 d for the difference, 3 |Dt| (the subtraction, LN2F and the
+               product), |lp| for the last subtraction
+      q^gamma, gamma q^(gamma-1), w, w', coef, w lp     as focal_coef_ref: Kqg = gamma Kq + 3 |gamma ln q| + 2 (the conditioning of
+               q^gamma in q's relative error, the |gamma log2 q| of the exp2f(gamma __log2f(q)) pair), Kdqg = Kqg + Kq + 2, Kw, Kdw;
+               E(coef) = w Kw + T1 (Kdw + Kp + 2) + w' p E(lp) + (w + T1);  E(w lp) = |w lp| (Kw + 1) + w E(lp)
+    Loss: the lane's f32 sum over the rows of its band (band_rows), then f64, one f32 cast.
+    Gradient: head_grad_bound's form: u (n_g + r_p) A with r_p = head_soft_p_count + 1 (the product coef inv), plus the coefficient's
+    own error through the same gather, scale grad_out My (E(coef) (p_k + [k == t])) Mx^T, plus head_slack.
+    V_EXP_F32 / V_LOG_F32 / V_RCP_F32 at 1 ulp: the vendor's figure (head_lse_err), not measured here"""
+    def __init__(self, ref, gamma, variant, alpha, grad_out, n):
+        import copy
+        C, CP = ref.C, head_cp(ref.C)
+        sz = head_slack_z(ref)
+        d = 10.0 * ref.zmax + sz / U32
+        z = ref.z.numpy()
+        valid = ref.valid.numpy()
+        hot = (np.arange(C)[None, :, None, None] == ref.t.numpy()[:, None]) & valid[:, None]
+        D = z - z.max(1, keepdims=True)
+        E = np.exp(D)
+        so, et, Dt = (E * ~hot).sum(1), (E * hot).sum(1), (D * hot).sum(1)
+        s = so + et
+        p, q = et / s, so / s
+        lead = valid & (Dt == 0) & (sz == 0)
+        lg = np.where(lead, np.log1p(so), np.log(s))
+        lp = np.where(valid, Dt - lg, 0.0)
+        assert (q[valid] > 2.0 ** -100).all()
+        Kso, Ket = 2 * d + 2 + CP, np.where(lead, 0.0, 2 * d + 2)
+        Ks = q * Kso + p * Ket + 1
+        Kp, Kq = Ket + Ks + 3, Kso + Ks + 3
+        Elg = np.where(lead, (Kso + 10) * lg, Ks + 4 * np.abs(lg))
+        Elp = np.where(lead, Elg, 2 * d + 3 * np.abs(Dt) + Elg + np.abs(lp))
+        w, wp, negcoef, wlp = focal_terms(p, q, lp, gamma, variant)
+        live = gamma != 0
+        Kqg = (gamma * Kq + 3 * gamma * np.abs(np.log(q)) + 2) if live else np.zeros_like(q)
+        Kdqg = Kqg + Kq + 2 if live else np.zeros_like(q)
+        qg = q ** gamma if live else np.ones_like(q)
+        Kw = qg * (Kqg + 2) + 2 if variant == 0 else Kqg
+        Kdw = (Kdqg + Kw + 1 if variant == 0 else Kdqg) if live else np.zeros_like(q)
+        T1 = np.abs(wp * p * lp)
+        vz = lambda a: np.where(valid, a, 0.0)
+        self.coef = vz(-negcoef)
+        self.coef_err = vz(U32 * 1.002 * (w * Kw + T1 * (Kdw + Kp + 2) + np.abs(wp) * p * Elp + (w + T1)))
+        Eterm = vz(U32 * 1.002 * (np.abs(wlp) * (Kw + 1 + n['band_rows']) + w * Elp))
+        self.wlp, self.term_err = vz(wlp), vz(U32 * 1.002 * (np.abs(wlp) * (Kw + 1) + w * Elp))
+        self.nvalid = nv = int(valid.sum())
+        a32, go = float(F32(alpha)), float(F32(grad_out))
+        self.scale = float(F32(a32 / nv)) if nv else 0.0
+        self.loss = -a32 * float(vz(wlp).sum()) / nv if nv else 0.0
+        self.loss_bound = (a32 / nv * float(Eterm.sum()) * (1 + 2.0 ** -40) + U32 * abs(self.loss) * 1.001) if nv else 0.0
+        r = copy.copy(ref).weights(pixw=torch.from_numpy(self.coef), grad_out=go * self.scale)
+        self.g, self.A = r.g, r.A
+        k = U32 * (head_grad_counts(n, ref.zmax, C, False)[0] + head_soft_p_count(ref.zmax, CP) + 1)
+        ce = torch.from_numpy(self.coef_err)[:, None] * (torch.softmax(ref.z, 1) + torch.from_numpy(hot.astype(np.float64)))
+        carried = go * self.scale * torch.einsum('oh,bcop,pw->bchw', ref.My, ce, ref.Mx)
+        self.g_bound = k / (1 - k) * self.A + carried + (head_slack(r)[2] if sz else 0.0)
+
+    def grad_bound(self, bf16):
+        return self.g_bound + (2.0 ** -8 * (self.g.abs() + self.g_bound) if bf16 else 0.0)
+
+
+def head_focal_coef_err(f):
+    """(relative error of one coef, of one w lp), units of u, per valid pixel (0 elsewhere) of the fused head's focal pass, from a
+    HeadFocalRef: counted from softhead_pass_kernel<., ., SH_FOCAL> and softhead.hip's focal_terms in that class's docstring (the lane's
+    band_rows additions of the loss sum are not part of one term)"""
+    rel = lambda e, v: np.where(v != 0, e / np.where(v != 0, np.abs(v), 1.0), 0.0) / U32
+    return rel(f.coef_err, f.coef), rel(f.term_err, f.wlp)

@@ -44,8 +44,10 @@ def _nhwc(x, unclamped):
 
 
 def ce_pass(x, labels, H, W, mode=0, weight=None, eps=0.0, pix=None, sel=None, grad_out=1.0, ignore_index=255, defect=None,
-            class_order=1):
-    """-> dict(loss, inv_count, dlow [B][C][h][w] f32, pix [B][H][W] f32); x [B][C][h][w] (values exact in f32)"""
+            class_order=1, coef=None, gamma=0.0, variant=0, alpha=1.0):
+    """-> dict(loss, inv_count, dlow [B][C][h][w] f32, pix [B][H][W] f32); x [B][C][h][w] (values exact in f32).
+    mode 'focal', 'dice_stats', 'dice_grad': softhead_pass_kernel of csrc/softhead.hip on the same walk (SOFT_MODES below);
+    ignore_index None: has_ignore = 0"""
     B, C, h, w = x.shape
     CP = X.head_cp(C)
     geo = X.head_geom(B, C, h, w, H, W)
@@ -73,6 +75,17 @@ def ce_pass(x, labels, H, W, mode=0, weight=None, eps=0.0, pix=None, sel=None, g
     pix_out = np.zeros((B, H, W), dtype=F32)
     tiles, rows = {}, {}
     lab = np.asarray(labels)
+    soft = None
+    if mode == 'dice_grad':       # Ca, Cb of the block: coef[c] and coef[24 + c], zeros past C
+        coef = np.asarray(coef, dtype=F32)
+        Ca, Cb = coef[:CP].copy(), coef[24:24 + CP].copy()
+        if defect == 'b_from_a':
+            Cb[20:] = coef[20:CP]
+        if defect == 'pad_in_S' and CP > C:
+            Cb[C:] = Cb[C - 1]
+        soft = (Ca, Cb)
+    elif mode == 'focal':
+        soft = (F32(gamma), variant)
     for b in range(B):
         for band in range(geo['nband']):
             ya, yb = X.head_band(geo, band, H)
@@ -108,9 +121,10 @@ def ce_pass(x, labels, H, W, mode=0, weight=None, eps=0.0, pix=None, sel=None, g
                         nk = Nn[k] * eC
                         Nn[k][:] = 0
                         hq = hq + nk[:, None] * Cw[None, :]
-                    prod = np.zeros((NT, CP), dtype=F32)
-                    prod[:, :C] = a[:, :C] * hq[:, :C]
-                    lsum = lsum - _seq_sum(prod, range(C))
+                    if mode not in SOFT_MODES:        # the cross-entropy's target-logit term; the soft losses sum theirs per pixel
+                        prod = np.zeros((NT, CP), dtype=F32)
+                        prod[:, :C] = a[:, :C] * hq[:, :C]
+                        lsum = lsum - _seq_sum(prod, range(C))
                     G = g - hq
                     for cell in range(ncell):
                         lo, hi = win[cell]
@@ -129,17 +143,19 @@ def ce_pass(x, labels, H, W, mode=0, weight=None, eps=0.0, pix=None, sel=None, g
                 for y in range(ya, yb):
                     t = lab[b, y, xc if defect == 'edge_lane' else np.where(xin, xs, 0)]
                     if int(yi0[y]) != rA:
-                        if mode != 1:
+                        if mode not in (1, 'dice_stats'):
                             flush(rA, kA, gA, aA)
                         kA ^= 1
                         rA = rB
                         rB = rA + (1 if rA < h - 1 else 0)
-                        aA, gA, gB = aB, gB, np.zeros((NT, CP), dtype=F32)
+                        aA = aB
+                        if mode != 'dice_stats':
+                            gA, gB = gB, np.zeros((NT, CP), dtype=F32)
                         aB = load_row(rB if defect != 'unclamped_i1' else rA + 1)
                     l0, l1 = yl0[y], yl1[y]
                     if defect == 'swap_last_row' and y == H - 1:
                         l0, l1 = l1, l0
-                    z = np.full((NT, CP), NEG, dtype=F32)
+                    z = np.full((NT, CP), F32(0) if defect == 'pad_in_S' else NEG, dtype=F32)
                     with np.errstate(invalid='ignore'):
                         z[:, :C] = l0 * aA[:, :C] + l1 * aB[:, :C]
                         m = z[:, order[0]].copy()
@@ -147,9 +163,19 @@ def ce_pass(x, labels, H, W, mode=0, weight=None, eps=0.0, pix=None, sel=None, g
                             m = np.maximum(m, z[:, c])          # fmaxf: the order does not matter
                         e = np.exp2(z - m[:, None]).astype(F32)
                     ssum = _seq_sum(e, order)
-                    valid = live & (t != ignore_index) & (t >= 0) & (t < C)
+                    valid = live & (t >= 0) & (t < C) & ((t != ignore_index) if ignore_index is not None else True)
                     tc = np.where(valid, t, 0).astype(np.int64)
                     lanes = np.nonzero(valid)[0]
+                    if mode in SOFT_MODES:
+                        if mode == 'dice_stats' and defect == 'edge_N':
+                            te = lab[b, y, xc]
+                            everyone = (te >= 0) & (te < C) & ((te != ignore_index) if ignore_index is not None else True)
+                            cnt_lanes, cnt_t = np.nonzero(everyone)[0], te
+                        else:
+                            cnt_lanes, cnt_t = lanes, tc
+                        with np.errstate(all='ignore'):
+                            gA, gB = _soft_pixel(mode, e, z, m, valid, lanes, tc, l0, l1, Hh, kA, gA, gB, lsum, lcnt, soft, defect, cnt_lanes, cnt_t)
+                        continue
                     if mode == 1:
                         zt = z[np.arange(NT), tc]
                         d = ((m - zt) + np.log2(ssum).astype(F32)) * LN2F
@@ -186,13 +212,24 @@ def ce_pass(x, labels, H, W, mode=0, weight=None, eps=0.0, pix=None, sel=None, g
                     gB = gB + l1 * pz
                 if mode == 1:
                     continue
+                if mode == 'dice_stats':      # the block's row: P from the lane sums, I and N from the lane tables, in f64
+                    rows[(b, band, strip)] = tuple(q.astype(np.float64).sum(0)[:C] for q in (gA, Hh[0], Hh[1]))
+                    continue
                 flush(rA, kA, gA, aA)
                 if rB != rA and defect != 'no_last_flush':
                     flush(rB, kA ^ 1, gB, aB)
-                rows[(b, band, strip)] = (float(np.sum(lsum.astype(np.float64) * LN2)), float(np.sum(lcnt.astype(np.float64))))
+                rows[(b, band, strip)] = (float(np.sum(lsum.astype(np.float64) * (1.0 if mode == 'focal' else LN2))),
+                                          float(np.sum(lcnt.astype(np.float64))))
     if mode == 1:
         return dict(pix=pix_out)
-    if mode == 2:
+    if mode == 'dice_stats':
+        return dict(stats=[sum(rows[k][i] for k in sorted(rows)) for i in range(3)])
+    if mode == 'focal':           # softhead_focal_finalize_kernel: loss = -alpha sum / n, scale = alpha / n; the gather takes scale
+        num, den = sum(rows[k][0] for k in sorted(rows)), sum(rows[k][1] for k in sorted(rows))
+        a64 = np.float64(F32(alpha))
+        loss = F32(-a64 * num / den) if den > 0 else F32(0)
+        inv_count = F32(a64 / den) if den > 0 else F32(0)
+    elif mode in (2, 'dice_grad'):
         loss, inv_count = None, F32(1)
     else:
         num = den = 0.0
@@ -221,6 +258,73 @@ def ce_pass(x, labels, H, W, mode=0, weight=None, eps=0.0, pix=None, sel=None, g
                         v = v + tiles[(b, band, strip)][r - r0, cx - sc['c0']]
                 dlow[b, :, r, cx] = (v * gs)[:C]
     return dict(loss=loss, inv_count=inv_count, dlow=dlow)
+
+
+SOFT_MODES = ('focal', 'dice_stats', 'dice_grad')
+
+
+def _soft_pixel(mode, e, z, m, valid, lanes, tc, l0, l1, Hh, kA, gA, gB, lsum, lcnt, soft, defect, cnt_lanes, cnt_t):
+    """one output row of softhead_pass_kernel past the exponentials e = exp2(z - m) [NT][CP] (0 for the pad classes): updates the lane
+    tables Hh and the lane sums in place and returns (gA, gB).  Defects: focal 'q_one_minus_p', 'no_log1p', 'no_second_term'; the
+    Dice ones are prepared by the caller ('b_from_a', 'pad_in_S': the coefficients and the pad logits; 'edge_N': cnt_lanes)"""
+    from tests import softloss_emu as SE
+    NTn, CP = e.shape
+    ar = np.arange(NTn)
+    if mode == 'focal':
+        gamma, variant = soft
+        hot = np.zeros((NTn, CP), dtype=bool)
+        hot[lanes, tc[lanes]] = True
+        so = _seq_sum(np.where(hot, F32(0), e), range(CP))
+        et = np.where(valid, e[ar, tc], F32(0))
+        s = so + et
+        logs = np.log2(s.astype(np.float64)).astype(F32) * LN2F
+        lead = logs * so * (F32(1) / (s - F32(1))).astype(F32)
+        lg = logs if defect == 'no_log1p' else np.where(et == 1, np.where(s == 1, so, lead), logs)
+        lp = (z[ar, tc] - m) * LN2F - lg
+        inv = (F32(1) / s).astype(F32)
+        p, q = et * inv, so * inv
+        if defect == 'q_one_minus_p':
+            q = F32(1) - p
+        wq, cf = SE.head_focal_terms(p, q, lp, gamma, variant)
+        if defect == 'no_second_term':
+            cf = wq
+        lsum[lanes] = lsum[lanes] + (wq * lp)[lanes]
+        lcnt[lanes] = lcnt[lanes] + F32(1)
+        Hh[kA][lanes, tc[lanes]] = Hh[kA][lanes, tc[lanes]] + l0 * cf[lanes]
+        Hh[kA ^ 1][lanes, tc[lanes]] = Hh[kA ^ 1][lanes, tc[lanes]] + l1 * cf[lanes]
+        pz = e * np.where(valid, cf * inv, F32(0)).astype(F32)[:, None]
+        return gA + l0 * pz, gB + l1 * pz
+    ssum = _seq_sum(e, range(CP))
+    inv = np.where(valid, (F32(1) / ssum).astype(F32), F32(0)).astype(F32)
+    p = e * inv[:, None]
+    if mode == 'dice_stats':
+        Hh[0][lanes, tc[lanes]] = Hh[0][lanes, tc[lanes]] + p[lanes, tc[lanes]]
+        Hh[1][cnt_lanes, cnt_t[cnt_lanes]] = Hh[1][cnt_lanes, cnt_t[cnt_lanes]] + F32(1)
+        return gA + p, gB
+    Ca, Cb = soft
+    S = _seq_sum(Cb[None, :] * p, range(CP))
+    hotv = Ca[tc] * p[ar, tc]
+    S[lanes] = S[lanes] + hotv[lanes]
+    Hh[kA][lanes, tc[lanes]] = Hh[kA][lanes, tc[lanes]] - l0 * hotv[lanes]
+    Hh[kA ^ 1][lanes, tc[lanes]] = Hh[kA ^ 1][lanes, tc[lanes]] - l1 * hotv[lanes]
+    pz = p * (Cb[None, :] - S[:, None])
+    return gA + l0 * pz, gB + l1 * pz
+
+
+def dice_finalize(stats, C, smooth):
+    """softhead_dice_finalize_kernel in f64: (coef [64] f32 with a at [0, 24), b at [24, 48), zeros past C; loss f32)"""
+    P, I, N = (np.asarray(q, np.float64) for q in stats)
+    coef = np.zeros(64, dtype=F32)
+    term = np.zeros(C)
+    if N.sum() > 0:
+        sm = np.float64(F32(smooth))
+        den, num = P + N + sm, 2.0 * I + sm
+        ok = den > 0
+        dd = np.where(ok, den, 1.0)
+        term = np.where(ok, 1.0 - num / dd, 1.0)
+        coef[:C] = np.where(ok, -2.0 / (C * dd), 0.0)
+        coef[24:24 + C] = np.where(ok, num / (C * dd * dd), 0.0)
+    return coef, F32(term.sum() / C)
 
 
 def argmax_walk(x, H, W, class_order=1, ge=False, chunk=None, chunk_ge=False):

@@ -2232,3 +2232,483 @@ def test_cast_sources_hold_the_planted_roundings():
     tie = low == 0x8000
     assert ((rb[tie] & 1) == 0).all()                             # torch rounds ties to even: the reference of the GPU test
     assert (rb[low == 0x8001] == ((b[low == 0x8001] >> 16) + 1) & 0xFFFF).all() and (rb[low == 0x7FFF] == (b[low == 0x7FFF] >> 16)).all()
+
+
+# ---------------------------------------------------------------------------------------------------------- soft losses and distillation
+from tests import cases, distill_ref, softloss_emu as SE          # noqa: E402
+
+DISTILL_KINDS = (('pixel', X.DISTILL_PIXEL_C, X.distill_pixel_cases), ('channel', X.DISTILL_CHANNEL_C, X.distill_channel_cases))
+DISTILL_ALL = [(kind, C) + case for kind, Cs, casef in DISTILL_KINDS for C in Cs for case in casef(C)]
+DISTILL_BY_NAME = {c[2]: c for c in DISTILL_ALL}
+
+
+def _distill_emu(case, bf16, defect=None):
+    kind, C, name, B, HW, cap, tau, hot = case
+    s, t = X.distill_operands(B, C, HW, 0, hot)
+    ref = X.DistillRef(s, t, tau, kind, 0.7, cap)
+    loss, stats, d = SE.distill(s, t, tau, kind, cap, 0.7, bf16, defect)
+    return s, t, ref, d, X.distill_ratios(ref, loss, stats, d, bf16)
+
+
+def _old_gradient_criterion(case, s, t, d, bf16):
+    """tests/test_gpu_distill.py's check on the gradient: cases.rel_err (max |a - b| / max |b| over the WHOLE tensor) against
+    max(2e-5, 3 d_ref), d_ref the restatement's own f32-vs-f64 distance; 2e-2 for a bf16 gradient.  (error, bound)"""
+    kind, C, name, B, HW, cap, tau, hot = case
+    nchw = lambda v: torch.from_numpy(np.ascontiguousarray(np.transpose(v, (0, 2, 1)))).reshape(B, C, HW, 1)
+    go = float(np.float32(0.7))
+    g64 = distill_ref.loss_and_grad(nchw(s), nchw(t), torch.float64, tau, kind)[1].numpy() * go
+    g32 = distill_ref.loss_and_grad(nchw(s), nchw(t), torch.float32, tau, kind)[1].double().numpy() * go
+    return cases.rel_err(nchw(d.astype(np.float64)).numpy(), g64), (2e-2 if bf16 else max(2e-5, 3 * cases.rel_err(g32, g64)))
+
+
+def test_distill_reference_is_the_restatement_and_its_operands_are_exact():
+    """DistillRef against tests/distill_ref.py in f64 (tau = 3 apart from fl(1 / 3)'s one rounding), and the premises: bf16-exact
+    operands, 1 / tau exact for the powers of two, the hot plants in place"""
+    for name in ('pixel_c19_p257', 'pixel_c19_p257_hot', 'channel_c9_hw129_b3_cap2', 'channel_c19_hw257_b3_cap0_hot', 'pixel_c8_p600'):
+        kind, C, _, B, HW, cap, tau, hot = DISTILL_BY_NAME[name]
+        s, t = X.distill_operands(B, C, HW, 0, hot)
+        for v in (s, t):
+            assert np.array_equal(torch.from_numpy(v).to(torch.bfloat16).double().numpy(), v)
+            assert (np.abs(v).max() == 200.0) == hot
+        ref = X.DistillRef(s, t, tau, kind, 1.0, cap)
+        assert (ref.inv * tau == 1.0) == (tau != 3.0)
+        nchw = lambda v: torch.from_numpy(np.ascontiguousarray(np.transpose(v, (0, 2, 1)))).reshape(B, C, HW, 1)
+        loss, g = distill_ref.loss_and_grad(nchw(s), nchw(t), torch.float64, 1.0 / ref.inv, kind)
+        assert abs(ref.loss * (1.0 / ref.inv / tau) ** 2 - float(loss)) <= 1e-12 * abs(float(loss))
+        want = g.numpy().reshape(B, C, HW).transpose(0, 2, 1) * (ref.norm / (1.0 / ref.inv / ref.units))
+        assert np.abs(ref.g - want).max() <= 1e-12 * np.abs(want).max()
+        assert (ref.q > 0).any() and abs(float(ref.q.sum(ref.ax).max()) - 1) < 1e-12
+
+
+def test_distill_cases_reach_what_they_are_listed_for():
+    """the restated planners on the listed shapes: the pixel kind's one block walking 600 pixels and the two-block grid of 257; the
+    channel kind's 1, 2, 3 and 32 vectors per row with an idle thread at 19 classes, S = 1, capped and uncapped, a block that walks
+    items of two images, a ragged last segment, several trips -- and the empty item, which only the added shape has"""
+    assert X.distill_pixel_grid(1) == 1 and X.distill_pixel_grid(257) == 2 and X.distill_pixel_grid(600, 1) == 1
+    assert X.distill_pixel_grid(600) == 3 and X.distill_pixel_grid(10 ** 7) == X.DISTILL_PIXEL_BLOCKS
+    assert [X.distill_channel_split(1, C, 1)['nch'] for C in X.DISTILL_CHANNEL_C] == [1, 2, 3, 32]
+    assert X.DISTILL_NT - 3 * X.distill_channel_split(1, 19, 1)['ppb'] == 1
+    seen = set()
+    for C in X.DISTILL_CHANNEL_C:
+        for (name, B, HW, cap, tau, hot) in X.distill_channel_cases(C):
+            sp = X.distill_channel_split(B, C, HW, cap)
+            segs = X.distill_segments(HW, sp['S'])
+            assert sp['S'] >= 1 and sp['grid'] >= 1 and sp['grid'] <= (cap or X.DISTILL_CHANNEL_BLOCKS) and segs[-1][1] == HW
+            assert sorted(i for a, b in segs for i in range(a, b)) == list(range(HW))          # every position in one segment
+            empty = any(a >= b for a, b in segs)
+            assert empty == name.endswith('_empty')
+            full = X.cdiv(HW, sp['ppb'])
+            seen.add('S1' if sp['S'] == 1 else 'capped' if sp['S'] < full else 'uncapped')
+            if sp['grid'] < sp['items'] and B > 1:
+                seen.add('two_images')
+            if segs[-1][1] - segs[-1][0] not in (0, sp['len']):
+                seen.add('ragged')
+            if sp['len'] > sp['ppb']:
+                seen.add('trips')
+            assert X.distill_depth('channel', B, C, HW, cap) == X.cdiv(sp['len'], sp['ppb']) + (sp['ppb'] - 1).bit_length() + sp['S']
+    assert seen == {'S1', 'capped', 'uncapped', 'two_images', 'ragged', 'trips'}
+
+
+def test_distill_channel_split_leaves_an_empty_item_only_where_the_cap_cuts_short_segments():
+    """over HW <= 4096, every vector count (C <= 256) and every S the caps 1 .. 512 can select: an item is empty exactly when
+    (S - 1) ceil(HW / S) >= HW.  That needs short segments (S > 1 <= ceil(HW / ppb)): it is reachable -- first at 32 vectors per row,
+    HW = 81, S = 10 -- and never with S at its uncapped value at the listed class counts' ppb >= 85"""
+    HW = np.arange(1, 4097)
+    first = {}
+    for nch in range(1, 33):
+        ppb = X.DISTILL_NT // nch
+        smax = -(-HW // ppb)
+        for S in range(2, 513):
+            e = (S <= smax) & ((S - 1) * -(-HW // S) >= HW)
+            if e.any():
+                first.setdefault(nch, (int(HW[e][0]), S))
+                first[nch] = min(first[nch], (int(HW[e][0]), S))
+    assert first[32] == (81, 10) and all(n not in first for n in (1, 2, 3))
+    segs = X.distill_segments(81, X.distill_channel_split(1, 256, 81, 10)['S'])
+    assert len(segs) == 10 and segs[-1] == (81, 81) and segs[-2] == (72, 81)
+
+
+@pytest.mark.parametrize('kind,C', [(k, C) for k, Cs, _ in DISTILL_KINDS for C in Cs])
+def test_distill_f32_emulation_meets_every_bound(kind, C):
+    """stats maxima bit for bit, log Z, loss and every gradient element of the emulated kernels within the bounds on every listed
+    case, f32 and bf16 gradient.  The f32 channel-kind ratios must stay <= 1 / 2 (a bf16 gradient's bound IS its rounding, 2^-8 |g|:
+    its ratio approaches 1 by construction)"""
+    for case in [c for c in DISTILL_ALL if c[0] == kind and c[1] == C]:
+        for bf16 in (False, True):
+            r = _distill_emu(case, bf16)[4]
+            print('SOFT_MARGIN_EMU %-36s %-4s max %d logz %.4f loss %.4f grad %.4f' % (case[2], 'bf16' if bf16 else 'f32', r['max'], r['logz'],
+                                                                                     r['loss'], r['grad']))
+            assert r['max'] and r['logz'] <= 1 and r['loss'] <= 1 and r['grad'] <= 1, (case[2], bf16, r)
+            if kind == 'channel' and not bf16:
+                assert max(r['logz'], r['loss'], r['grad']) <= 0.5, (case[2], r)
+
+
+# (defect, case on which the elementwise bound fails while the old whole-tensor criterion passes, bf16 gradient)
+DISTILL_DEFECT_CASES = (('own_max', 'channel_c8_hw770_b1_cap0', True),
+                        ('drop_tail', 'channel_c19_hw257_b3_cap3', True),
+                        ('drop_tail', 'channel_c9_hw386_b1_cap2', True),
+                        ('fused_stats', 'pixel_c19_p257_hot', False),
+                        ('fused_stats', 'channel_c19_hw257_b3_cap0_hot', False))
+
+
+@pytest.mark.parametrize('defect,name,bf16', DISTILL_DEFECT_CASES)
+def test_distill_emulation_with_one_defect_fails_the_elementwise_bound_where_the_old_criterion_passes(defect, name, bf16):
+    case = DISTILL_BY_NAME[name]
+    s, t, ref, d, r = _distill_emu(case, bf16, defect)
+    err, bound = _old_gradient_criterion(case, s, t, d, bf16)
+    print('defect %-12s %-34s new grad ratio %.3f logz ratio %.3f | old %.3e <= %.3e' % (defect, name, r['grad'], r['logz'], err, bound))
+    assert r['grad'] > 1, (defect, name, r)
+    assert err <= bound, (defect, name, err, bound)
+    if defect != 'fused_stats':           # the forward's sums are wrong: the saved log Z fails its own bound too
+        assert r['logz'] > 1
+    s, t, ref, d, r = _distill_emu(case, bf16)
+    assert r['grad'] <= 1 and _old_gradient_criterion(case, s, t, d, bf16)[0] <= bound
+
+
+# --- planar focal and soft Dice
+import functools                     # noqa: E402
+
+from tests import softloss_ref       # noqa: E402
+
+SOFT_ALPHA, SOFT_GO = 0.25, 0.7
+SOFT_VARIANTS = {0: 'reference', 1: 'lin'}
+SOFT_IDS = lambda s: 'x'.join(str(v) for v in s)
+
+
+@functools.lru_cache(maxsize=None)
+def _planar(shape, has_ignore=True):
+    x, lab, plants = X.soft_planar_operands(*shape, behind=shape == X.SOFT_BEHIND)
+    return x, lab, plants, X.PlanarRef(x, lab, 255, has_ignore)
+
+
+def _restated(fn, x, lab, *args):
+    """(f64 loss, f64 gradient times grad_out, the old criterion's f32 bound) of tests/softloss_ref.py"""
+    B, C, HW = x.shape
+    xt, lt = torch.from_numpy(x).reshape(B, C, HW, 1), torch.from_numpy(lab).reshape(B, HW, 1)
+    l64, g64 = softloss_ref.loss_and_grad(fn, xt, lt, torch.float64, *args)
+    _, g32 = softloss_ref.loss_and_grad(fn, xt, lt, torch.float32, *args)
+    go = float(np.float32(SOFT_GO))
+    g64 = g64.numpy().reshape(B, C, HW) * go
+    d_ref = cases.rel_err(g32.numpy().reshape(B, C, HW) * go, g64) if bool(torch.isfinite(g32).all()) else None
+    return float(l64), g64, (2e-5 if d_ref is None else max(2e-5, 3 * d_ref))
+
+
+def _old_planar_criterion(d, g64, f32_bound, bf16):
+    """tests/test_gpu_softloss.py's check on the gradient: cases.rel_err over the WHOLE tensor; (error, bound)"""
+    return cases.rel_err(np.asarray(d, np.float64), g64), (2e-2 if bf16 else f32_bound)
+
+
+def _half_but_last(out, ref, bound, last):
+    """the f32 emulation stays at 1 / 2 of a bound whose last `last` roundings are taken out at their exact size: |out - ref| <=
+    last hu(ref) + (bound - last hu(ref)) / 2, hu = half an ulp of the f32 number nearest ref.  Where ONE rounding of the stored value
+    dominates (lse = m + lg at a leading target: u |lse| of a bound of u (|lse| + 1 + ...); coef = -(T1 + w) near -1 or -e: the
+    exponential's and the sum's) a value just above a power of two uses u |v| in full -- half an ulp IS u |v| there -- so the plain
+    ratio reaches 0.8 with nothing missing, exactly as a bf16 gradient's reaches 0.99.  What is left after those roundings must still
+    fit half of what is left of the bound: a missing term would show here"""
+    ref = np.asarray(ref, np.float64)
+    hu = np.where(ref != 0, 2.0 ** (np.floor(np.log2(np.where(ref != 0, np.abs(ref), 1.0))) - 24), 0.0)
+    err = np.abs(np.asarray(out, np.float64) - ref)
+    return bool((err <= last * hu + np.maximum(bound - last * hu, 0.0) / 2 + 1e-300).all())
+
+
+def test_soft_planar_cases_reach_what_they_are_listed_for():
+    assert X.soft_grid(1, 2056, 0, X.SOFT_FOCAL_BLOCKS) == (2, 1) and 2056 // 8 - X.SOFT_NT == 1          # the second block: one lane
+    assert 3 * (1000 // 8) == 375 and 375 % X.SOFT_NT != 0
+    assert [X.cdiv(C, X.SOFT_DICE_CP) for C in (24, 25, 48, 49)] == [1, 2, 2, 3]
+    assert X.soft_grid(3, 1000, 1, X.SOFT_DICE_BLOCKS) == (1, 2) and X.soft_grid(3, 1000, 2, X.SOFT_DICE_BLOCKS) == (2, 1)
+    for shape in X.SOFT_PLANAR:
+        B, C, HW = shape
+        x, lab, plants, ref = _planar(shape)
+        assert HW % 8 == 0 and np.array_equal(torch.from_numpy(x).to(torch.bfloat16).double().numpy(), x)
+        assert (lab == 255).any() or HW * B <= 16
+        if C >= 19:
+            i0, i1, i2, i3 = (plants['gap%g' % g] for g in (0, 0.25, 16, -16))
+            assert ref.valid[0, [i0, i1, i2, i3]].all()
+            assert ref.lead[0, i0] and (ref.D[0, :, i0] == 0).sum() == 2                 # et == 1 with a tie: s = 2 + ...
+            assert ref.lead[0, i1] and np.sort(ref.D[0, :, i1])[-2] == -0.25
+            assert ref.lead[0, i2] and ref.q[0, i2] < 1e-4 and ref.pt[0, i3] < 1e-6 and not ref.lead[0, i3]
+            n = ref.onehot.sum((0, 2))
+            assert n[plants['absent']] == 0 and n[plants['single']] == 1
+        if C == 1:
+            assert (ref.q == 0).all() and ref.lead[ref.valid].all()
+    _, lab, _, ref = _planar((1, 256, 16), False)
+    assert ((lab == 255) <= ref.valid).all() and (lab == 255).any()                     # without an ignore index 255 is a class
+    x, lab, _, ref = _planar(X.SOFT_BEHIND)
+    assert ref.valid.all() and (ref.Dt == -6).all()
+
+
+@pytest.mark.parametrize('shape', [(2, 2, 8), (3, 19, 1000), (1, 25, 64), X.SOFT_BEHIND], ids=SOFT_IDS)
+def test_soft_planar_reference_is_the_restatement(shape):
+    x, lab, _, ref = _planar(shape)
+    for gamma in X.SOFT_GAMMAS:
+        for variant in (0, 1):
+            fr = X.FocalPlanarRef(ref, gamma, variant, SOFT_ALPHA, SOFT_GO)
+            loss, g, _ = _restated(softloss_ref.focal_loss, x, lab, float(np.float32(SOFT_ALPHA)), gamma, 255, SOFT_VARIANTS[variant])
+            assert abs(fr.loss - loss) <= 1e-12 * abs(loss)
+            assert np.abs(fr.g * (float(np.float32(SOFT_ALPHA)) / fr.nvalid / fr.scale) - g).max() <= 1e-11 * np.abs(g).max()
+    for smooth in (0.0, 1.0):
+        dr = X.DicePlanarRef(ref, smooth, SOFT_GO)
+        loss, g, _ = _restated(softloss_ref.dice_loss, x, lab, shape[1], smooth, 255)
+        assert abs(dr.loss - loss) <= 1e-12 and np.abs(dr.g - g).max() <= 1e-12 * np.abs(g).max()
+
+
+@pytest.mark.parametrize('shape', X.SOFT_PLANAR + [X.SOFT_BEHIND], ids=SOFT_IDS)
+def test_soft_planar_f32_emulation_meets_every_bound(shape):
+    """lse, pixel_coef, loss, scale and every gradient element of the emulated focal kernels for every gamma and both variants; lse,
+    a_c, b_c, loss and every gradient element of the emulated Dice kernels for both smooth values, with and without the ignore
+    index, at max_blocks 0, 1, 2; f32 and bf16 gradients"""
+    x, lab, _, ref = _planar(shape)
+    C = shape[1]
+    for gamma in X.SOFT_GAMMAS:
+        for variant in (0, 1):
+            fr = X.FocalPlanarRef(ref, gamma, variant, SOFT_ALPHA, SOFT_GO)
+            l, a, loss, scale = SE.focal_fwd(x, lab, gamma, variant, SOFT_ALPHA)
+            assert (a[~ref.valid] == 0).all()
+            for bf16 in (False, True):
+                d = SE.focal_bwd(x, lab, l, a, scale, SOFT_GO, bf16)
+                r = X.focal_planar_ratios(fr, l, a, loss, scale, d, bf16)
+                print('SOFT_MARGIN_EMU focal %-12s g%.1f v%d %-4s' % (SOFT_IDS(shape), gamma, variant, 'bf16' if bf16 else 'f32'), r)
+                assert r['scale'] and max(r['lse'], r['coef'], r['loss'], r['grad']) <= 1, (shape, gamma, variant, bf16, r)
+                if not bf16:
+                    assert r['loss'] <= 0.5 and r['grad'] <= 0.5, (shape, gamma, variant, r)
+                    assert _half_but_last(l, fr.lse, fr.lse_bound, 1) and _half_but_last(a, fr.coef, fr.coef_bound, 2), (shape, gamma, variant, r)
+    for has_ignore in (True, False):
+        refd = _planar(shape, has_ignore)[3]
+        for smooth in (0.0, 1.0):
+            for cap in (0, 1, 2):
+                dr = X.DicePlanarRef(refd, smooth, SOFT_GO, cap)
+                l, coef, loss, (P, I, N) = SE.dice_fwd(x, lab, smooth, 255, has_ignore, cap)
+                assert np.array_equal(N, dr.N)
+                for bf16 in (False, True):
+                    d = SE.dice_bwd(x, lab, l, coef, SOFT_GO, 255, has_ignore, bf16)
+                    r = X.dice_planar_ratios(dr, l, coef, loss, d, bf16)
+                    print('SOFT_MARGIN_EMU dice %-12s ign%d s%.0f cap%d %-4s' % (SOFT_IDS(shape), has_ignore, smooth, cap, 'bf16' if bf16 else 'f32'), r)
+                    assert max(r.values()) <= 1, (shape, has_ignore, smooth, cap, bf16, r)
+                    if not bf16:
+                        assert max(r[k] for k in ('a', 'b', 'loss', 'grad')) <= 0.5, (shape, has_ignore, smooth, cap, r)
+                        assert _half_but_last(l, dr.lse, dr.lse_bound, 1), (shape, r)
+
+
+# (defect, shape, gamma, variant, bf16 gradient): the elementwise bound fails there while the old whole-tensor criterion passes
+SOFT_FOCAL_DEFECT_CASES = (('q_one_minus_p', (2, 2, 8), 0.5, 1, False),           # the lead-by-16 pixel: q ~ 1e-7, 1 - p is 0 or 2^-24 steps
+                           ('no_log1p', (2, 2, 8), 0.5, 1, False),                # the same pixel: log(fl(1 + so)) loses so's bits
+                           ('no_second_term', X.SOFT_BEHIND, 0.5, 0, True))
+
+
+@pytest.mark.parametrize('defect,shape,gamma,variant,bf16', SOFT_FOCAL_DEFECT_CASES)
+def test_focal_emulation_with_one_defect_fails_the_elementwise_bound_where_the_old_criterion_passes(defect, shape, gamma, variant, bf16):
+    x, lab, _, ref = _planar(shape)
+    fr = X.FocalPlanarRef(ref, gamma, variant, SOFT_ALPHA, SOFT_GO)
+    _, g64, f32_bound = _restated(softloss_ref.focal_loss, x, lab, float(np.float32(SOFT_ALPHA)), gamma, 255, SOFT_VARIANTS[variant])
+    out = {}
+    for dfc in (None, defect):
+        l, a, loss, scale = SE.focal_fwd(x, lab, gamma, variant, SOFT_ALPHA, defect=dfc)
+        d = SE.focal_bwd(x, lab, l, a, scale, SOFT_GO, bf16)
+        out[dfc] = (X.focal_planar_ratios(fr, l, a, loss, scale, d, bf16), _old_planar_criterion(d, g64 * (fr.scale * fr.nvalid / float(np.float32(SOFT_ALPHA))), f32_bound, bf16))
+        print('defect %-15s' % dfc, out[dfc])
+    (r0, (e0, b0)), (r1, (e1, b1)) = out[None], out[defect]
+    assert max(r0['lse'], r0['coef'], r0['loss'], r0['grad']) <= 1 and e0 <= b0
+    assert r1['coef'] > 1, (defect, r1)
+    assert e1 <= b1, (defect, e1, b1)
+
+
+def test_dice_emulation_that_skips_the_last_group_fails_the_coefficient_bounds_where_the_old_criterion_passes():
+    """375 groups, one full block and a ragged one: the statistics lose 8 of 3000 pixels, every coefficient moves by a few parts in a
+    thousand and with it every gradient element -- inside 2e-2 of the largest for a bf16 gradient, far outside da, db and the
+    elementwise bound"""
+    shape, smooth, bf16 = (3, 19, 1000), 0.0, True
+    x, lab, _, ref = _planar(shape)
+    dr = X.DicePlanarRef(ref, smooth, SOFT_GO)
+    _, g64, f32_bound = _restated(softloss_ref.dice_loss, x, lab, shape[1], smooth, 255)
+    out = {}
+    for dfc in (None, 'skip_last_group'):
+        l, coef, loss, _ = SE.dice_fwd(x, lab, smooth, defect=dfc)
+        d = SE.dice_bwd(x, lab, l, coef, SOFT_GO, bf16=bf16)
+        out[dfc] = (X.dice_planar_ratios(dr, l, coef, loss, d, bf16), _old_planar_criterion(d, g64, f32_bound, bf16))
+        print('defect %-15s' % dfc, out[dfc])
+    (r0, (e0, b0)), (r1, (e1, b1)) = out[None], out['skip_last_group']
+    assert max(r0.values()) <= 1 and e0 <= b0
+    assert r1['a'] > 1 and r1['b'] > 1 and r1['grad'] > 1 and r1['loss'] > 1 and e1 <= b1
+
+
+def test_focal_coef_emulation_meets_the_bound_and_a_leaked_coef_is_seen():
+    """focal_coef_kernel's emulation on the hand-made cross-entropies (0, a denormal, 2^-24, 1, 40, 200 among multiples of 2^-4) for
+    every gamma and both variants, every n with its tail group; a coef left at a pixel that does not count is not an exact 0"""
+    for n in X.SOFT_CE_N:
+        ce, lab = X.soft_ce_operands(n)
+        assert tuple(ce[:min(n, 6)].astype(np.float64)) == tuple(np.float32(X.SOFT_CE_VALUES[:min(n, 6)]).astype(np.float64))
+        for gamma in X.SOFT_GAMMAS:
+            for variant in (0, 1):
+                r = X.focal_coef_ref(ce, lab, 19, gamma, variant, SOFT_ALPHA)
+                cf, loss, scale = SE.focal_coef_from_ce(ce, lab, 19, gamma, variant, SOFT_ALPHA)
+                assert (cf[~r['valid']] == 0).all() and float(scale) == r['scale']
+                assert X.worst_ratio(np.abs(cf - r['coef']), r['coef_bound']) <= 1, (n, gamma, variant)
+                assert X.worst_ratio(abs(float(loss) - r['loss']), r['loss_bound']) <= 1, (n, gamma, variant)
+    ce, lab = X.soft_ce_operands(1027)
+    r = X.focal_coef_ref(ce, lab, 19, 2.0, 0, SOFT_ALPHA)
+    assert 0 < (~r['valid']).sum() < 200 and r['nvalid'] + (~r['valid']).sum() == 1027
+    cf = SE.focal_coef_from_ce(ce, lab, 19, 2.0, 0, SOFT_ALPHA, defect='leak')[0]
+    assert (cf[~r['valid']] != 0).any() and X.worst_ratio(np.abs(cf - r['coef']), r['coef_bound']) == float('inf')
+
+
+def test_a_coef_leaked_at_an_ignored_pixel_fails_the_exact_zero_check_where_the_old_criterion_passes():
+    """the wide route on c33: tss_focal_coef_from_ce's emulation on the case's own cross-entropies (an exact 0 where the pixel does
+    not count, as tss_upsample_pixel_ce_wide stores it) with the coef of those pixels left as computed -- w(q = 0) = 1 at gamma = 2,
+    variant 0.  The MODE 5 instance of wide_ce_kernel gates both halves of its gradient on the label (`valid`, `inv = valid ? wsm :
+    0`), which HeadRef.weights(pixw=...) restates: the leaked values never reach the gathered gradient, so the old whole-tensor
+    criterion passes with error 0 and only the new per-pixel exact-0 check sees the defect.  Both halves asserted"""
+    import copy
+    c = X.HEAD_BY_NAME['c33']
+    x, labels, _, ref = _head(c)
+    ce = ref.pix.float().reshape(-1).numpy()
+    lab = labels.reshape(-1).numpy()
+    r = X.focal_coef_ref(ce, lab, c.C, 2.0, 0, SOFT_ALPHA)
+    assert np.array_equal(r['valid'], ref.valid.reshape(-1).numpy()) and (ce[~r['valid']] == 0).all() and (~r['valid']).sum() > 5
+    g = {}
+    for dfc in (None, 'leak'):
+        cf, _, scale = SE.focal_coef_from_ce(ce, lab, c.C, 2.0, 0, SOFT_ALPHA, defect=dfc)
+        zero_ok = bool((cf[~r['valid']] == 0).all())
+        within = X.worst_ratio(np.abs(cf - r['coef']), r['coef_bound']) <= 1
+        g[dfc] = copy.copy(ref).weights(pixw=torch.from_numpy(cf.astype(np.float64)).reshape(labels.shape), grad_out=SOFT_GO * float(scale)).g.numpy()
+        assert (zero_ok and within) == (dfc is None), (dfc, zero_ok, within)
+        if dfc == 'leak':
+            assert (cf[~r['valid']] == 1).all()
+    old = cases.rel_err(g['leak'], g[None])
+    assert old == 0.0 and old <= 2e-5 and np.abs(g[None]).max() > 0
+    assert X.soft_grid(1, 8 * X.cdiv(1027, 4), 0, 4096)[0] == 2                   # 257 groups of 4: two blocks, the second of one lane
+
+
+# --- soft Dice and focal on the fused head (csrc/softhead.hip)
+HEAD_SOFT_EMU = HEAD_EMU + [X.HEAD_SOFT_EXTRA]
+HEAD_FULL_BLOCK = ('one_lane_strip', 'no_table', 'identity', 'prod')       # W >= 256: a block with every lane live
+_head_soft_refs = {}
+
+
+def _head_soft(c, rare=False, ignore_index=255):
+    key = (c.name, rare, ignore_index)
+    if key not in _head_soft_refs:
+        x, labels, _ = X.head_soft_inputs(c, rare)
+        _head_soft_refs[key] = (x, labels, X.HeadRef(x, labels, ignore_index=ignore_index, weighted=False))
+    return _head_soft_refs[key]
+
+
+def _head_dice_emu(c, smooth, rare=False, ignore_index=255, defect=None, bf16=False):
+    """(HeadDiceRef, ratios of a, b, loss, gradient; N exact; the old whole-tensor error of the gradient)"""
+    x, labels, ref = _head_soft(c, rare, ignore_index)
+    d = X.dice_ref(ref, smooth, SOFT_GO, c.counts())
+    kw = dict(ignore_index=ignore_index, defect=defect)
+    st = HE.ce_pass(x.numpy(), labels.numpy(), c.H, c.W, mode='dice_stats', **kw)['stats']
+    coef, loss = HE.dice_finalize(st, c.C, smooth)
+    dl = HE.ce_pass(x.numpy(), labels.numpy(), c.H, c.W, mode='dice_grad', coef=coef, grad_out=SOFT_GO, **kw)['dlow']
+    dl = SE.to_bf16(dl) if bf16 else dl
+    C, g = c.C, d.g.numpy()
+    r = dict(a=X.worst_ratio(np.abs(coef[:C] - d.a), d.da), b=X.worst_ratio(np.abs(coef[24:24 + C] - d.b), d.db),
+             loss=X.worst_ratio(abs(float(loss) - d.loss), d.loss_bound), grad=X.worst_ratio(np.abs(dl - g), d.grad_bound(bf16).numpy()))
+    assert (coef[C:24] == 0).all() and (coef[24 + C:] == 0).all()
+    return d, r, np.array_equal(st[2], d.N), cases.rel_err(dl.astype(np.float64), g)
+
+
+def test_head_soft_cases_reach_what_they_are_listed_for():
+    for c in HEAD_SOFT_EMU:
+        x, labels, ref = _head_soft(c)
+        if c.C >= 5:
+            n = torch.zeros(c.C).scatter_add_(0, ref.t[ref.valid], torch.ones(int(ref.valid.sum())))
+            assert n[1] == 0 and n[2] == 1, c                                            # an absent class, a class of one pixel
+        assert X.head_cp(c.C) - c.C == {5: 15, 19: 1, 20: 0, 21: 3, 24: 0}[c.C]          # pad classes or none
+    c = X.HEAD_BY_NAME['cp24']
+    x, labels, ref = _head_soft(c, rare=True)
+    p = torch.softmax(ref.z, 1)
+    assert float(p[:, 20:].max()) < 1e-7 and not ((ref.t >= 20) & ref.valid).any() and (labels == 255).any()
+    assert X.HEAD_SOFT_EXTRA.W % X.HEAD_NT == X.HEAD_NT - 1                              # one lane past the image edge
+    _, labels, ref = _head_soft(c, ignore_index=None)
+    assert ref.valid[labels == 255].sum() == 0 and ref.valid.sum() == ((labels >= 0) & (labels < c.C)).sum()
+
+
+@pytest.mark.parametrize('c', HEAD_SOFT_EMU, ids=repr)
+def test_head_dice_f32_emulation_meets_the_bounds(c):
+    """the emulated statistics pass, finalize and gradient pass + gather within da, db, the loss bound and the elementwise gradient
+    bound for smooth 0 and 1, with and without the ignore index, and on the rare-class operands; N_c exact; the full-block cases at
+    no more than half of every bound"""
+    for smooth, rare, ign in ((0.0, False, 255), (1.0, False, 255), (1.0, False, None)) + (((1.0, True, 255),) if c.C > 20 else ()):
+        for bf16 in (False, True):
+            d, r, n_exact, _ = _head_dice_emu(c, smooth, rare, ign, bf16=bf16)
+            print('SOFT_MARGIN_EMU head_dice %-14s s%.0f rare%d ign%s %-4s' % (c.name, smooth, rare, ign, 'bf16' if bf16 else 'f32'), r)
+            assert n_exact and max(r.values()) <= 1, (c, smooth, rare, ign, bf16, r)
+            if c.name in HEAD_FULL_BLOCK and not bf16:
+                assert max(r.values()) <= 0.5, (c, r)
+
+
+# (defect, case, rare operands): the elementwise bound fails while the old whole-tensor criterion of a bf16 gradient (2e-2) passes
+HEAD_DICE_DEFECTS = (('b_from_a', 'cp24', True),          # classes 20 .. 23 carry p < 1e-7: their planes are invisible next to the largest element
+                     ('pad_in_S', 'near', False),
+                     ('edge_N', 'edge_few', False))         # one lane past the edge: N_c moves by at most 9 of ~120
+
+
+@pytest.mark.parametrize('defect,name,rare', HEAD_DICE_DEFECTS)
+def test_head_dice_emulation_with_one_defect_fails_the_elementwise_bound_where_the_old_criterion_passes(defect, name, rare):
+    c = X.HEAD_SOFT_EXTRA if name == 'edge_few' else X.HEAD_BY_NAME[name]
+    _, r0, n0, old0 = _head_dice_emu(c, 1.0, rare, bf16=True)
+    _, r1, n1, old1 = _head_dice_emu(c, 1.0, rare, defect=defect, bf16=True)
+    print('defect %-9s %-9s new grad ratio %.2f (correct %.3f) | old %.3e (correct %.3e) <= 2e-2' % (defect, name, r1['grad'], r0['grad'], old1, old0))
+    assert max(r0.values()) <= 1 and n0 and old0 <= 2e-2
+    assert r1['grad'] > 1 and old1 <= 2e-2, (defect, r1, old1)
+    if defect == 'edge_N':
+        assert not n1 and r1['a'] > 1 and r1['b'] > 1
+
+
+def _head_focal_emu(c, gamma, variant, defect=None, bf16=False):
+    """(loss ratio, gradient ratio, scale exact, the old whole-tensor error of the gradient) of the emulated focal one-pass"""
+    key = (c.name, 'focal')
+    if key not in _head_soft_refs:
+        x, labels, plants = X.head_soft_inputs(c, focal=True)
+        _head_soft_refs[key] = (x, labels, X.HeadRef(x, labels, weighted=False), plants)
+    x, labels, ref, _ = _head_soft_refs[key]
+    f = X.HeadFocalRef(ref, gamma, variant, SOFT_ALPHA, SOFT_GO, c.counts())
+    o = HE.ce_pass(x.numpy(), labels.numpy(), c.H, c.W, mode='focal', gamma=gamma, variant=variant, alpha=SOFT_ALPHA, grad_out=SOFT_GO, defect=defect)
+    dl = SE.to_bf16(o['dlow']) if bf16 else o['dlow']
+    g = f.g.numpy()
+    return (X.worst_ratio(abs(float(o['loss']) - f.loss), f.loss_bound), X.worst_ratio(np.abs(dl - g), f.grad_bound(bf16).numpy()),
+            float(o['inv_count']) == f.scale, cases.rel_err(dl.astype(np.float64), g))
+
+
+def test_head_focal_plants_reach_every_branch():
+    c = X.HEAD_BY_NAME['identity']
+    x, labels, plants = X.head_soft_inputs(c, focal=True)
+    ref = X.HeadRef(x, labels, weighted=False)
+    assert [g for g, _, _ in plants] == [0.0, 0.25, 16.0, -16.0]
+    for gap, y, xo in plants:
+        z = ref.z[0, :, y, xo]
+        t = int(labels[0, y, xo])
+        assert bool(ref.valid[0, y, xo]) and float(z[t] - z[torch.arange(c.C) != t].max()) == gap
+    assert all(len(X.head_soft_inputs(k, focal=True)[2]) == (4 if k.exact and k.h * k.w >= 4 else 0) for k in HEAD_EMU)
+
+
+@pytest.mark.parametrize('c', HEAD_EMU, ids=repr)
+def test_head_focal_f32_emulation_meets_the_bounds(c):
+    """loss, scale and every element of the gathered gradient of the emulated focal one-pass for gamma in {0, 0.5, 2} x both variants,
+    f32 and bf16 gradient; the full-block cases at no more than half of the bounds"""
+    for gamma in X.SOFT_GAMMAS:
+        for variant in (0, 1):
+            for bf16 in (False, True):
+                rl, rg, exact_scale, _ = _head_focal_emu(c, gamma, variant, bf16=bf16)
+                print('SOFT_MARGIN_EMU head_focal %-14s g%.1f v%d %-4s loss %.4f grad %.4f' % (c.name, gamma, variant, 'bf16' if bf16 else 'f32', rl, rg))
+                assert exact_scale and rl <= 1 and rg <= 1, (c, gamma, variant, bf16, rl, rg)
+                if c.name in HEAD_FULL_BLOCK and not bf16:
+                    assert rl <= 0.5 and rg <= 0.5, (c, gamma, variant, rl, rg)
+
+
+# (defect, case, gamma, variant, bf16 gradient)
+HEAD_FOCAL_DEFECTS = (('q_one_minus_p', 'identity', 2.0, 1, False), ('no_log1p', 'identity', 0.5, 1, False), ('no_second_term', 'h1', 0.5, 0, True))
+
+
+@pytest.mark.parametrize('defect,name,gamma,variant,bf16', HEAD_FOCAL_DEFECTS)
+def test_head_focal_emulation_with_one_defect_fails_the_gradient_bound_where_the_old_criterion_passes(defect, name, gamma, variant, bf16):
+    """the old criterion: cases.rel_err over the whole gathered gradient <= 2e-5 (the floor of max(2e-5, 3 d_ref): the strictest it can
+    be) in f32, 2e-2 in bf16"""
+    c = X.HEAD_BY_NAME[name]
+    old_bound = 2e-2 if bf16 else 2e-5
+    rl0, rg0, _, old0 = _head_focal_emu(c, gamma, variant, bf16=bf16)
+    rl1, rg1, _, old1 = _head_focal_emu(c, gamma, variant, defect=defect, bf16=bf16)
+    print('defect %-15s %-9s new grad ratio %.2f (correct %.3f) | old %.3e (correct %.3e) <= %.0e' % (defect, name, rg1, rg0, old1, old0, old_bound))
+    assert rg0 <= 1 and rl0 <= 1 and old0 <= old_bound
+    assert rg1 > 1 and old1 <= old_bound, (defect, rg1, old1)
