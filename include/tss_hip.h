@@ -1034,6 +1034,37 @@ int tss_classmix_select(const unsigned char* label, const unsigned int* keys, un
 int tss_mix_batch(const void* image, const unsigned char* label, const int* partner, const unsigned char* sel, const int* boxes,
                   void* image_out, long long* target_out, long B, int Ci, int H, int W, int dtype, void* stream);
 
+/* ---- per-sample loss groups on the fused head (csrc/groupce.hip) ---------------------------------------------------------
+ * L = sum_g L_g,  L_g = (sum_{b in g} lambda_b S_b) / N_g,  N_g = sum_{b in g} n_b, where (S_b, n_b) are the sums of the loss
+ * rows of sample b (sum of the per-pixel loss, sum of the valid pixels' weights): every group is normalised over its own pixels,
+ * e.g. L_sup + lambda L_unsup of a self-training step from ONE head pass.
+ *   tss_upsample_ce_group_finalize runs AFTER tss_upsample_ce_fwd / _fwd_ex (wide = 0) or tss_upsample_ce_wide_fwd (wide = 1) has
+ *     filled ws with the same B, C, h, w, H, W (those entries' own loss / inv_count go to scratch words).  One block, f64, a fixed
+ *     order (sample sums: lane l of a wave adds rows l, l + 64, ..., then a butterfly; groups: ascending b; loss: ascending g), no
+ *     atomics, no host read-back: capturable.  All in DEVICE memory: group int32 [B] with ids in [0, B); weight float [B] =
+ *     lambda_b, NULL: all ones; *loss = (float) sum_g L_g; group_loss[g] = (float) L_g for g in [0, B), 0 for an id no sample
+ *     uses; scale[b] = (float)(lambda_b / N_g(b)).  An EMPTY group (N_g = 0, or not > 0) gives L_g = 0 and scale 0, i.e. a zero
+ *     gradient -- the rule of the focal and Dice operators, NOT the nan of the ungrouped mean.  A sample whose id lies outside
+ *     [0, B) belongs to no group and gets scale 0 (nothing is indexed by it).  0 * nan is nan: a sample of weight 0 whose logits hold
+ *     nan still poisons its group.  B <= tss_upsample_ce_group_max_batch() (1024: the block's LDS tables).
+ *   tss_upsample_ce_bwd_rows / tss_upsample_ce_wide_bwd_rows: tss_upsample_ce_bwd / _wide_bwd with scale[b] (float [B]) in place
+ *     of *inv_count: dlow[b] = (T)(scale[b] * grad_out * sum of the tiles), one product scale[b] * grad_out first, as there.
+ *   tss_selftrain_weights: the rows of a self-training batch of B labelled + B unlabelled samples, one small block:
+ *     group[i] = i < B ? 0 : 1,  weight[i] = i < B ? 1 : u, with u = *lam (mode 0) or, mode 1,
+ *     u = (float)((double)*lam * (double)(sum_b kept[b]) / ((double)B * (double)n_pixels)) -- the batch's share of kept pixels;
+ *     the sum is an integer sum.  kept: DEVICE int64 [B] (may be NULL in mode 0), lam: DEVICE float [1].  1 <= B <= 512.
+ * Contract (else TSS_ERR_SHAPE, nothing launched): the head's shape rules with its class caps (24 / 256), no NULL pointer but
+ * weight and grad_out, the batch caps above, mode 0 or 1, n_pixels >= 1.  ws / dlow off 16 bytes: TSS_ERR_ALIGN. */
+int tss_upsample_ce_group_max_batch(void);
+int tss_upsample_ce_group_finalize(const float* ws, int B, int C, int h, int w, int H, int W, int wide, const int* group,
+                                   const float* weight, float* loss, float* scale, float* group_loss, void* stream);
+int tss_upsample_ce_bwd_rows(const float* ws, const float* scale, const float* grad_out, void* dlow, long ldl,
+                             int B, int C, int h, int w, int H, int W, int dtype, void* stream);
+int tss_upsample_ce_wide_bwd_rows(const float* ws, const float* scale, const float* grad_out, void* dlow, long ldl,
+                                  int B, int C, int h, int w, int H, int W, int dtype, void* stream);
+int tss_selftrain_weights(const long long* kept, long n_pixels, const float* lam, int mode, int* group, float* weight, int B,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ from .ops import OHEMLoss, ohem_loss, Upsample  # noqa: F401
 from .ops import LovaszSoftmaxFn, LovaszSoftmaxLoss, lovasz_softmax_loss  # noqa: F401
 from .ops import FocalFn, FocalLoss, focal_loss, DiceFn, DiceLoss, dice_loss  # noqa: F401
 from .ops import upsample_focal_loss, upsample_dice_loss  # noqa: F401
+from .ops import UpsampleGroupedCrossEntropyFn, check_sample_groups  # noqa: F401
 from .ops import DistillFn, DistillationLoss, distillation_loss  # noqa: F401
 from .ops import label_histogram, enet_class_weights  # noqa: F401
 from .ops import TrainAugment, augment_batch, remap_labels  # noqa: F401

@@ -1,4 +1,4 @@
-// The band walk of the fused decoder head: what loss.hip, softhead.hip, widehead.hip and msflip.hip share.
+// The band walk of the fused decoder head: what loss.hip, softhead.hip, widehead.hip, msflip.hip and groupce.hip share.
 //
 // Block layout.  A block owns 256 consecutive output columns (a strip) x a band of output rows of one image; block index =
 //   (b * nband + band) * nstrip + strip (head_block); lane = one output column (head_taps: its column taps in a map).  The column taps
@@ -15,7 +15,8 @@
 //   weights are fixed per block: gather_windows before the block's first barrier, gather_weights after it), stores the sum into the
 //   tile, barrier, and the lane clears its part of Hh[k].  (LDS float atomics for the scatter were measured at ~180 cycles per wave
 //   instruction.)  An instance that never flushes compiles the tables and the flush out.
-// Who uses what.  Host geometry, head_gather and ce_finalize_rows_kernel: every file.  head_block / head_taps: softhead_pass_kernel,
+// Who uses what.  Host geometry, head_gather and ce_finalize_rows_kernel: every file (groupce.hip: the geometry and the gather with a
+//   scale per sample, head_gather's ROWS; its finalize is its own).  head_block / head_taps: softhead_pass_kernel,
 //   wide_upsample_argmax_kernel and the two multi-scale kernels.  load_row: softhead.hip and msflip.hip.  The tables and the flush:
 //   softhead_pass_kernel.  upsample_ce_onepass_kernel, upsample_argmax_kernel (loss.hip) and wide_ce_kernel keep these steps written
 //   out, and every kernel its own advance of the two-row window: the compiler's register allocation and its choice of which products
@@ -242,11 +243,12 @@ __device__ __forceinline__ void head_flush_row(const Gather& gt, const HeadGeom&
 // ---- the gather and the row finalize ---------------------------------------------------------------------------
 // dlow[b][r][cx][:] = (T)(grad_out / count * sum over the tiles that hold cell (r, cx), in (band, strip) order); thread = one
 // cell x 8 channels.  CPT: the tile pitch at compile time; 0, the wide head: geo.cp at run time, bands of WROWS rows.  Channels >= pitch
-// (padding) are written as zeros.
-template <typename T, int CPT>
+// (padding) are written as zeros.  ROWS (groupce.hip): inv_count is a row of B per-sample scales and sample b's cells take
+// inv_count[b] * grad_out; the instances without it are the text they were.
+template <typename T, int CPT, bool ROWS = false>
 __device__ __forceinline__ void head_gather(const float* tiles, const float* inv_count, const float* grad_out, T* dlow, long ldl, int B,
                                             int h, int w, int H, int W, const HeadGeom& geo) {
-  const float gs = (*inv_count) * (grad_out ? *grad_out : 1.f);
+  const float g0 = (ROWS ? 1.f : *inv_count) * (grad_out ? *grad_out : 1.f);   // ROWS: grad_out alone (1.f * x is x)
   const float sy = ac_scale(h, H), sx = ac_scale(w, W);
   constexpr bool WIDE = CPT == 0;          // the wide head also keeps three compares that always hold, as it always did
   const int cv = (int)(ldl / 8), cp = WIDE ? geo.cp : CPT, band_rows = WIDE ? WROWS : geo.band_rows;
@@ -278,6 +280,7 @@ __device__ __forceinline__ void head_gather(const float* tiles, const float* inv
         if (c8 + 8 <= cp) { float u[4]; V4<float>::load(t + 4, u); v[4] += u[0]; v[5] += u[1]; v[6] += u[2]; v[7] += u[3]; }
       }
     }
+    const float gs = ROWS ? inv_count[b] * g0 : g0;
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] *= gs;
     V8<T>::store(dlow + ((b * h + r) * (long)w + cx) * ldl + c8, v);

@@ -3036,8 +3036,32 @@ class CrossEntropyLoss(torch.nn.Module):
         self.label_smoothing = _check_smoothing(label_smoothing)
         weight = _class_weight(weight, None)
         self.register_buffer('weight', None if weight is None else weight.clone())
+        self.sample_group = self.sample_weight = self.group_loss_out = None
+
+    def set_sample_groups(self, group, weight=None, group_loss_out=None):
+        """Per-sample loss groups for every following call (upsample_cross_entropy's sample_group / sample_weight / group_loss_out):
+        each group is normalised over its own valid pixels and the loss is the sum of the groups' terms.  The module holds DEVICE
+        tensors (int32 [B], float32 [B]) that the kernels read, so an in-place update between replays of a captured step takes
+        effect without a re-capture; host sequences are validated and copied to the current device here.  The rows are plain
+        attributes, not buffers: they belong to a batch layout, not to the state dict."""
+        on_dev = torch.is_tensor(group) and group.is_cuda
+        batch = int(group.shape[0]) if on_dev else len(group)
+        host = [t is not None and not (torch.is_tensor(t) and t.is_cuda) for t in (group, weight)]
+        if host[0] or host[1]:
+            check_sample_groups(group if host[0] else list(range(batch)), weight if host[1] else None, batch)
+        dev = group.device if on_dev else (weight.device if torch.is_tensor(weight) and weight.is_cuda
+                                           else torch.device('cuda', torch.cuda.current_device()))
+        self.sample_group, self.sample_weight = _sample_rows(group, weight, batch, dev)
+        self.group_loss_out = group_loss_out
+
+    def clear_sample_groups(self):
+        self.sample_group = self.sample_weight = self.group_loss_out = None
 
     def forward(self, input, target):
+        if self.sample_group is not None:      # groups exist on the fused head: the same operator at the logits' own size
+            return upsample_cross_entropy(input, target, size=tuple(input.shape[2:]), ignore_index=self.ignore_index, weight=self.weight,
+                                          label_smoothing=self.label_smoothing, sample_group=self.sample_group,
+                                          sample_weight=self.sample_weight, group_loss_out=self.group_loss_out)
         return cross_entropy(input, target, self.ignore_index, self.weight, self.label_smoothing)
 
 
@@ -3726,12 +3750,146 @@ class UpsampleCrossEntropyFn(Function):
         return base.permute(0, 3, 1, 2)[:, :C], None, None, None, None, None, None
 
 
-def upsample_cross_entropy(low, target, scale_factor=None, size=None, ignore_index=-100, weight=None, label_smoothing=0.0):
+GROUP_MAX_BATCH = 1024       # tss_upsample_ce_group_max_batch(): the samples whose sums the grouped finalize keeps on chip
+
+
+def check_sample_groups(group, weight, batch):
+    """Host-side validation of per-sample loss groups, before anything touches the device: `group` a sequence of `batch` integers
+    in [0, batch), `weight` None or a sequence of `batch` finite, non-negative numbers.  Returns them as (int32 array, float32 array
+    or None); ValueError otherwise."""
+    import numpy as np
+    g = group.numpy() if torch.is_tensor(group) else np.asarray(group)
+    if g.ndim != 1 or g.shape[0] != batch:
+        raise ValueError('sample_group must have length B = %d, got shape %s' % (batch, tuple(g.shape)))
+    if g.dtype.kind not in 'iu':
+        raise ValueError('sample_group must hold integers, got %s' % g.dtype)
+    if g.size and (int(g.min()) < 0 or int(g.max()) >= batch):
+        raise ValueError('sample_group ids must lie in [0, %d), got [%d, %d]' % (batch, int(g.min()), int(g.max())))
+    if weight is None:
+        return g.astype(np.int32), None
+    w = weight.numpy() if torch.is_tensor(weight) else np.asarray(weight)
+    if w.dtype.kind not in 'fiu':
+        raise ValueError('sample_weight must hold numbers, got %s' % w.dtype)
+    w = w.astype(np.float64)
+    if w.ndim != 1 or w.shape[0] != batch:
+        raise ValueError('sample_weight must have length B = %d, got shape %s' % (batch, tuple(w.shape)))
+    if not np.isfinite(w).all() or (w < 0).any():
+        raise ValueError('sample_weight must be finite and non-negative, got %s' % (w.tolist(),))
+    return g.astype(np.int32), w.astype(np.float32)
+
+
+def _sample_rows(group, weight, batch, dev):
+    """The rows of a grouped loss as the kernels read them (int32 [B], float32 [B] or None).  Device tensors are taken as they are
+    (dtype, shape and contiguity checked, values not: the kernel gives an id outside [0, B) the weight 0), so an in-place update
+    reaches a captured step; host sequences are validated (check_sample_groups) and copied."""
+    on_dev = [torch.is_tensor(t) and t.is_cuda for t in (group, weight)]
+    host = check_sample_groups(list(range(batch)) if on_dev[0] else group, None if on_dev[1] else weight, batch)
+    rows = []
+    for t, is_dev, h, dtype, name in ((group, on_dev[0], host[0], torch.int32, 'sample_group'),
+                                      (weight, on_dev[1], host[1], torch.float32, 'sample_weight')):
+        if t is None:
+            rows.append(None)
+        elif is_dev:
+            if t.dtype != dtype or tuple(t.shape) != (batch,) or not t.is_contiguous() or t.device != dev:
+                raise ValueError('%s on the device must be a contiguous %s tensor of shape (%d,) on %s' % (name, dtype, batch, dev))
+            rows.append(t.detach())
+        else:
+            rows.append(torch.from_numpy(h).to(dev))
+    return rows
+
+
+class UpsampleGroupedCrossEntropyFn(Function):
+    """upsample_cross_entropy with per-sample loss groups: sum over the groups g of (sum_{b in g} lambda_b CE_sum(b)) / N_g, every
+    group normalised over its own valid pixels (their class weights).  The forward entry of UpsampleCrossEntropyFn runs as it is
+    (its own loss and 1 / count go to two scratch words); tss_upsample_ce_group_finalize turns its loss rows into the loss, the
+    per-group terms and one gradient scale per sample, and backward is the gather that reads its scale per sample.  f64 sums in a
+    fixed order, no atomics, no host read-back: the same bits on every run, capturable.  An empty group contributes 0 and a zero
+    gradient (the rule of focal_loss / dice_loss, not the nan of the ungrouped mean)."""
+
+    @staticmethod
+    def forward(ctx, low, target, ho, wo, ignore_index, weight, eps, rows):
+        group, sweight, group_loss = rows
+        B, C, h, w = low.shape
+        dev = low.device
+        target = target.contiguous()
+        nws = getattr(N.lib(), 'tss_upsample_ce%s_ws' % _wide(C))(B, C, h, w, ho, wo)
+        ws = torch.empty(nws, dtype=torch.float32, device=dev)
+        scratch = torch.empty(2, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        scale = torch.empty(B, dtype=torch.float32, device=dev)
+        head = (B, C, h, w, ho, wo, int(ignore_index), N.dtype_code(low.dtype), stream())
+        if _wide(C):
+            call('tss_upsample_ce_wide_fwd', ptr(low), ld(low), ptr(target), ptr(weight), eps, ptr(ws), ptr(scratch[0:1]),
+                 ptr(scratch[1:2]), *head)
+        elif weight is None and eps == 0.0:
+            call('tss_upsample_ce_fwd', ptr(low), ld(low), ptr(target), ptr(ws), ptr(scratch[0:1]), ptr(scratch[1:2]), *head)
+        else:
+            call('tss_upsample_ce_fwd_ex', ptr(low), ld(low), ptr(target), ptr(weight), eps, ptr(ws), ptr(scratch[0:1]),
+                 ptr(scratch[1:2]), *head)
+        call('tss_upsample_ce_group_finalize', ptr(ws), B, C, h, w, ho, wo, 1 if _wide(C) else 0, ptr(group), ptr(sweight), ptr(loss),
+             ptr(scale), ptr(group_loss), stream())
+        ctx.geom = (B, C, h, w, ho, wo, ld(low), low.dtype)
+        ctx.save_for_backward(ws, scale)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        ws, scale = ctx.saved_tensors
+        B, C, h, w, ho, wo, ldl, dtype = ctx.geom
+        gout = gout.to(torch.float32).contiguous()
+        base = torch.empty((B, h, w, ldl), dtype=dtype, device=ws.device)   # pad channels are written as zeros
+        call('tss_upsample_ce%s_bwd_rows' % _wide(C), ptr(ws), ptr(scale), ptr(gout), ptr(base), ldl, B, C, h, w, ho, wo,
+             N.dtype_code(dtype), stream())
+        return base.permute(0, 3, 1, 2)[:, :C], None, None, None, None, None, None, None
+
+
+def _upsample_grouped_cross_entropy(low, target, scale_factor, size, ignore_index, weight, eps, sample_group, sample_weight,
+                                    group_loss_out):
+    B = low.shape[0]
+    if not 1 <= B <= GROUP_MAX_BATCH:
+        raise ValueError('sample groups take a batch of 1 to %d samples, got %d' % (GROUP_MAX_BATCH, B))
+    host = [t is not None and not (torch.is_tensor(t) and t.is_cuda) for t in (sample_group, sample_weight)]
+    if host[0] or host[1]:      # host sequences: refused here, before the first device access
+        check_sample_groups(sample_group if host[0] else list(range(B)), sample_weight if host[1] else None, B)
+    ho, wo = _out_size(low, size, scale_factor)
+    if low.shape[1] > WIDEHEAD_MAX_CLASSES or ho < low.shape[2] or wo < low.shape[3]:
+        raise ValueError('sample groups exist on the fused head only (at most %d classes, an output no smaller than the map): got %d '
+                         'classes, %dx%d -> %dx%d' % (WIDEHEAD_MAX_CLASSES, low.shape[1], low.shape[2], low.shape[3], ho, wo))
+    low = to_nhwc(materialize(low))
+    _check_head_target(low, target, ho, wo)
+    dev = low.device
+    group, sweight = _sample_rows(sample_group, sample_weight, B, dev)
+    if group_loss_out is None:
+        group_loss_out = torch.empty(B, dtype=torch.float32, device=dev)
+    elif not (torch.is_tensor(group_loss_out) and group_loss_out.dtype == torch.float32 and tuple(group_loss_out.shape) == (B,)
+              and group_loss_out.is_contiguous() and group_loss_out.device == dev):
+        raise ValueError('group_loss_out must be a contiguous float32 tensor of shape (%d,) on %s' % (B, dev))
+    return UpsampleGroupedCrossEntropyFn.apply(low, target, ho, wo, ignore_index, _class_weight(weight, low.shape[1], dev), eps,
+                                               (group, sweight, group_loss_out))
+
+
+def upsample_cross_entropy(low, target, scale_factor=None, size=None, ignore_index=-100, weight=None, label_smoothing=0.0,
+                           sample_group=None, sample_weight=None, group_loss_out=None):
     """Fused decoder head + loss:
     F.cross_entropy(F.interpolate(low, scale_factor, mode='bilinear', align_corners=True), target, weight=weight,
     ignore_index=ignore_index, label_smoothing=label_smoothing)
-    computed from the low-resolution logits; the full-resolution logits are never materialised."""
+    computed from the low-resolution logits; the full-resolution logits are never materialised.
+
+    sample_group (B ids in [0, B)) splits the batch into loss groups, each normalised over its OWN valid pixels:
+        loss = sum_g (sum_{b in g} sample_weight[b] * CE_sum(b)) / N_g,    N_g = sum_{b in g} (valid pixels' class weights of b)
+    e.g. L_sup + lambda * L_unsup of a self-training batch from one head pass.  sample_weight: B non-negative numbers, None = ones.
+    group_loss_out: a float32 [B] device tensor that receives the term of every group id (0 for an id no sample uses).  An empty
+    group (no valid pixel) contributes 0.0 and a zero gradient -- the rule of focal_loss and dice_loss, NOT the nan of the
+    ungrouped mean.  Host sequences are validated before they are copied (ValueError: a wrong length, an id outside [0, B), a
+    negative or non-finite weight); device tensors (int32 / float32 [B]) are taken as they are and read by the kernels, so an
+    in-place update reaches a captured step (an id outside [0, B) then gives its sample the weight 0).  Grouping exists on the
+    fused head only: more than 256 classes or an output smaller than the map is a ValueError, there is no unfused route."""
     eps = _check_smoothing(label_smoothing)
+    if sample_group is not None:
+        return _upsample_grouped_cross_entropy(low, target, scale_factor, size, ignore_index, weight, eps, sample_group,
+                                               sample_weight, group_loss_out)
+    if sample_weight is not None or group_loss_out is not None:
+        raise ValueError('sample_weight and group_loss_out need sample_group')
     low = to_nhwc(materialize(low))
     ho, wo = _out_size(low, size, scale_factor)
     if low.shape[1] > WIDEHEAD_MAX_CLASSES or ho < low.shape[2] or wo < low.shape[3]:

@@ -167,13 +167,31 @@ class SelfTraining:
     seeded by `seed`) and the threshold (`set_threshold`) live in device memory and are read by the kernels, so one graph serves every
     draw and a threshold schedule.  `last_kept` is the per-sample count of kept pseudo-labels of the last step (a device tensor).
 
-    Weighting: the loss is the trainer's mean over the valid pixels of all 2B samples, so the unlabelled half weighs in by its share
-    of kept pixels.  A separate weight lambda for the unlabelled term needs two head losses and is not offered here.
+    Weighting: with unsup_weight=None the loss is the trainer's mean over the valid pixels of all 2B samples, so the unlabelled half
+    weighs in by its share of kept pixels.  unsup_weight=lambda (a float >= 0) makes it L = L_sup + lambda * L_unsup, each term a mean
+    over its OWN valid pixels, from the same single head pass (per-sample loss groups, ops.upsample_cross_entropy's sample_group):
+    the prologue writes the rows of the batch (tss_selftrain_weights: labelled half group 0 / weight 1, unlabelled half group 1 /
+    weight lambda) and the trainer's CrossEntropyLoss reads them.  lambda lives in device memory: `set_unsup_weight` moves it from the
+    next step on, captured or eager, so a ramp-up needs no re-capture.  unsup_weighting='kept_share' multiplies lambda by the batch's
+    share of confident pixels, sum_b last_kept[b] / (B * H * W), the weight of ClassMix and DACS -- from the counts BEFORE mixing
+    (last_kept), where ClassMix's own code counts the mixed pseudo-label map; the two differ by what the pasted classes cover.  An
+    unlabelled half with no kept pixel contributes 0 and a zero gradient.  `last_group_loss` (device, float32 [2]) holds the two terms
+    of the last step: L_sup and the weighted lambda * L_unsup; their sum is the returned loss.  Needs a trainer whose loss is
+    tssa.CrossEntropyLoss on the fused-head route (ValueError otherwise) and B <= 512.
     Data parallel needs nothing extra: every rank draws its own rows (give the ranks different seeds)."""
 
-    def __init__(self, trainer, teacher, num_classes, threshold=0.95, mix='classmix', cut_area=(0.25, 0.5), ignore_index=255, seed=0):
+    def __init__(self, trainer, teacher, num_classes, threshold=0.95, mix='classmix', cut_area=(0.25, 0.5), ignore_index=255, seed=0,
+                 unsup_weight=None, unsup_weighting='mean'):
         if mix not in ('classmix', 'cutmix', None):
             raise ValueError("mix must be 'classmix', 'cutmix' or None, got %r" % (mix,))
+        if unsup_weighting not in ('mean', 'kept_share'):
+            raise ValueError("unsup_weighting must be 'mean' or 'kept_share', got %r" % (unsup_weighting,))
+        self.unsup_weighting = unsup_weighting
+        self._lam0 = None if unsup_weight is None else self._check_lambda(unsup_weight)
+        if self._lam0 is not None and not (type(trainer.loss_fn) is ops.CrossEntropyLoss and trainer.fuse_head_loss
+                                           and not (trainer.model._forward_hooks or trainer.model._forward_pre_hooks)):
+            raise ValueError('SelfTraining(unsup_weight=...): the trainer must run tssa.CrossEntropyLoss on the fused-head route '
+                             '(a model with forward_lowres and no forward hooks), got %s' % type(trainer.loss_fn).__name__)
         if not hasattr(teacher, 'forward_lowres'):
             raise NotImplementedError('SelfTraining: the teacher (%s) has no forward_lowres()' % type(teacher).__name__)
         if not 1 <= int(num_classes) <= 255 or not int(num_classes) <= int(ignore_index) <= 255:
@@ -213,6 +231,14 @@ class SelfTraining:
         self.sel = torch.zeros((B, 256), dtype=torch.uint8, device=dev)
         self.threshold = torch.full((1,), self._threshold0, dtype=torch.float32, device=dev)
         self.last_kept = torch.zeros(B, dtype=torch.int64, device=dev)
+        if self._lam0 is not None:
+            if 2 * B > ops.GROUP_MAX_BATCH:
+                raise ValueError('SelfTraining(unsup_weight=...) takes at most %d labelled samples, got %d' % (ops.GROUP_MAX_BATCH // 2, B))
+            self.group = torch.zeros(2 * B, dtype=torch.int32, device=dev)
+            self.weight = torch.ones(2 * B, dtype=torch.float32, device=dev)
+            self.lam = torch.full((1,), self._lam0, dtype=torch.float32, device=dev)
+            self._group_loss = torch.zeros(2 * B, dtype=torch.float32, device=dev)
+            self.last_group_loss = self._group_loss[:2]         # L_sup, lambda * L_unsup
         if self.trainer.use_graph:
             self.trainer.static_batch(self.x_all, self.y_all, self.slot, adopt=True)
 
@@ -221,6 +247,21 @@ class SelfTraining:
         self._threshold0 = float(value)
         if self.x_all is not None:
             self.threshold.fill_(float(value))
+
+    @staticmethod
+    def _check_lambda(value):
+        v = float(value)
+        if not (v >= 0.0 and v != float('inf')):
+            raise ValueError('unsup_weight must be a finite number >= 0, got %r' % (value,))
+        return v
+
+    def set_unsup_weight(self, value):
+        """lambda of L_sup + lambda * L_unsup from the next step on (the prologue's kernel reads it from device memory)."""
+        if self._lam0 is None:
+            raise ValueError('set_unsup_weight needs a SelfTraining built with unsup_weight')
+        self._lam0 = self._check_lambda(value)
+        if self.x_all is not None:
+            self.lam.fill_(self._lam0)
 
     def draw(self):
         """The rows of one step as host arrays: (partner int32 [B], keys uint32 [B,256], boxes int32 [B,4])."""
@@ -251,6 +292,11 @@ class SelfTraining:
                 call('tss_classmix_select', ptr(self.pseudo), ptr(self.keys), ptr(self.sel), B, H * W, self.num_classes, stream())
             mix_batch(self.xu, self.pseudo, self.partner, sel=self.sel if self.mix == 'classmix' else None,
                       boxes=None if self.mix == 'classmix' else self.boxes, out_image=self.x_all[B:], out_target=self.y_all[B:])
+            if self._lam0 is not None:
+                call('tss_selftrain_weights', ptr(self.last_kept), H * W, ptr(self.lam), 1 if self.unsup_weighting == 'kept_share' else 0,
+                     ptr(self.group), ptr(self.weight), B, stream())
+                loss_fn = self.trainer.loss_fn
+                loss_fn.sample_group, loss_fn.sample_weight, loss_fn.group_loss_out = self.group, self.weight, self._group_loss
 
     def step(self, x, y, xu):
         """One self-training step on the labelled batch (x, y) and the unlabelled frames xu; returns the loss as a device tensor."""
