@@ -1065,6 +1065,34 @@ int tss_upsample_ce_wide_bwd_rows(const float* ws, const float* scale, const flo
 int tss_selftrain_weights(const long long* kept, long n_pixels, const float* lam, int mode, int* group, float* weight, int B,
                           void* stream);
 
+/* ---- photometric strong augmentation: colour jitter and Gaussian blur of a normalised batch (csrc/strongaug.hip) ----------
+ * image, out: [B][3][H][W] (TSS_F32 | TSS_BF16), normalised with mean3 / std3 (HOST float[3], NULL: 0 / 1).  Per sample, in DEVICE
+ * memory: color float [B][8] = (apply, fb, fc, fs, dh, 0, 0, 0), radius int32 [B] = R, taps float [B][12] = (w_0 .. w_8, 0, 0, 0).
+ *   apply == 0 and R == 0: out[b] = image[b] on bits.  Otherwise per pixel, in f32 (a bf16 input is widened exactly):
+ *   u_c = x_c std_c + mean_c;  if apply != 0, in this order
+ *     brightness  u = clamp(u fb, 0, 1)
+ *     contrast    u = clamp(m + fc (u - m), 0, 1), m = the mean over the sample's H W pixels of grey = 0.299 r + 0.587 g + 0.114 b
+ *                 AFTER brightness: grey per pixel in f32, summed in f64 into 64 partial rows per sample (ws) that are added in a
+ *                 fixed order (no atomics), m rounded to f32 once
+ *     saturation  u = clamp(grey(u) + fs (u - grey(u)), 0, 1)
+ *     hue         hsv_shift of tss_augment_batch_u8_ex with ds = dv = 0 and a shift of 180 dh (dh in [-0.5, 0.5] of a turn) on
+ *                 255 u, the result divided by 255
+ *   blur, if R > 0: v(y, x) = sum_{k=-R..R} w_|k| u(y, refl(x + k)), horizontal then vertical, refl = mirror reflection that does not
+ *     repeat the edge pixel (-1 -> 1, W -> W - 2); the value between the passes stays f32 on chip; nothing is clamped after it
+ *   x' = v (1 / std_c) - mean_c / std_c, both constants formed on the host in f32; stored as f32 or rounded once to bf16.
+ * The rows are NOT validated: R is clamped into [0, 8] and dh into [-0.5, 0.5].  Two launches (statistics, tiles of
+ * TSS_STRONGAUG_TH x TSS_STRONGAUG_TW outputs), no float atomics, no host read-back: capturable, the same bits on every run.
+ * Contract (else TSS_ERR_SHAPE, nothing launched): Ci == 3, W % 8 == 0, W >= 16, H >= 9 (R = 8 reflects inside the image),
+ * H, W <= 32768, B <= 65535, no NULL pointer but mean3 / std3, out != image.  image / out off 16 bytes, ws off 8: TSS_ERR_ALIGN.
+ * B == 0: TSS_OK without a launch.  tss_strong_augment_ws: the bytes of ws for that shape (-1 outside the contract);
+ * tss_strong_augment_tile: the tile, for tests that aim at its edges. */
+#define TSS_STRONGAUG_TH 32
+#define TSS_STRONGAUG_TW 32
+int tss_strong_augment_tile(int* th, int* tw);
+long tss_strong_augment_ws(long B, int H, int W);
+int tss_strong_augment(const void* image, void* out, const float* color, const int* radius, const float* taps, const float* mean3,
+                       const float* std3, void* ws, long B, int Ci, int H, int W, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,5 +16,6 @@ from .ops import multiscale_argmax_confusion, resize_flip_image  # noqa: F401
 from .engine import benchmark_model, GraphedInference, MultiScaleEvaluator  # noqa: F401
 from .engine import FlatOptimizer, FlatAdamW, FlatSGD, ModelEMA  # noqa: F401
 from .selftrain import upsample_pseudo_labels, classmix_select, mix_batch, SelfTraining  # noqa: F401
+from .selftrain import gaussian_taps, StrongAugment, strong_augment  # noqa: F401
 
 __version__ = '0.1.0'

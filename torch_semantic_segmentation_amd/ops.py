@@ -3751,6 +3751,7 @@ class UpsampleCrossEntropyFn(Function):
 
 
 GROUP_MAX_BATCH = 1024       # tss_upsample_ce_group_max_batch(): the samples whose sums the grouped finalize keeps on chip
+STRONGAUG_TILE = (32, 32)    # tss_strong_augment_tile(): (TH, TW), the output tile of one block of csrc/strongaug.hip
 
 
 def check_sample_groups(group, weight, batch):

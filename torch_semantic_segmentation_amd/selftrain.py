@@ -149,6 +149,146 @@ def mix_batch(image, labels, partner, sel=None, boxes=None, out_image=None, out_
     return out_image, out_target
 
 
+STRONG_MAX_RADIUS = 8
+STRONG_MAX_SIGMA = 8.0 / 3.0
+
+
+def gaussian_taps(sigma):
+    """(R, taps): the one-sided taps of a normalised Gaussian of standard deviation `sigma`, R = min(ceil(3 sigma), 8),
+    w_k = exp(-k^2 / 2 sigma^2) / sum_{j=-R..R} exp(-j^2 / 2 sigma^2) for k = 0..R, computed in float64 and rounded to float32;
+    taps is a float32 array of 12 with zeros past R.  sigma = 0 gives R = 0 (no blur, taps (1, 0, ...)).  ValueError for sigma < 0
+    or sigma > 8/3 (the kernel's halo is 8 pixels)."""
+    s = float(sigma)
+    if not 0.0 <= s <= STRONG_MAX_SIGMA:
+        raise ValueError('sigma must lie in [0, 8/3], got %r' % (sigma,))
+    taps = np.zeros(12, dtype=np.float32)
+    if s == 0.0:
+        taps[0] = 1.0
+        return 0, taps
+    R = min(int(np.ceil(3.0 * s)), STRONG_MAX_RADIUS)
+    k = np.arange(R + 1, dtype=np.float64)
+    e = np.exp(-k * k / (2.0 * s * s))
+    taps[:R + 1] = (e / (e[0] + 2.0 * e[1:].sum())).astype(np.float32)
+    return R, taps
+
+
+class StrongAugment:
+    """The photometric strong augmentation of the student's unlabelled input (ClassMix, DACS, CutMix-Seg, FixMatch): colour jitter
+    with probability `color_p`, then a Gaussian blur with probability `blur_p`, drawn on the host and applied on the device by
+    strong_augment (csrc/strongaug.hip; include/tss_hip.h has the formulas).  mean / std: the Normalize constants of the batch
+    (None: 0 / 1).  brightness, contrast, saturation = a: the factor is uniform in [max(0, 1 - a), 1 + a]; hue: the shift is uniform
+    in [-hue, hue] of a turn (hue <= 0.5); sigma = (lo, hi): the blur's standard deviation, uniform, at most 8/3.
+
+    draw(B, generator) returns the host rows (color float32 [B,8] = (apply, fb, fc, fs, dh, 0, 0, 0), radius int32 [B],
+    taps float32 [B,12]); `generator` is a numpy Generator (None: a fresh default_rng()), seven uniform numbers per sample, every
+    parameter drawn whether or not its step applies, so the stream does not depend on the outcome.  Labels are not touched."""
+
+    def __init__(self, mean=None, std=None, color_p=0.8, brightness=0.25, contrast=0.25, saturation=0.25, hue=0.25, blur_p=0.5,
+                 sigma=(0.15, 1.15)):
+        self.mean = None if mean is None else tuple(float(v) for v in mean)
+        self.std = None if std is None else tuple(float(v) for v in std)
+        for name, v in (('mean', self.mean), ('std', self.std)):
+            if v is not None and (len(v) != 3 or not all(np.isfinite(v)) or (name == 'std' and min(v) <= 0.0)):
+                raise ValueError('%s must be three finite numbers%s, got %r' % (name, ' > 0' if name == 'std' else '', v))
+        self.color_p, self.blur_p = float(color_p), float(blur_p)
+        self.brightness, self.contrast, self.saturation, self.hue = float(brightness), float(contrast), float(saturation), float(hue)
+        self.sigma = (float(sigma[0]), float(sigma[1]))
+        for name in ('color_p', 'blur_p'):
+            if not 0.0 <= getattr(self, name) <= 1.0:
+                raise ValueError('%s must be a probability, got %r' % (name, getattr(self, name)))
+        for name in ('brightness', 'contrast', 'saturation'):
+            v = getattr(self, name)
+            if not (v >= 0.0 and v != float('inf')):
+                raise ValueError('%s must be a finite number >= 0, got %r' % (name, v))
+        if not 0.0 <= self.hue <= 0.5:
+            raise ValueError('hue must lie in [0, 0.5] of a turn, got %r' % (hue,))
+        if not 0.0 <= self.sigma[0] <= self.sigma[1] <= STRONG_MAX_SIGMA:
+            raise ValueError('sigma must be 0 <= lo <= hi <= 8/3, got %r' % (sigma,))
+
+    def draw(self, B, generator=None):
+        rng = np.random.default_rng() if generator is None else generator
+        u = rng.random((int(B), 7))
+        color = np.zeros((int(B), 8), dtype=np.float32)
+        color[:, 0] = u[:, 0] < self.color_p
+        for j, a in enumerate((self.brightness, self.contrast, self.saturation)):
+            lo = max(0.0, 1.0 - a)
+            color[:, 1 + j] = lo + (1.0 + a - lo) * u[:, 1 + j]
+        color[:, 4] = np.clip(self.hue * (2.0 * u[:, 4] - 1.0), -self.hue, self.hue)
+        sig = np.where(u[:, 5] < self.blur_p, np.clip(self.sigma[0] + (self.sigma[1] - self.sigma[0]) * u[:, 6], *self.sigma), 0.0)
+        radius = np.zeros(int(B), dtype=np.int32)
+        taps = np.zeros((int(B), 12), dtype=np.float32)
+        for b in range(int(B)):
+            radius[b], taps[b] = gaussian_taps(sig[b])
+        return color, radius, taps
+
+
+def _strong_rows(color, radius, taps, B, dev):
+    """The three row tensors on the device: device tensors are taken as they are (dtype, shape), host rows are validated, copied."""
+    out = []
+    for t, name, shape, dtype in ((color, 'color', (B, 8), torch.float32), (radius, 'radius', (B,), torch.int32),
+                                  (taps, 'taps', (B, 12), torch.float32)):
+        if isinstance(t, torch.Tensor) and t.is_cuda:
+            if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                raise ValueError('%s on the device must be a contiguous %s tensor of shape %s on %s' % (name, dtype, shape, dev))
+            out.append(t)
+            continue
+        a = t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        if tuple(a.shape) != shape:
+            raise ValueError('%s must have shape %s, got %s' % (name, shape, tuple(a.shape)))
+        if name == 'radius':
+            if a.dtype.kind not in 'iu' or (a.size and (int(a.min()) < 0 or int(a.max()) > STRONG_MAX_RADIUS)):
+                raise ValueError('radius must hold integers in [0, %d], got %s' % (STRONG_MAX_RADIUS, a))
+            a = a.astype(np.int32)
+        else:
+            if a.dtype.kind not in 'fiu':
+                raise ValueError('%s must hold numbers, got %s' % (name, a.dtype))
+            a = a.astype(np.float32)
+            if not np.isfinite(a).all():
+                raise ValueError('%s must be finite' % name)
+            if name == 'color' and a.size and (float(a[:, 1:4].min()) < 0.0 or float(np.abs(a[:, 4]).max()) > 0.5):
+                raise ValueError('color rows need factors >= 0 and |dh| <= 0.5, got %s' % (a,))
+        out.append(torch.from_numpy(np.ascontiguousarray(a)).to(dev))
+    return out
+
+
+def strong_augment(image, color, radius, taps, mean=None, std=None, out=None, workspace=None):
+    """Colour jitter and Gaussian blur of a normalised batch, two launches (tss_strong_augment; include/tss_hip.h has the formulas,
+    StrongAugment.draw / gaussian_taps make the rows).  image [B,3,H,W] float32 | bfloat16, contiguous, W % 8 == 0, W >= 16, H >= 9;
+    mean / std: the constants the batch was normalised with (None: 0 / 1).  color [B,8], radius [B], taps [B,12] as host arrays /
+    tensors are validated (shapes, 0 <= R <= 8, finite factors >= 0, |dh| <= 0.5) and copied; as device tensors (float32, int32,
+    float32) they are taken as they are and the kernel clamps R and dh into range.  A sample with apply = 0 and R = 0 is copied on
+    bits.  `out` must not alias `image`; `workspace`: a float64 device tensor of tss_strong_augment_ws bytes to reuse between calls
+    (SelfTraining keeps one).  No ATen fall-back: anything outside the contract is a ValueError."""
+    ops._check_device(image)
+    if image.dim() != 4 or not image.is_contiguous() or image.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError('image must be a contiguous float32 / bfloat16 [B,3,H,W] tensor, got %s %s' % (image.dtype, tuple(image.shape)))
+    B, Ci, H, W = image.shape
+    if Ci != 3 or W % 8 or W < 16 or H < 9:
+        raise ValueError('strong_augment needs 3 channels, a width that is a multiple of 8 and >= 16 and a height >= 9, got %s'
+                         % (tuple(image.shape),))
+    dev = image.device
+    for name, v in (('mean', mean), ('std', std)):
+        if v is not None and (len(v) != 3 or not all(np.isfinite([float(x) for x in v])) or (name == 'std' and min(float(x) for x in v) <= 0)):
+            raise ValueError('%s must be three finite numbers%s, got %r' % (name, ' > 0' if name == 'std' else '', v))
+    color, radius, taps = _strong_rows(color, radius, taps, B, dev)
+    if out is None:
+        out = torch.empty_like(image)
+    elif out.dtype != image.dtype or tuple(out.shape) != (B, Ci, H, W) or not out.is_contiguous() or out.device != dev:
+        raise ValueError('out must be a contiguous %s tensor of shape %s on %s' % (image.dtype, (B, Ci, H, W), dev))
+    if out.data_ptr() == image.data_ptr() and B:
+        raise ValueError('out must not alias image')
+    need = N.lib().tss_strong_augment_ws(B, H, W)
+    if need < 0:
+        raise ValueError('strong_augment: shape %s is outside the kernel\'s contract' % (tuple(image.shape),))
+    if workspace is None:
+        workspace = torch.empty(max(need // 8, 1), dtype=torch.float64, device=dev)
+    elif workspace.dtype != torch.float64 or workspace.numel() * 8 < need or not workspace.is_contiguous() or workspace.device != dev:
+        raise ValueError('workspace must be a contiguous float64 tensor of at least %d bytes on %s' % (need, dev))
+    call('tss_strong_augment', ptr(image), ptr(out), ptr(color), ptr(radius), ptr(taps), ops._float3(mean, 0.0), ops._float3(std, 1.0),
+         ptr(workspace), B, Ci, H, W, N.dtype_code(image.dtype), stream())
+    return out
+
+
 class SelfTraining:
     """Mean-teacher self-training through an existing (captured or eager) engine.Trainer.
 
@@ -178,10 +318,19 @@ class SelfTraining:
     unlabelled half with no kept pixel contributes 0 and a zero gradient.  `last_group_loss` (device, float32 [2]) holds the two terms
     of the last step: L_sup and the weighted lambda * L_unsup; their sum is the returned loss.  Needs a trainer whose loss is
     tssa.CrossEntropyLoss on the fused-head route (ValueError otherwise) and B <= 512.
-    Data parallel needs nothing extra: every rank draws its own rows (give the ranks different seeds)."""
+    Data parallel needs nothing extra: every rank draws its own rows (give the ranks different seeds).
+
+    strong=tssa.StrongAugment(...) adds the photometric strong augmentation of the student's unlabelled input (colour jitter and
+    Gaussian blur, strong_augment): the mix then writes into a scratch batch and the augmentation writes x_all[B:], both in the
+    captured prologue; y_all[B:] is the mix's target as before.  Its rows are drawn in step() after the mix rows, from the same
+    generator, into fixed device buffers; last_rows grows by (color, radius, taps).  With mix=None this is FixMatch's pair: the
+    teacher on xu, the student on strong(xu).  Needs 3 channels, H >= 9, W >= 16.  strong=None: the launches and bits as before."""
 
     def __init__(self, trainer, teacher, num_classes, threshold=0.95, mix='classmix', cut_area=(0.25, 0.5), ignore_index=255, seed=0,
-                 unsup_weight=None, unsup_weighting='mean'):
+                 unsup_weight=None, unsup_weighting='mean', strong=None):
+        if strong is not None and not isinstance(strong, StrongAugment):
+            raise ValueError('strong must be a tssa.StrongAugment or None, got %s' % type(strong).__name__)
+        self.strong = strong
         if mix not in ('classmix', 'cutmix', None):
             raise ValueError("mix must be 'classmix', 'cutmix' or None, got %r" % (mix,))
         if unsup_weighting not in ('mean', 'kept_share'):
@@ -220,6 +369,8 @@ class SelfTraining:
             raise ValueError('SelfTraining: the target must be int64 of shape %s' % ((B, H, W),))
         if W % 8:
             raise ValueError('SelfTraining needs a width that is a multiple of 8, got %d' % W)
+        if self.strong is not None and (Ci != 3 or H < 9 or W < 16):
+            raise ValueError('SelfTraining(strong=...) needs 3 channels, a height >= 9 and a width >= 16, got %s' % ((Ci, H, W),))
         self.geom = (B, Ci, H, W)
         self.x_all = torch.empty((2 * B, Ci, H, W), dtype=x.dtype, device=dev)
         self.y_all = torch.empty((2 * B, H, W), dtype=torch.int64, device=dev)
@@ -231,6 +382,12 @@ class SelfTraining:
         self.sel = torch.zeros((B, 256), dtype=torch.uint8, device=dev)
         self.threshold = torch.full((1,), self._threshold0, dtype=torch.float32, device=dev)
         self.last_kept = torch.zeros(B, dtype=torch.int64, device=dev)
+        if self.strong is not None:
+            self.mixed = torch.empty((B, Ci, H, W), dtype=x.dtype, device=dev)
+            self.sa_color = torch.zeros((B, 8), dtype=torch.float32, device=dev)
+            self.sa_radius = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.sa_taps = torch.zeros((B, 12), dtype=torch.float32, device=dev)
+            self.sa_ws = torch.zeros(N.lib().tss_strong_augment_ws(B, H, W) // 8, dtype=torch.float64, device=dev)
         if self._lam0 is not None:
             if 2 * B > ops.GROUP_MAX_BATCH:
                 raise ValueError('SelfTraining(unsup_weight=...) takes at most %d labelled samples, got %d' % (ops.GROUP_MAX_BATCH // 2, B))
@@ -291,7 +448,11 @@ class SelfTraining:
             if self.mix == 'classmix':
                 call('tss_classmix_select', ptr(self.pseudo), ptr(self.keys), ptr(self.sel), B, H * W, self.num_classes, stream())
             mix_batch(self.xu, self.pseudo, self.partner, sel=self.sel if self.mix == 'classmix' else None,
-                      boxes=None if self.mix == 'classmix' else self.boxes, out_image=self.x_all[B:], out_target=self.y_all[B:])
+                      boxes=None if self.mix == 'classmix' else self.boxes,
+                      out_image=self.x_all[B:] if self.strong is None else self.mixed, out_target=self.y_all[B:])
+            if self.strong is not None:
+                strong_augment(self.mixed, self.sa_color, self.sa_radius, self.sa_taps, self.strong.mean, self.strong.std,
+                               out=self.x_all[B:], workspace=self.sa_ws)
             if self._lam0 is not None:
                 call('tss_selftrain_weights', ptr(self.last_kept), H * W, ptr(self.lam), 1 if self.unsup_weighting == 'kept_share' else 0,
                      ptr(self.group), ptr(self.weight), B, stream())
@@ -313,4 +474,10 @@ class SelfTraining:
         else:
             self.boxes.copy_(torch.from_numpy(boxes))
         self.last_rows = (partner, keys, boxes)
+        if self.strong is not None:
+            color, radius, taps = self.strong.draw(B, self.rng)
+            self.sa_color.copy_(torch.from_numpy(color))
+            self.sa_radius.copy_(torch.from_numpy(radius))
+            self.sa_taps.copy_(torch.from_numpy(taps))
+            self.last_rows += (color, radius, taps)
         return self.trainer.step_async(self.x_all, self.y_all, self.slot, prologue=self._prepare)
