@@ -17,6 +17,9 @@ and tss_cast_weights (tests/test_gpu_bnfin_exact.py) have the last section of th
 whose last steps are IEEE float32 operations, integer slab rows on which every output but invstd is held bit for bit (invstd: one f32
 rounding of an f64 value), a bounded tier whose slabs tss_tensor_stats writes from stored values near 30, and the restated grids and
 chains of the statistics and column-sum kernels.  The dropout masks are predicted by tests/philox_ref.py (Philox4x32-10 in numpy).
+The last two sections restate the Lovasz-Softmax path (csrc/lovasz.hip: planner, key, stable order, integer weights, tile sums, final
+tree, backward; tests/test_gpu_lovasz_exact.py) and carry the bounds of the planar cross-entropy and OHEM kernels
+(tests/test_gpu_planar_ce_exact.py).
 
 Every operand is a DYADIC bf16 value, +-(1 + k/128) * 2^e with e in [-4, 2): 8 significant bits.  BatchNorm scales are powers of two in
 [1/2, 4], the backward pair (ga, gb) powers of two in [1/4, 2] and [2^-6, 2^-3].  Then the on-load transforms of the kernels
@@ -3137,3 +3140,342 @@ def head_focal_coef_err(f):
     band_rows additions of the loss sum are not part of one term)"""
     rel = lambda e, v: np.where(v != 0, e / np.where(v != 0, np.abs(v), 1.0), 0.0) / U32
     return rel(f.coef_err, f.coef), rel(f.term_err, f.wlp)
+
+
+# ---------------------------------------------------------------------------------------------------------- Lovasz-Softmax (csrc/lovasz.hip)
+# Restated in numpy: the workspace planner, the symmetric key, the two-pass f64 softmax behind it, the stable order, the closed-form
+# integer weights, the tile sums, the final reduction tree and the backward formula.  After the key everything is integers or IEEE f64
+# in the kernel's operation order, so tests/test_gpu_lovasz_exact.py compares it bit for bit GIVEN the kernel's own keys; the key itself
+# is held to an interval (LovaszRef).  tests/test_exact_bounds.py pins this restatement to tests/lovasz_ref.py.
+LV_NT, LV_ITEMS = 256, 16                      # lsw::NT, ITEMS
+LV_TILE = LV_NT * LV_ITEMS                     # TILE: pairs of a sort tile
+LV_HALF_BITS = 0x3F000000                      # bits(0.5f)
+LV_KEY_MAX = 2 * LV_HALF_BITS                  # the largest key of a kept pixel: e == 0
+LV_DROPPED = 0xFFFFFFFF
+LV_SORT_BYTES_CAP = 2 << 30
+LV_IGNORE = 255
+LV_GRAD_OUT = 0.7
+LV_PARTIAL_REL = 2.0 ** -45                    # a tile's sum: any order of 4096 f64 terms stays within 4096 * 2^-53 = 2^-41 of sum |terms|; the
+#   kernel's tree is 16 fused multiply-adds per lane, 6 wave_sum levels and 4 waves added in turn: depth 26, one product rounding, so
+#   27 * 2^-53 sum |terms|, and the reference's own pairwise sum stays below 13 * 2^-53: 40 * 2^-53 < 2^-47 < 2^-45
+
+
+def up256(x):
+    return cdiv(x, 256) * 256
+
+
+def lovasz_plan(N, C, chunk_classes=0):
+    """make_plan of csrc/lovasz.hip: byte offsets of G, partial, W, key0/1, pay0/1, hist, dtot and tcnt, each rounded up to 256"""
+    ntiles = cdiv(N, LV_TILE)
+    cc = chunk_classes if chunk_classes > 0 else LV_SORT_BYTES_CAP // (16 * N)
+    Cc = max(1, min(C, cc))
+    p, o = dict(N=N, C=C, Cc=Cc, ntiles=ntiles), 0
+    p['G'], o = o, up256(o + 4 * C)
+    p['partial'], o = o, up256(o + 8 * C * ntiles)
+    p['W'], o = o, up256(o + 4 * C * N)
+    plane = up256(4 * Cc * N)
+    for k in ('key0', 'key1', 'pay0', 'pay1'):
+        p[k], o = o, o + plane
+    p['hist'], o = o, up256(o + 4 * Cc * 256 * ntiles)
+    p['dtot'], o = o, up256(o + 4 * Cc * 256)
+    p['tcnt'], o = o, up256(o + 4 * Cc * ntiles)
+    p['total'] = o
+    p['last_c0'] = (C - 1) // Cc * Cc            # first class of the last chunk: its sorted pairs are what buffer 0 holds afterwards
+    return p
+
+
+def _f32_bits(v):
+    return np.ascontiguousarray(np.asarray(v, np.float64).astype(np.float32)).view(np.uint32).astype(np.int64)
+
+
+def _bits_f32(b):
+    return np.ascontiguousarray(np.asarray(b).astype(np.uint32)).view(np.float32).astype(np.float64)
+
+
+def lovasz_key(e):
+    """error_key: e clamped to [0, 1]; k = bits((float)e) for e <= 1/2, 2 bits(1/2) - bits((float)(1 - e)) above; the key is KEY_MAX - k"""
+    e = np.clip(np.asarray(e, np.float64), 0.0, 1.0)
+    k = np.where(e <= 0.5, _f32_bits(e), LV_KEY_MAX - _f32_bits(1.0 - e))
+    return (LV_KEY_MAX - k).astype(np.uint32)
+
+
+def lovasz_key_error(key):
+    """key_error: the f64 error a key stands for (anything for DROPPED, which no caller reads)"""
+    k = LV_KEY_MAX - np.asarray(key).astype(np.int64)
+    return np.where(k <= LV_HALF_BITS, _bits_f32(np.clip(k, 0, None)), 1.0 - _bits_f32(np.clip(LV_KEY_MAX - k, 0, LV_HALF_BITS)))
+
+
+def lovasz_p_count(C):
+    """units of 2^-52, RELATIVE to p_c, by which the kernel's p = exp(v - m) * (1 / sum_c exp(v_c - m)) and numpy's differ.  One
+    evaluation: v - m is exact (f32 operands a few binades apart); exp within 1 ulp <= 2^-52 relative (the figure of the device library
+    and of numpy's libm, not measured) on the numerator, and on every term of the sum, which are positive, so 2^-52 on the sum;
+    C - 1 additions, 2^-53 each; the reciprocal 2^-53; the product 2^-53: (C + 5) 2^-53.  Two evaluations: (C + 5) 2^-52, + 1 for the
+    second order.  p <= 1, so this is also the ABSOLUTE error A of the issue; relative to p it is the tighter statement"""
+    return C + 6
+
+
+class LovaszRef:
+    """f64 state of one case: [C][N] planes p (two-pass softmax, exp * (1 / s) as softmax_stats and the key kernel form it), fg, e = |fg - p|,
+    A = the error of e (lovasz_p_count * 2^-52 * p, + 2^-52 e for the rounding of 1 - p where it is not exact), and the key interval
+    [key_lo, key_hi] = [key(e + A), key(e - A)] (the key falls as e grows) with the point key(e) in `key`; DROPPED where not kept.
+    fgb: the foreground term of the backward, which loads the labels without the ignore index"""
+    def __init__(self, x, labels, ignore_index=LV_IGNORE, has_ignore=True):
+        B, C, HW = x.shape
+        N = B * HW
+        lab = labels.reshape(N)
+        self.shape, self.N = (B, C, HW), N
+        self.kept = ~((lab == ignore_index) & bool(has_ignore))
+        inrange = (lab >= 0) & (lab < C)
+        cls = np.arange(C)[:, None]
+        self.fg = (cls == np.where(inrange & self.kept, lab, -1)[None, :])
+        self.fgb = (cls == np.where(inrange, lab, -1)[None, :])
+        m = x.max(1)
+        E = np.exp(x - m[:, None])
+        inv = 1.0 / E.sum(1)
+        self.p = (E * inv[:, None]).transpose(1, 0, 2).reshape(C, N)
+        self.e = np.abs(self.fg - self.p)
+        self.A = 2.0 ** -52 * (lovasz_p_count(C) * self.p + self.e)
+        drop = lambda k: np.where(self.kept[None, :], k, np.uint32(LV_DROPPED))
+        self.key, self.key_lo, self.key_hi = drop(lovasz_key(self.e)), drop(lovasz_key(self.e + self.A)), drop(lovasz_key(self.e - self.A))
+        self.G = self.fg.sum(1)
+
+    def one_key(self):
+        """[C][N]: the interval is a single key, so the kernel's key is checked bit for bit (dropped pixels count as such)"""
+        return self.key_lo == self.key_hi
+
+    def open_sign(self):
+        """[C][N]: |fgb - p| within its own error, where lovasz_bwd_kernel's sign branch may go either way"""
+        d = np.abs(self.fgb - self.p)
+        return d <= 2.0 ** -52 * (lovasz_p_count(self.shape[1]) * self.p + d)
+
+
+def lovasz_order(keys, fg_kept):
+    """the stable ascending order of one class's keys [N] and the payload plane it implies: pixel | fg << 31"""
+    order = np.argsort(keys, kind='stable')
+    return order, (order.astype(np.uint32) | (fg_kept[order].astype(np.uint32) << np.uint32(31)))
+
+
+def lovasz_weights(fg_sorted, kept_sorted, variant):
+    """lovasz_weight_kernel's g per RANK in f64, in its operation order (IEEE division: reproducible bit for bit), 0 at dropped ranks:
+    I = G - F_r, U = G + (r + 1) - F_r; berman (variant 1) and rank 0: 1 / U at a foreground rank, I / (U (U - 1)) at a background one;
+    reference (variant 0): ((r + 1) U0 - U) / (U U0) with U0 = G (rank 0 foreground) or G + 1.  All zeros for an absent class"""
+    n = fg_sorted.size
+    fg = fg_sorted.astype(np.int64)
+    G = int(fg.sum())
+    if G == 0:
+        return np.zeros(n), G
+    Fr = np.cumsum(fg)
+    r1 = np.arange(1, n + 1, dtype=np.int64)
+    I, U = G - Fr, G + r1 - Fr
+    U0 = G if fg_sorted[0] else G + 1
+    Ud = U.astype(np.float64)
+    berman = np.where(fg_sorted, 1.0 / Ud, I.astype(np.float64) / (Ud * np.maximum(U - 1, 1).astype(np.float64)))
+    if variant == 1:
+        g = berman
+    else:
+        g = (r1 * U0 - U).astype(np.float64) / (Ud * float(U0))
+        g[0] = berman[0]
+    return np.where(kept_sorted, g, 0.0), G
+
+
+def lovasz_tile_sums(keys_sorted, g):
+    """(sum, sum |.|) of key_error(key) * g over the ranks of every tile, f64"""
+    kept = keys_sorted != np.uint32(LV_DROPPED)
+    t = np.where(kept, lovasz_key_error(np.where(kept, keys_sorted, 0)) * g, 0.0)
+    at = np.arange(0, t.size, LV_TILE)
+    return np.add.reduceat(t, at), np.add.reduceat(np.abs(t), at)
+
+
+def wave_sum_lane0(v):
+    """lane 0 of wave_sum (csrc/common.h): v += shfl_xor(v, m) for m = 32 .. 1, over [..., 64]"""
+    idx = np.arange(64)
+    for m in (32, 16, 8, 4, 2, 1):
+        v = v + v[..., idx ^ m]
+    return v[..., 0]
+
+
+def lovasz_final(partial, G):
+    """lovasz_final_kernel on the rows partial [C][ntiles]: thread t adds tiles t, t + NT, ... in turn, wave_sum, the 4 waves in turn, the
+    present classes in turn; (float)(total / present).  Returns (f32 loss, present)"""
+    C, ntiles = partial.shape
+    total, present = 0.0, 0
+    for c in range(C):
+        if G[c] == 0:
+            continue
+        s = np.zeros(LV_NT)
+        for i0 in range(0, ntiles, LV_NT):
+            seg = partial[c, i0:i0 + LV_NT]
+            s[:seg.size] = s[:seg.size] + seg
+        lc = 0.0
+        for w in wave_sum_lane0(s.reshape(LV_NT // 64, 64)):
+            lc = lc + float(w)
+        total, present = total + lc, present + 1
+    return (np.float32(total / present) if present else np.float32(0.0)), present
+
+
+def lovasz_bwd_slack(C):
+    """units of 2^-52, relative to T = p (|D| + sum_c p_c |D_c|) scale, of lovasz_bwd_kernel's f64 value against numpy's.  p carries
+    a = lovasz_p_count(C) (both evaluations).  Per evaluation: D is exact; a term D_c p_c one rounding and the C additions of dot one each,
+    (C + 1) 2^-53 of sum |terms|; D - dot, the product with p and with scale one each, 3 * 2^-53 (scale itself is the same IEEE
+    quotient on both sides).  The |D| part: a + 3 * 2^-53 each side; the dot part: 2 a (p enters twice) + (C + 4) 2^-53 each side.  Two sides:
+    2 a + (C + 4) = 3 C + 16, + 1 for the second order"""
+    return 2 * lovasz_p_count(C) + C + 4 + 1
+
+
+def lovasz_bwd_ref(ref, W, n_present, grad_out, open_option=None):
+    """lovasz_bwd_kernel in f64 with the kernel's own weight plane W [C][N] (f32 values): diff = fgb - p, D = -w (diff > 0), w (diff < 0),
+    0; dot = sum_c D_c p_c; d = p (D - dot) scale, scale = (double)(float)grad_out / n_present (0 when nothing is present; grad_out None:
+    1).  open_option in (-1, 0, 1): the sign taken where the branch is open (ref.open_sign()).  Returns (d, T) as [C][N]"""
+    scale = float(np.float32(1.0 if grad_out is None else grad_out)) / float(n_present) if n_present > 0 else 0.0
+    diff = ref.fgb - ref.p
+    sign = np.where(diff > 0, -1.0, np.where(diff < 0, 1.0, 0.0))
+    if open_option is not None:
+        sign = np.where(ref.open_sign(), float(open_option), sign)
+    W = np.asarray(W, np.float64)
+    D = sign * W
+    dot = (D * ref.p).sum(0)
+    return ref.p * (D - dot[None, :]) * scale, ref.p * (W + (ref.p * W).sum(0)[None, :]) * abs(scale)
+
+
+def lovasz_bwd_bound(g, T, C, bf16):
+    """one rounding of the stored type on the f64 value, the f64 slack, and the smallest normal f32 (a flushed denormal)"""
+    return (2.0 ** -8 if bf16 else 2.0 ** -24) * np.abs(g) + 2.0 ** -52 * lovasz_bwd_slack(C) * T + 2.0 ** -126
+
+
+class LvCase:
+    def __init__(self, name, B, C, HW, chunks=(0,), has_ignore=(1,), populated=False, equal=False):
+        self.name, self.B, self.C, self.HW, self.chunks, self.has_ignore = name, B, C, HW, chunks, has_ignore
+        self.populated, self.equal = populated, equal
+        self.N = B * HW
+
+    def __repr__(self):
+        return self.name
+
+
+LV_CASES = [LvCase('smallest', 1, 2, 8),                                  # one group; a tile of 4088 idle lanes that act as the largest digit
+            LvCase('one_tile', 1, 3, 4096),                               # exactly one tile
+            LvCase('tile_and_group', 1, 3, 4104),                         # a second tile of 8 elements
+            LvCase('three_ragged', 3, 5, 2736),                           # 3 tiles, the last ragged; images end inside a tile
+            LvCase('carry', 1, 2, 1052680, populated=True),               # 257 tiles and a group: the second trip of both carry loops, the strided digit total
+            LvCase('carry_batched', 2, 2, 526344),                        # the same tile count from two images, one run
+            LvCase('chunked', 1, 19, 4104, chunks=(0, 4, 1)),             # chunks of 19, 4 (the last ragged: 4 * 4 + 3) and 1 classes
+            LvCase('c256', 1, 256, 16, has_ignore=(1, 0)),                # label 255 ignored, then a class
+            LvCase('all_equal', 1, 2, 4104, populated=True, equal=True)]  # added: every kept error 1/2 exactly, the seam of the key, tied in all 4 digits
+LV_BY_NAME = {c.name: c for c in LV_CASES}
+LV_SMALL = [c for c in LV_CASES if c.N <= 8208]
+
+
+def lovasz_operands(case):
+    """(x [B][C][HW] f64, labels [B][HW] int64, plants {name: flat pixel}).  Logits: multiples of 2^-4 in [-4, 4] (7 significant bits: exact
+    in bf16), so that no error is below e^-8 / C and the key of a random pixel is decided far from an f32 rounding seam; `equal`: all 0.
+    Labels: about 10 % 255; -1 at three pixels, 300 at two; the last pixels a run of 255, so that real DROPPED keys sit next to the padding
+    lanes of the last tile.  C >= 3: class 1 absent, class `single` (C - 1; 254 of 256, where 255 is the ignore label) at one pixel,
+    planted classes t = 0 and o = single.  C == 2 populated: both classes drawn, t = 0, o = 1.  C == 2 otherwise: class 1 absent, class
+    0 at the planted pixel alone and every other kept label out of range (-1 or 300).
+    Plants (image 0; exempt from the one-key condition):
+      'zero'  label t, x_t = 32 and every other class -32: p_t = 1 and e = 0 exactly in f64 on both sides: key KEY_MAX, the branch diff == 0
+      'one'   label t, x_t = -32, x_o = 32, the rest -32: e_t = 1 - e^-64 = 1 exactly (key 0, a FOREGROUND rank 0 of class t) and e_o =
+              p_o = 1 exactly (key 0, a BACKGROUND rank 0 of class o): both values of U0
+    (`smallest` and `carry_batched` have no second pixel of class 0, so no 'zero'; `all_equal` has no plants)"""
+    B, C, HW, N = case.B, case.C, case.HW, case.N
+    g = case_gen(4714, B, C, HW, int(case.equal))
+    x = (torch.randint(-64, 65, (B, C, HW), generator=g).double() / 16).numpy()
+    if case.equal:
+        x[:] = 0.0
+    lab = torch.randint(0, C, (B, HW), generator=g).numpy()
+    r = torch.rand((B, HW), generator=g).numpy()
+    sparse = C == 2 and not case.populated
+    single = None
+    if C >= 3:
+        single = C - 1 if C != 256 else 254
+        lab[(lab == 1) | (lab == single)] = 0
+    if sparse:
+        lab = np.where(lab == 0, -1, 300)
+    lab[r < 0.10] = LV_IGNORE
+    flat = lab.reshape(N)
+    if N >= 16:
+        flat[7:10], flat[10:12] = -1, 300
+    flat[N - max(2, min(24, N // 4)):] = LV_IGNORE
+    plants = {}
+    if not case.equal:
+        t, o = 0, (single if C >= 3 else 1)
+        if single is not None:
+            flat[5] = single
+        if not sparse:
+            plants['zero'] = 1
+            flat[1] = t
+            x[0, :, 1], x[0, t, 1] = -32.0, 32.0
+        i = 2 if not sparse else 0
+        plants['one'] = i
+        flat[i] = t
+        x[0, :, i], x[0, t, i], x[0, o, i] = -32.0, -32.0, 32.0
+    return x, lab, plants
+
+
+def lovasz_pipeline(x, labels, variant, ignore_index=LV_IGNORE, has_ignore=True, grad_out=None, ref=None):
+    """the whole restated forward and backward in f64 on the point keys: dict(loss (f64, before its f32 rounding), present, G [C],
+    W [C][N] (f32 values as f64), grad [B][C][HW]); with `ref` (a LovaszRef) x and labels are not read.  What tests/test_exact_bounds.py
+    pins to tests/lovasz_ref.py"""
+    ref = ref or LovaszRef(x, labels, ignore_index, has_ignore)
+    B, C, HW = ref.shape
+    W, total, present = np.zeros((C, ref.N)), 0.0, 0
+    for c in range(C):
+        fgk = ref.fg[c]
+        order, _ = lovasz_order(ref.key[c], fgk)
+        ks = ref.key[c][order]
+        g, G = lovasz_weights(fgk[order], ks != np.uint32(LV_DROPPED), variant)
+        W[c, order] = g.astype(np.float32)
+        if G > 0:
+            total, present = total + float(lovasz_tile_sums(ks, g)[0].sum()), present + 1
+    d, _ = lovasz_bwd_ref(ref, W, present, grad_out)
+    return dict(loss=total / present if present else 0.0, present=present, G=ref.G, W=W,
+                grad=d.reshape(C, B, HW).transpose(1, 0, 2))
+
+
+# ---------------------------------------------------------------------------------------------------------- planar cross-entropy and OHEM
+# tss_cross_entropy_fwd / _bwd (ce_fwd_kernel, ce_bwd_kernel of csrc/loss.hip) and tss_ohem_fwd / _bwd (ohem_pixel_kernel, ohem_bwd_kernel of
+# csrc/ohem.hip): lsw::lse8 and lsw::grad8 of csrc/losssweep.h, which soft_lse_count and soft_p_count above already count.
+PLANAR_CE_BIG = (1, 1, 4097 * 256 * 8)       # 4097 * 256 groups: one more block than tss::grid_for's cap of 4096, so block 0's lanes take two trips
+PLANAR_CE_SHAPES = SOFT_PLANAR + [SOFT_BEHIND, PLANAR_CE_BIG]
+PLANAR_CE_SUM_REL = 2.0 ** -40               # the f64 loss sum: <= 2 * 8 terms per lane, 6 wave_sum levels, 4 waves, <= 4096 atomics in any order:
+#                                              under 4200 * 2^-53 < 2^-40 of sum |terms|
+
+
+def planar_ce_operands(shape):
+    """soft_planar_operands and, with C >= 2, one more planted pixel 'exact' (image 0, pixel 6): label 0 at 16 and every other class at -16.
+    The other classes add (C - 1) e^-32 < 2^-38 to a running sum of 1.f, which stays 1.f, and __logf(1.f) is 0: the stored lse IS x_t and
+    the pixel's cross-entropy an exact 0 (in f64 it is 2e-13, inside the bound of lse).  With C == 1 every pixel is such a pixel"""
+    x, lab, plants = soft_planar_operands(*shape, behind=shape == SOFT_BEHIND)
+    if shape[1] >= 2 and shape != SOFT_BEHIND:
+        x[0, :, 6], x[0, 0, 6], lab[0, 6] = -16.0, 16.0, 0
+        plants['exact'] = 6
+    return x, lab, plants
+
+
+class PlanarCeRef:
+    """reference and bounds of the planar cross-entropy on a PlanarRef (has_ignore: both entries always apply their ignore index):
+      lse, lse_bound      per pixel: U32 soft_lse_count
+      ce, ce_bound        per pixel: max(lse - x_t, 0) where the pixel counts, 0 elsewhere; lse's bound and the subtraction's rounding
+      total, total_bound  the f64 sum of the counted lse - x_t: the per-pixel bounds added up, + PLANAR_CE_SUM_REL sum |terms|"""
+    def __init__(self, ref):
+        self.ref = ref
+        self.k = soft_lse_count(ref)
+        self.lse, self.lse_bound = ref.lse, U32 * self.k * 1.001
+        xt = np.take_along_axis(ref.x, ref.t[:, None, :], 1)[:, 0]
+        self.ce = np.where(ref.valid, np.maximum(ref.lse - xt, 0.0), 0.0)
+        self.ce_bound = np.where(ref.valid, self.lse_bound + U32 * 1.001 * self.ce, 0.0)
+        self.total = float(self.ce.sum())
+        self.total_bound = float(self.ce_bound.sum()) + PLANAR_CE_SUM_REL * self.total
+        self.kp = None
+
+    def grad(self, w, bf16):
+        """(g, bound) [B][C][HW] of lsw::grad8<false> with the per-pixel weight w [B][HW] (f64 of the f32 the kernel forms; 0 where the pixel
+        does not count): g = (p - h) w.  e = __expf(x - l) from the stored l: soft_p_count, relative to p; the weight's own product, h - e
+        and the product with w one rounding each, relative to p + h (soft_p_count's docstring); __expf may flush a result below 2^-126"""
+        ref = self.ref
+        if self.kp is None:
+            self.kp = _first_order(soft_p_count(ref, self.k))
+        h = ref.onehot.astype(np.float64)
+        g = (ref.p - h) * w[:, None]
+        bound = np.abs(w)[:, None] * (ref.p * self.kp + (ref.p + h) * (3 * U32 * 1.001) + 2.0 ** -126)
+        return g, bound + (2.0 ** -8 * (np.abs(g) + bound) if bf16 else 0.0)

@@ -2712,3 +2712,286 @@ def test_head_focal_emulation_with_one_defect_fails_the_gradient_bound_where_the
     print('defect %-15s %-9s new grad ratio %.2f (correct %.3f) | old %.3e (correct %.3e) <= %.0e' % (defect, name, rg1, rg0, old1, old0, old_bound))
     assert rg0 <= 1 and rl0 <= 1 and old0 <= old_bound
     assert rg1 > 1 and old1 <= old_bound, (defect, rg1, old1)
+
+
+# --- Lovasz-Softmax: the restated pipeline of tests/exact.py (section "Lovasz-Softmax") that tests/test_gpu_lovasz_exact.py holds the kernels to
+from tests import lovasz_ref         # noqa: E402
+
+LV_IDS = lambda c: c.name
+
+
+@functools.lru_cache(maxsize=None)
+def _lovasz(name, has_ignore=1):
+    case = X.LV_BY_NAME[name]
+    x, lab, plants = X.lovasz_operands(case)
+    return x, lab, plants, X.LovaszRef(x, lab, X.LV_IGNORE, has_ignore)
+
+
+def test_lovasz_plan_restates_make_plan():
+    """the offsets by hand at one shape, the chunk rule, and the tile counts the cases are listed for"""
+    p = X.lovasz_plan(4104, 19, 4)
+    assert (p['ntiles'], p['Cc'], p['last_c0']) == (2, 4, 16)
+    assert p['G'] == 0 and p['partial'] == 256 and p['W'] == 256 + 512 and p['key0'] == 768 + X.up256(4 * 19 * 4104)
+    plane = X.up256(4 * 4 * 4104)
+    assert p['key1'] - p['key0'] == plane and p['pay0'] - p['key0'] == 2 * plane and p['hist'] - p['pay1'] == plane
+    assert p['dtot'] - p['hist'] == 4 * 4 * 256 * 2 and p['tcnt'] - p['dtot'] == 4 * 4 * 256 and p['total'] - p['tcnt'] == 256
+    assert X.lovasz_plan(4104, 19, 0)['Cc'] == 19 and X.lovasz_plan(4104, 19, 1)['last_c0'] == 18 and X.lovasz_plan(4104, 19, 40)['Cc'] == 19
+    assert X.lovasz_plan(8 * 1024 * 2048, 19, 0)['Cc'] == 8            # the production shape sorts 8 classes at a time
+    tiles = {c.name: X.lovasz_plan(c.N, c.C)['ntiles'] for c in X.LV_CASES}
+    assert tiles == dict(smallest=1, one_tile=1, tile_and_group=2, three_ragged=3, carry=258, carry_batched=258, chunked=2, c256=1, all_equal=2)
+    assert 4104 - 4096 == 8 and 8208 % 4096 == 16 and 2736 % 4096 != 0
+    assert 1052680 == 257 * 4096 + 8 and 258 > X.LV_NT       # 257 whole tiles and one group: the second trip of the carry loops holds 2 tiles
+
+
+def test_lovasz_key_is_monotonic_and_round_trips():
+    rng = X.np_rng(4714)
+    sample = np.concatenate([rng.uniform(0, 1, 20000), 2.0 ** rng.uniform(-149, 0, 20000), 1 - 2.0 ** rng.uniform(-24, -1, 20000)])
+    f = np.unique(np.clip(sample, 0, 1).astype(np.float32)).astype(np.float64)
+    lo, hi = f[f <= 0.5], 1.0 - f[f <= 0.5]                            # every f32 below the seam, and its mirror above it
+    for v in (lo, hi[hi > 0.5]):
+        k = X.lovasz_key(v)
+        assert np.array_equal(X.lovasz_key_error(k), v)                 # round trip on values the key holds exactly
+    e = np.sort(np.concatenate([sample, lo, hi]))
+    k = X.lovasz_key(e).astype(np.int64)
+    assert (np.diff(k) <= 0).all() and k.max() <= X.LV_KEY_MAX and k.min() >= 0      # the key falls as the error grows
+    back = X.lovasz_key_error(k)
+    assert (np.diff(back) >= 0).all() and (np.abs(back - e) <= 2.0 ** -24 * np.minimum(e, 1 - e) + 2.0 ** -150).all()
+    above = float(np.nextafter(np.float32(0.5), np.float32(1)))
+    special = np.array([0.0, 2.0 ** -149, 0.5, above, 1 - 2.0 ** -24, 1.0])
+    ks = X.lovasz_key(special).astype(np.int64)
+    assert ks.tolist() == [X.LV_KEY_MAX, X.LV_KEY_MAX - 1, X.LV_HALF_BITS, X.LV_HALF_BITS - 2, 0x33800000, 0]       # above the seam 1 - e has twice f32's resolution of e
+    assert np.array_equal(X.lovasz_key_error(ks), special)
+    assert X.lovasz_key(-1e-3) == X.LV_KEY_MAX and X.lovasz_key(1 + 1e-9) == 0 and X.LV_KEY_MAX == 0x7E000000 < X.LV_DROPPED
+
+
+@pytest.mark.parametrize('case', X.LV_CASES, ids=LV_IDS)
+def test_lovasz_case_inputs_hold_their_conditions(case):
+    """per case input: bf16-exact logits; the labels the issue lists; at least 99 % of the kept (class, pixel) keys outside the planted
+    pixels have a one-key interval (so the GPU test checks them bit for bit); the planted keys; the sign branch of the backward is open
+    at the 'zero' plant alone; rank 0 is foreground for class t and background for class o"""
+    for h in case.has_ignore:
+        x, lab, plants, ref = _lovasz(case.name, h)
+        B, C, HW, N = case.B, case.C, case.HW, case.N
+        flat = lab.reshape(N)
+        assert HW % 8 == 0 and np.array_equal(torch.from_numpy(x).to(torch.bfloat16).double().numpy(), x)
+        assert (flat[-2:] == 255).all() and (flat == 255).sum() >= 2
+        if N >= 16:
+            assert (flat == -1).sum() >= 3 and (flat == 300).sum() >= 2 and 0.05 < (flat == 255).mean() < 0.4
+        if not case.populated:
+            assert ref.G[1] == 0 and (ref.G == 1).sum() >= 1              # an absent class, a class of one pixel
+        spots = sorted(plants.values())
+        free = np.ones(N, bool)
+        free[spots] = False
+        ok = ref.one_key()[:, free & ref.kept]
+        print('lovasz %-14s ign%d one-key fraction %.6f of %d' % (case.name, h, ok.mean() if ok.size else 1.0, ok.size))
+        assert ok.size == 0 or ok.mean() >= 0.99
+        opened = np.argwhere(ref.open_sign())
+        assert opened.tolist() == ([[0, plants['zero']]] if 'zero' in plants else []), opened[:4]
+        if 'zero' in plants:
+            assert ref.e[0, plants['zero']] == 0 and ref.key[0, plants['zero']] == X.LV_KEY_MAX
+        if 'one' in plants:
+            i, o = plants['one'], int(np.argmax(x[0, :, plants['one']]))
+            assert ref.e[0, i] == 1 and ref.key[0, i] == 0 and ref.fg[0, i] and (ref.key[0] == 0).sum() == 1          # U0 = G
+            assert ref.e[o, i] == 1 and ref.key[o, i] == 0 and not ref.fg[o, i] and (ref.key[o] == 0).sum() == 1      # U0 = G + 1
+            assert ref.G[0] > 0 and (ref.G[o] > 0 or (C == 2 and not case.populated) or (C == 256 and h == 1 and o == 255))
+        if case.equal:
+            assert (ref.e == 0.5).all() and (ref.key[:, ref.kept] == X.LV_HALF_BITS).all() and ref.G.min() > 1000
+    if case.name == 'c256':
+        assert _lovasz('c256', 1)[3].G[255] == 0 and _lovasz('c256', 0)[3].G[255] >= 2 and _lovasz('c256', 0)[3].kept.all()
+
+
+def _oracle_loss_and_grad(x, lab, C, ignore, variant, key_order):
+    """tests/lovasz_ref.py in f64: lovasz_softmax_loss(..., stable=True) and its autograd gradient.  key_order: the same lines of that
+    function (class_errors, a stable descending sort, lovasz_weights, the mean) with the sort taken on the errors AT THE KEY'S RESOLUTION
+    -- key_error(key(e)) -- which is the kernel's documented tie rule: errors that differ below 2^-24 keep ascending pixel index"""
+    B, _, HW = x.shape
+    xt = torch.from_numpy(x).reshape(B, C, HW, 1).clone().requires_grad_(True)
+    lt = torch.from_numpy(lab).reshape(B, HW, 1)
+    if not key_order:
+        loss = lovasz_ref.lovasz_softmax_loss(xt, lt, C, ignore, variant, stable=True)
+    else:
+        losses = []
+        for _c, errors, fg in lovasz_ref.class_errors(xt, lt, C, ignore):
+            q = torch.from_numpy(X.lovasz_key_error(X.lovasz_key(errors.detach().numpy())))
+            idx = torch.sort(q, dim=0, descending=True, stable=True)[1]
+            losses.append(torch.dot(errors[idx], lovasz_ref.lovasz_weights(fg[idx], variant)))
+        loss = torch.stack(losses).mean() if losses else xt.sum() * 0
+    loss.backward()
+    return float(loss.detach()), xt.grad.numpy().reshape(B, C, HW)
+
+
+@pytest.mark.parametrize('variant', (0, 1))
+@pytest.mark.parametrize('case', X.LV_SMALL, ids=LV_IDS)
+def test_lovasz_restated_pipeline_is_the_oracle_pinned_restatement(case, variant):
+    """X.lovasz_pipeline (keys, stable order, closed-form weights, tile sums, backward formula) against tests/lovasz_ref.py's loss and
+    autograd gradient in f64, stable order.  The pipeline reads every error back from its f32 key (2^-24 relative to min(e, 1 - e)) and
+    stores the weights in f32 (2^-24), the oracle keeps both in f64: the loss within 2^-22, every gradient element within 2^-22 of
+    p (w + sum_c p_c w_c) / present.  Where the f32 keys order the kept pixels exactly as the f64 errors do, the oracle is
+    lovasz_softmax_loss(..., stable=True) itself; on the larger cases two pixels whose logits are permutations of each other have
+    errors one f64 ulp apart and ONE key, and the oracle sorts at the key's resolution (_oracle_loss_and_grad)"""
+    for h in case.has_ignore:
+        x, lab, plants, ref = _lovasz(case.name, h)
+        B, C, HW = x.shape
+        same = all(np.array_equal(np.argsort(ref.key[c][ref.kept], kind='stable'), np.argsort(-ref.e[c][ref.kept], kind='stable')) for c in range(C))
+        assert same or case.N > 16
+        out = X.lovasz_pipeline(x, lab, variant, X.LV_IGNORE, h, grad_out=None, ref=ref)
+        l64, g64 = _oracle_loss_and_grad(x, lab, C, X.LV_IGNORE if h else None, lovasz_ref.VARIANTS[variant], not same)
+        assert out['present'] == int((ref.G > 0).sum())
+        assert abs(out['loss'] - l64) <= 2.0 ** -22 * abs(l64)
+        _, T = X.lovasz_bwd_ref(ref, out['W'], out['present'], None)
+        T = T.reshape(C, B, HW).transpose(1, 0, 2)
+        r = X.worst_ratio(np.abs(out['grad'] - g64), 2.0 ** -22 * T + 1e-300)
+        print('lovasz %-14s v%d ign%d loss %.9f | gradient vs the oracle restatement, ratio %.3f%s' % (case.name, variant, h, l64, r, '' if same else ' (key order)'))
+        assert r <= 1
+
+
+def test_lovasz_closed_form_weights_are_lovasz_refs_formula():
+    rng = X.np_rng(4715)
+    for n, pfg in ((1, 1.0), (7, 0.5), (5000, 0.1), (5000, 0.9)):
+        fg = rng.uniform(size=n) < pfg
+        fg[0] = True
+        for first in (True, False):
+            if n > 1:
+                fg[0], fg[1] = first, True
+            for variant in (0, 1):
+                g, G = X.lovasz_weights(fg, np.ones(n, bool), variant)
+                want = lovasz_ref.closed_form_weights(torch.from_numpy(fg), lovasz_ref.VARIANTS[variant]).numpy()
+                assert G == fg.sum() and np.array_equal(g, want), (n, first, variant)       # the same IEEE operations: the same bits
+    g, G = X.lovasz_weights(np.zeros(9, bool), np.ones(9, bool), 0)
+    assert G == 0 and (g == 0).all()
+
+
+def test_lovasz_final_tree_and_a_broken_carry_are_seen():
+    """lovasz_final on rows it can sum exactly; and what a dropped `carry += tot` of the offset scan does to a 257-tile plane: tile 256's
+    elements land on tile 0's, which a permutation check sees"""
+    part = np.arange(2 * 300, dtype=np.float64).reshape(2, 300)
+    loss, present = X.lovasz_final(part, np.array([3, 0]))
+    assert present == 1 and loss == np.float32(part[0].sum())
+    loss, present = X.lovasz_final(part, np.array([0, 0]))
+    assert present == 0 and loss == 0
+    v = np.arange(64, dtype=np.float64)[None, :] * np.ones((4, 1))
+    assert (X.wave_sum_lane0(v) == 2016).all()
+
+
+# --- planar cross-entropy and OHEM (tests/test_gpu_planar_ce_exact.py)
+from tests import softloss_emu       # noqa: E402
+
+
+def _planar_ce_emu(shape, bf16=False, defect=None):
+    """ce_fwd_kernel / ohem_pixel_kernel and ce_bwd_kernel in f32 (tests/softloss_emu.py: lse8, expf): (lse, per-pixel loss, gradient with
+    w = fl(fl(1 / n) 0.7)).  defect 'last_plane': grad8 leaves the last class plane as the plane before it"""
+    x, lab, plants = X.planar_ce_operands(shape)
+    ref = X.PlanarRef(x, lab, 255, True)
+    x32 = x.astype(np.float32)
+    lse = softloss_emu.lse8(x32)
+    xt = np.take_along_axis(x32, ref.t[:, None, :], 1)[:, 0]
+    pix = np.where(ref.valid, np.maximum(lse - xt, np.float32(0)), np.float32(0))
+    gs = np.float32(1.0 / ref.nvalid) * np.float32(0.7)
+    w = np.where(ref.valid, gs, np.float32(0))
+    g = (softloss_emu.expf(x32 - lse[:, None]) - ref.onehot.astype(np.float32)) * w[:, None]
+    if defect == 'last_plane':
+        g[:, -1] = g[:, -2]
+    if bf16:
+        g = softloss_emu.to_bf16(g)
+    return x, lab, plants, ref, X.PlanarCeRef(ref), lse, pix, g.astype(np.float64), float(gs)
+
+
+@pytest.mark.parametrize('shape', X.PLANAR_CE_SHAPES[:-1], ids=SOFT_IDS)
+def test_planar_ce_f32_emulation_meets_every_bound(shape):
+    """lse, the per-pixel loss and every gradient element of an f32 evaluation in the kernels' order stay inside the bounds the GPU test
+    uses; the planted 'exact' pixel stores lse == x_t and a loss of +0; the 2^-8 of a bf16 gradient is enough"""
+    for bf16 in (False, True):
+        x, lab, plants, ref, cr, lse, pix, g, gs = _planar_ce_emu(shape, bf16)
+        want, bound = cr.grad(np.where(ref.valid, gs, 0.0), bf16)
+        r = (X.worst_ratio(np.abs(lse - cr.lse), cr.lse_bound), X.worst_ratio(np.abs(pix - cr.ce), cr.ce_bound), X.worst_ratio(np.abs(g - want), bound))
+        print('planar CE emulation %-12s bf16 %d: lse %.3f pixel loss %.3f gradient %.3f' % ((SOFT_IDS(shape), bf16) + r))
+        assert max(r) <= 1
+        assert not np.signbit(pix).any() and (pix[~ref.valid] == 0).all()
+        if 'exact' in plants:
+            i = plants['exact']
+            assert ref.valid[0, i] and lse[0, i] == x[0, 0, i] == 16 and pix[0, i] == 0 and 0 < cr.ce[0, i] < 1e-11
+    assert abs(float(pix.astype(np.float64).sum()) - cr.total) <= cr.total_bound
+
+
+def test_planar_ce_big_shape_takes_a_second_trip():
+    B, C, HW = X.PLANAR_CE_BIG
+    groups = B * (HW // 8)
+    assert X.soft_grid(B, HW, 0, 4096) == (4096, 2) and groups == 4097 * X.SOFT_NT      # block 0 alone goes round twice
+
+
+def test_planar_ce_emulation_that_repeats_a_class_plane_fails_the_elementwise_bound():
+    """grad8 writing plane C - 2 once more in place of the last one of 19: the elementwise bound sees it in f32 and bf16 alike (on the GPU
+    a plane that is skipped outright stays NaN, which the harness sees before any bound)"""
+    shape = (3, 19, 1000)
+    for bf16 in (False, True):
+        x, lab, plants, ref, cr, lse, pix, g, gs = _planar_ce_emu(shape, bf16, defect='last_plane')
+        want, bound = cr.grad(np.where(ref.valid, gs, 0.0), bf16)
+        assert X.worst_ratio(np.abs(g - want), bound) > 1
+
+
+# --- the two sort mutations that are not run on a device (their unwritten slots end as payloads that index past W): in numpy
+def _lovasz_sort_emu(keys, pay, defect=None):
+    """the 4 LSD passes of csrc/lovasz.hip (hist, digit totals, the offset scan with its carry loop over NT tiles at a time, the scatter
+    with a rank among equal digits of the tile) on one class plane.  The destination starts as 0xFFFFFFFF, as the GPU test's workspace
+    does, with spare slots behind it for a position past the end.  Defects: 'carry' drops the `carry += tot` of lovasz_offset_kernel;
+    'below' forms the scatter's `below` with the lane's own bit set, so that no lane ever updates the wave's running count"""
+    N = keys.size
+    ntiles = X.cdiv(N, X.LV_TILE)
+    idx = np.arange(N)
+    tile = idx // X.LV_TILE
+    k, q = keys.copy(), pay.copy()
+    for shift in (0, 8, 16, 24):
+        d = ((k >> np.uint32(shift)) & np.uint32(255)).astype(np.int64)
+        hist = np.zeros((256, ntiles), np.int64)
+        np.add.at(hist, (d, tile), 1)
+        dtot = hist.sum(1)
+        carry, offs = np.cumsum(dtot) - dtot, np.empty_like(hist)
+        for i0 in range(0, ntiles, X.LV_NT):
+            seg = hist[:, i0:i0 + X.LV_NT]
+            offs[:, i0:i0 + X.LV_NT] = carry[:, None] + np.cumsum(seg, 1) - seg
+            if defect != 'carry':
+                carry = carry + seg.sum(1)
+        group = (tile if defect != 'below' else idx // 64) * 256 + d        # equal digits of a tile; of one wave round under 'below'
+        order = np.argsort(group, kind='stable')
+        gs = group[order]
+        start = np.flatnonzero(np.r_[True, gs[1:] != gs[:-1]])
+        rank = np.empty(N, np.int64)
+        rank[order] = idx - np.repeat(start, np.diff(np.r_[start, N]))
+        pos = offs[d, tile] + rank + (1 if defect == 'below' else 0)
+        assert pos.max() < N + 64
+        k2, q2 = np.full(N + 64, X.LV_DROPPED, np.uint32), np.full(N + 64, X.LV_DROPPED, np.uint32)
+        k2[pos], q2[pos] = k, q
+        if defect is None:
+            k, q = k2[:N], q2[:N]
+        else:
+            return k2[:N], q2[:N], int(pos.max())                # one broken pass is enough
+    return k, q, N - 1
+
+
+def _is_permutation(pay, N):
+    pix = (pay & np.uint32(0x7FFFFFFF)).astype(np.int64)
+    return pix.max() < N and np.array_equal(np.bincount(pix, minlength=N), np.ones(N, np.int64))
+
+
+def test_lovasz_sort_emulation_and_the_two_mutations_that_are_not_run_on_a_device():
+    """the emulated passes give the stable argsort; without the offset scan's `carry += tot` nothing changes up to 256 tiles (every case of
+    tests/test_gpu_lovasz.py) and pay0 stops being a permutation at 258 (the `carry` case); with the lane's own bit in `below` it stops
+    being one on a single tile, and the last position lies one past the plane.  In both, slots stay unwritten, which on a device hold
+    whatever was there before: a payload that the weight kernel would use as an index.  So these two are shown here and not run there"""
+    x, lab, plants, ref = _lovasz('three_ragged')
+    keys = ref.key[0]
+    pay = np.arange(keys.size, dtype=np.uint32) | (ref.fg[0].astype(np.uint32) << np.uint32(31))
+    k, q, _ = _lovasz_sort_emu(keys, pay)
+    order, want = X.lovasz_order(keys, ref.fg[0])
+    assert np.array_equal(q, want) and np.array_equal(k, keys[order])
+    k1, q1, _ = _lovasz_sort_emu(keys, pay, 'carry')
+    k0, q0, last = _lovasz_sort_emu(keys, pay, 'below')
+    assert _is_permutation(q1, keys.size) and not _is_permutation(q0, keys.size)
+    assert last == keys.size                                                          # the run of ignored pixels ends the plane: one past it
+    x, lab, plants, ref = _lovasz('carry')
+    keys = ref.key[0]
+    pay = np.arange(keys.size, dtype=np.uint32) | (ref.fg[0].astype(np.uint32) << np.uint32(31))
+    head = 256 * X.LV_TILE
+    assert _is_permutation(_lovasz_sort_emu(keys[:head], pay[:head], 'carry')[1], head)         # 256 tiles: one trip, the carry is never used
+    k1, q1, _ = _lovasz_sort_emu(keys, pay, 'carry')
+    assert not _is_permutation(q1, keys.size) and (q1 == np.uint32(X.LV_DROPPED)).any()         # 258 tiles: tiles 256, 257 land on tiles 0, 1
