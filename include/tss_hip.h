@@ -1065,6 +1065,35 @@ int tss_upsample_ce_wide_bwd_rows(const float* ws, const float* scale, const flo
 int tss_selftrain_weights(const long long* kept, long n_pixels, const float* lam, int mode, int* group, float* weight, int B,
                           void* stream);
 
+/* ---- per-pixel loss weights on the fused head (csrc/pixwce.hip) -----------------------------------------------------------
+ * loss = sum_valid k_i ce_i / D with k_i = omega_i w_{t_i}: omega = pixel_weight, a DEVICE float32 [B][H][W] map (4-byte aligned), w =
+ * class_weight, DEVICE float [C] or NULL (ones); a pixel is valid iff target != ignore_index and 0 <= target < C.  norm picks the
+ * D-part a block adds up: 0 sum_valid k_i, 1 sum_valid w_{t_i}, 2 the number of its pixels inside the image, ignored ones included.
+ * The entries here leave per-block f64 rows (sum k ce in nats, D-part) at index (b * nband + band) * nstrip + strip and UNSCALED
+ * gradient tiles of sum k (p - onehot) in the layout of tss_upsample_ce_ws / tss_upsample_ce_wide_ws (not initialised by the caller);
+ * tss_upsample_ce_group_finalize (wide = 0 / 1) divides -- D = 0 gives loss 0 and scale 0 -- and tss_upsample_ce[_wide]_bwd_rows
+ * gathers.  omega is taken as it is (negative values, nan; 0 * nan = nan) and USED for valid pixels only (the register pass loads it one row ahead
+ * of the label, so the value under an ignored pixel is loaded and discarded); it is never read past column W - 1 of a
+ * row.  No label smoothing.  No atomics, no host read-back: capturable, the same bits on every run.
+ *   tss_upsample_ce_pixw_fwd, 1 <= C <= 24: one pass over the low-res NHWC logits (the contract of tss_upsample_ce_fwd for low, ldl,
+ *     target, ws), rows and tiles at once.
+ *   24 < C <= 256, three launches: tss_upsample_pixel_ce_wide writes ce into pix (float [B][H][W]); tss_upsample_ce_pixw_coef_wide,
+ *     on the wide head's grid (bands of 16 rows x strips of 256 columns), turns pix IN PLACE into k (0 for a pixel that does not
+ *     count) and writes the rows at the head of ws_rows = the tss_upsample_ce_wide_ws workspace; tss_upsample_coef_grad_wide with
+ *     coef := pix fills that workspace's tiles and leaves the rows alone.
+ *   tss_mix_plane: tss_mix_batch's mask (sel[b][label] or the box; partner and boxes clamped, exactly one of sel / boxes) on ONE
+ *     float32 [B][H][W] plane: out[b] = mask ? plane[b] : plane[partner[b]], a select on bits (the value not chosen never arrives).
+ *     W % 8 == 0, B <= 65535, plane / out 16-byte and label 8-byte aligned, out must not alias plane.
+ * Contract (else TSS_ERR_SHAPE, nothing launched): the head's shape rules (C <= 24 / 256, ldl, H >= h, W >= w), a grid of at most
+ * 2^31 - 1 blocks, norm in {0, 1, 2}, no NULL pointer but class_weight.  ws / ws_rows / low off 16 bytes, a map off 4: TSS_ERR_ALIGN.
+ * B * H * W == 0: TSS_OK, nothing launched. */
+int tss_upsample_ce_pixw_fwd(const void* low, long ldl, const long long* target, const float* pixel_weight, const float* class_weight,
+                             int norm, float* ws, int B, int C, int h, int w, int H, int W, int ignore_index, int dtype, void* stream);
+int tss_upsample_ce_pixw_coef_wide(float* pix, const long long* target, const float* pixel_weight, const float* class_weight, int norm,
+                                   float* ws_rows, int B, int C, int H, int W, int ignore_index, void* stream);
+int tss_mix_plane(const float* plane, const unsigned char* label, const int* partner, const unsigned char* sel, const int* boxes,
+                  float* out, long B, int H, int W, void* stream);
+
 /* ---- photometric strong augmentation: colour jitter and Gaussian blur of a normalised batch (csrc/strongaug.hip) ----------
  * image, out: [B][3][H][W] (TSS_F32 | TSS_BF16), normalised with mean3 / std3 (HOST float[3], NULL: 0 / 1).  Per sample, in DEVICE
  * memory: color float [B][8] = (apply, fb, fc, fs, dh, 0, 0, 0), radius int32 [B] = R, taps float [B][12] = (w_0 .. w_8, 0, 0, 0).

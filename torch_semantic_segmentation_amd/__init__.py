@@ -17,5 +17,7 @@ from .engine import benchmark_model, GraphedInference, MultiScaleEvaluator  # no
 from .engine import FlatOptimizer, FlatAdamW, FlatSGD, ModelEMA  # noqa: F401
 from .selftrain import upsample_pseudo_labels, classmix_select, mix_batch, SelfTraining  # noqa: F401
 from .selftrain import gaussian_taps, StrongAugment, strong_augment  # noqa: F401
+from .ops import upsample_pixel_weighted_cross_entropy, UpsamplePixelWeightedCrossEntropyFn  # noqa: F401
+from .selftrain import mix_plane  # noqa: F401
 
 __version__ = '0.1.0'

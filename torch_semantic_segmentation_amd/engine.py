@@ -623,9 +623,13 @@ class Trainer:
                     if getattr(self.loss_fn, 'sample_group', None) is not None:      # CrossEntropyLoss.set_sample_groups
                         groups = dict(sample_group=self.loss_fn.sample_group, sample_weight=self.loss_fn.sample_weight,
                                       group_loss_out=self.loss_fn.group_loss_out)
-                    loss = ops.upsample_cross_entropy(low, y, scale_factor=self.model.logit_scale,
-                                                      ignore_index=self.loss_fn.ignore_index, weight=self.loss_fn.weight,
-                                                      label_smoothing=self.loss_fn.label_smoothing, **groups)
+                    head_loss = ops.upsample_cross_entropy
+                    if getattr(self.loss_fn, 'pixel_weight', None) is not None:      # CrossEntropyLoss.set_pixel_weight
+                        head_loss = ops.upsample_pixel_weighted_cross_entropy
+                        groups.update(pixel_weight=self.loss_fn.pixel_weight, pixel_norm=self.loss_fn.pixel_norm)
+                    loss = head_loss(low, y, scale_factor=self.model.logit_scale,
+                                     ignore_index=self.loss_fn.ignore_index, weight=self.loss_fn.weight,
+                                     label_smoothing=self.loss_fn.label_smoothing, **groups)
             elif self.teacher is not None:
                 low_kd, y_pred = self._forward_with_lowres(x)
                 loss = self.loss_fn(y_pred, y)

@@ -3037,6 +3037,7 @@ class CrossEntropyLoss(torch.nn.Module):
         weight = _class_weight(weight, None)
         self.register_buffer('weight', None if weight is None else weight.clone())
         self.sample_group = self.sample_weight = self.group_loss_out = None
+        self.pixel_weight, self.pixel_norm = None, 'weight'
 
     def set_sample_groups(self, group, weight=None, group_loss_out=None):
         """Per-sample loss groups for every following call (upsample_cross_entropy's sample_group / sample_weight / group_loss_out):
@@ -3057,7 +3058,30 @@ class CrossEntropyLoss(torch.nn.Module):
     def clear_sample_groups(self):
         self.sample_group = self.sample_weight = self.group_loss_out = None
 
+    def set_pixel_weight(self, pixel_weight, norm='weight'):
+        """A per-pixel weight map for every following call (upsample_pixel_weighted_cross_entropy's pixel_weight / pixel_norm): a contiguous
+        float32
+        [B,H,W] DEVICE tensor that the kernels read, so an in-place update between replays of a captured step takes effect without
+        a re-capture.  A plain attribute like the sample rows, not a buffer; label smoothing must be 0."""
+        if norm not in PIXEL_NORMS:
+            raise ValueError("norm must be 'weight', 'valid' or 'pixels', got %r" % (norm,))
+        if self.label_smoothing > 0.0:
+            raise ValueError('label smoothing together with a per-pixel weight map is not supported')
+        if not (torch.is_tensor(pixel_weight) and pixel_weight.is_cuda and pixel_weight.dtype == torch.float32 and pixel_weight.dim() == 3
+                and pixel_weight.is_contiguous()):
+            raise ValueError('pixel_weight must be a contiguous float32 [B,H,W] tensor on the device')
+        self.pixel_weight, self.pixel_norm = pixel_weight.detach(), norm
+
+    def clear_pixel_weight(self):
+        self.pixel_weight, self.pixel_norm = None, 'weight'
+
     def forward(self, input, target):
+        if self.pixel_weight is not None:      # the map exists on the fused head: the same operator at the logits' own size
+            return upsample_pixel_weighted_cross_entropy(input, target, self.pixel_weight, size=tuple(input.shape[2:]),
+                                                         ignore_index=self.ignore_index, weight=self.weight,
+                                                         label_smoothing=self.label_smoothing, pixel_norm=self.pixel_norm,
+                                                         sample_group=self.sample_group, sample_weight=self.sample_weight,
+                                                         group_loss_out=self.group_loss_out)
         if self.sample_group is not None:      # groups exist on the fused head: the same operator at the logits' own size
             return upsample_cross_entropy(input, target, size=tuple(input.shape[2:]), ignore_index=self.ignore_index, weight=self.weight,
                                           label_smoothing=self.label_smoothing, sample_group=self.sample_group,
@@ -3869,6 +3893,120 @@ def _upsample_grouped_cross_entropy(low, target, scale_factor, size, ignore_inde
                                                (group, sweight, group_loss_out))
 
 
+PIXEL_NORMS = {'weight': 0, 'valid': 1, 'pixels': 2}      # the `norm` argument of csrc/pixwce.hip's entries
+
+
+def check_pixel_weight(pixel_weight, shape, dev, pixel_norm='weight'):
+    """Host-side validation of a per-pixel weight map: a contiguous float32 tensor of `shape` = (B, H, W) on the logits' device `dev`
+    (a host tensor is refused: the map is too large to copy silently), and a known pixel_norm.  ValueError otherwise."""
+    if pixel_norm not in PIXEL_NORMS:
+        raise ValueError("pixel_norm must be 'weight', 'valid' or 'pixels', got %r" % (pixel_norm,))
+    if not torch.is_tensor(pixel_weight):
+        raise ValueError('pixel_weight must be a tensor, got %s' % type(pixel_weight).__name__)
+    if (pixel_weight.dtype != torch.float32 or tuple(pixel_weight.shape) != tuple(shape) or not pixel_weight.is_contiguous()
+            or pixel_weight.device != torch.device(dev)):
+        raise ValueError('pixel_weight must be a contiguous float32 tensor of shape %s on %s, got %s %s on %s'
+                         % (tuple(shape), dev, pixel_weight.dtype, tuple(pixel_weight.shape), pixel_weight.device))
+
+
+class UpsamplePixelWeightedCrossEntropyFn(Function):
+    """upsample_pixel_weighted_cross_entropy: a per-pixel weight map omega (csrc/pixwce.hip): loss = sum_valid k ce / D, k = omega w_t, D by
+    `norm`.  Up to 24 classes one pass leaves the rows (sum k ce, D-part) and the unscaled gradient tiles; up to 256 the wide head's
+    per-pixel cross-entropy is turned in place into k by tss_upsample_ce_pixw_coef_wide, which also writes the rows, and
+    tss_upsample_coef_grad_wide fills the tiles.  Both always finish through tss_upsample_ce_group_finalize (without sample groups:
+    one group of weight 1) and the per-sample gather, so D = 0 gives 0.0 and an exactly zero gradient.  No atomics, no host
+    read-back: the same bits on every run, capturable; omega is read from device memory by every replay."""
+
+    @staticmethod
+    def forward(ctx, low, target, ho, wo, ignore_index, weight, pixw, norm, rows):
+        group, sweight, group_loss = rows
+        B, C, h, w = low.shape
+        dev = low.device
+        target = target.contiguous()
+        code = N.dtype_code(low.dtype)
+        ws = torch.empty(getattr(N.lib(), 'tss_upsample_ce%s_ws' % _wide(C))(B, C, h, w, ho, wo), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        scale = torch.empty(B, dtype=torch.float32, device=dev)
+        if _wide(C):
+            pix = torch.empty((B, ho, wo), dtype=torch.float32, device=dev)
+            call('tss_upsample_pixel_ce_wide', ptr(low), ld(low), ptr(target), ptr(pix), B, C, h, w, ho, wo, int(ignore_index), code, stream())
+            call('tss_upsample_ce_pixw_coef_wide', ptr(pix), ptr(target), ptr(pixw), ptr(weight), norm, ptr(ws), B, C, ho, wo,
+                 int(ignore_index), stream())
+            call('tss_upsample_coef_grad_wide', ptr(low), ld(low), ptr(target), ptr(pix), ptr(ws), B, C, h, w, ho, wo, int(ignore_index),
+                 code, stream())
+        else:
+            call('tss_upsample_ce_pixw_fwd', ptr(low), ld(low), ptr(target), ptr(pixw), ptr(weight), norm, ptr(ws), B, C, h, w, ho, wo,
+                 int(ignore_index), code, stream())
+        call('tss_upsample_ce_group_finalize', ptr(ws), B, C, h, w, ho, wo, 1 if _wide(C) else 0, ptr(group), ptr(sweight), ptr(loss),
+             ptr(scale), ptr(group_loss), stream())
+        ctx.geom = (B, C, h, w, ho, wo, ld(low), low.dtype)
+        ctx.save_for_backward(ws, scale)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        ws, scale = ctx.saved_tensors
+        B, C, h, w, ho, wo, ldl, dtype = ctx.geom
+        gout = gout.to(torch.float32).contiguous()
+        base = torch.empty((B, h, w, ldl), dtype=dtype, device=ws.device)   # pad channels are written as zeros
+        call('tss_upsample_ce%s_bwd_rows' % _wide(C), ptr(ws), ptr(scale), ptr(gout), ptr(base), ldl, B, C, h, w, ho, wo,
+             N.dtype_code(dtype), stream())
+        return base.permute(0, 3, 1, 2)[:, :C], None, None, None, None, None, None, None, None
+
+
+_ONE_GROUP = {}
+
+
+def upsample_pixel_weighted_cross_entropy(low, target, pixel_weight, scale_factor=None, size=None, ignore_index=-100, weight=None,
+                                          label_smoothing=0.0, pixel_norm='weight', sample_group=None, sample_weight=None,
+                                          group_loss_out=None):
+    """upsample_cross_entropy with every pixel's cross-entropy weighted by a map, from the low-resolution logits (csrc/pixwce.hip); a
+    function of its own, so that upsample_cross_entropy keeps its parameter list.  pixel_weight: a contiguous float32 [B,H,W] tensor on
+    the logits' device, a constant (no gradient flows to it; a tensor that requires grad is detached).  With k_i = pixel_weight_i *
+    weight[t_i] over the valid pixels (target != ignore_index and 0 <= target < C),
+        loss = sum_valid k_i ce_i / D,    D = sum_valid k_i ('weight', the weighted mean), sum_valid weight[t_i] ('valid', what the
+        plain loss divides by) or B*H*W, ignored pixels included ('pixels': torch.mean(ce * pixel_weight) of DACS / DAFormer).
+    The kernels read the map from device memory as it is (negative values and nan included), so an in-place update reaches a
+    captured step; a pixel of weight 0 still counts as valid for 'valid' and 'pixels'.  sample_group / sample_weight / group_loss_out
+    are upsample_cross_entropy's (N_g is the sum of D over the group's samples); D = 0 gives 0.0 and a zero gradient, with or without
+    groups.  ValueError: a host map, a wrong shape, dtype or strides, an unknown pixel_norm, label_smoothing > 0 (not supported with a
+    map), more than 256 classes, an output smaller than the map, a batch of more than GROUP_MAX_BATCH samples -- there is no unfused
+    route."""
+    eps = _check_smoothing(label_smoothing)
+    if pixel_norm not in PIXEL_NORMS:
+        raise ValueError("pixel_norm must be 'weight', 'valid' or 'pixels', got %r" % (pixel_norm,))
+    if eps > 0.0:
+        raise ValueError('label smoothing together with a per-pixel weight map is not supported')
+    B = low.shape[0]
+    if not 1 <= B <= GROUP_MAX_BATCH:
+        raise ValueError('a per-pixel weight map takes a batch of 1 to %d samples, got %d' % (GROUP_MAX_BATCH, B))
+    if sample_group is None and (sample_weight is not None or group_loss_out is not None):
+        raise ValueError('sample_weight and group_loss_out need sample_group')
+    host = [t is not None and not (torch.is_tensor(t) and t.is_cuda) for t in (sample_group, sample_weight)]
+    if host[0] or host[1]:
+        check_sample_groups(sample_group if host[0] else list(range(B)), sample_weight if host[1] else None, B)
+    ho, wo = _out_size(low, size, scale_factor)
+    if low.shape[1] > WIDEHEAD_MAX_CLASSES or ho < low.shape[2] or wo < low.shape[3]:
+        raise ValueError('a per-pixel weight map exists on the fused head only (at most %d classes, an output no smaller than the map): '
+                         'got %d classes, %dx%d -> %dx%d' % (WIDEHEAD_MAX_CLASSES, low.shape[1], low.shape[2], low.shape[3], ho, wo))
+    low = to_nhwc(materialize(low))
+    check_pixel_weight(pixel_weight, (B, ho, wo), low.device, pixel_norm)
+    _check_head_target(low, target, ho, wo)
+    dev = low.device
+    if sample_group is None:        # one group of weight 1: ids all 0, a NULL weight row
+        group = _per_device(_ONE_GROUP, dev, lambda: torch.zeros(GROUP_MAX_BATCH, dtype=torch.int32, device=dev))[:B]
+        sweight = None
+    else:
+        group, sweight = _sample_rows(sample_group, sample_weight, B, dev)
+    if group_loss_out is None:
+        group_loss_out = torch.empty(B, dtype=torch.float32, device=dev)
+    elif not (torch.is_tensor(group_loss_out) and group_loss_out.dtype == torch.float32 and tuple(group_loss_out.shape) == (B,)
+              and group_loss_out.is_contiguous() and group_loss_out.device == dev):
+        raise ValueError('group_loss_out must be a contiguous float32 tensor of shape (%d,) on %s' % (B, dev))
+    return UpsamplePixelWeightedCrossEntropyFn.apply(low, target, ho, wo, ignore_index, _class_weight(weight, low.shape[1], dev),
+                                                     pixel_weight.detach(), PIXEL_NORMS[pixel_norm], (group, sweight, group_loss_out))
+
+
 def upsample_cross_entropy(low, target, scale_factor=None, size=None, ignore_index=-100, weight=None, label_smoothing=0.0,
                            sample_group=None, sample_weight=None, group_loss_out=None):
     """Fused decoder head + loss:
@@ -3884,7 +4022,8 @@ def upsample_cross_entropy(low, target, scale_factor=None, size=None, ignore_ind
     ungrouped mean.  Host sequences are validated before they are copied (ValueError: a wrong length, an id outside [0, B), a
     negative or non-finite weight); device tensors (int32 / float32 [B]) are taken as they are and read by the kernels, so an
     in-place update reaches a captured step (an id outside [0, B) then gives its sample the weight 0).  Grouping exists on the
-    fused head only: more than 256 classes or an output smaller than the map is a ValueError, there is no unfused route."""
+    fused head only: more than 256 classes or an output smaller than the map is a ValueError, there is no unfused route.
+    A per-pixel weight map: upsample_pixel_weighted_cross_entropy."""
     eps = _check_smoothing(label_smoothing)
     if sample_group is not None:
         return _upsample_grouped_cross_entropy(low, target, scale_factor, size, ignore_index, weight, eps, sample_group,

@@ -26,14 +26,16 @@ def _threshold_tensor(threshold, dev):
     return _THRESHOLDS[key]
 
 
-def upsample_pseudo_labels(low, threshold, scale_factor=None, size=None, ignore_index=255, want_confidence=False, kept=None, out=None):
+def upsample_pseudo_labels(low, threshold, scale_factor=None, size=None, ignore_index=255, want_confidence=False, kept=None, out=None,
+                           out_confidence=None):
     """Pseudo-labels of F.interpolate(low, bilinear, align_corners=True) without the full-resolution logits
     (tss_upsample_pseudo_label[_wide]): per pixel the arg-max class (lowest index wins ties) where its softmax probability reaches
     `threshold`, `ignore_index` elsewhere.  low: the NHWC map of forward_lowres, read in place, or an NCHW tensor; threshold: a float
     (kept in a cached device scalar) or a one-element float32 device tensor, read by the kernel -- a captured step follows its value.
     Returns (labels uint8 [B,H,W], confidence float32 [B,H,W] or None, kept int64 [B]): confidence is written for every pixel; kept
     counts the labels kept per sample and is zero-filled here unless the caller passes a tensor of their own to accumulate into.
-    `out`: a uint8 [B,H,W] tensor to write the labels into.  Up to 24 classes the scores of a pixel live in registers, up to 255
+    `out`: a uint8 [B,H,W] tensor to write the labels into; `out_confidence`: a float32 [B,H,W] tensor to write the confidence into
+    (it implies want_confidence).  Up to 24 classes the scores of a pixel live in registers, up to 255
     the class-chunked kernel runs.  ValueError: more than 255 classes, ignore_index outside [C, 255] (the label is a byte and must
     not collide with a class), an output smaller than the map."""
     low = ops.to_nhwc(ops.materialize(low))
@@ -52,7 +54,12 @@ def upsample_pseudo_labels(low, threshold, scale_factor=None, size=None, ignore_
         out = torch.empty((B, ho, wo), dtype=torch.uint8, device=dev)
     elif out.dtype != torch.uint8 or tuple(out.shape) != (B, ho, wo) or not out.is_contiguous() or out.device != dev:
         raise ValueError('out must be a contiguous uint8 tensor of shape %s on %s' % ((B, ho, wo), dev))
-    conf = torch.empty((B, ho, wo), dtype=torch.float32, device=dev) if want_confidence else None
+    if out_confidence is not None:
+        conf = out_confidence
+        if conf.dtype != torch.float32 or tuple(conf.shape) != (B, ho, wo) or not conf.is_contiguous() or conf.device != dev:
+            raise ValueError('out_confidence must be a contiguous float32 tensor of shape %s on %s' % ((B, ho, wo), dev))
+    else:
+        conf = torch.empty((B, ho, wo), dtype=torch.float32, device=dev) if want_confidence else None
     if kept is None:
         kept = torch.zeros(B, dtype=torch.int64, device=dev)
     elif kept.dtype != torch.int64 or tuple(kept.shape) != (B,) or not kept.is_contiguous() or kept.device != dev:
@@ -147,6 +154,49 @@ def mix_batch(image, labels, partner, sel=None, boxes=None, out_image=None, out_
     call('tss_mix_batch', ptr(image), ptr(labels), ptr(partner), ptr(sel), ptr(boxes), ptr(out_image), ptr(out_target), B, Ci, H, W,
          N.dtype_code(image.dtype), stream())
     return out_image, out_target
+
+
+def mix_plane(plane, labels, partner, sel=None, boxes=None, out=None):
+    """mix_batch's select on ONE float32 [B,H,W] plane, one launch (tss_mix_plane): with mask = sel[b][labels[b]] or the box,
+        out[b] = mask ? plane[b] : plane[partner[b]]
+    on bits (the value that is not chosen never reaches the output) -- a confidence map that follows the mixed pseudo-labels, or
+    DACS's two-valued source / target map from constant planes.  W % 8 == 0; labels uint8 [B,H,W] (read for `sel` only); partner,
+    sel and boxes as for mix_batch (host rows validated and copied, device rows taken as they are and clamped).  Exactly one of
+    sel / boxes.  Returns out, which must not alias plane."""
+    ops._check_device(plane)
+    if (sel is None) == (boxes is None):
+        raise ValueError('mix_plane takes exactly one of sel (ClassMix) and boxes (CutMix)')
+    if plane.dim() != 3 or plane.dtype != torch.float32 or not plane.is_contiguous():
+        raise ValueError('plane must be a contiguous float32 [B,H,W] tensor, got %s %s' % (plane.dtype, tuple(plane.shape)))
+    B, H, W = plane.shape
+    dev = plane.device
+    if W % 8:
+        raise ValueError('mix_plane needs a width that is a multiple of 8, got %d' % W)
+    if labels.dtype != torch.uint8 or tuple(labels.shape) != (B, H, W) or not labels.is_contiguous() or labels.device != dev:
+        raise ValueError('labels must be a contiguous uint8 tensor of shape %s on %s' % ((B, H, W), dev))
+    partner = _rows(partner, 'partner', (B,), 0, max(B, 1), dev)
+    if boxes is not None:
+        if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda):
+            b = boxes.numpy() if isinstance(boxes, torch.Tensor) else np.asarray(boxes)
+            if b.ndim == 2 and b.shape[1] == 4 and b.size and b.dtype.kind in 'iu' and (int(b[:, 0::2].max()) > H or int(b[:, 1::2].max()) > W):
+                raise ValueError('boxes must lie inside the %dx%d image' % (H, W))
+        boxes = _rows(boxes, 'boxes', (B, 4), 0, max(H, W) + 1, dev)
+    else:
+        if not (isinstance(sel, torch.Tensor) and sel.dtype == torch.uint8 and tuple(sel.shape) == (B, 256)):
+            raise ValueError('sel must be a uint8 tensor of shape (%d, 256)' % B)
+        if not sel.is_cuda:
+            if int(sel.max()) > 1:
+                raise ValueError('sel must hold 0 / 1')
+            sel = sel.to(dev)
+        sel = sel.contiguous()
+    if out is None:
+        out = torch.empty_like(plane)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, H, W) or not out.is_contiguous() or out.device != dev:
+        raise ValueError('out must be a contiguous float32 tensor of shape %s on %s' % ((B, H, W), dev))
+    if out.data_ptr() == plane.data_ptr() and B:
+        raise ValueError('out must not alias plane')
+    call('tss_mix_plane', ptr(plane), ptr(labels), ptr(partner), ptr(sel), ptr(boxes), ptr(out), B, H, W, stream())
+    return out
 
 
 STRONG_MAX_RADIUS = 8
@@ -324,10 +374,33 @@ class SelfTraining:
     Gaussian blur, strong_augment): the mix then writes into a scratch batch and the augmentation writes x_all[B:], both in the
     captured prologue; y_all[B:] is the mix's target as before.  Its rows are drawn in step() after the mix rows, from the same
     generator, into fixed device buffers; last_rows grows by (color, radius, taps).  With mix=None this is FixMatch's pair: the
-    teacher on xu, the student on strong(xu).  Needs 3 channels, H >= 9, W >= 16.  strong=None: the launches and bits as before."""
+    teacher on xu, the student on strong(xu).  Needs 3 channels, H >= 9, W >= 16.  strong=None: the launches and bits as before.
+
+    pixel_weighting='confidence' weights every pseudo-labelled pixel's loss by the teacher's confidence (the softmax probability of
+    its arg-max class): the prologue asks upsample_pseudo_labels for the confidence map, mixes it with the mask of the labels
+    (mix_plane) into w_all[B:] -- w_all is float32 [2B,H,W], its labelled half ones -- and hands w_all to the trainer's
+    CrossEntropyLoss (upsample_pixel_weighted_cross_entropy, normalised by `pixel_norm`).  The threshold keeps working (rejected
+    pixels are ignore_index; threshold=0 is pure soft weighting) and it composes with unsup_weight.  Needs the trainer of
+    unsup_weight, label smoothing 0 and B <= 512.  pixel_weighting=None: the launches and bits as before.
+
+    What stays set: the prologue assigns the trainer's CrossEntropyLoss its map (pixel_weighting) and its sample rows (unsup_weight),
+    both sized for the 2B samples of a step, and leaves them there for the next step.  Before the SAME module scores a batch of
+    another size (validation, a plain supervised step) call loss_fn.clear_pixel_weight() / loss_fn.clear_sample_groups(), or it raises
+    ValueError for the shape; the next step() sets them again."""
 
     def __init__(self, trainer, teacher, num_classes, threshold=0.95, mix='classmix', cut_area=(0.25, 0.5), ignore_index=255, seed=0,
-                 unsup_weight=None, unsup_weighting='mean', strong=None):
+                 unsup_weight=None, unsup_weighting='mean', strong=None, pixel_weighting=None, pixel_norm='weight'):
+        if pixel_weighting not in (None, 'confidence'):
+            raise ValueError("pixel_weighting must be None or 'confidence', got %r" % (pixel_weighting,))
+        if pixel_norm not in ops.PIXEL_NORMS:
+            raise ValueError("pixel_norm must be 'weight', 'valid' or 'pixels', got %r" % (pixel_norm,))
+        self.pixel_weighting, self.pixel_norm = pixel_weighting, pixel_norm
+        if pixel_weighting is not None and not (type(trainer.loss_fn) is ops.CrossEntropyLoss and trainer.fuse_head_loss
+                                                and not (trainer.model._forward_hooks or trainer.model._forward_pre_hooks)
+                                                and trainer.loss_fn.label_smoothing == 0.0):
+            raise ValueError('SelfTraining(pixel_weighting=...): the trainer must run tssa.CrossEntropyLoss without label smoothing on '
+                             'the fused-head route (a model with forward_lowres and no forward hooks), got %s'
+                             % type(trainer.loss_fn).__name__)
         if strong is not None and not isinstance(strong, StrongAugment):
             raise ValueError('strong must be a tssa.StrongAugment or None, got %s' % type(strong).__name__)
         self.strong = strong
@@ -388,6 +461,11 @@ class SelfTraining:
             self.sa_radius = torch.zeros(B, dtype=torch.int32, device=dev)
             self.sa_taps = torch.zeros((B, 12), dtype=torch.float32, device=dev)
             self.sa_ws = torch.zeros(N.lib().tss_strong_augment_ws(B, H, W) // 8, dtype=torch.float64, device=dev)
+        if self.pixel_weighting is not None:
+            if 2 * B > ops.GROUP_MAX_BATCH:
+                raise ValueError('SelfTraining(pixel_weighting=...) takes at most %d labelled samples, got %d' % (ops.GROUP_MAX_BATCH // 2, B))
+            self.w_all = torch.ones((2 * B, H, W), dtype=torch.float32, device=dev)     # the labelled half stays ones
+            self.conf = torch.empty((B, H, W), dtype=torch.float32, device=dev)
         if self._lam0 is not None:
             if 2 * B > ops.GROUP_MAX_BATCH:
                 raise ValueError('SelfTraining(unsup_weight=...) takes at most %d labelled samples, got %d' % (ops.GROUP_MAX_BATCH // 2, B))
@@ -444,12 +522,18 @@ class SelfTraining:
         with torch.no_grad(), self._teacher_prep:
             low = ops.materialize(self.teacher.forward_lowres(self.xu))
             self.last_kept.zero_()
-            upsample_pseudo_labels(low, self.threshold, size=(H, W), ignore_index=self.ignore_index, kept=self.last_kept, out=self.pseudo)
+            conf = self.conf if self.pixel_weighting is not None else None
+            upsample_pseudo_labels(low, self.threshold, size=(H, W), ignore_index=self.ignore_index, kept=self.last_kept, out=self.pseudo,
+                                   out_confidence=conf)
             if self.mix == 'classmix':
                 call('tss_classmix_select', ptr(self.pseudo), ptr(self.keys), ptr(self.sel), B, H * W, self.num_classes, stream())
             mix_batch(self.xu, self.pseudo, self.partner, sel=self.sel if self.mix == 'classmix' else None,
                       boxes=None if self.mix == 'classmix' else self.boxes,
                       out_image=self.x_all[B:] if self.strong is None else self.mixed, out_target=self.y_all[B:])
+            if self.pixel_weighting is not None:        # the confidence follows the mask of the labels (mix=None: the whole-frame box copies)
+                mix_plane(self.conf, self.pseudo, self.partner, sel=self.sel if self.mix == 'classmix' else None,
+                          boxes=None if self.mix == 'classmix' else self.boxes, out=self.w_all[B:])
+                self.trainer.loss_fn.pixel_weight, self.trainer.loss_fn.pixel_norm = self.w_all, self.pixel_norm
             if self.strong is not None:
                 strong_augment(self.mixed, self.sa_color, self.sa_radius, self.sa_taps, self.strong.mean, self.strong.std,
                                out=self.x_all[B:], workspace=self.sa_ws)
